@@ -2,7 +2,18 @@
 """bench.py -- headline benchmark of the hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg2sf|cfg3b|cfg4f|cfg4b|cfg5|cfg5aug]
+                    [--full] [--dump-outputs DIR]
                     [--configs all|none|a,b,c] [--scaling weak|strong] [--gather K] [--shard-of N [--shard-rank R]] [--cold]
+
+A plain run (no --full) sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and
+prints the line: `value`, `ms_per_step` and the roofline of the timed steps.  Everything else below -- the untimed check against
+the reference's folds, the fill / copy-mix yardsticks, the per-step event pass, `sustained`, `e2e`, `loader`, `cpu_baseline`,
+`configs` and bench_full.json -- needs --full.
+
+--dump-outputs DIR (rank 0) writes what the LAST timed step computed, in float32 / float64: DIR/output_sample.npy, every value
+of a fixed, seeded sample of the batch's sequences (the output with its batch axis cut down to the sample, <= 48 MiB), and
+DIR/output_digest.npy, one exact float64 weighted sum per sequence over ALL of that sequence's output values (fixed, seeded
+integer weights), so that two builds can be compared output for output.
 
 A "step" is ONE pass of the hot path over one batch of synthetic input that is already resident
 in HBM (packed chars + offsets on the device, output preallocated): for the default workload
@@ -478,6 +489,39 @@ class Batch:
                                     "onehot_bcl": "batch_onehot_encode(layout=bcl)"}.get(self.op, "BLOSUM62 augment + batch_tokenize"),
             self.n, cfg["lo"], cfg["hi"], self.P, self.C, str(self.tdt).replace("torch.", ""),
             "(P,B,C)" if self.op == "onehot" else "(B,C,P)" if self.op == "onehot_bcl" else ("(B,P)" if self.batch_first else "(P,B)"))
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # float32 bytes of output_sample.npy at most (+ 8 bytes per sequence of output_digest.npy: < 64 MB in all)
+
+
+def batch_axis(op, batch_first):
+    """which axis of the output tensor (Batch.out_shape) runs over the sequences"""
+    return {"onehot": 1, "onehot_bcl": 0}.get(op, 0 if batch_first else 1)
+
+
+def dump_outputs(out, axis, path, seed=20250101):
+    """--dump-outputs: `out` as its caller receives it, in float32 / float64 -- output_sample.npy = the sequences of a fixed, seeded
+    sample (in ascending order) with all their values, output_digest.npy = one weighted sum per sequence over all its values.  Every
+    output of the hot path is integer-valued with |v| <= 127 and the weights are integers in [1, 1024), so each digest is an integer
+    below 2^53 and exact in float64 whatever the summation order.  Returns the names and shapes written."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = out.shape[axis]
+    per_seq = out.numel() // max(B, 1)
+    rng = np.random.default_rng(seed)
+    k = min(B, max(1, DUMP_SAMPLE_BYTES // (4 * max(per_seq, 1))))
+    idx = np.sort(rng.choice(B, size=k, replace=False))
+    sample = out.index_select(axis, torch.from_numpy(idx).to(out.device)).to(torch.float32).cpu().numpy()
+    o = out.movedim(axis, 0)
+    w = torch.from_numpy(rng.integers(1, 1024, size=tuple(o.shape[1:])).astype(np.float64)).to(out.device)
+    digest = torch.empty(B, dtype=torch.float64, device=out.device)
+    chunk = max(1, (256 << 20) // (8 * max(per_seq, 1)))  # <= 256 MiB of float64 at a time
+    for b0 in range(0, B, chunk):
+        digest[b0:b0 + chunk] = (o[b0:b0 + chunk].to(torch.float64) * w).reshape(min(chunk, B - b0), -1).sum(1)
+    files = {"output_sample": sample, "output_digest": digest.cpu().numpy()}
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
 
 
 def timed_loop(fn, n, warm, stream):
@@ -981,7 +1025,7 @@ def _r(v, sig=5):
     return v
 
 
-def compact_line(res):
+def compact_line(res, full_file="bench_full.json"):
     """The ONE stdout line: the contract's keys + `roofline` + `cpu_baseline` + `check.ok` + `build_id`, and `configs` reduced to
     {name: {ms, frac, cold, ok}} -- at most LINE_LIMIT bytes whatever was measured.  Everything else of `res` (sustained, e2e, two_streams,
     into_root, yardsticks, prose) goes to bench_full.json (`emit`)."""
@@ -1007,7 +1051,8 @@ def compact_line(res):
             c["single_thread"] = {"value": _r(st.get("value")), "cores": st.get("cores")}
         line["cpu_baseline"] = c
     line["gb_per_s_written"] = _r(res.get("gb_per_s_written"))
-    line["check"] = {"ok": bool((res.get("check") or {}).get("ok"))}
+    if "check" in res:  # (a plain run does no check: --full)
+        line["check"] = {"ok": bool((res.get("check") or {}).get("ok"))}
     line["build_id"] = res.get("build_id")
     for k in ("cold", "shard"):
         if isinstance(res.get(k), dict):
@@ -1029,7 +1074,8 @@ def compact_line(res):
             if m4 is not None:
                 e["multi4"] = _r(m4, 3)
             line["configs"][name] = e
-    line["full"] = "bench_full.json"
+    if full_file:
+        line["full"] = full_file
     text = json.dumps(line, separators=(",", ":"))
     # whatever a future round adds: the line never outgrows its reader again (drop the optional parts in this order)
     for drop in ("loader_us_per_batch", "gather", "shard", "cold", "configs"):
@@ -1088,8 +1134,17 @@ def main():
                          "(sharding.encode_on_devices); with fewer GPUs visible the entries repeat")
     ap.add_argument("--full-line", action="store_true",
                     help="print the FULL result object on stdout (the lab scripts and gpu_evidence.sh read it) instead of the compact "
-                         "<= 4-KB line the driver parses; bench_full.json is written either way")
+                         "<= 4-KB line the driver parses; with --full, bench_full.json is written either way")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the timed steps: the untimed check against the reference's folds, yardsticks, per-step events, "
+                         "sustained loop, e2e, loader, CPU baseline, `configs` (default 'all' for cfg3) and bench_full.json; "
+                         "a plain run only sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/output_sample.npy (float32: a fixed, seeded "
+                         "sample of the sequences) and DIR/output_digest.npy (float64: one exact weighted sum per sequence); rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1178,39 +1233,46 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # untimed: validate lengths, run once, check a size-independent property and (full-size single-rank batches) the reference's folds
-    check = b.check()
+    check = fill_gbps = fill_best = mix_gbps = event_floor_ms = None
+    if args.full:
+        # untimed: validate lengths, run once, check a size-independent property and (full-size single-rank batches) the reference's folds
+        check = b.check()
 
-    # write-bandwidth yardstick: a plain fill (one 1-KiB store per wave, one aligned 4-KiB chunk per workgroup, blocks in
-    # address order) over the same output buffer, in its BEST-KNOWN configuration: 3 resident workgroups per CU (unused
-    # LDS as the cap; profiles/r01/fill_occupancy.txt: 6.84 TB/s uncapped, 7.38 at 3 per CU), and uncapped for reference.
-    # Measured BEFORE the warm-up steps: its launches also lift the clocks out of idle.
-    capi.check(lib.bsq_tuning_set(b"fill_mode", 1))
-    fill_bytes = (out_bytes // 16) * 16
-    fill_gbps = {}
-    for name, pad in (("uncapped", 0), ("3_workgroups_per_cu", 53000)):
-        capi.check(lib.bsq_tuning_set(b"fill_pad", pad))
-        fill_gbps[name] = fill_bytes / (timed_loop(lambda: capi.check(lib.bsq_fill_device(out.data_ptr(), fill_bytes, 0, sh)), 5, 10, stream) * 1e-3) / 1e9
-    capi.check(lib.bsq_tuning_set(b"fill_pad", 0))
-    fill_best = max(fill_gbps.values())
-    # read + write yardstick of the token workloads: the kernel's stream shape (one wave = one aligned 4-KiB chunk of the
-    # output + its share of the characters, two dependent load steps like offsets -> characters) with none of its work
-    mix_gbps = None
-    if op in ("tokenize", "augment+tokenize") and batch_first and sz == 1 and out_bytes % 4096 == 0 and total >= 16:
-        src_bytes = (total // 16) * 16
-        mix_ms = timed_loop(lambda: capi.check(lib.bsq_copy_mix_device(out.data_ptr(), out_bytes, d_chars.data_ptr(), src_bytes, 1, 1, sh)), 20, 10, stream)
-        mix_gbps = (src_bytes + out_bytes) / (mix_ms * 1e-3) / 1e9
-    # what one event pair around ONE tiny launch reads: the floor under every per-step event time below
-    tiny = torch.empty(4096, dtype=torch.uint8, device=dev)
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-    for ea, eb in pairs:
-        ea.record(stream)
-        capi.check(lib.bsq_fill_device(tiny.data_ptr(), 4096, 0, sh))
-        eb.record(stream)
-    torch.cuda.synchronize()
-    event_floor_ms = float(np.median([ea.elapsed_time(eb) for ea, eb in pairs]))
+        # write-bandwidth yardstick: a plain fill (one 1-KiB store per wave, one aligned 4-KiB chunk per workgroup, blocks in
+        # address order) over the same output buffer, in its BEST-KNOWN configuration: 3 resident workgroups per CU (unused
+        # LDS as the cap; profiles/r01/fill_occupancy.txt: 6.84 TB/s uncapped, 7.38 at 3 per CU), and uncapped for reference.
+        # Measured BEFORE the warm-up steps: its launches also lift the clocks out of idle.
+        capi.check(lib.bsq_tuning_set(b"fill_mode", 1))
+        fill_bytes = (out_bytes // 16) * 16
+        fill_gbps = {}
+        for name, pad in (("uncapped", 0), ("3_workgroups_per_cu", 53000)):
+            capi.check(lib.bsq_tuning_set(b"fill_pad", pad))
+            fill_gbps[name] = fill_bytes / (timed_loop(lambda: capi.check(lib.bsq_fill_device(out.data_ptr(), fill_bytes, 0, sh)), 5, 10, stream) * 1e-3) / 1e9
+        capi.check(lib.bsq_tuning_set(b"fill_pad", 0))
+        fill_best = max(fill_gbps.values())
+        # read + write yardstick of the token workloads: the kernel's stream shape (one wave = one aligned 4-KiB chunk of the
+        # output + its share of the characters, two dependent load steps like offsets -> characters) with none of its work
+        if op in ("tokenize", "augment+tokenize") and batch_first and sz == 1 and out_bytes % 4096 == 0 and total >= 16:
+            src_bytes = (total // 16) * 16
+            mix_ms = timed_loop(lambda: capi.check(lib.bsq_copy_mix_device(out.data_ptr(), out_bytes, d_chars.data_ptr(), src_bytes, 1, 1, sh)), 20, 10, stream)
+            mix_gbps = (src_bytes + out_bytes) / (mix_ms * 1e-3) / 1e9
+        # what one event pair around ONE tiny launch reads: the floor under every per-step event time below
+        tiny = torch.empty(4096, dtype=torch.uint8, device=dev)
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+        for ea, eb in pairs:
+            ea.record(stream)
+            capi.check(lib.bsq_fill_device(tiny.data_ptr(), 4096, 0, sh))
+            eb.record(stream)
+        torch.cuda.synchronize()
+        event_floor_ms = float(np.median([ea.elapsed_time(eb) for ea, eb in pairs]))
 
     ramp(step, stream)
+    if op == "augment+tokenize":
+        # augmentation mutates the batch in place and ramp() runs as many steps as its timing asks for: start the warm-up from the
+        # pristine batch and seed 0, so that every run with the same arguments feeds the same inputs to every step after this
+        torch.cuda.synchronize()
+        d_chars.copy_(torch.from_numpy(chars).to(dev))
+        b.aug_seed = 0
     for _ in range(args.warmup):
         step()
     # THE timed region: exactly K steps between barriers.  One pair of HIP events around the same K launches (recorded on
@@ -1227,26 +1289,31 @@ def main():
     barrier()
     wall = time.perf_counter() - t0
     loop_ms = la.elapsed_time(lb) / args.steps
+    dumped = None
+    if args.dump_outputs and rank == 0:  # what the LAST timed step wrote, before anything below overwrites it
+        dumped = dump_outputs(out, batch_axis(op, batch_first), args.dump_outputs)
 
-    # Afterwards, untimed: the same K steps once more with one event pair PER STEP (spread: min / median).  The event
-    # records cost ~2 us of queue time per step -- 10 % of the 17-35 us steps of cfg2 / cfg5, nothing on the others --
-    # which is why they are not in the timed region.
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for ea, eb in ev:
-        ea.record(stream)
-        step()
-        eb.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = [ea.elapsed_time(eb) for ea, eb in ev]
-    kern_avg_ms = float(np.mean(kern_ms))
-    if os.environ.get("BSQ_BENCH_DUMP"):  # per-step device times, for variance hunting
-        print("per-step ms:", " ".join("%.3f" % v for v in kern_ms), file=sys.stderr)
+    kern_ms = None
+    if args.full:
+        # Afterwards, untimed: the same K steps once more with one event pair PER STEP (spread: min / median).  The event
+        # records cost ~2 us of queue time per step -- 10 % of the 17-35 us steps of cfg2 / cfg5, nothing on the others --
+        # which is why they are not in the timed region.
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for ea, eb in ev:
+            ea.record(stream)
+            step()
+            eb.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = [ea.elapsed_time(eb) for ea, eb in ev]
+        kern_avg_ms = float(np.mean(kern_ms))
+        if os.environ.get("BSQ_BENCH_DUMP"):  # per-step device times, for variance hunting
+            print("per-step ms:", " ".join("%.3f" % v for v in kern_ms), file=sys.stderr)
     if op == "augment+tokenize":
         d_chars.copy_(torch.from_numpy(chars).to(dev))
 
     # Sustained: the same step looped for at least one second of wall clock (clocks, thermals), untimed for `value`.
     sustained = None
-    if world == 1 and not args.no_sustained:
+    if world == 1 and args.full and not args.no_sustained:
         sustained = sustained_loop(b, 1.0, args.steps, loop_ms, stream)
     step_calls_main = b.step_calls
     cold = None
@@ -1379,18 +1446,22 @@ def main():
                          "traffic": traffic, "traffic_stale": traffic_stale(args.workload, lib), "kernel": kernel_name,
                          "algorithmic_bytes_per_launch": algo_bytes,
                          "kernel_avg_ms": loop_ms,                    # the K timed steps between ONE pair of events, / K
-                         "kernel_avg_ms_per_step_events": kern_avg_ms,  # second, untimed pass: one event pair per step
-                         "frac_per_step_events": algo_bytes / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                         "kernel_min_ms": float(np.min(kern_ms)), "kernel_median_ms": float(np.median(kern_ms)),
-                         "event_pair_floor_ms": event_floor_ms,  # one event pair around one 4-KiB fill: what per-step events add
                          "traffic_source": ("profiles/traffic.json (separate rocprofv3 --pmc passes of this workload, committed; "
-                                            "not measured in this run)") if traffic is not None else None,
-                         "fill_yardstick_gbps": fill_best, "fill_yardsticks_gbps": fill_gbps,
-                         "frac_of_fill": (out_bytes / (loop_ms * 1e-3) / 1e9) / fill_best,
-                         "copy_mix_yardstick_gbps": mix_gbps,
-                         "frac_of_copy_mix": (achieved / mix_gbps) if mix_gbps else None},
+                                            "not measured in this run)") if traffic is not None else None},
         }
-        res["check"] = check
+        if args.full:
+            res["roofline"].update({
+                "kernel_avg_ms_per_step_events": kern_avg_ms,  # second, untimed pass: one event pair per step
+                "frac_per_step_events": algo_bytes / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                "kernel_min_ms": float(np.min(kern_ms)), "kernel_median_ms": float(np.median(kern_ms)),
+                "event_pair_floor_ms": event_floor_ms,  # one event pair around one 4-KiB fill: what per-step events add
+                "fill_yardstick_gbps": fill_best, "fill_yardsticks_gbps": fill_gbps,
+                "frac_of_fill": (out_bytes / (loop_ms * 1e-3) / 1e9) / fill_best,
+                "copy_mix_yardstick_gbps": mix_gbps,
+                "frac_of_copy_mix": (achieved / mix_gbps) if mix_gbps else None})
+            res["check"] = check
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         res["build_id"] = lib.bsq_build_id().decode()  # of the loaded libbsq_hip.so (profiles/traffic.json records the one it was measured on)
         # which step() calls of this process were the K timed ones (the rocprofv3 summaries under profiles/ keep exactly those dispatches)
         res["timed"] = {"first_step_index": first_timed_step, "steps": args.steps, "step_calls_total": step_calls_main}
@@ -1408,17 +1479,18 @@ def main():
                 raise SystemExit("bsq_augment_tokenize_device: %d token waves gave up waiting" % res["fused_wait_failures"])
         if gather_info is not None:
             res["gather"] = gather_info
-        if world == 1 and not args.no_e2e and op in ("onehot", "tokenize"):
+        side = world == 1 and args.full  # the side figures of the N = 1 run: --full only
+        if side and not args.no_e2e and op in ("onehot", "tokenize"):
             res["e2e"] = e2e_python_surface(cfg, op, destchar, batch_first, chars, offsets, dev, args.devices)
-        if world == 1 and not args.no_e2e and args.workload == "cfg3":
+        if side and not args.no_e2e and args.workload == "cfg3":
             try:
                 res["loader"] = loader_epochs(dev)
             except Exception as ex:  # noqa: BLE001 -- a side figure must never cost the driver its line
                 res["loader"] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if side and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, op, destchar, batch_first, chars, offsets, args.cpu_threads or None)
-        # every other BASELINE workload in the same line (N = 1; default: only beside the headline workload)
-        which = "none" if args.no_configs else (args.configs if args.configs is not None else ("all" if args.workload == "cfg3" else "none"))
+        # every other BASELINE workload in the same line (N = 1; default: only beside the headline workload, with --full)
+        which = "none" if args.no_configs else (args.configs if args.configs is not None else ("all" if side and args.workload == "cfg3" else "none"))
         names = DEFAULT_CONFIGS if which == "all" else [] if which == "none" else [w for w in which.split(",") if w]
         if world == 1 and (names or args.shard_of > 1):
             del b, d_chars, d_offs, out, step
@@ -1439,7 +1511,10 @@ def main():
                     full_ms = loop_ms if wname == args.workload else (full or {}).get("ms_per_step_cache_resident", (full or {}).get("ms_per_step"))
                     full_cold = ((full or {}).get("cold") or {}).get("ms_per_step")
                     res["configs"]["%s_shard8" % wname] = run_shard(wname, 8, lib, dev, stream, args.steps, args.warmup, full_ms=full_ms, full_cold_ms=full_cold)
-        emit(res, args.full_line)
+        if args.full:
+            emit(res, args.full_line)
+        else:  # a plain run: the line alone, no bench_full.json
+            print(json.dumps(res) if args.full_line else compact_line(res, full_file=None), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -3,9 +3,9 @@
 #
 #   scripts/gpu_evidence.sh tests [pytest args]        GPU suite -> gpurun_out/<TAG>/gputest.txt
 #   scripts/gpu_evidence.sh fuzz [seconds] [seed]       randomised harness -> gpurun_out/<TAG>/fuzz.txt
-#   scripts/gpu_evidence.sh bench                       the driver's line (python3 bench.py) + one line per workload -> bench_*.json, bench_lines.txt
+#   scripts/gpu_evidence.sh bench                       the driver's line with --full (python3 bench.py --full) + one line per workload -> bench_*.json, bench_lines.txt
 #   scripts/gpu_evidence.sh profile [workloads...]      per workload: rocprofv3 --kernel-trace --stats, then SEPARATE --pmc WRITE_SIZE and
-#                                                       --pmc FETCH_SIZE passes of `bench.py --workload W --no-configs`, condensed by
+#                                                       --pmc FETCH_SIZE passes of `bench.py --full --workload W --no-configs`, condensed by
 #                                                       summarize_prof.py -> gpurun_out/<TAG>_<W>/summary.{txt,json}
 #   scripts/gpu_evidence.sh sq [workloads...]           SQ / TCC counter passes -> gpurun_out/<TAG>_sq_<W>/summary.txt
 #   scripts/gpu_evidence.sh dispatch                    scripts/check_dispatch.py over scripts/dispatch_shapes.json (the automatic one-hot path against every
@@ -28,11 +28,11 @@ do_tests() { ( cd "$REPO" && time timeout 3000 python3 -m pytest tests -m gpu -q
 do_fuzz() { ( cd "$REPO" && timeout $(( ${1:-300} + 600 )) python3 tests/fuzz_gpu.py "${1:-300}" "${2:-77}" ) 2>&1 | tail -2 | tee "$OUT/fuzz.txt"; }
 do_bench() {
   cd "$REPO"
-  # exactly the driver's command: its stdout is the compact <= 4-KB line; the full object lands in bench_full.json beside bench.py
-  ( time python3 bench.py ) > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"
+  # the driver's command with --full: its stdout is the compact <= 4-KB line; the full object lands in bench_full.json beside bench.py
+  ( time python3 bench.py --full ) > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"
   cp "$REPO/bench_full.json" "$OUT/bench_default.json"
   wc -c "$OUT/bench_default_line.json"
-  for w in $ALL; do python3 bench.py --full-line --workload $w --no-configs --no-cpu-baseline --cold > "$OUT/bench_$w.json" 2>> "$OUT/bench.err"; done
+  for w in $ALL; do python3 bench.py --full --full-line --workload $w --no-configs --no-cpu-baseline --cold > "$OUT/bench_$w.json" 2>> "$OUT/bench.err"; done
   python3 - "$OUT" $ALL <<'PY' | tee "$OUT/bench_lines.txt"
 import json, sys
 out = sys.argv[1]
@@ -56,7 +56,7 @@ PY
 do_profile() {
   for w in "$@"; do
     P=$REPO/gpurun_out/${TAG}_$w; mkdir -p "$P"; cd /tmp
-    A="--full-line --workload $w --no-configs --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-sustained"
+    A="--full --full-line --workload $w --no-configs --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-sustained"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 "$REPO/bench.py" $A > "$P/bench_trace.json" 2> "$P/trace.err"
     timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$P/pmc_write" -- python3 "$REPO/bench.py" $A > "$P/bench_pmc_write.json" 2> "$P/pmc_write.err"
     timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$P/pmc_fetch" -- python3 "$REPO/bench.py" $A > "$P/bench_pmc_fetch.json" 2> "$P/pmc_fetch.err"
@@ -71,7 +71,7 @@ do_sq() {
     P=$REPO/gpurun_out/${TAG}_sq${COLD:+cold}_$w; mkdir -p "$P"; cd /tmp
     # COLD=1: the cold-input regime (bench.py --cold: thousands of dispatches cycling over > 512 MiB of distinct batches dominate every
     # average; the copy-mix yardstick runs the same way and is listed beside the kernel)
-    A="--workload $w --no-configs --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-sustained ${COLD:+--cold}"
+    A="--full --workload $w --no-configs --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-sustained ${COLD:+--cold}"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 "$REPO/bench.py" $A > /dev/null 2> "$P/trace.err"
     timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d "$P/sq1" -- python3 "$REPO/bench.py" $A > /dev/null 2> "$P/sq1.err"
     timeout 300 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM --output-format csv -d "$P/sq2" -- python3 "$REPO/bench.py" $A > /dev/null 2> "$P/sq2.err"

@@ -197,3 +197,58 @@ def test_driver_line_is_compact_and_round_trips(bench, tmp_path, monkeypatch, ca
     out = capsys.readouterr().out
     assert out.count("\n") == 1 and json.loads(out) == json.loads(bench.compact_line(full))
     assert json.load(open(tmp_path / "bench_full.json")) == full
+
+
+def test_dump_outputs_sample_and_digest(bench, tmp_path):
+    """--dump-outputs: float32 / float64 files only, a fixed seeded sample of whole sequences along the batch axis, and a per-sequence
+    digest that is the exact weighted sum over every value of the sequence (the same files from the same output, every time)."""
+    import torch
+    rng = np.random.default_rng(5)
+    for shape, axis, dt in (((7, 300, 5), 1, torch.float32), ((300, 9), 0, torch.int8), ((9, 300), 1, torch.int8)):
+        out = torch.from_numpy(rng.integers(-127 if dt == torch.int8 else 0, 128 if dt == torch.int8 else 2, size=shape)).to(dt)
+        got = bench.dump_outputs(out, axis, str(tmp_path / "a"))
+        s, d = np.load(tmp_path / "a" / "output_sample.npy"), np.load(tmp_path / "a" / "output_digest.npy")
+        assert s.dtype == np.float32 and d.dtype == np.float64 and got == {"output_sample": list(s.shape), "output_digest": [300]}
+        o = np.moveaxis(out.numpy().astype(np.int64), axis, 0)
+        w = np.random.default_rng(20250101)
+        w.choice(300, size=min(300, bench.DUMP_SAMPLE_BYTES // (4 * o[0].size)), replace=False)  # (the draw of the sample comes first)
+        w = w.integers(1, 1024, size=o.shape[1:])
+        assert d.tolist() == [float((o[b] * w).sum()) for b in range(300)]
+        bench.dump_outputs(out, axis, str(tmp_path / "b"))
+        for f in ("output_sample.npy", "output_digest.npy"):
+            assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    # a big output is sampled: whole sequences, at most DUMP_SAMPLE_BYTES of float32
+    big = torch.zeros((4, 1 << 16, 64), dtype=torch.int8)
+    big[:, :, 3] = torch.arange(1 << 16, dtype=torch.int64).remainder(100).to(torch.int8)
+    got = bench.dump_outputs(big, 1, str(tmp_path / "c"))
+    s = np.load(tmp_path / "c" / "output_sample.npy")
+    k = got["output_sample"][1]
+    assert s.shape == (4, k, 64) and 4 * s.size <= bench.DUMP_SAMPLE_BYTES < 4 * (s.size + 4 * 64) and k < (1 << 16)
+    assert len(set(s[0, :, 3].tolist())) > 90 and (s[:, :, :3] == 0).all()
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_k_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """A plain run (no --full): the contract's keys, exactly --steps timed steps, no check / side figures / bench_full.json, and
+    --dump-outputs writes the same files for the same arguments."""
+    import subprocess
+    import sys
+    lines = []
+    for d in ("d1", "d2"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "cfg1oh",
+               "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert not {"check", "configs", "cpu_baseline", "full"} & set(line)
+    assert not (tmp_path / "bench_full.json").exists()
+    s = np.load(tmp_path / "d1" / "output_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (256, 1000, 7)  # cfg1 one-hot (P, B, C): small enough to be dumped whole
+    for f in ("output_sample.npy", "output_digest.npy"):
+        assert (tmp_path / "d1" / f).read_bytes() == (tmp_path / "d2" / f).read_bytes()

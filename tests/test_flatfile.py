@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+import refrecord
+
 EXPECT = [b"MKVLAAGIVGLLLAQPSNA", b"", b"ACDEFGHIKLMNPQRSTVWYacdef", b"ACGTN", b"WWWW"]
 
 
@@ -103,13 +105,13 @@ def _random_fastx(rng):
 
 def test_native_fastx_reader_equals_the_compiled_reference(oracle, tmp_path):
     """Differential: bioseq_amd.FlatFile(fastx, out) / getstats against oracle/_ref = the reference's own fxstats.cpp
-    (kseq + zlib) on 400 random texts, plain and gzipped.  Skipped where the reference build is absent."""
+    (kseq + zlib) on 400 random texts, plain and gzipped.  Where the reference build is absent: against its results recorded in
+    tests/golden/ref_fastx_random.json.gz (tests/refrecord.py)."""
     import gzip
     import bioseq_amd
     from bioseq_amd.flatfile import FlatFile
-    ref = oracle.load_reference()
-    if ref is None or not hasattr(ref, "FlatFile"):
-        pytest.skip("oracle/_ref (the compiled reference) is not present")
+    ref = _reference(oracle)
+    rec = refrecord.Record("fastx_random")
     rng = np.random.default_rng(2026)
     nonempty = 0
     for case in range(400):
@@ -117,41 +119,57 @@ def test_native_fastx_reader_equals_the_compiled_reference(oracle, tmp_path):
         src = str(tmp_path / ("c%d.fx" % case)) + (".gz" if case % 5 == 0 else "")
         with (gzip.open if src.endswith(".gz") else open)(src, "wb") as f:
             f.write(text)
-        want_lens = ref.getstats([src])[0]
         got_lens = bioseq_amd.getstats([src])[0]
-        assert got_lens.dtype == np.uint64 and got_lens.tolist() == want_lens.tolist(), (case, text)
         a, b = str(tmp_path / "ref.ff"), str(tmp_path / "mine.ff")
-        ref.FlatFile(src, a)
         mine = FlatFile(src, b)
-        assert open(b, "rb").read() == open(a, "rb").read(), (case, text)
-        assert len(mine) == len(want_lens)
-        nonempty += len(want_lens) > 0
+        assert got_lens.dtype == np.uint64
+        if ref is not None:
+            want_lens = ref.getstats([src])[0]
+            assert got_lens.tolist() == want_lens.tolist(), (case, text)
+            ref.FlatFile(src, a)
+            assert open(b, "rb").read() == open(a, "rb").read(), (case, text)
+        # (recording: the reference's results, equal to these as just asserted)
+        rec.see([case, refrecord.digest(text)], [got_lens.tolist(), refrecord.digest(open(b, "rb").read())])
+        assert len(mine) == len(got_lens)
+        nonempty += len(got_lens) > 0
         os.remove(src)
+    rec.close()
     assert nonempty > 200
     with pytest.raises(RuntimeError, match="failed to open"):
         FlatFile(str(tmp_path / "does_not_exist.fa"), str(tmp_path / "o.ff"))
 
 
+def _reference(oracle):
+    """the compiled reference (oracle/_ref) with its FASTX reader, or None; recording its results needs it"""
+    ref = oracle.load_reference()
+    if ref is not None and not hasattr(ref, "FlatFile"):
+        ref = None
+    assert ref is not None or not refrecord.recording(), "BSQ_RECORD_REF=1 needs oracle/_ref"
+    return ref
+
+
 def test_native_fastx_reader_long_lines_and_truncated_gzip(oracle, tmp_path):
     """Differential against the compiled reference on what a streaming parser of untrusted text gets wrong first: lines around the
     reader's buffer sizes (16 383 / 16 384 / 16 385 / 131 072 bytes, FASTA and FASTQ, with and without a final newline) and gzip
-    streams cut off at every kind of place.  Runs under ASan / UBSan in scripts/asan_host.sh."""
+    streams cut off at every kind of place.  Runs under ASan / UBSan in scripts/asan_host.sh.  Where the
+    reference build is absent: against its results recorded in tests/golden/ref_fastx_long_lines.json.gz."""
     import gzip
     import bioseq_amd
     from bioseq_amd.flatfile import FlatFile
-    ref = oracle.load_reference()
-    if ref is None or not hasattr(ref, "FlatFile"):
-        pytest.skip("oracle/_ref (the compiled reference) is not present")
+    ref = _reference(oracle)
+    rec = refrecord.Record("fastx_long_lines")
     rng = np.random.default_rng(16384)
 
-    def same(src, tag):
-        want = ref.getstats([src])[0]
+    def same(src, tag, text):
         got = bioseq_amd.getstats([src])[0]
-        assert got.tolist() == want.tolist(), tag
         a, b = str(tmp_path / "ref.ff"), str(tmp_path / "mine.ff")
-        ref.FlatFile(src, a)
         FlatFile(src, b)
-        assert open(b, "rb").read() == open(a, "rb").read(), tag
+        if ref is not None:
+            want = ref.getstats([src])[0]
+            assert got.tolist() == want.tolist(), tag
+            ref.FlatFile(src, a)
+            assert open(b, "rb").read() == open(a, "rb").read(), tag
+        rec.see(list(tag) + [refrecord.digest(text)], [got.tolist(), refrecord.digest(open(b, "rb").read())])
 
     texts = []
     for n in (16383, 16384, 16385, 32767, 32768, 131072):
@@ -165,28 +183,33 @@ def test_native_fastx_reader_long_lines_and_truncated_gzip(oracle, tmp_path):
         src = str(tmp_path / ("l%d.fx" % i))
         with open(src, "wb") as f:
             f.write(text)
-        same(src, ("plain", i))
+        same(src, ("plain", i), text)
         if i % 3 == 0:
             with gzip.open(src + ".gz", "wb", compresslevel=1) as f:
                 f.write(text)
-            same(src + ".gz", ("gz", i))
+            same(src + ".gz", ("gz", i), text)
             os.remove(src + ".gz")
         os.remove(src)
     # truncated gzip members: both readers see the same prefix of records (or both fail)
     text = b"".join(b">r%d\n" % k + bytes(rng.choice(list(b"ACGT"), size=int(rng.integers(1, 300))).astype(np.uint8)) + b"\n" for k in range(400))
-    whole = gzip.compress(text, compresslevel=6)
+    whole = gzip.compress(text, compresslevel=6, mtime=0)
     for j, cut in enumerate([1, 9, 10, 11, 18, 64, len(whole) // 3, len(whole) // 2, len(whole) - 9, len(whole) - 8, len(whole) - 1]):
         src = str(tmp_path / ("t%d.fa.gz" % j))
         with open(src, "wb") as f:
             f.write(whole[:cut])
         try:
-            want = ref.getstats([src])[0].tolist()
+            got = bioseq_amd.getstats([src])[0].tolist()
         except RuntimeError:
-            with pytest.raises(RuntimeError):
-                bioseq_amd.getstats([src])
-            continue
-        assert bioseq_amd.getstats([src])[0].tolist() == want, ("truncated", cut)
+            got = "RuntimeError"
+        if ref is not None:
+            try:
+                want = ref.getstats([src])[0].tolist()
+            except RuntimeError:
+                want = "RuntimeError"
+            assert got == want, ("truncated", cut)
+        rec.see(["truncated", cut, refrecord.digest(whole[:cut])], got)  # both readers: the same prefix of records, or both fail
         os.remove(src)
+    rec.close()
 
 
 def test_native_fastx_reader_streams_a_large_fastq(tmp_path):

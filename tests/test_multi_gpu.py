@@ -1,6 +1,6 @@
 """The N > 1 path on the GPU box.
 
-* `bench.py --gpus 2` exactly as the driver's SCALE run calls it -- self-launching, strong and weak scaling, every whole-batch
+* `bench.py --gpus 2 --full` -- the driver's SCALE run with its check -- self-launching, strong and weak scaling, every whole-batch
   assembly timed AND compared by content with the single-rank encode -- with two ranks SHARING this box's GPU over gloo
   (BSQ_BENCH_BACKEND / BSQ_BENCH_SHARE_GPU: a code-path test, never a measurement).
 * With two or more devices visible (an 8-GPU GPUTEST box; skipped on today's 1-GPU boxes): the same two commands over nccl = RCCL,
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(extra_env, *args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full-line"] + list(args)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--full-line"] + list(args)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

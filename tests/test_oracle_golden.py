@@ -2,7 +2,7 @@
 
 Pins the checker itself: README known-answer vector, LUTs / ids of all 20 keys x 8 flag combos,
 raw arrays and sha256 digests produced by the reference's own C++ (tests/golden/make_golden.py),
-and -- when oracle/_ref is present (build container) -- a live differential run.
+and a differential run: live when oracle/_ref is present (build container), else against its recorded results.
 """
 import hashlib
 import itertools
@@ -10,6 +10,7 @@ import itertools
 import numpy as np
 import pytest
 
+import refrecord
 from bioseq_amd import synth
 
 COMBOS = list(itertools.product([0, 1], repeat=3))
@@ -130,10 +131,11 @@ def test_dtype_dispatch_and_errors(oracle):
 
 
 def test_live_differential_vs_compiled_reference(oracle):
-    """Build container only: oracle vs the reference's own C++ (oracle/_ref) on random ragged batches."""
+    """Oracle vs the reference's own C++ (oracle/_ref) on random ragged batches; where the reference build is absent, vs its
+    results recorded in tests/golden/ref_oracle_differential.json.gz (tests/refrecord.py)."""
     ref = oracle.load_reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (build container only)")
+    assert ref is not None or not refrecord.recording(), "BSQ_RECORD_REF=1 needs oracle/_ref"
+    rec = refrecord.Record("oracle_differential")
     rng = np.random.default_rng(7)
     for trial in range(6):
         n, hi = int(rng.integers(1, 120)), int(rng.integers(0, 90))
@@ -141,14 +143,23 @@ def test_live_differential_vs_compiled_reference(oracle):
         seqs = synth.unpack(chars, offs)
         P = hi + 2
         mask = [(rng.random(len(s)) < 0.5).astype(np.uint8) if i % 3 else None for i, s in enumerate(seqs)]
+        inputs = refrecord.digest(chars, offs, *[m for m in mask if m is not None])
         for key in ("AMINO20", "SEB8", "DNA5", "KETO", "LIA10", "BYTES"):
             for eos, bos, pad in COMBOS:
-                r, o = ref.Tokenizer(key, eos, bos, pad), oracle.OracleTokenizer(key, eos, bos, pad)
+                r, o = (ref.Tokenizer(key, eos, bos, pad) if ref is not None else None), oracle.OracleTokenizer(key, eos, bos, pad)
                 for d in "bhiqfd":
+                    outs = []
                     for bf in (False, True):
-                        a = r.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf)
                         b = o.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf)
-                        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
-                    a = r.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask)
+                        if r is not None:
+                            a = r.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf)
+                            assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+                        outs.append(a if r is not None else b)
                     b = o.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask)
-                    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+                    if r is not None:
+                        a = r.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask)
+                        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+                    outs.append(a if r is not None else b)
+                    # the reference's outputs where it is present (recording), else the oracle's: the same digest either way
+                    rec.see([trial, inputs, key, eos, bos, pad, d], refrecord.digest(*outs))
+    rec.close()

@@ -38,21 +38,45 @@ def test_onehot_token_relationship_and_padding(oracle, seqs, key, eos, bos, pad,
         assert hot[bos + L + eos:, i].all() == bool(pad) or tail.size == 0
 
 
-@settings(max_examples=40, deadline=None, suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
-@given(seqs=batches, key=st.sampled_from(KEYS + ["BYTES"]), eos=st.booleans(), bos=st.booleans(), pad=st.booleans(),
-       d=st.sampled_from("bhiqfd"), data=st.data())
-def test_oracle_matches_compiled_reference(oracle, seqs, key, eos, bos, pad, d, data):
+def test_oracle_matches_compiled_reference(oracle):
+    """The oracle against the reference's own C++ (oracle/_ref) on 40 generated batches; where the reference build is absent, on the
+    batches recorded with the reference's results in tests/golden/ref_oracle_properties.json.gz (tests/refrecord.py)."""
+    import refrecord
     ref = oracle.load_reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (build container only)")
-    r, o = ref.Tokenizer(key, eos, bos, pad), oracle.OracleTokenizer(key, eos, bos, pad)
-    P = max([len(s) for s in seqs] + [0]) + eos + bos + data.draw(st.integers(0, 3))
-    if P <= 0:
-        P = 1
-    mask = [np.array(data.draw(st.lists(st.integers(0, 1), min_size=len(s), max_size=len(s))), dtype=np.uint8)
-            if data.draw(st.booleans()) else None for s in seqs]
-    for bf in (False, True):
-        a, b = r.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf), o.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf)
-        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-    a, b = r.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask), o.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask)
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    assert ref is not None or not refrecord.recording(), "BSQ_RECORD_REF=1 needs oracle/_ref"
+    recorded = []
+
+    def outputs(tk, seqs, P, d, mask):
+        return [tk.batch_tokenize(seqs, padlen=P, destchar=d, batch_first=bf) for bf in (False, True)] + \
+               [tk.batch_onehot_encode(seqs, padlen=P, destchar=d, mask=mask)]
+
+    if ref is not None:
+        @settings(max_examples=40, deadline=None, suppress_health_check=[HealthCheck.too_slow])
+        @given(seqs=batches, key=st.sampled_from(KEYS + ["BYTES"]), eos=st.booleans(), bos=st.booleans(), pad=st.booleans(),
+               d=st.sampled_from("bhiqfd"), data=st.data())
+        def live(seqs, key, eos, bos, pad, d, data):
+            r, o = ref.Tokenizer(key, eos, bos, pad), oracle.OracleTokenizer(key, eos, bos, pad)
+            P = max([len(s) for s in seqs] + [0]) + eos + bos + data.draw(st.integers(0, 3))
+            if P <= 0:
+                P = 1
+            mask = [np.array(data.draw(st.lists(st.integers(0, 1), min_size=len(s), max_size=len(s))), dtype=np.uint8)
+                    if data.draw(st.booleans()) else None for s in seqs]
+            want, got = outputs(r, seqs, P, d, mask), outputs(o, seqs, P, d, mask)
+            for a, b in zip(want, got):
+                assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+            recorded.append([[seqs, key, eos, bos, pad, d, P, [None if m is None else m.tolist() for m in mask]],
+                             refrecord.digest(*want)])
+        live()
+    if refrecord.recording():
+        rec = refrecord.Record("oracle_properties")
+        for inp, dg in recorded:
+            rec.see(inp, dg)
+        rec.close()
+        return
+    # the recorded batches (where the reference is present too: the record must still hold)
+    rec = refrecord.Record("oracle_properties")
+    for inp, _ in list(rec.items):
+        seqs, key, eos, bos, pad, d, P, mask = inp
+        mask = [None if m is None else np.array(m, dtype=np.uint8) for m in mask]
+        rec.see(inp, refrecord.digest(*outputs(oracle.OracleTokenizer(key, eos, bos, pad), seqs, P, d, mask)))
+    rec.close()
