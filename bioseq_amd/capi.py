@@ -25,6 +25,12 @@ class Desc(ctypes.Structure):
                 ("bos", ctypes.c_int32), ("padchar", ctypes.c_int32)]
 
 
+class Mlm(ctypes.Structure):
+    """struct bsq_mlm"""
+    _fields_ = [("frac", ctypes.c_double), ("mask_prob", ctypes.c_double), ("random_prob", ctypes.c_double), ("mask_token", ctypes.c_int64),
+                ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -98,6 +104,9 @@ def load():
         "bsq_decode_sizes_device": (i32, [dp, vp, i32, i64, i64, i64, i64, vp, i64p, i64p, vp]),
         "bsq_decode_write_device": (i32, [dp, vp, i32, i64, i64, i64, i64, vp, vp, vp]),
         "bsq_argmax_tokens_device": (i32, [vp, i32, i64, i32, i64, vp, i32, vp]),
+        "bsq_mlm_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Mlm), c_int, vp, c_int, vp, vp]),
+        "bsq_random_mask_device": (i32, [dp, vp, vp, i64, ctypes.POINTER(Mlm), vp, vp]),
+        "bsq_random_mask_host": (i32, [dp, vp, vp, i64, ctypes.POINTER(Mlm), vp]),
         "bsq_gather_packed_device": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
         "bsq_blosum62_normrows": (i32, [vp]),
         "bsq_augment_device": (i32, [vp, vp, i64, i32, ctypes.c_double, ctypes.c_uint64, vp]),

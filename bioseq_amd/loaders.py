@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import blosum
+from . import blosum, masking
 from .flatfile import FlatFile
 
 
@@ -41,9 +41,17 @@ class FlatFileDataset(torch.utils.data.Dataset):
     `augment` BLOSUM62 point mutations are applied to a sequence with probability `augment_frac`
     (>= 1: always) before encoding.  `get_batch(start, stop)` / `__getitems__(indices)` return the
     stacked batch -- (B, P) int64 or (B, C, P) float32 on `device` -- from a single encode.
+
+    masked=True (keyword; off by default): batches are masked-LM pairs drawn on the device at rate `maskfrac` --
+    (inputs, labels) of BERT's 80/10/10 replacement (masking.mlm_tokenize_packed; labels int64 with ignore_index -100,
+    mask token = tokenizer.alphabet_size()) for token rows, (masked one-hot (B, C, P) float32, labels) for cnn=True
+    (masking.onehot_masked_packed).  The masks come from `seed` and the call: every get_batch / __getitems__ call and
+    every `batches()` epoch draws with the next key of the dataset's own counter (a rebuilt dataset repeats them), and
+    inside an epoch a row is keyed by its index in the epoch's order -- `group` and `prefetch` hand out the same masks.
+    With `augment` the mutations come first, on the batch's own copy.
     """
 
-    def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0):
+    def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -65,6 +73,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
         # `batches()`: how many batches are encoded ahead of the consumer on the two side streams (0: in order on the current stream)
         self.prefetch = int(prefetch)
         self._side = None
+        self.masked = bool(masked)
+        self._mask_calls = 0
 
     def __len__(self):
         return self.ff.nseqs()
@@ -79,6 +89,22 @@ class FlatFileDataset(torch.utils.data.Dataset):
         else:  # arbitrary index set (a shuffling sampler): rebuilt on the device from the resident store, no host gather
             chars, offs = self.ff.gather_device(indices, self.device, validate=not trusted, distinct=trusted)
         return chars, offs
+
+    def _mask_key(self):
+        """Seed of the next masked call: the dataset's seed and its own counter of masked calls."""
+        self._mask_calls += 1
+        return (self._seed * 0x9E3779B97F4A7C15 + self._mask_calls) & (2 ** 64 - 1)
+
+    def _encode_masked(self, chars, offs, mask_seed, first_row):
+        trusted = self._trusted_lengths
+        if self.augment:
+            self._calls += 1
+            blosum.augment_packed(chars, offs, self.augment, self.augment_frac, self._seed + self._calls)
+        if self.cnn:
+            return masking.onehot_masked_packed(self.tokenizer, chars, offs, self.max_seq_len, "f", "bcl", frac=self.maskfrac, seed=mask_seed,
+                                                first_row=first_row, validate=not trusted)
+        return masking.mlm_tokenize_packed(self.tokenizer, chars, offs, self.max_seq_len, self.token_dtype, True, frac=self.maskfrac,
+                                           seed=mask_seed, first_row=first_row, validate=not trusted)
 
     def _encode(self, chars, offs):
         """augment_seq, then encode (bioseq/loaders.py:83-84, :102-103) on the batch's own copy.  Token rows go through the
@@ -102,6 +128,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
 
     def get_batch(self, start, stop):
         """Sequences [start, stop) as one encoded batch on the device."""
+        if self.masked:
+            return self._encode_masked(*self._packed_device(start, stop), self._mask_key(), 0)
         return self._encode(*self._packed_device(start, stop))
 
     def _index(self, i):
@@ -119,17 +147,22 @@ class FlatFileDataset(torch.utils.data.Dataset):
         re-stack it with a copy, and device tensors cannot cross worker processes).  A list of host integers costs one
         upload of 8 bytes per index; an int64 tensor on the device (see `batches`) costs none."""
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
-            return self._encode(*self._packed_device(0, 0, indices))
-        idx = [self._index(i) for i in indices]
-        if idx and idx == list(range(idx[0], idx[0] + len(idx))):
-            return self.get_batch(idx[0], idx[-1] + 1)
-        return self._encode(*self._packed_device(0, 0, idx))
+            packed = self._packed_device(0, 0, indices)
+        else:
+            idx = [self._index(i) for i in indices]
+            if idx and idx == list(range(idx[0], idx[0] + len(idx))):
+                return self.get_batch(idx[0], idx[-1] + 1)
+            packed = self._packed_device(0, 0, idx)
+        if self.masked:
+            return self._encode_masked(*packed, self._mask_key(), 0)
+        return self._encode(*packed)
 
     def batches(self, batch_size, shuffle=True, drop_last=False, generator=None, prefetch=None, group=1):
         """One epoch of encoded batches with the sampler ON THE DEVICE: a `torch.randperm` drawn on `self.device` (or the
         identity), cut into index tensors that never leave HBM.  Nothing is copied host -> device per batch: the store is
         resident (FlatFile.to_device), the indices are device tensors, the batch is gathered, augmented and encoded there.
-        Yields (B, P) int64 tokens or (B, C, P) float32 one-hots, like `__getitems__`.
+        Yields (B, P) int64 tokens or (B, C, P) float32 one-hots, like `__getitems__` (masked=True: the (inputs, labels) pairs, one
+        mask key per epoch, rows keyed by their index in the epoch's order).
 
         Consecutive batches are independent, and this loop is the one place that knows it (round 6):
 
@@ -149,7 +182,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
         n = len(self)
         order = (torch.randperm(n, device=self.device, generator=generator) if shuffle
                  else torch.arange(n, device=self.device))
-        fused = bool(self.augment) and not self.cnn and str(self.token_dtype)[:1].lower() == "b"  # int8 rows take the one-launch entry, whose in-kernel wait can (in theory) expire
+        fused = bool(self.augment) and not self.cnn and not self.masked and str(self.token_dtype)[:1].lower() == "b"  # int8 rows take the one-launch entry, whose in-kernel wait can (in theory) expire
         depth = int(self.prefetch if prefetch is None else prefetch)
         batch_size = int(batch_size)
         if batch_size <= 0:
@@ -157,18 +190,24 @@ class FlatFileDataset(torch.utils.data.Dataset):
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
+        mask_seed = self._mask_key() if self.masked else None
 
         def encode(first):
             stop = min(n_eff, first + span)
-            if shuffle:
-                return self._encode(*self._packed_device(0, 0, order[first:stop], trusted=True))
-            return self.get_batch(first, stop)
+            packed = self._packed_device(0, 0, order[first:stop], trusted=True) if shuffle else self._packed_device(first, stop)
+            if self.masked:
+                return self._encode_masked(*packed, mask_seed, first)
+            return self._encode(*packed)
 
         def hand_out(big):
-            if big.shape[0] <= batch_size:
+            rows = big[0].shape[0] if self.masked else big.shape[0]
+            if rows <= batch_size:
                 yield big
+            elif self.masked:
+                for r in range(0, rows, batch_size):
+                    yield big[0][r:r + batch_size], big[1][r:r + batch_size]
             else:
-                for r in range(0, big.shape[0], batch_size):
+                for r in range(0, rows, batch_size):
                     yield big[r:r + batch_size]
 
         try:
@@ -215,7 +254,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
                     issue()  # the next one goes out BEFORE this one is handed over: it runs under whatever the consumer does with it
                     now = torch.cuda.current_stream()
                     now.wait_event(ready)
-                    big.record_stream(now)
+                    for t in (big if self.masked else (big,)):
+                        t.record_stream(now)
                     if fused:
                         blosum.check_fused()
                     yield from hand_out(big)
@@ -228,6 +268,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
             s, e, st = index.indices(len(self))
             return self.__getitems__(list(range(s, e, st)))
         index = self._index(index)
+        if self.masked:
+            inputs, labels = self.get_batch(index, index + 1)
+            return inputs[0], labels[0]
         return self.get_batch(index, index + 1)[0]
 
     def fetch(self, index, return_items=False):

@@ -30,7 +30,9 @@
 extern "C" {
 #endif
 
-#define BSQ_ABI_VERSION 7 /* 7 (round 6): bsq_tokenize_device_multi, bsq_augment_device_multi, bsq_augment_tokenize_device_multi, bsq_enable_peer_access, bsq_tokenize_kernel_name; nothing removed */
+#define BSQ_ABI_VERSION 7 /* 7 (round 6): bsq_tokenize_device_multi, bsq_augment_device_multi, bsq_augment_tokenize_device_multi, bsq_enable_peer_access, bsq_tokenize_kernel_name; nothing removed.
+                           * Added since, without a version bump (nothing changed or removed): bsq_mlm, bsq_mlm_tokenize_device,
+                           * bsq_random_mask_device, bsq_random_mask_host */
 
 typedef int32_t bsq_status;
 enum {
@@ -246,6 +248,50 @@ bsq_status bsq_augment_device_multi(int32_t n, const bsq_batch *batches, int32_t
                                     void *hip_stream);
 bsq_status bsq_augment_tokenize_device_multi(const bsq_desc *d, int32_t n, const bsq_batch *batches, int64_t P, int32_t batch_first,
                                              bsq_dtype t, int32_t chain_len, double frac, const uint64_t *seeds, void *hip_stream);
+
+/* ---- masked-LM batches on the device: the objective training/cnnpretrain.py:119-124 of the reference reaches for (a random
+ * keep-mask, then the masked one-hot), plus the token form of BERT's 80/10/10 replacement with a label matrix for a
+ * cross-entropy with `ignore_index`.
+ *
+ * THE DRAW.  A character's fate depends on (seed, row, j) only: row = first_row + i for sequence i of the batch, j = its index
+ * inside the sequence (before any BOS shift) -- never on padlen, layout, element type, BOS / EOS / PAD, batch size, how the batch
+ * is cut into pieces or shards, or the stream.  With mix64 the splitmix64 finalizer and T_x = floor(p_x * 65536 + 0.5):
+ *     h_row = mix64((seed ^ 0x4D4C4D5F4D41534B) + 0x9E3779B97F4A7C15 * (row + 1))
+ *     w     = mix64(h_row + 0xD1342543DE82EF95 * ((j >> 2) + 1))          one selection word per 4 characters
+ *     sel16 = (w >> (16 * (j & 3))) & 0xFFFF
+ *     selected  <=>  sel16 < T_frac  and  lut[c] >= 0                       (unmapped characters are never selected)
+ *     v     = mix64(~h_row + 0xD1342543DE82EF95 * (j + 1))                  (selected characters only)
+ *     cat16 = v & 0xFFFF, rnd16 = (v >> 16) & 0xFFFF
+ *     input = mask_token                 if cat16 < T_mask
+ *             (rnd16 * nchars) >> 16     if cat16 < T_mask + T_random     (a uniform alphabet id)
+ *             the plain token            otherwise
+ * frac = 1 selects every mapped character.  BOS / EOS / PAD positions are never selected.  Labels: the plain token at selected
+ * positions, ignore_index everywhere else.  Values are converted to the element types as bsq_tokenize_device converts tokens
+ * (ignore_index = -100 as BSQ_U64 is the int64 -100 of torch).
+ * Argument errors (BSQ_ERR_INVALID_ARG, nothing launched): a probability outside [0, 1], mask_prob + random_prob > 1,
+ * first_row < 0, both outputs null. */
+typedef struct bsq_mlm {
+    double frac;          /* share of the (mapped) characters that are selected */
+    double mask_prob;     /* of the selected: replaced by mask_token (BERT: 0.8) */
+    double random_prob;   /* of the selected: replaced by a uniform alphabet id (BERT: 0.1); the rest keep their token */
+    int64_t mask_token;   /* usually bsq_alphabet_size(d): one past the last id */
+    int64_t ignore_index; /* label of every position that is not selected (torch: -100) */
+    uint64_t seed;
+    int64_t first_row;    /* row key of the batch's first sequence (a shard or a piece of a larger batch: its first row there) */
+} bsq_mlm;
+/* Masked inputs and / or labels of a packed batch in ONE launch: (B, P) when batch_first else (P, B), each C-contiguous, with
+ * bsq_tokenize_device's positions (BOS / EOS / PAD, over-long sequences clamped).  Either output may be NULL, not both. */
+bsq_status bsq_mlm_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                   int32_t batch_first, const bsq_mlm *m, bsq_dtype in_dtype, void *inputs_or_null,
+                                   bsq_dtype label_dtype, void *labels_or_null, void *hip_stream);
+/* The selection alone, one byte per character in the packed layout of chars: mask_out[offsets[i] + j] = 0 if character j of
+ * sequence i is selected, else 1 -- the `mask_or_null` convention of bsq_onehot_device / bsq_onehot_bcl_device (a masked
+ * character gets the all-zero one-hot row).  Bytes outside [offsets[0], offsets[B]) are not written.  (mask_prob, random_prob and
+ * mask_token play no part; they are checked all the same.)  bsq_random_mask_host: the same on host buffers (CPU, the same code). */
+bsq_status bsq_random_mask_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_mlm *m,
+                                  uint8_t *mask_out, void *hip_stream);
+bsq_status bsq_random_mask_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_mlm *m,
+                                uint8_t *mask_out);
 
 /* ---- index-list batches from a packed store resident in HBM: replaces the per-item fetch of FlatFileDataset.__getitem__
  * (bioseq/loaders.py:76-104: ff.access(i) on the host for every sample) under a shuffling sampler.  Rebuilds the packed
