@@ -36,6 +36,12 @@ class Batch(ctypes.Structure):
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+class OnehotBatch(ctypes.Structure):
+    """struct bsq_onehot_batch: one packed batch of a multi-batch one-hot call (device pointers; mask may be null)"""
+    _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("B", ctypes.c_int64),
+                ("out", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -91,6 +97,8 @@ def load():
         "bsq_onehot_block_device": (i32, [dp, vp, vp, vp, i64, i64, c_int, vp, i64, vp]),
         "bsq_tokenize_block_device": (i32, [dp, vp, vp, i64, i64, c_int, vp, i64, vp]),
         "bsq_onehot_kernel_name": (ctypes.c_char_p, [dp, i64, i64, c_int]),
+        "bsq_onehot_device_multi": (i32, [dp, i32, ctypes.POINTER(OnehotBatch), i64, i32, c_int, vp]),
+        "bsq_onehot_multi_plan": (i32, [dp, i32, ctypes.POINTER(OnehotBatch), i64, i32, c_int, ctypes.POINTER(i32)]),
         "bsq_tokenize_kernel_name": (ctypes.c_char_p, [dp, i64, i64, i32, c_int, i32]),
         "bsq_tokenize_device_generic": (i32, [dp, vp, vp, i64, i64, i32, c_int, vp, vp]),
         "bsq_onehot_device_generic": (i32, [dp, vp, vp, vp, i64, i64, c_int, vp, vp]),

@@ -125,6 +125,15 @@ bsq_status launch_tokens_multi(const bsq_desc *d, int32_t n, const bsq_batch *ba
 // below its two-pass threshold and for masked batches)
 bsq_status launch_onehot_bcl_chunks(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, const uint8_t *mask_or_null, int64_t B,
                                     int64_t P, bsq_dtype t, void *out, hipStream_t s);
+// bsq_tokens.hip: bsq_onehot_device_multi's family 3 -- whether a batch's channels-first one-hot runs k_tokenize_chunks<HOT> in its plain form, and
+// n (1 ... 8) such batches in one launch
+bool onehot_bcl_chunks_fusable(int64_t B, int64_t P, int32_t C, bsq_dtype t, const void *out);
+bsq_status launch_onehot_bcl_chunks_multi(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, bsq_dtype t, hipStream_t s);
+// bsq_tokens8.hip: bsq_onehot_device_multi's family 2 -- the one-piece raw-id passes of n (1 ... 8) batches in one launch (ws[i]: batch i's
+// (P, B rounded up to 256) scratch region, 64-byte aligned), and the paired-tail flag of such a pass, which the batches of a launch share
+bool tokens_pb8_raw_paired(int64_t B, int64_t P);
+bsq_status launch_tokens_pb8_raw_multi(const bsq_desc *d, int32_t n, const uint8_t *const *chars, const int64_t *const *offsets, const int64_t *Bs,
+                                       int64_t P, uint8_t *const *ws, bool nib, hipStream_t s);
 // bsq_generic.hip: the element kernels as blocks of a wider destination (row_seqs sequences per position row; = B: the whole tensor / matrix)
 bsq_status onehot_generic_block(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, const uint8_t *mask_or_null, int64_t B,
                                 int64_t P, bsq_dtype t, void *out, int64_t row_seqs, void *hip_stream);

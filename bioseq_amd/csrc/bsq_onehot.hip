@@ -246,6 +246,91 @@ __device__ __forceinline__ ChunkCoord chunk_coord(const EParams &p, int64_t k, i
 // the scratch of alphabets with at most 15 classes at half its bytes (see two_pass_nibbles).  A template flag: as a runtime one its
 // shift / mask arithmetic cost the BYTE form 13 % on cfg4 f32 (670 -> 759 us).
 template <typename ST, bool NT, int MATH, bool GATE = false, bool NIB = false>
+__device__ __forceinline__ void expand_chunks_body(const uint32_t blk, const EParams &p) {
+    constexpr int PIECE = kChunk;             // bytes per wave
+    constexpr int NS = PIECE / 1024;          // 16-byte stores per lane
+    __shared__ __align__(16) uint8_t s_img[4][PIECE];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint8_t *img = s_img[wave];
+#pragma unroll
+    for (int u = 0; u < NS; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
+
+    // chunk of this wave: class = blockIdx % 8 (pinned to the XCD the block lands on).  The wave index goes through
+    // readfirstlane so that the chunk arithmetic below is scalar-ALU work.
+    const int wave_s = MATH == 1 ? __builtin_amdgcn_readfirstlane(wave) : wave;
+    int64_t group = static_cast<int64_t>(blk >> 3);
+    int32_t cls = static_cast<int32_t>(blk & 7u);
+    const int64_t slot = group * 4 + wave_s;
+    const int64_t k = static_cast<int64_t>(cls) + 8 * slot;
+    if (k >= p.nchunks) return;
+    uint32_t gate = 0;
+    if constexpr (GATE) gate = __hip_atomic_load(reinterpret_cast<const uint32_t *>(p.tok) + (blk & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
+    const ST one = static_cast<ST>(p.one_bits);
+    const ChunkCoord cc = chunk_coord<MATH>(p, k, rowbytes);
+    if (!cc.live) return;
+    const int64_t lo = cc.lo, b_lo = cc.b_lo, t_lo = cc.t_lo;
+    const int32_t len = cc.len, skip = cc.skip, nr = cc.nr;
+    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
+    const uint8_t *tok = NIB ? p.tok + ((t_lo * p.Bp + b_lo) >> 1) : p.tok + t_lo * p.Bp + b_lo;
+    const int32_t par0 = NIB ? static_cast<int32_t>(b_lo & 1) : 0;
+    if constexpr (GATE) tok += (gate == 0xFEFEFEFDu && p.nchunks < 0) ? 1 : 0;  // never taken: the token loads wait for the gate load
+    constexpr uint32_t nmask = NIB ? 0xFu : kNone;  // "no one"
+    const int64_t wrap_at = p.B - b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
+    // scatter: row r_lo + i has its one at image byte i*rowbytes - skip + tok*sizeof(ST).
+    // NS (1..4) coalesced token loads in flight per step, straight-line per NS: the number of 64-row slots a
+    // step needs and the (rare) row-wrap case are wave-uniform, so they are scalar branches.
+    const int32_t nr_s = __builtin_amdgcn_readfirstlane(nr);
+    const bool wraps = wrap_at < nr_s;  // the piece runs over the end of position t_lo's rows
+    auto step = [&](auto ns_tag, int32_t i0) {
+        constexpr int NS = decltype(ns_tag)::value;
+        uint32_t tk[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int32_t i = i0 + 64 * q + lane;
+            int64_t a = i;
+            if (wraps && i >= wrap_at) {
+                const int64_t w = (i - wrap_at) / p.B + 1;
+                a = i + w * (p.Bp - p.B);
+            }
+            if constexpr (NIB) {
+                const int64_t ia = a + par0;
+                tk[q] = i < nr_s ? (static_cast<uint32_t>(tok[ia >> 1]) >> ((static_cast<uint32_t>(ia) & 1u) << 2)) & 0xFu : nmask;
+            } else {
+                tk[q] = i < nr_s ? static_cast<uint32_t>(tok[a]) : kNone;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int32_t i = i0 + 64 * q + lane;
+            const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk[q]) * static_cast<int32_t>(sizeof(ST));
+            if (tk[q] != nmask && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
+        }
+    };
+    for (int32_t i0 = 0; i0 < nr_s; i0 += 256) {
+        const int32_t left = p.force4 ? 256 : nr_s - i0;
+        if (left > 192) step(std::integral_constant<int, 4>{}, i0);
+        else if (left > 128) step(std::integral_constant<int, 3>{}, i0);
+        else if (left > 64) step(std::integral_constant<int, 2>{}, i0);
+        else step(std::integral_constant<int, 1>{}, i0);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint8_t *g = p.out + lo + t_lo * p.row_gap;
+    if (len == PIECE && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        uint4 v[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) v[u] = *reinterpret_cast<const uint4 *>(img + u * 1024 + lane * 16);
+#pragma unroll
+        for (int u = 0; u < NS; ++u) store16<NT>(g + u * 1024 + lane * 16, v[u]);
+    } else {  // clipped first / last piece of the tensor
+        for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
+            *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
+    }
+}
+// (Twin: expand_chunks_body above, the same statements for k_expand_chunks_multi.  The one-batch kernel keeps its own text: as a call of that
+//  function it compiled to different code, and cfg3 ran 0.5 % slower.  A change here belongs in both.)
+template <typename ST, bool NT, int MATH, bool GATE = false, bool NIB = false>
 __global__ __launch_bounds__(kThreads) void k_expand_chunks(const EParams p) {
     constexpr int PIECE = kChunk;             // bytes per wave
     constexpr int NS = PIECE / 1024;          // 16-byte stores per lane
@@ -341,6 +426,135 @@ __global__ __launch_bounds__(kThreads) void k_expand_chunks(const EParams p) {
 // over the end of a position row of a padded id matrix (Bp != B) take the byte loop at the end -- a few hundred chunks of a million.
 // NIB (end of round 5): the id matrix holds nibbles as in k_expand_chunks<..., NIB> -- a lane's <= 6 ids and the parity of its first one
 // are one unaligned 4-byte window.
+template <bool NT, int NR, bool NIB = false>
+__device__ __forceinline__ void expand_rows1_body(const uint32_t blk, const EParams &p) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const int64_t slot = static_cast<int64_t>(blk >> 3) * 4 + wave_s;
+    const int64_t k = static_cast<int64_t>(blk & 7u) + 8 * slot;
+    if (k >= p.nchunks) return;
+    const int32_t rb = p.C;  // bytes per row (one-byte elements)
+    const ChunkCoord cc = chunk_coord<0>(p, k, rb);
+    if (!cc.live) return;
+    const int32_t len = cc.len, skip = cc.skip;
+    const int32_t nr_s = __builtin_amdgcn_readfirstlane(cc.nr);
+    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
+    const uint8_t *tok = NIB ? p.tok + ((cc.t_lo * p.Bp + cc.b_lo) >> 1) : p.tok + cc.t_lo * p.Bp + cc.b_lo;
+    const uint32_t par0 = NIB ? static_cast<uint32_t>(cc.b_lo & 1) : 0u;
+    constexpr uint32_t kNo = NIB ? 0xFu : kNone;  // "no one"
+    const int64_t wrap_at = p.B - cc.b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
+    const bool wraps = p.Bp != p.B && wrap_at < nr_s;  // (wave-uniform) the chunk runs over the end of a position row of a PADDED id matrix
+    uint8_t *g = p.out + cc.lo + cc.t_lo * p.row_gap;
+    const uint32_t one = static_cast<uint32_t>(p.one_bits) & 0xFFu;
+    // the id of row i of the chunk (rows behind wrap_at lie in later position rows of the matrix, Bp - B ids further each)
+    auto id_of = [&](uint32_t i) -> uint32_t {
+        int64_t at = i;
+        if (static_cast<int64_t>(i) >= wrap_at) at += ((static_cast<int64_t>(i) - wrap_at) / p.B + 1) * (p.Bp - p.B);
+        if constexpr (NIB) {
+            at += par0;
+            return (static_cast<uint32_t>(tok[at >> 1]) >> ((static_cast<uint32_t>(at) & 1u) << 2)) & 0xFu;
+        } else {
+            return static_cast<uint32_t>(tok[at]);
+        }
+    };
+    constexpr int IDB = NIB ? 4 : 8;  // bits per id in a lane's window
+    if (len == kChunk && (reinterpret_cast<uintptr_t>(g) & 15) == 0 && nr_s >= 8) {
+        uint64_t ids[4];
+        uint32_t ph[4];
+        if (!wraps && NIB) {
+            typedef uint32_t u32u __attribute__((aligned(1)));
+            uint32_t w[4], sh[4];
+            const uint32_t lb = (par0 + static_cast<uint32_t>(nr_s) - 1u) >> 1;  // the last byte of ids this chunk owns (>= 3: nr_s >= 8)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together: NR <= 6 nibbles + a parity fit four bytes
+                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
+                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
+                ph[u] = o - q * static_cast<uint32_t>(rb);
+                const uint32_t n0 = q + par0, bo = n0 >> 1;
+                const uint32_t off = bo + 3u <= lb ? bo : lb - 3u;  // pulled back to END at the chunk's last id byte (rows < nr_s lie in bo ... lb)
+                sh[u] = (bo - off) * 8u + ((n0 & 1u) << 2);
+                w[u] = *reinterpret_cast<const u32u *>(tok + off);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ids[u] = w[u] >> sh[u];
+        } else if (!wraps) {
+            typedef uint32_t u32x2u __attribute__((ext_vector_type(2), aligned(1)));
+            u32x2u w[4];
+            uint32_t sh[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together
+                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
+                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
+                ph[u] = o - q * static_cast<uint32_t>(rb);
+                // the last lanes' windows are pulled back to END at the chunk's last row: never a byte beyond the ids this chunk owns
+                const uint32_t off = q + 8u <= static_cast<uint32_t>(nr_s) ? q : static_cast<uint32_t>(nr_s) - 8u;
+                sh[u] = (q - off) * 8u;
+                w[u] = *reinterpret_cast<const u32x2u *>(tok + off);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ids[u] = ((static_cast<uint64_t>(w[u].y) << 32) | w[u].x) >> sh[u];
+        } else {  // one chunk per position row: the NR ids of a window one by one, across the padding (all 4 NR byte loads in flight together)
+            uint32_t b[4][NR];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
+                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
+                ph[u] = o - q * static_cast<uint32_t>(rb);
+#pragma unroll
+                for (int j = 0; j < NR; ++j) b[u][j] = q + j < static_cast<uint32_t>(nr_s) ? id_of(q + j) : kNo;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                ids[u] = 0;
+#pragma unroll
+                for (int j = 0; j < NR; ++j) ids[u] |= static_cast<uint64_t>(b[u][j]) << (IDB * j);
+            }
+        }
+        const uint32_t cmask = (1u << rb) - 1u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            uint32_t bits = 0;
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const uint32_t id = static_cast<uint32_t>(ids[u] >> (IDB * j)) & (NIB ? 0xFu : 0xFFu);
+                const uint32_t m = (1u << (id & 31u)) & cmask;  // id 255 (no one) -> bit 31 -> 0; nibble 15 -> bit 15 -> 0 (rows of <= 15 bytes)
+                const int32_t at = j * rb;                      // wave-uniform; strings that start at bit >= 32 lie beyond the lane's bits
+                if (at < 32) bits |= m << at;
+            }
+            bits >>= ph[u];
+            uint4 o;
+            o.x = (((bits >> 0) & 15u) * 0x204081u) & 0x01010101u;
+            o.y = (((bits >> 4) & 15u) * 0x204081u) & 0x01010101u;
+            o.z = (((bits >> 8) & 15u) * 0x204081u) & 0x01010101u;
+            o.w = (((bits >> 12) & 15u) * 0x204081u) & 0x01010101u;
+            if (one != 1u) {
+                o.x *= one;
+                o.y *= one;
+                o.z *= one;
+                o.w *= one;
+            }
+            store16<NT>(g + u * 1024 + lane * 16, o);
+        }
+        return;
+    }
+    // the clipped first / last chunk of the tensor, a result that is not 16-byte aligned: byte by byte, eight independent ids at a time
+    for (int32_t o0 = lane; o0 < len; o0 += 64 * 8) {
+        uint32_t idv[8], cv[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int32_t o = o0 + 64 * m;
+            const uint32_t a = static_cast<uint32_t>(o + skip);
+            const uint32_t i = fast_div(a, p.rb_magic, p.rb_shift, p.rb_pow2);
+            cv[m] = a - i * static_cast<uint32_t>(rb);
+            idv[m] = o < len ? id_of(i) : kNo;
+        }
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+            if (o0 + 64 * m < len) g[o0 + 64 * m] = idv[m] == cv[m] ? static_cast<uint8_t>(one) : uint8_t(0);
+    }
+}
+// (Twin: expand_rows1_body above, for k_expand_rows1_multi; the one-batch kernel keeps its own text as k_expand_chunks does.  A change here
+//  belongs in both.)
 template <bool NT, int NR, bool NIB = false>
 __global__ __launch_bounds__(kThreads) void k_expand_rows1(const EParams p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -467,6 +681,19 @@ __global__ __launch_bounds__(kThreads) void k_expand_rows1(const EParams p) {
         for (int m = 0; m < 8; ++m)
             if (o0 + 64 * m < len) g[o0 + 64 * m] = idv[m] == cv[m] ? static_cast<uint8_t>(one) : uint8_t(0);
     }
+}
+
+// The two expansions of several one-piece two-pass batches in one launch each (bsq_onehot_device_multi, family 2; see k_onehot_chunks_multi
+// for the table): every batch's ids lie in its own region of one scratch, written by ONE k_tokens_pb8_fast_multi launch before.
+template <typename ST, bool NT, int MATH, bool GATE = false, bool NIB = false>
+__global__ __launch_bounds__(kThreads) void k_expand_chunks_multi(const OnehotMulti<EParams> m) {
+    const uint32_t i = onehot_multi_batch_of(m, blockIdx.x);
+    expand_chunks_body<ST, NT, MATH, GATE, NIB>(blockIdx.x - m.first_block[i], m.b[i]);
+}
+template <bool NT, int NR, bool NIB = false>
+__global__ __launch_bounds__(kThreads) void k_expand_rows1_multi(const OnehotMulti<EParams> m) {
+    const uint32_t i = onehot_multi_batch_of(m, blockIdx.x);
+    expand_rows1_body<NT, NR, NIB>(blockIdx.x - m.first_block[i], m.b[i]);
 }
 
 
@@ -603,6 +830,119 @@ bsq_status dispatch_onehot_tile(KParams &k, hipStream_t s) {
 // 8192 x 1024 AMINO20 f32 0.10 -> 0.11 ms, profiles/r02/ab_owner_rounds.txt): the extra registers cost the occupancy
 // this kernel lives on.)
 // ------------------------------------------------------------------------------------------
+struct CFields {  // (what is per batch in k_onehot_chunks_multi: everything but the alphabet table)
+    const uint8_t *chars;
+    const int64_t *offsets;
+    const uint8_t *mask;
+    uint8_t *out;
+    int64_t total;    // output bytes
+    int64_t nchunks;
+    int64_t B, P;
+    int32_t head;     // out & 4095
+    int32_t C;
+    int32_t bos;
+    uint32_t bos_id, at_len_id, fill_id;
+    int32_t room;     // P - bos - eos (length clamp)
+    int32_t cpw;
+    uint64_t one_bits;
+    double inv_rowbytes, inv_B;  // reciprocals for div_by()
+    uint32_t rb_magic, rb_shift, rb_pow2;  // fast_div() constants of rowbytes
+};
+
+// The kernel's body for block `blk` of one batch's grid (k_onehot_chunks: blockIdx.x; k_onehot_chunks_multi: the block inside the batch's range).
+// Fewer resident workgroups stream faster (see launch_chunks): the launch caps the occupancy at 4 per CU.
+template <typename ST, bool NT>
+__device__ __forceinline__ void onehot_chunks_body(const uint32_t blk, const int8_t *plut, const CFields &p) {
+    __shared__ __align__(16) uint8_t s_img[4][kChunk];
+    __shared__ __align__(16) uint8_t s_lut4[4][256];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint8_t *img = s_img[wave];
+    uint8_t *lut = s_lut4[wave];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
+    {   // wave-private copy of the alphabet table (unmapped / >= 0x80 -> kNone): no workgroup barrier needed
+        uint32_t w = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int idx = lane * 4 + q;
+            const int8_t v = plut[idx];
+            const uint32_t e = (idx < 128 && v >= 0) ? static_cast<uint32_t>(v) : kNone;
+            w |= e << (8 * q);
+        }
+        reinterpret_cast<uint32_t *>(lut)[lane] = w;
+    }
+    const int32_t cls = static_cast<int32_t>(blk & 7u);
+    const int64_t group = static_cast<int64_t>(blk >> 3);
+    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
+    const ST one = static_cast<ST>(p.one_bits);
+    int64_t j = (group * 4 + wave) * p.cpw;
+    for (int32_t it = 0; it < p.cpw; ++it, ++j) {
+        const int64_t k = cls + 8 * j;
+        if (k >= p.nchunks) break;  // wave-uniform
+        int64_t lo = k * kChunk - p.head, hi = lo + kChunk;
+        if (lo < 0) lo = 0;
+        if (hi > p.total) hi = p.total;
+        const int32_t len = static_cast<int32_t>(hi - lo);
+        int64_t skip64, b_lo;
+        const int64_t r_lo = div_by(lo, rowbytes, p.inv_rowbytes, &skip64);
+        const int32_t skip = static_cast<int32_t>(skip64);
+        const int32_t nr = static_cast<int32_t>(fast_div(static_cast<uint32_t>(skip + len + rowbytes - 1), p.rb_magic,
+                                                         p.rb_shift, p.rb_pow2));
+        const int64_t t_lo = div_by(r_lo, p.B, p.inv_B, &b_lo);
+        for (int32_t i0 = 0; i0 < nr; i0 += 64) {
+            const int32_t i = i0 + lane;
+            if (i < nr) {
+                int64_t b = b_lo + i, t = t_lo;
+                if (b >= p.B) {  // the chunk runs over the end of position t's rows
+                    const int64_t q = b / p.B;
+                    t += q;
+                    b -= q * p.B;
+                }
+                uint32_t tk;
+                const int64_t start = p.offsets[b];
+                int64_t L = p.offsets[b + 1] - start;
+                L = L > p.room ? p.room : L;
+                const int64_t jj = t - p.bos;
+                if (jj < 0) {
+                    tk = p.bos_id;
+                } else if (jj < L) {
+                    tk = lut[p.chars[start + jj]];
+                    if (p.mask && p.mask[start + jj] == 0) tk = kNone;
+                } else {
+                    tk = (jj == L) ? p.at_len_id : p.fill_id;
+                }
+                const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk) * static_cast<int32_t>(sizeof(ST));
+                if (tk != kNone && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint8_t *g = p.out + lo;
+        if (len == kChunk) {
+            const uint4 v0 = *reinterpret_cast<const uint4 *>(img + lane * 16);
+            const uint4 v1 = *reinterpret_cast<const uint4 *>(img + 1024 + lane * 16);
+            const uint4 v2 = *reinterpret_cast<const uint4 *>(img + 2048 + lane * 16);
+            const uint4 v3 = *reinterpret_cast<const uint4 *>(img + 3072 + lane * 16);
+            store16<NT>(g + lane * 16, v0);
+            store16<NT>(g + 1024 + lane * 16, v1);
+            store16<NT>(g + 2048 + lane * 16, v2);
+            store16<NT>(g + 3072 + lane * 16, v3);
+        } else {
+            for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
+                *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
+        }
+        if (it + 1 < p.cpw) {  // image is reused: wipe it (wave-private, in-order LDS)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
+        }
+    }
+}
+
+// (Twin: onehot_chunks_body above, for k_onehot_chunks_multi.  A change here belongs in both.)
+// The one-batch form keeps its own parameter block and text (as k_expand_chunks does: moved into onehot_chunks_body it compiled to
+// different code, 8192 x 1024 AMINO20 f32 ran 1 % slower).
 struct CParams {
     int8_t lut[256];
     const uint8_t *chars;
@@ -713,6 +1053,37 @@ __global__ __launch_bounds__(kThreads) void k_onehot_chunks(const CParams p) {
     }
 }
 
+struct CMulti {
+    int8_t lut[256];
+    OnehotMulti<CFields> m;
+};
+template <typename ST, bool NT>
+__global__ __launch_bounds__(kThreads) void k_onehot_chunks_multi(const CMulti p) {
+    const uint32_t i = onehot_multi_batch_of(p.m, blockIdx.x);
+    onehot_chunks_body<ST, NT>(blockIdx.x - p.m.first_block[i], p.lut, p.m.b[i]);
+}
+
+// grid of one batch's chunk-owner stream (a multiple of 8 blocks)
+int64_t chunks_grid(const CFields &c) {
+    const int64_t per_class = (c.nchunks + 7) / 8;
+    return (per_class + int64_t(4) * c.cpw - 1) / (int64_t(4) * c.cpw) * 8;
+}
+
+// Occupancy cap of the chunk-owner kernels (unused dynamic LDS; see launch_chunks)
+size_t chunks_pad() {
+    const int padv = bsq_internal::tuning().chunks_pad;
+    return padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(22528));
+}
+
+template <typename ST>
+bsq_status launch_chunks_multi(const CMulti &c, int64_t blocks, hipStream_t s) {
+    if (bsq_internal::nontemporal_stores())
+        hipLaunchKernelGGL((k_onehot_chunks_multi<ST, true>), dim3(unsigned(blocks)), dim3(kThreads), chunks_pad(), s, c);
+    else
+        hipLaunchKernelGGL((k_onehot_chunks_multi<ST, false>), dim3(unsigned(blocks)), dim3(kThreads), chunks_pad(), s, c);
+    return check_launch("k_onehot_chunks_multi");
+}
+
 template <typename ST>
 bsq_status launch_chunks(const CParams &c, hipStream_t s) {
     const int64_t per_class = (c.nchunks + 7) / 8;
@@ -730,9 +1101,10 @@ bsq_status launch_chunks(const CParams &c, hipStream_t s) {
     return check_launch("k_onehot_chunks");
 }
 
-bsq_status onehot_chunk_owner(const KParams &k, size_t sz, hipStream_t s) {
-    CParams c;
-    for (int i = 0; i < 256; ++i) c.lut[i] = k.lut[i];
+// The chunk-owner parameters of one batch, into a CParams (k_onehot_chunks) or a CFields (a row of k_onehot_chunks_multi's table): the same
+// field names.  false: the output is too large for the kernel's grid arithmetic.
+template <typename F>
+bool chunk_owner_fields(const KParams &k, size_t sz, F &c) {
     c.chars = k.chars;
     c.offsets = k.offsets;
     c.mask = k.mask;
@@ -754,13 +1126,58 @@ bsq_status onehot_chunk_owner(const KParams &k, size_t sz, hipStream_t s) {
     c.inv_rowbytes = 1.0 / double(k.C * int64_t(sz));
     c.inv_B = 1.0 / double(k.B);
     div_constants(uint32_t(k.C * int64_t(sz)), &c.rb_magic, &c.rb_shift, &c.rb_pow2);
-    if ((c.nchunks + 7) / 8 / (4 * c.cpw) + 1 >= (int64_t(1) << 28)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    return (c.nchunks + 7) / 8 / (4 * c.cpw) + 1 < (int64_t(1) << 28);
+}
+
+bsq_status onehot_chunk_owner(const KParams &k, size_t sz, hipStream_t s) {
+    CParams c;
+    for (int i = 0; i < 256; ++i) c.lut[i] = k.lut[i];
+    if (!chunk_owner_fields(k, sz, c)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
     switch (sz) {
     case 1: return launch_chunks<uint8_t>(c, s);
     case 2: return launch_chunks<uint16_t>(c, s);
     case 4: return launch_chunks<uint32_t>(c, s);
     default: return launch_chunks<uint64_t>(c, s);
     }
+}
+
+// Which expansion kernel a (P,B,C) expansion runs, and its occupancy pad (launch_expand, launch_expand_multi).
+struct ExpandChoice {
+    bool rows1;   // k_expand_rows1<NR> (else k_expand_chunks)
+    int nr;
+    bool gated;   // k_expand_chunks<..., GATE>
+    size_t pad;   // unused dynamic LDS
+};
+template <typename ST>
+ExpandChoice expand_choice(const EParams &e) {
+    ExpandChoice c;
+    c.rows1 = false;
+    c.nr = 0;
+    c.gated = false;
+    const int padv = bsq_internal::tuning().expand_pad;
+    const bool big_rows = e.C * int64_t(sizeof(ST)) >= 64;
+    // (nibble ids, rows below 64 bytes: 12 KiB = FIVE workgroups per CU -- 16 KiB + the 16-KiB image + the kernel's few bytes of static LDS
+    //  round up to four; cfg4 f32 with nibbles 714 us at four, 648 at five, 662 at six; byte ids 673 / 690 / 703: profiles/r05/nibble_ids_lab.txt)
+    c.pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : (big_rows ? size_t(36864) : (e.nib ? size_t(12288) : size_t(16384))));
+    // (Scalar 64-bit reciprocal multiplies instead of the double reciprocals for the chunk arithmetic: ~90 SALU instructions instead of
+    // ~130 VALU ones, ahead where a wave's latency is exposed (2 workgroups per CU: 0.938 vs 0.969 ms on cfg3) and 1 % BEHIND at the
+    // bandwidth optimum (3 per CU: 0.741 vs 0.734 ms) -- profiles/r02/math_lab1.txt; not built any more.)
+    // one-byte elements, rows of 3 ... 15 bytes: the LDS-free form (knob "expand_rows1": 0 automatic, 1 never, 2 whenever it applies)
+    if constexpr (sizeof(ST) == 1) {
+        const int rk = bsq_internal::tuning().expand_rows1;
+        const int rb = e.C;
+        if (rk != 1 && rb >= 3 && rb <= 15) {
+            c.rows1 = true;
+            c.nr = (rb + 14) / rb + 1;  // rows a lane's 16 bytes can touch: 6, 5, 4, 4, 4, 3 ... 3, 2
+            c.pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(32768));  // (no static LDS here: 5 workgroups per CU)
+            return c;
+        }
+    }
+    // knob "expand_gate": 0 automatic (rows of 24 ... 63 bytes), 1 never, 2 always (the scratch holds at least 256 bytes: Bp >= 256)
+    const int gk = bsq_internal::tuning().expand_gate;
+    const int64_t rowb = e.C * int64_t(sizeof(ST));
+    c.gated = (gk == 2 || (gk == 0 && rowb >= 24 && rowb < 64)) && e.Bp >= 256;
+    return c;
 }
 
 template <typename ST>
@@ -784,21 +1201,11 @@ bsq_status launch_expand(const EParams &e, hipStream_t s) {
     // (k_expand_small -- dword token loads -- lost: once the token scratch is written in XCD-aware tile order the byte-load kernel under
     // an occupancy cap is 1-2 % ahead of it, and two or four chunks per wave were 20-40 % slower: profiles/r02/pad_lab*.txt, expand_lab3.txt;
     // its source is csrc/labs/bsq_expand_small.inc.)
-    const int padv = bsq_internal::tuning().expand_pad;
-    const bool big_rows = e.C * int64_t(sizeof(ST)) >= 64;
-    // (nibble ids, rows below 64 bytes: 12 KiB = FIVE workgroups per CU -- 16 KiB + the 16-KiB image + the kernel's few bytes of static LDS
-    //  round up to four; cfg4 f32 with nibbles 714 us at four, 648 at five, 662 at six; byte ids 673 / 690 / 703: profiles/r05/nibble_ids_lab.txt)
-    const size_t pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : (big_rows ? size_t(36864) : (e.nib ? size_t(12288) : size_t(16384))));
-    // (Scalar 64-bit reciprocal multiplies instead of the double reciprocals for the chunk arithmetic: ~90 SALU instructions instead of
-    // ~130 VALU ones, ahead where a wave's latency is exposed (2 workgroups per CU: 0.938 vs 0.969 ms on cfg3) and 1 % BEHIND at the
-    // bandwidth optimum (3 per CU: 0.741 vs 0.734 ms) -- profiles/r02/math_lab1.txt; not built any more.)
-    // one-byte elements, rows of 3 ... 15 bytes: the LDS-free form (knob "expand_rows1": 0 automatic, 1 never, 2 whenever it applies)
+    const ExpandChoice ch = expand_choice<ST>(e);
+    const size_t pad = ch.pad;
     if constexpr (sizeof(ST) == 1) {
-        const int rk = bsq_internal::tuning().expand_rows1;
-        const int rb = e.C;
-        if (rk != 1 && rb >= 3 && rb <= 15) {
-            const int nrows = (rb + 14) / rb + 1;  // rows a lane's 16 bytes can touch: 6, 5, 4, 4, 4, 3 ... 3, 2
-            const size_t rpad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(32768));  // (no static LDS here: 5 workgroups per CU)
+        if (ch.rows1) {
+            const size_t rpad = ch.pad;
             const bool nt = bsq_internal::nontemporal_stores();
 #define BSQ_ROWS1(NRV)                                                                                       \
     case NRV:                                                                                                \
@@ -810,7 +1217,7 @@ bsq_status launch_expand(const EParams &e, hipStream_t s) {
             else hipLaunchKernelGGL((k_expand_rows1<false, NRV>), grid, dim3(kThreads), rpad, s, e);         \
         }                                                                                                    \
         break;
-            switch (nrows) {
+            switch (ch.nr) {
                 BSQ_ROWS1(2) BSQ_ROWS1(3) BSQ_ROWS1(4) BSQ_ROWS1(5) BSQ_ROWS1(6)
             default: return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "k_expand_rows1: rows per lane");
             }
@@ -818,10 +1225,7 @@ bsq_status launch_expand(const EParams &e, hipStream_t s) {
             return check_launch(e.nib ? "k_expand_rows1<nibbles>" : "k_expand_rows1");
         }
     }
-    // knob "expand_gate": 0 automatic (rows of 24 ... 63 bytes), 1 never, 2 always (the scratch holds at least 256 bytes: Bp >= 256)
-    const int gk = bsq_internal::tuning().expand_gate;
-    const int64_t rowb = e.C * int64_t(sizeof(ST));
-    const bool gated = (gk == 2 || (gk == 0 && rowb >= 24 && rowb < 64)) && e.Bp >= 256;
+    const bool gated = ch.gated;
     if constexpr (sizeof(ST) >= 2) {
         if (e.nib) {  // ids as nibbles (two_pass_nibbles)
 #define BSQ_EXPN(NTV, GV) hipLaunchKernelGGL((k_expand_chunks<ST, NTV, 0, GV, true>), grid, dim3(kThreads), pad, s, e)
@@ -840,6 +1244,51 @@ bsq_status launch_expand(const EParams &e, hipStream_t s) {
         else hipLaunchKernelGGL((k_expand_chunks<ST, false, 0>), grid, dim3(kThreads), pad, s, e);
     }
     return check_launch("k_expand_chunks");
+}
+
+
+// The expansions of several batches (family 2 of bsq_onehot_device_multi) in one launch: the kernel expand_choice picks for m.b[0], which the
+// plan made the same for every batch of the launch.
+template <typename ST>
+bsq_status launch_expand_multi(const OnehotMulti<EParams> &m, int64_t blocks, hipStream_t s) {
+    const EParams &e = m.b[0];
+    const ExpandChoice ch = expand_choice<ST>(e);
+    const dim3 grid{unsigned(blocks)};
+    const size_t pad = ch.pad;
+    const bool nt = bsq_internal::nontemporal_stores();
+    if constexpr (sizeof(ST) == 1) {
+        if (ch.rows1) {
+#define BSQ_ROWS1M(NRV)                                                                                           \
+    case NRV:                                                                                                     \
+        if (e.nib) {                                                                                              \
+            if (nt) hipLaunchKernelGGL((k_expand_rows1_multi<true, NRV, true>), grid, dim3(kThreads), pad, s, m); \
+            else hipLaunchKernelGGL((k_expand_rows1_multi<false, NRV, true>), grid, dim3(kThreads), pad, s, m);   \
+        } else {                                                                                                  \
+            if (nt) hipLaunchKernelGGL((k_expand_rows1_multi<true, NRV>), grid, dim3(kThreads), pad, s, m);       \
+            else hipLaunchKernelGGL((k_expand_rows1_multi<false, NRV>), grid, dim3(kThreads), pad, s, m);         \
+        }                                                                                                         \
+        break;
+            switch (ch.nr) {
+                BSQ_ROWS1M(2) BSQ_ROWS1M(3) BSQ_ROWS1M(4) BSQ_ROWS1M(5) BSQ_ROWS1M(6)
+            default: return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "k_expand_rows1_multi: rows per lane");
+            }
+#undef BSQ_ROWS1M
+            return check_launch(e.nib ? "k_expand_rows1_multi<nibbles>" : "k_expand_rows1_multi");
+        }
+    }
+#define BSQ_EXPM(NTV, GV, NIBV) hipLaunchKernelGGL((k_expand_chunks_multi<ST, NTV, 0, GV, NIBV>), grid, dim3(kThreads), pad, s, m)
+    if constexpr (sizeof(ST) >= 2) {
+        if (e.nib) {
+            if (nt) { if (ch.gated) BSQ_EXPM(true, true, true); else BSQ_EXPM(true, false, true); }
+            else { if (ch.gated) BSQ_EXPM(false, true, true); else BSQ_EXPM(false, false, true); }
+            return check_launch("k_expand_chunks_multi<nibbles>");
+        }
+    }
+    if (e.nib) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "nibble ids: elements of 2 bytes and more, or one-byte rows of 3 ... 15 bytes");
+    if (nt) { if (ch.gated) BSQ_EXPM(true, true, false); else BSQ_EXPM(true, false, false); }
+    else { if (ch.gated) BSQ_EXPM(false, true, false); else BSQ_EXPM(false, false, false); }
+#undef BSQ_EXPM
+    return check_launch("k_expand_chunks_multi");
 }
 
 // Two-pass one-hot: raw (P,B) tokens into `workspace` (P*B bytes), then the chunk expansion.
@@ -875,8 +1324,8 @@ bsq_status launch_tokens_raw(KParams &k, void *tokens, int64_t pitch, hipStream_
 }
 
 // Pass 2: the (P, B, C) one-hot as the flat expansion of a (P, pitch) raw token matrix.
-bsq_status launch_expansion(const uint8_t *tokens, int64_t pitch, int64_t B, int64_t P, int32_t C, size_t sz,
-                            uint64_t one_bits, void *out, hipStream_t s, int64_t row_gap = 0, bool nib = false) {
+EParams expansion_params(const uint8_t *tokens, int64_t pitch, int64_t B, int64_t P, int32_t C, size_t sz, uint64_t one_bits, void *out,
+                         int64_t row_gap, bool nib) {
     EParams e;
     e.row_gap = row_gap;
     e.nib = nib ? 1 : 0;  // (k_expand_chunks only: see two_pass_nibbles)
@@ -905,6 +1354,11 @@ bsq_status launch_expansion(const uint8_t *tokens, int64_t pitch, int64_t B, int
     e.dv_rb = div64_constants(uint64_t(C * int64_t(sz)));
     div_constants(uint32_t(C * int64_t(sz)), &e.rb_magic, &e.rb_shift, &e.rb_pow2);
     e.force4 = bsq_internal::tuning().expand_slots == 4;
+    return e;
+}
+bsq_status launch_expansion(const uint8_t *tokens, int64_t pitch, int64_t B, int64_t P, int32_t C, size_t sz,
+                            uint64_t one_bits, void *out, hipStream_t s, int64_t row_gap = 0, bool nib = false) {
+    const EParams e = expansion_params(tokens, pitch, B, P, C, sz, one_bits, out, row_gap, nib);
     switch (sz) {
     case 1: return launch_expand<uint8_t>(e, s);
     case 2: return launch_expand<uint16_t>(e, s);
@@ -1262,6 +1716,23 @@ bsq_status bsq_onehot_from_raw_tokens_device(const uint8_t *tokens, int64_t pitc
     return launch_expansion(tokens, pitch, B, P, C, sz, one_bits_of(t), out, static_cast<hipStream_t>(hip_stream));
 }
 
+// Which form bsq_onehot_bcl_device runs: 2 two-pass (raw (B,P) ids, then k_expand_bcl), 3 the chunk kernel k_tokenize_chunks<HOT>, 0 the
+// generic element kernel (bsq_onehot_device_multi plans with it too).
+static int choose_bcl_path(const bsq_desc *d, int32_t C, size_t sz, int64_t B, int64_t P, const void *out) {
+    // Two-pass form (raw (B,P) ids, then k_expand_bcl) for large outputs, masked or not; knob "bcl_path": 0 automatic,
+    // 1 never, 2 whenever it applies.
+    const int bcl_path = bsq_internal::tuning().bcl_path;
+    const int64_t total_bytes = B * int64_t(C) * P * int64_t(sz);
+    if (bcl_path != 1 && (bcl_path == 2 || total_bytes >= (int64_t(256) << 20)) && C <= 250 &&
+        reinterpret_cast<uintptr_t>(out) % 16 == 0 && P % 16 == 0 && B * int64_t(C) * P < (int64_t(1) << 51) &&
+        bsq_internal::tokens_bp8_applicable(d, B, P, out))
+        return 2;
+    if (C <= 250 && reinterpret_cast<uintptr_t>(out) % sz == 0 &&
+        ((reinterpret_cast<uintptr_t>(out) % 16 == 0 && P % int64_t(16 / sz) == 0) || bcl_path != 3))  // knob 3: aligned only
+        return 3;
+    return 0;
+}
+
 // Channels-first one-hot (B, C, P).  Fast path: chunk kernel (needs P % (16/sizeof(T)) == 0, a 16-byte
 // aligned base and 8-bit ids); otherwise the generic element kernel.
 bsq_status bsq_onehot_bcl_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets,
@@ -1275,13 +1746,8 @@ bsq_status bsq_onehot_bcl_device(const bsq_desc *d, const uint8_t *chars, const 
     if (sz == 0) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     k.one_bits = one_bits_of(t);
-    // Two-pass form (raw (B,P) ids, then k_expand_bcl) for large outputs, masked or not; knob "bcl_path": 0 automatic,
-    // 1 never, 2 whenever it applies.
-    const int bcl_path = bsq_internal::tuning().bcl_path;
-    const int64_t total_bytes = B * int64_t(k.C) * P * int64_t(sz);
-    if (bcl_path != 1 && (bcl_path == 2 || total_bytes >= (int64_t(256) << 20)) && k.C <= 250 &&
-        reinterpret_cast<uintptr_t>(out) % 16 == 0 && P % 16 == 0 && B * int64_t(k.C) * P < (int64_t(1) << 51) &&
-        bsq_internal::tokens_bp8_applicable(d, B, P, out)) {
+    const int path = choose_bcl_path(d, k.C, sz, B, P, out);
+    if (path == 2) {
         // In SLICES of sequences once the (B,P) id matrix exceeds 128 MB (round 5: like the seq-first two-pass form, the expansion holds the
         // roof only while its ids come out of the Infinity Cache -- 262 144 x 1024 f32: 0.60 of the roof in one piece).  A sequence's rows
         // are contiguous in the (B,C,P) result, so a slice is simply a smaller batch: sequences [b0, b0 + nb) with offsets + b0 (the
@@ -1313,11 +1779,256 @@ bsq_status bsq_onehot_bcl_device(const bsq_desc *d, const uint8_t *chars, const 
         bsq_internal::workspace_release(ws, s);
         return wst;
     }
-    if (k.C <= 250 && reinterpret_cast<uintptr_t>(out) % sz == 0 &&
-        ((reinterpret_cast<uintptr_t>(out) % 16 == 0 && P % int64_t(16 / sz) == 0) || bcl_path != 3)) {  // knob 3: aligned only
+    if (path == 3) {
         return bsq_internal::launch_onehot_bcl_chunks(d, chars, offsets, mask_or_null, B, P, t, out, s);  // (bsq_tokens.hip: k_tokenize_chunks<HOT>)
     }
     return bsq_internal::onehot_generic_bcl(d, chars, offsets, mask_or_null, B, P, t, out, hip_stream);
+}
+
+
+}  // extern "C"
+
+static_assert(sizeof(CMulti) <= 4096 && sizeof(OnehotMulti<EParams>) <= 4096, "multi tables live in the kernel-argument segment");
+
+namespace {
+struct MultiItem {
+    int32_t family;  // 0 single call, 1 chunk-owner, 2 one-piece two-pass, 3 channels-first chunk stream
+    bool nib;        // family 2: the launch pair's key -- ids as nibbles, the raw pass's paired tail (the expansion kernel, its gate and pad
+    bool paired;     //   follow from C, the dtype and nib, which the call's batches share)
+    int64_t pitch;   // family 2: ids per scratch row; the batch's scratch region (as its single call acquires it); the ids' bytes as stored
+    int64_t ws_bytes, stored;
+};
+
+// The family of one batch by itself (before the group's rules).  Arguments already checked.
+MultiItem multi_candidate(const bsq_desc *d, const bsq_onehot_batch &b, int64_t P, int32_t layout, bsq_dtype t) {
+    MultiItem it{};
+    const size_t sz = bsq_dtype_size(t);
+    const int32_t C = bsq_alphabet_size(d);
+    if (b.B <= 0) return it;
+    if (layout == 1) {  // (B,C,P): the chunk stream in its plain form fuses (the two-pass form, the ragged and generic fallbacks run alone)
+        if (choose_bcl_path(d, C, sz, b.B, P, b.out) == 3 && bsq_internal::onehot_bcl_chunks_fusable(b.B, P, C, t, b.out)) it.family = 3;
+        return it;
+    }
+    const int path = choose_onehot_path(C, sz, b.B, P, reinterpret_cast<uintptr_t>(b.out) % 64 != 0, b.mask != nullptr);
+    KParams k;
+    if (fill_common(k, d, b.chars, b.offsets, b.mask, b.B, P, b.out) != BSQ_OK) return it;
+    k.one_bits = one_bits_of(t);
+    if (path == 3) {
+        CFields c;
+        if (chunk_owner_fields(k, sz, c)) it.family = 1;
+        return it;
+    }
+    // two-pass: unmasked, one piece (no sequence blocks, no position slices), the raw pass in k_tokens_pb8_fast (launch_tokens_raw)
+    if (path != 2 || b.mask || two_pass_sequence_block(k, sz, b.out) != 0) return it;
+    const TwoPassPlan pl = two_pass_plan(k, sz);
+    if (pl.tiles_per_slice < pl.ntt || bsq_internal::tuning().raw_mode != 0 ||
+        !bsq_internal::tokens_pb8_applicable(d, b.B, P, reinterpret_cast<const void *>(uintptr_t(256)), pl.pitch))
+        return it;
+    const EParams e = expansion_params(nullptr, pl.pitch, b.B, P, C, sz, k.one_bits, b.out, 0, pl.nib);
+    if (((e.nchunks + 7) / 8 + 3) / 4 * 8 >= (int64_t(1) << 31)) return it;
+    it.family = 2;
+    it.nib = pl.nib;
+    it.paired = bsq_internal::tokens_pb8_raw_paired(b.B, P);
+    it.pitch = pl.pitch;
+    it.ws_bytes = int64_t(pl.ws_bytes);
+    it.stored = (pl.pitch >> (pl.nib ? 1 : 0)) * P;
+    return it;
+}
+
+// The group's plan: it[i].family after the group rules (a family with a single member runs as its single call; a family-2 set is the batches
+// of one key, in order, while their ids together stay within the one-piece limit of the single path).  Returns the number of fused launches.
+int32_t multi_plan_group(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, int64_t P, int32_t layout, bsq_dtype t, MultiItem *it) {
+    for (int32_t i = 0; i < g; ++i) it[i] = multi_candidate(d, grp[i], P, layout, t);
+    int32_t launches = 0;
+    for (const int32_t fam : {1, 3}) {
+        int32_t cnt = 0;
+        for (int32_t i = 0; i < g; ++i) cnt += it[i].family == fam ? 1 : 0;
+        if (cnt >= 2) ++launches;
+        else
+            for (int32_t i = 0; i < g; ++i)
+                if (it[i].family == fam) it[i].family = 0;
+    }
+    const int64_t limit = int64_t(128) << 20;  // (two_pass_plan: an id matrix beyond 128 MB as stored is cut into slices)
+    for (int key = 0; key < 4; ++key) {
+        const bool nib = (key & 1) != 0, paired = (key & 2) != 0;
+        int64_t sum = 0;
+        int32_t cnt = 0, last = -1;
+        for (int32_t i = 0; i < g; ++i) {
+            if (it[i].family != 2 || it[i].nib != nib || it[i].paired != paired) continue;
+            if (sum + it[i].stored > limit) {
+                it[i].family = 0;
+                continue;
+            }
+            sum += it[i].stored;
+            ++cnt;
+            last = i;
+        }
+        if (cnt >= 2) launches += 2;
+        else if (cnt == 1) it[last].family = 0;
+    }
+    return launches;
+}
+
+bsq_status multi_check(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, int32_t layout, bsq_dtype t) {
+    if (!d || n < 0 || (n > 0 && !batches) || (layout != 0 && layout != 1))
+        return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "null descriptor, n < 0, a null table or a layout other than 0 / 1");
+    if (bsq_dtype_size(t) == 0) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
+    for (int32_t i = 0; i < n; ++i) {  // the single calls' checks, for every batch before anything runs
+        KParams k;
+        const bsq_status st = fill_common(k, d, batches[i].chars, batches[i].offsets, batches[i].mask, batches[i].B, P, batches[i].out);
+        if (st != BSQ_OK) return st;
+    }
+    return BSQ_OK;
+}
+
+// up to eight non-empty batches from *pos on (B == 0 skipped); returns how many
+int32_t next_group(int32_t n, const bsq_onehot_batch *batches, int32_t *pos, bsq_onehot_batch *grp) {
+    int32_t g = 0;
+    while (*pos < n && g < kOnehotMultiMax) {
+        if (batches[*pos].B > 0) grp[g++] = batches[*pos];
+        ++*pos;
+    }
+    return g;
+}
+
+bsq_status run_family1(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, const MultiItem *it, int64_t P, bsq_dtype t, hipStream_t s) {
+    const size_t sz = bsq_dtype_size(t);
+    CMulti cm;
+    for (int i = 0; i < 256; ++i) cm.lut[i] = d->lut[i];
+    for (int i = 0; i < kOnehotMultiMax; ++i) cm.m.first_block[i] = 0xFFFFFFFFu;
+    int64_t blocks = 0;
+    int32_t j = 0;
+    for (int32_t i = 0; i < g; ++i) {
+        if (it[i].family != 1) continue;
+        KParams k;
+        bsq_status st = fill_common(k, d, grp[i].chars, grp[i].offsets, grp[i].mask, grp[i].B, P, grp[i].out);
+        if (st != BSQ_OK) return st;
+        k.one_bits = one_bits_of(t);
+        if (!chunk_owner_fields(k, sz, cm.m.b[j])) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+        cm.m.first_block[j++] = uint32_t(blocks);
+        blocks += chunks_grid(cm.m.b[j - 1]);
+    }
+    if (j == 0) return BSQ_OK;
+    if (blocks >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    switch (sz) {
+    case 1: return launch_chunks_multi<uint8_t>(cm, blocks, s);
+    case 2: return launch_chunks_multi<uint16_t>(cm, blocks, s);
+    case 4: return launch_chunks_multi<uint32_t>(cm, blocks, s);
+    default: return launch_chunks_multi<uint64_t>(cm, blocks, s);
+    }
+}
+
+// one family-2 set (the members of key `key`): one raw-id launch into one scratch -- a region per batch, each the size its single call
+// acquires --, then one expansion launch
+bsq_status run_family2_set(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, const MultiItem *it, int key, int64_t P, bsq_dtype t,
+                           hipStream_t s) {
+    const bool nib = (key & 1) != 0, paired = (key & 2) != 0;
+    const size_t sz = bsq_dtype_size(t);
+    const int32_t C = bsq_alphabet_size(d);
+    int32_t idx[kOnehotMultiMax], m = 0;
+    size_t total = 0;
+    for (int32_t i = 0; i < g; ++i)
+        if (it[i].family == 2 && it[i].nib == nib && it[i].paired == paired) {
+            idx[m++] = i;
+            total += (size_t(it[i].ws_bytes) + 255) / 256 * 256;
+        }
+    if (m < 2) return BSQ_OK;
+    std::lock_guard<std::mutex> two_pass_turn(bsq_internal::workspace_mutex());  // see onehot_two_pass
+    void *ws = nullptr;
+    bsq_status st = bsq_internal::workspace_acquire(total, s, &ws);
+    if (st != BSQ_OK) return st;
+    const uint8_t *chars[kOnehotMultiMax];
+    const int64_t *offsets[kOnehotMultiMax];
+    int64_t Bs[kOnehotMultiMax];
+    uint8_t *wsp[kOnehotMultiMax];
+    OnehotMulti<EParams> em;
+    for (int i = 0; i < kOnehotMultiMax; ++i) em.first_block[i] = 0xFFFFFFFFu;
+    size_t at = 0;
+    int64_t blocks = 0;
+    const uint64_t one = one_bits_of(t);
+    for (int32_t j = 0; j < m; ++j) {
+        const MultiItem &x = it[idx[j]];
+        const bsq_onehot_batch &b = grp[idx[j]];
+        chars[j] = b.chars, offsets[j] = b.offsets, Bs[j] = b.B, wsp[j] = static_cast<uint8_t *>(ws) + at;
+        at += (size_t(x.ws_bytes) + 255) / 256 * 256;
+        em.b[j] = expansion_params(wsp[j], x.pitch, b.B, P, C, sz, one, b.out, 0, nib);
+        em.first_block[j] = uint32_t(blocks);
+        blocks += ((em.b[j].nchunks + 7) / 8 + 3) / 4 * 8;
+    }
+    if (blocks >= (int64_t(1) << 31)) st = bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    if (st == BSQ_OK) st = bsq_internal::launch_tokens_pb8_raw_multi(d, m, chars, offsets, Bs, P, wsp, nib, s);
+    if (st == BSQ_OK) {
+        switch (sz) {
+        case 1: st = launch_expand_multi<uint8_t>(em, blocks, s); break;
+        case 2: st = launch_expand_multi<uint16_t>(em, blocks, s); break;
+        case 4: st = launch_expand_multi<uint32_t>(em, blocks, s); break;
+        default: st = launch_expand_multi<uint64_t>(em, blocks, s); break;
+        }
+    }
+    bsq_internal::workspace_release(ws, s);
+    return st;
+}
+
+bsq_status run_family3(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, const MultiItem *it, int64_t P, bsq_dtype t, hipStream_t s) {
+    bsq_onehot_batch sel[kOnehotMultiMax];
+    int32_t m = 0;
+    for (int32_t i = 0; i < g; ++i)
+        if (it[i].family == 3) sel[m++] = grp[i];
+    if (m == 0) return BSQ_OK;
+    return bsq_internal::launch_onehot_bcl_chunks_multi(d, m, sel, P, t, s);
+}
+}  // namespace
+
+extern "C" {
+
+int32_t bsq_onehot_multi_plan(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, int32_t layout, bsq_dtype t,
+                              int32_t *family) {
+    const bsq_status st = multi_check(d, n, batches, P, layout, t);
+    if (st != BSQ_OK) return -st;
+    if (family)
+        for (int32_t i = 0; i < n; ++i) family[i] = 0;
+    int32_t launches = 0, pos = 0;
+    while (pos < n) {
+        bsq_onehot_batch grp[kOnehotMultiMax];
+        int32_t where[kOnehotMultiMax], g = 0;
+        while (pos < n && g < kOnehotMultiMax) {  // (next_group, keeping the batches' indices)
+            if (batches[pos].B > 0) where[g] = pos, grp[g++] = batches[pos];
+            ++pos;
+        }
+        if (g == 0) break;
+        MultiItem it[kOnehotMultiMax];
+        launches += multi_plan_group(d, g, grp, P, layout, t, it);
+        if (family)
+            for (int32_t i = 0; i < g; ++i) family[where[i]] = it[i].family;
+    }
+    return launches;
+}
+
+bsq_status bsq_onehot_device_multi(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, int32_t layout, bsq_dtype t,
+                                   void *hip_stream) {
+    bsq_status st = multi_check(d, n, batches, P, layout, t);
+    if (st != BSQ_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    int32_t pos = 0;
+    bsq_onehot_batch grp[kOnehotMultiMax];
+    while (int32_t g = next_group(n, batches, &pos, grp)) {
+        MultiItem it[kOnehotMultiMax];
+        const int32_t launches = multi_plan_group(d, g, grp, P, layout, t, it);
+        if (launches > 0) {
+            st = run_family1(d, g, grp, it, P, t, s);
+            for (int key = 0; key < 4 && st == BSQ_OK; ++key) st = run_family2_set(d, g, grp, it, key, P, t, s);
+            if (st == BSQ_OK) st = run_family3(d, g, grp, it, P, t, s);
+            if (st != BSQ_OK) return st;
+        }
+        for (int32_t i = 0; i < g; ++i) {  // family 0: the single call, in order
+            if (it[i].family != 0) continue;
+            const bsq_onehot_batch &b = grp[i];
+            st = layout == 0 ? bsq_onehot_device(d, b.chars, b.offsets, b.mask, b.B, P, t, b.out, hip_stream)
+                             : bsq_onehot_bcl_device(d, b.chars, b.offsets, b.mask, b.B, P, t, b.out, hip_stream);
+            if (st != BSQ_OK) return st;
+        }
+    }
+    return BSQ_OK;
 }
 
 }  // extern "C"

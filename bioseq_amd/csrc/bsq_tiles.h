@@ -540,4 +540,23 @@ bsq_status fill_common(KParams &k, const bsq_desc *d, const uint8_t *chars, cons
     return BSQ_OK;
 }
 
+// SEVERAL INDEPENDENT BATCHES IN ONE LAUNCH (bsq_onehot_device_multi: k_onehot_chunks_multi,
+// k_expand_*_multi, k_tokenize_chunks_multi; the pattern of k_tokens_bp8_fast_multi, bsq_tokens8.hip): the grid is
+// the concatenation of up to kOnehotMultiMax batches' grids, every batch's range starting at a multiple of 8 (block % 8 stays the chunk class of the
+// batch's own stream, the XCD pinning holds).  Per batch: a row of the table in the kernel-argument segment, picked by a compare chain on the
+// block index; shared: the alphabet table (once), the element type, and what the batches' common tokenizer and padlen fix.
+constexpr int kOnehotMultiMax = 8;
+template <typename T>
+struct OnehotMulti {
+    uint32_t first_block[kOnehotMultiMax];  // multiples of 8, ascending; entries behind the last batch: 0xFFFFFFFF
+    T b[kOnehotMultiMax];
+};
+template <typename T>
+__device__ __forceinline__ uint32_t onehot_multi_batch_of(const OnehotMulti<T> &m, uint32_t blk) {
+    uint32_t i = 0;
+#pragma unroll
+    for (int k = 1; k < kOnehotMultiMax; ++k) i += blk >= m.first_block[k] ? 1u : 0u;
+    return i;
+}
+
 }  // namespace

@@ -1090,6 +1090,20 @@ __global__ __launch_bounds__(kThreads) void k_tokens_pb8_fast_multi(uint32_t P, 
                                      shift, room, packed, 0u, tab, rules, lut);
 }
 
+// The raw-id passes of several one-piece two-pass one-hots in one launch (bsq_onehot_device_multi, family 2): raw mode (packed bit 1, no one =
+// 0xFF), every batch's ids into its own (P, pitch) region of the scratch with the two-pass pitch B rounded up to 256 (kRawTB) -- as
+// launch_tokens_pb8(raw = true) writes one batch's -- as bytes or (NIB) as nibbles; plain stores: the expansion re-reads the ids right away.
+template <int LK, bool NIB>
+__global__ __launch_bounds__(kThreads) void k_tokens_pb8_fast_raw_multi(uint32_t P, uint32_t ntt, uint32_t magic, uint32_t shift, int32_t room,
+                                                                        uint32_t packed, T8Tab tab, T8Rules rules, T8Lut lut, T8Multi m) {
+    const uint32_t blk = blockIdx.x;
+    const uint32_t i = multi_batch_of(m, blk);
+    const uint32_t Bi = m.B[i];
+    tokens_pb8_body<false, 256, LK, 1, false, false, NIB>(blk - m.first_block[i], m.offsets[i], m.chars[i], m.out[i],
+                                                          static_cast<int64_t>((Bi + 255u) & ~255u), Bi, P, m.units[i], ntt, magic, shift, room,
+                                                          packed, 0u, tab, rules, lut);
+}
+
 template <bool NT, int LK>
 void launch_variant(const T8Params &c, dim3 grid, size_t pad, hipStream_t s) {
     if (c.mask)  // raw ids for the masked channels-first one-hot (aligned shapes only: see launch_tokens_bp8)
@@ -1458,6 +1472,10 @@ bool tokens_pb8_applicable(const bsq_desc *d, int64_t B, int64_t P, const void *
            bsq_alphabet_size(d) <= 250;
 }
 
+// The paired tail (packed bit 3) of the aligned class-pinned form: the last position tile holds 1 ... 32 positions and there is more than one
+// group of 8 sequence tiles (knob "tokens_pb8_pair" = 1: never).  Shared with the raw-id multi launch (tokens_pb8_raw_paired).
+static bool pb8_paired_tail(int64_t ntb, int64_t P) { return P % 64 != 0 && P % 64 <= 32 && ntb > 8 && tuning().tokens_pb8_pair != 1; }
+
 bsq_status launch_tokens_pb8(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, void *out,
                              int64_t pitch, hipStream_t s, bool raw, bsq_dtype t, bool nib, int64_t tt0, int64_t ntt_count) {
     const uint32_t none_v = raw ? 0xFFu : 0u;
@@ -1510,7 +1528,7 @@ bsq_status launch_tokens_pb8(const bsq_desc *d, const uint8_t *chars, const int6
     if (pow2) magic = 0;  // the kernel shifts (magic 0 marks a power of two)
     // paired tail (see the kernel): the last position tile holds 1 ... 32 positions, the aligned class-pinned form, more than one group of 8 sequence
     // tiles (knob "tokens_pb8_pair" = 1: never)
-    if (!contig && !ua && P % TT != 0 && P % TT <= 32 && ntb > 8 && tuning().tokens_pb8_pair != 1) packed |= 8u;
+    if (!contig && !ua && pb8_paired_tail(ntb, P)) packed |= 8u;
 #define BSQ_PB8U(NTV, LKV, SZV, FLTV, UAV)                                                                                             \
     hipLaunchKernelGGL((k_tokens_pb8_fast<NTV, 256, LKV, SZV, FLTV, UAV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, offsets, chars,  \
                        static_cast<uint8_t *>(out), pitch, uint32_t(B), uint32_t(P), uint32_t(ntb), uint32_t(ntt), magic, shift,    \
@@ -1700,6 +1718,69 @@ bsq_status launch_tokens_multi(const bsq_desc *d, int32_t n, const bsq_batch *bt
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_hip_error("k_tokens_pb8_fast_multi", e);
     *taken = true;
+    return BSQ_OK;
+}
+
+// The paired-tail flag (packed bit 3) launch_tokens_pb8 sets for the raw pass of a B-sequence batch into an aligned scratch of the two-pass pitch
+bool tokens_pb8_raw_paired(int64_t B, int64_t P) { return pb8_paired_tail((B + 255) / 256, P); }
+
+// n (1 ... kMultiMax) raw-id passes -- exactly what launch_tokens_pb8(d, chars, offsets, B, P, ws[i], pitch = B rounded up to 256, raw = true,
+// BSQ_I8, nib) launches for each -- in ONE launch.  Every ws[i] 64-byte aligned; the batches share the paired-tail flag (tokens_pb8_raw_paired).
+bsq_status launch_tokens_pb8_raw_multi(const bsq_desc *d, int32_t n, const uint8_t *const *chars, const int64_t *const *offsets, const int64_t *Bs,
+                                       int64_t P, uint8_t *const *ws, bool nib, hipStream_t s) {
+    if (n < 1 || n > kMultiMax || P <= 0 || P > (int64_t(1) << 30)) return set_error(BSQ_ERR_INVALID_ARG, "raw multi: 1 ... 8 batches, padlen");
+    if (nib && bsq_alphabet_size(d) > 15) return set_error(BSQ_ERR_INVALID_ARG, "nibble ids: at most 15 classes");
+    const uint32_t none_v = 0xFFu;
+    T8Tab tab;
+    const bool foldable = fold_table(d->lut, tab.t, none_v);
+    int lk = tuning().tokens8_lookup;  // as launch_tokens_pb8
+    if (lk == 0) lk = foldable ? 2 : 1;
+    if (lk == 2 && !foldable) lk = 1;
+    T8Lut lut;
+    for (int w = 0; w < 64; ++w) {
+        uint32_t v = 0;
+        for (int k = 0; k < 4; ++k) {
+            const int c = 4 * w + k;
+            const uint32_t tkn = (c < 128 && d->lut[c] >= 0) ? uint32_t(uint8_t(d->lut[c])) : none_v;
+            v |= tkn << (8 * k);
+        }
+        lut.w[w] = v;
+    }
+    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : none_v;
+    const uint32_t at_len = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
+    const uint32_t bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
+    T8Rules rules;
+    build_rules(fill, at_len, rules);
+    const int64_t room64 = P - d->bos - d->eos;
+    const int32_t room = int32_t(room64 < 0 ? 0 : room64);
+    const int TT = 64;
+    const int64_t ntt = (P + TT - 1) / TT;
+    const bool paired = tokens_pb8_raw_paired(Bs[0], P);
+    uint32_t packed = uint32_t(d->bos != 0) | 2u | (paired ? 8u : 0u) | (bos_id << 8) | ((at_len & 0xFFu) << 16) | ((fill & 0xFFu) << 24);
+    T8Multi m;
+    multi_clear(m);
+    int64_t blocks = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t B = Bs[i], pitch = (B + 255) / 256 * 256;
+        if (!tokens_pb8_applicable(d, B, P, ws[i], pitch) || reinterpret_cast<uintptr_t>(ws[i]) % 64 != 0 || tokens_pb8_raw_paired(B, P) != paired)
+            return set_error(BSQ_ERR_INVALID_ARG, "raw multi: a batch the one-piece raw pass does not take alike");
+        const int64_t ntb = (B + 255) / 256;
+        m.offsets[i] = offsets[i], m.chars[i] = chars[i], m.out[i] = ws[i];
+        m.first_block[i] = uint32_t(blocks), m.units[i] = uint32_t(ntb), m.B[i] = uint32_t(B);
+        blocks += (ntb + 7) / 8 * 8 * ntt;
+    }
+    if (blocks >= (int64_t(1) << 31)) return set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    uint32_t magic = 0, shift = 0, pow2 = 0;
+    div_constants(uint32_t(ntt), &magic, &shift, &pow2);
+    if (pow2) magic = 0;  // the kernel shifts (magic 0 marks a power of two)
+#define BSQ_PB8RM(LKV, NIBV)                                                                                                                   \
+    hipLaunchKernelGGL((k_tokens_pb8_fast_raw_multi<LKV, NIBV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, uint32_t(P), uint32_t(ntt), magic, \
+                       shift, room, packed, tab, rules, lut, m)
+    if (nib) { if (lk == 2) BSQ_PB8RM(1, true); else BSQ_PB8RM(0, true); }
+    else { if (lk == 2) BSQ_PB8RM(1, false); else BSQ_PB8RM(0, false); }
+#undef BSQ_PB8RM
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_hip_error(nib ? "k_tokens_pb8_fast_raw_multi<nibbles>" : "k_tokens_pb8_fast_raw_multi", e);
     return BSQ_OK;
 }
 

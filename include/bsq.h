@@ -32,7 +32,7 @@ extern "C" {
 
 #define BSQ_ABI_VERSION 7 /* 7 (round 6): bsq_tokenize_device_multi, bsq_augment_device_multi, bsq_augment_tokenize_device_multi, bsq_enable_peer_access, bsq_tokenize_kernel_name; nothing removed.
                            * Added since, without a version bump (nothing changed or removed): bsq_mlm, bsq_mlm_tokenize_device,
-                           * bsq_random_mask_device, bsq_random_mask_host */
+                           * bsq_random_mask_device, bsq_random_mask_host, bsq_onehot_device_multi, bsq_onehot_multi_plan; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -155,6 +155,36 @@ typedef struct bsq_batch {
 } bsq_batch;
 bsq_status bsq_tokenize_device_multi(const bsq_desc *d, int32_t n, const bsq_batch *batches, int64_t P, int32_t batch_first,
                                      bsq_dtype t, void *hip_stream);
+/* The same for the one-hot: n packed batches of ONE tokenizer, padlen, layout and element type, each with its own characters, offsets,
+ * optional mask and output.  layout 0: (P, B_i, C) as bsq_onehot_device; 1: (B_i, C, P) as bsq_onehot_bcl_device.  The results equal n
+ * calls of that function on the same stream, byte for byte, for any shape, dtype, mask, alignment and n.  Batches are taken in groups of
+ * up to eight non-empty ones (B == 0 is skipped); inside a group every batch takes the kernel family its single call takes, and the batches
+ * of one fusable family whose kernels match share that family's launch(es):
+ *   1  chunk-owner (P,B,C) one-hot (k_onehot_chunks; small and mid-size outputs, masked or not)      -> ONE k_onehot_chunks_multi launch
+ *   2  unmasked two-pass (P,B,C) one-hot in ONE piece (no position slices, no sequence blocks), with the same id form (bytes / nibbles),
+ *      expansion kernel and launch parameters, while the batches' ids together stay within the one-piece limit of 128 MB
+ *                                                                  -> ONE raw-id launch into one scratch + ONE expansion launch
+ *   3  channels-first (B,C,P) chunk stream (k_tokenize_chunks; below 256 MB, 16-byte aligned output, P % (16 / sizeof(T)) == 0, masked or not)
+ *                                                                  -> ONE k_tokenize_chunks_multi launch
+ *   0  everything else (tiled, generic, sliced or sequence-blocked two-pass, masked two-pass, (B,C,P) two-pass, the ragged (B,C,P) form),
+ *      and a family with a single member in its group: the batch's single call, in order.
+ * Outputs must not overlap; chars, offsets and masks may be shared between batches.  n < 0, a null table with n > 0 or a layout other
+ * than 0 / 1: BSQ_ERR_INVALID_ARG; a bad dtype: BSQ_ERR_DTYPE; and the per-batch checks of the single calls.  Every argument of every batch
+ * is checked before the first launch: an error leaves every output untouched. */
+typedef struct bsq_onehot_batch {
+    const uint8_t *chars;   /* device: packed characters */
+    const int64_t *offsets; /* device: B + 1 offsets into chars */
+    const uint8_t *mask;    /* device, one byte per character (0 = masked, as bsq_onehot_device), or NULL */
+    int64_t B;              /* sequences */
+    void *out;              /* device: the batch's own result, (P, B, C) or (B, C, P), contiguous */
+} bsq_onehot_batch;
+bsq_status bsq_onehot_device_multi(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, int32_t layout, bsq_dtype t,
+                                   void *hip_stream);
+/* Host only; never dereferences the batches' pointers (it reads their values, for alignment): which batches bsq_onehot_device_multi would
+ * fuse.  family[i] (n entries, may be NULL): 0 = runs as its own single call (or B == 0), 1 / 2 / 3 = the fused families above.  Returns
+ * the number of fused launches (a family-2 set counts two), or a negative bsq_status. */
+int32_t bsq_onehot_multi_plan(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, int32_t layout, bsq_dtype t,
+                              int32_t *family);
 /* Name of the kernel(s) bsq_onehot_device would launch for this shape (profiling / bench labels). */
 const char *bsq_onehot_kernel_name(const bsq_desc *d, int64_t B, int64_t P, bsq_dtype t);
 /* The same for bsq_tokenize_device (augment = 0) and bsq_augment_tokenize_device (augment = its chain_len > 0), for a 16-byte aligned
