@@ -16,6 +16,7 @@ DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bsq_diag.h")
 
 I8, I16, I32, U64, F32, F64 = range(6)
 SPACE_HOST, SPACE_DEVICE = 0, 1
+CROP_RANDOM, CROP_HEAD, CROP_CENTER = range(3)
 OK, ERR_INVALID_KEY, ERR_INVALID_ARG, ERR_DTYPE, ERR_SEQ_TOO_LONG, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = range(8)
 
 
@@ -29,6 +30,12 @@ class Mlm(ctypes.Structure):
     """struct bsq_mlm"""
     _fields_ = [("frac", ctypes.c_double), ("mask_prob", ctypes.c_double), ("random_prob", ctypes.c_double), ("mask_token", ctypes.c_int64),
                 ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
+
+
+class Crop(ctypes.Structure):
+    """struct bsq_crop"""
+    _fields_ = [("window", ctypes.c_int64), ("mode", ctypes.c_int32), ("revcomp_frac", ctypes.c_double), ("seed", ctypes.c_uint64),
+                ("first_row", ctypes.c_int64)]
 
 
 class Batch(ctypes.Structure):
@@ -116,6 +123,10 @@ def load():
         "bsq_random_mask_device": (i32, [dp, vp, vp, i64, ctypes.POINTER(Mlm), vp, vp]),
         "bsq_random_mask_host": (i32, [dp, vp, vp, i64, ctypes.POINTER(Mlm), vp]),
         "bsq_gather_packed_device": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "bsq_crop_packed_device": (i32, [vp, vp, i64, vp, i64, ctypes.POINTER(Crop), vp, i64, vp, vp, vp, vp, vp]),
+        "bsq_crop_plan_host": (i32, [vp, i64, vp, i64, ctypes.POINTER(Crop), vp, vp, vp]),
+        "bsq_views_packed_device": (i32, [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp]),
+        "bsq_complement_table": (i32, [vp]),
         "bsq_blosum62_normrows": (i32, [vp]),
         "bsq_augment_device": (i32, [vp, vp, i64, i32, ctypes.c_double, ctypes.c_uint64, vp]),
         "bsq_augment_tokenize_device": (i32, [vp, vp, vp, i64, i64, i32, i32, vp, i32, ctypes.c_double, ctypes.c_uint64, vp]),

@@ -259,6 +259,22 @@ class FlatFile:
             raise IndexError("Accessing sequence out of range (position %d of the index list)" % (bad % max(n, 1)))
         return (out_chars[:capacity] if not on_device else out_chars), out_offs
 
+    def windows_device(self, window, stride=None, start=0, stop=None, device="cuda", both_strands=False):
+        """Sequences [start, stop) tiled into windows of at most `window` characters (`views.tile_plan`: starts 0, stride, 2 * stride,
+        ... and one window ending at the sequence's end; both_strands: each window forward, then reverse-complemented), cut from the
+        uploaded store on the device (`views.gather_views`).  Returns (chars, offsets, (seq, start, strand)): the packed views and,
+        per row, the store index of its sequence, the view's start in it and its strand (numpy arrays) -- what maps an inference
+        result back to its sequence."""
+        from . import views
+        stop = self._n if stop is None else min(int(stop), self._n)
+        start = max(0, int(start))
+        seq, vstart, vlen, strand = views.tile_plan(np.diff(self._offsets[start:max(start, stop) + 1]), window, stride, both_strands,
+                                                    lengths=True)
+        seq = seq + start
+        chars, offs = self.to_device(device)
+        out_chars, out_offs = views.gather_views(chars, offs, seq, vstart, vlen, strand if both_strands else None, validate=False)
+        return out_chars, out_offs, (seq, vstart, strand)
+
     def _top_lengths_cumsum(self):
         """cumsum of the store's sequence lengths in descending order: entry n - 1 bounds the characters of any n distinct sequences."""
         if self._top_cum is None:

@@ -32,7 +32,8 @@ extern "C" {
 
 #define BSQ_ABI_VERSION 7 /* 7 (round 6): bsq_tokenize_device_multi, bsq_augment_device_multi, bsq_augment_tokenize_device_multi, bsq_enable_peer_access, bsq_tokenize_kernel_name; nothing removed.
                            * Added since, without a version bump (nothing changed or removed): bsq_mlm, bsq_mlm_tokenize_device,
-                           * bsq_random_mask_device, bsq_random_mask_host, bsq_onehot_device_multi, bsq_onehot_multi_plan; nothing removed */
+                           * bsq_random_mask_device, bsq_random_mask_host, bsq_onehot_device_multi, bsq_onehot_multi_plan,
+                           * bsq_crop_packed_device, bsq_crop_plan_host, bsq_views_packed_device, bsq_complement_table; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -338,6 +339,57 @@ bsq_status bsq_random_mask_host(const bsq_desc *d, const uint8_t *chars, const i
 bsq_status bsq_gather_packed_device(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index,
                                     int64_t n, uint8_t *out_chars, int64_t out_capacity, int64_t *out_offsets,
                                     int64_t *status_dev, void *hip_stream);
+
+/* ---- views of a packed store: fixed-width crops and reverse-complement strands, rebuilt on the device as a packed batch that
+ * every encode path takes as it is.  Every encode path requires len + bos + eos <= padlen (the reference aborts on a longer
+ * sequence, tokenize.h:359-362), so without this one outlier of the store sets the width of every batch.
+ *
+ * THE DRAW.  A row's view depends on (seed, row, L, window, mode, revcomp_frac) only: row = first_row + i for row i of the call,
+ * L = the length of its source sequence -- never on the batch size, how a batch is cut into shards, the stream or the launch form.
+ * With mix64 the splitmix64 finalizer and mulhi64(a, b) the high 64 bits of the 128-bit product a * b:
+ *     h_row  = mix64((seed ^ 0x43524F5056494557) + 0x9E3779B97F4A7C15 * (row + 1))
+ *     length = L                                 if window == 0 or L <= window
+ *              window                            otherwise
+ *     start  = 0                                 if length == L
+ *              mulhi64(h_row, L - window + 1)    BSQ_CROP_RANDOM  (uniform in [0, L - window])
+ *              0                                 BSQ_CROP_HEAD
+ *              (L - window) / 2                  BSQ_CROP_CENTER
+ *     rc     = (mix64(~h_row) >> 48) < T_rc,  T_rc = floor(revcomp_frac * 65536 + 0.5)     (revcomp_frac = 1: always)
+ *     out[k] = src[start + k]                                forward
+ *              comp(src[start + length - 1 - k])             reverse complement
+ * comp is a fixed 256-byte involution that keeps the case: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H in upper and lower case;
+ * every other byte (N, S, W, the other letters, every non-letter) maps to itself.  bsq_complement_table copies it out.
+ *
+ * Conventions of bsq_gather_packed_device: stream-ordered, never synchronises; *status_dev (device int64, may be NULL) = -1 ok,
+ * i in [0, n) = row i was a bad index or an out-of-range view (it becomes an empty row; its start and strand read 0), n + i = row i
+ * did not fit into out_capacity bytes (the batch is cut there, nothing is written past the buffer).  n * window always suffices
+ * when window > 0.  Argument errors (BSQ_ERR_INVALID_ARG, nothing launched): window < 0, an unknown mode, revcomp_frac outside
+ * [0, 1] or NaN, first_row < 0, null pointers, index_or_null == NULL with n > n_store.  Lists of up to 4096 rows take ONE launch. */
+enum { BSQ_CROP_RANDOM = 0, BSQ_CROP_HEAD = 1, BSQ_CROP_CENTER = 2 };
+typedef struct bsq_crop {
+    int64_t window;      /* >= 0; 0 = no cropping (the strand draw only) */
+    int32_t mode;        /* BSQ_CROP_RANDOM, BSQ_CROP_HEAD or BSQ_CROP_CENTER */
+    double revcomp_frac; /* share of the rows that are reverse-complemented, in [0, 1] */
+    uint64_t seed;
+    int64_t first_row;   /* row key of the call's first row (a shard or a piece of a larger list: its first row there), >= 0 */
+} bsq_crop;
+/* Row i = store sequence index[i] (index_or_null == NULL: sequence i, n <= n_store) viewed as above.  starts_or_null[i] <- the
+ * view's start in its source sequence, strand_or_null[i] <- 1 if it was reverse-complemented, else 0. */
+bsq_status bsq_crop_packed_device(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index_or_null, int64_t n,
+                                  const bsq_crop *c, uint8_t *out_chars, int64_t out_capacity, int64_t *out_offsets,
+                                  int64_t *starts_or_null, uint8_t *strand_or_null, int64_t *status_dev, void *hip_stream);
+/* CPU twin of the draw (the same code): starts / lengths / strand of every row, from the store's offsets on the host.  An index
+ * out of [0, n_store) is an argument error here. */
+bsq_status bsq_crop_plan_host(const int64_t *offsets, int64_t n_store, const int64_t *index_or_null, int64_t n, const bsq_crop *c,
+                              int64_t *starts, int64_t *lengths, uint8_t *strand);
+/* Explicit views (inference tiling): row i = length[i] characters of store sequence seq[i] from start[i], reverse-complemented
+ * when strand_or_null[i] != 0 (NULL: every row forward).  A view outside its sequence (start < 0, length < 0, start + length > L)
+ * or a bad seq[i] is an empty row reported in *status_dev. */
+bsq_status bsq_views_packed_device(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *seq, const int64_t *start,
+                                   const int64_t *length, const uint8_t *strand_or_null, int64_t n, uint8_t *out_chars, int64_t out_capacity,
+                                   int64_t *out_offsets, int64_t *status_dev, void *hip_stream);
+/* out[c] <- comp(c) for every byte c: the library's own complement table. */
+bsq_status bsq_complement_table(uint8_t out[256]);
 
 /* ---- FASTA / FASTQ (plain or gzip) -> FlatFile on the host: replaces FlatFile::make (fxstats.cpp:33-64) and getlens /
  * getstats (:12-23, :202-219).  Same record grammar as the reference's kseq loop (bsq_fastx.cpp lists it), but streaming:
