@@ -15,11 +15,7 @@ namespace {
 
 using namespace bsq_dev;
 
-bsq_status check_launch(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-    return BSQ_OK;
-}
+using bsq_internal::check_launch;
 
 __global__ __launch_bounds__(kThreads) void k_fill(uint4 *dst, size_t n16, uint32_t pattern) {
     const size_t stride = static_cast<size_t>(gridDim.x) * kThreads;

@@ -116,11 +116,7 @@ __global__ __launch_bounds__(kThreads) void k_first_too_long(const int64_t *offs
     }
 }
 
-bsq_status check_launch(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-    return BSQ_OK;
-}
+using bsq_internal::check_launch;
 
 void fill_generic(GParams &g, const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, const uint8_t *mask,
                   int64_t B, int64_t P, int batch_first, void *out) {

@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cstdint>
 #include <mutex>
+#include <type_traits>
 
 #include "bsq.h"
 
@@ -11,6 +13,47 @@ namespace bsq_internal {
 // Record a thread-local error message (returned by bsq_last_error()) and pass the status through.
 bsq_status set_error(bsq_status st, const char *msg);
 bsq_status set_hip_error(const char *what, hipError_t e);
+// The status of the launch just enqueued (`what`: the kernel's name, for the message).
+inline bsq_status check_launch(const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? set_hip_error(what, e) : BSQ_OK;
+}
+
+// Run-time flags as compile-time constants: f(std::true_type / std::false_type ...), one argument per flag, in order.  A launcher names
+// its kernel ONCE, as k<NT(), ...>, inside a generic lambda; every combination of the flags is instantiated, so a ladder that is
+// deliberately partial guards the missing variants with `if constexpr` in the lambda.
+template <typename F>
+auto with_flags(F &&f) {
+    return f();
+}
+template <typename F, typename... Bs>
+auto with_flags(F &&f, bool b, Bs... rest) {
+    return b ? with_flags([&](auto... cs) { return f(std::true_type{}, cs...); }, rest...)
+             : with_flags([&](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
+}
+// f(ST{}) with the unsigned integer of `sz` bytes (the kernels that move elements as bit patterns; sz: 1, 2, 4, else 8).
+template <typename F>
+auto with_elem_size(size_t sz, F &&f) {
+    switch (sz) {
+    case 1: return f(uint8_t{});
+    case 2: return f(uint16_t{});
+    case 4: return f(uint32_t{});
+    default: return f(uint64_t{});
+    }
+}
+// f(T{}) with the value type of `t` (the kernels that convert token values); f returns a bsq_status.
+template <typename F>
+bsq_status with_value_type(bsq_dtype t, F &&f) {
+    switch (t) {
+    case BSQ_I8: return f(int8_t{});
+    case BSQ_I16: return f(int16_t{});
+    case BSQ_I32: return f(int32_t{});
+    case BSQ_U64: return f(uint64_t{});
+    case BSQ_F32: return f(float{});
+    case BSQ_F64: return f(double{});
+    }
+    return set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
+}
 // Tuning / diagnostic knobs (bsq_tuning_set, or environment BSQ_<NAME> read once, at the first launch):
 // (speed only -- results never depend on them; every variant is covered by the GPU parity tests.  The knobs of experiments that lost
 //  -- chunks_cpw, tokenize_nch, expand_mode, xcd_claim, chunk_math, tokens8_abl, tokens8_ring, augment_mode, raw_mode 2 / 3 -- left the
@@ -94,6 +137,7 @@ std::mutex &workspace_mutex();
 bool tokens_bp8_applicable(const bsq_desc *d, int64_t B, int64_t P, const void *out);
 int64_t tokens_bp8_chunks(int64_t B, int64_t P);                                              // 4-KiB chunks of the (B,P) int8 matrix
 bool tokens_bp8_fast_form(const bsq_desc *d, int64_t B, int64_t P, bool aligned_out);         // k_tokens_bp8_fast (else k_tokens_bp8)
+bool tokens_bp8_fused_form(const bsq_desc *d, int64_t B, int64_t P, bool aligned_out);        // augmentation in the token launch (one of the two forms below)
 bool tokens_bp8_nowait_form(int64_t nchunks);                                                 // fused augmentation: no-wait form (else the flag form)
 // raw = false: token VALUES (batch_tokenize); raw = true: ids with BSQ_NO_TOKEN (255) where a one-hot row is all zero
 // fuse != nullptr: the BLOSUM62 augmentation of `fuse->chars` (the same buffer as `chars`) in the SAME launch when the fast form applies

@@ -272,11 +272,7 @@ bsq_status fill_params(MlmParams &p, const bsq_desc *d, const uint8_t *chars, co
 
 bool dtype_ok(bsq_dtype t) { return t >= BSQ_I8 && t <= BSQ_F64; }
 
-bsq_status check_launch(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-    return BSQ_OK;
-}
+using bsq_internal::check_launch;
 
 template <typename TI>
 bsq_status launch_bp_in(const MlmParams &p, bsq_dtype tl, unsigned grid, hipStream_t s) {

@@ -791,10 +791,8 @@ bsq_status launch_onehot_tile(const KParams &k, hipStream_t s) {
     const size_t smem = tile_fixed_bytes<TB>() + 4 * size_t(row_pad);
     const int64_t ntt = (k.P + kTT - 1) / kTT;
     const int64_t grid = tile_grid(k, ntt);
-    if (bsq_internal::nontemporal_stores())
-        hipLaunchKernelGGL((k_onehot_tile<ST, TB, true>), dim3(unsigned(grid)), dim3(kThreads), smem, s, k);
-    else
-        hipLaunchKernelGGL((k_onehot_tile<ST, TB, false>), dim3(unsigned(grid)), dim3(kThreads), smem, s, k);
+    with_flags([&](auto NT) { hipLaunchKernelGGL((k_onehot_tile<ST, TB, NT()>), dim3(unsigned(grid)), dim3(kThreads), smem, s, k); },
+               bsq_internal::nontemporal_stores());
     return check_launch("k_onehot_tile");
 }
 
@@ -1063,13 +1061,16 @@ __global__ __launch_bounds__(kThreads) void k_onehot_chunks_multi(const CMulti p
     onehot_chunks_body<ST, NT>(blockIdx.x - p.m.first_block[i], p.lut, p.m.b[i]);
 }
 
-// grid of one batch's chunk-owner stream (a multiple of 8 blocks)
-int64_t chunks_grid(const CFields &c) {
+// grid of one batch's chunk-owner stream (a multiple of 8 blocks); F: CParams or CFields
+template <typename F>
+int64_t chunks_grid(const F &c) {
     const int64_t per_class = (c.nchunks + 7) / 8;
     return (per_class + int64_t(4) * c.cpw - 1) / (int64_t(4) * c.cpw) * 8;
 }
 
-// Occupancy cap of the chunk-owner kernels (unused dynamic LDS; see launch_chunks)
+// Occupancy cap of the chunk-owner kernels through unused dynamic LDS: 4 workgroups per CU (17 KiB + 22 KiB each) stream at 7.2 TB/s
+// on cfg3; 5 (the VGPR limit) at 6.9, 3 at 6.6, 2 at 4.8 (profiles/r01/chunks_occupancy.txt).  The same
+// holds for a plain fill: 6.8 TB/s at 8 workgroups per CU, 7.4 at 3.  Knob "chunks_pad" overrides (bytes).
 size_t chunks_pad() {
     const int padv = bsq_internal::tuning().chunks_pad;
     return padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(22528));
@@ -1077,27 +1078,15 @@ size_t chunks_pad() {
 
 template <typename ST>
 bsq_status launch_chunks_multi(const CMulti &c, int64_t blocks, hipStream_t s) {
-    if (bsq_internal::nontemporal_stores())
-        hipLaunchKernelGGL((k_onehot_chunks_multi<ST, true>), dim3(unsigned(blocks)), dim3(kThreads), chunks_pad(), s, c);
-    else
-        hipLaunchKernelGGL((k_onehot_chunks_multi<ST, false>), dim3(unsigned(blocks)), dim3(kThreads), chunks_pad(), s, c);
+    with_flags([&](auto NT) { hipLaunchKernelGGL((k_onehot_chunks_multi<ST, NT()>), dim3(unsigned(blocks)), dim3(kThreads), chunks_pad(), s, c); },
+               bsq_internal::nontemporal_stores());
     return check_launch("k_onehot_chunks_multi");
 }
 
 template <typename ST>
 bsq_status launch_chunks(const CParams &c, hipStream_t s) {
-    const int64_t per_class = (c.nchunks + 7) / 8;
-    const int64_t groups = (per_class + int64_t(4) * c.cpw - 1) / (int64_t(4) * c.cpw);
-    const dim3 grid(unsigned(groups * 8));
-    // Occupancy cap through unused dynamic LDS: 4 workgroups per CU (17 KiB + 22 KiB each) stream at 7.2 TB/s
-    // on cfg3; 5 (the VGPR limit) at 6.9, 3 at 6.6, 2 at 4.8 (profiles/r01/chunks_occupancy.txt).  The same
-    // holds for a plain fill: 6.8 TB/s at 8 workgroups per CU, 7.4 at 3.  Knob "chunks_pad" overrides (bytes).
-    const int padv = bsq_internal::tuning().chunks_pad;
-    const size_t pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(22528));
-    if (bsq_internal::nontemporal_stores())
-        hipLaunchKernelGGL((k_onehot_chunks<ST, true>), grid, dim3(kThreads), pad, s, c);
-    else
-        hipLaunchKernelGGL((k_onehot_chunks<ST, false>), grid, dim3(kThreads), pad, s, c);
+    with_flags([&](auto NT) { hipLaunchKernelGGL((k_onehot_chunks<ST, NT()>), dim3(unsigned(chunks_grid(c))), dim3(kThreads), chunks_pad(), s, c); },
+               bsq_internal::nontemporal_stores());
     return check_launch("k_onehot_chunks");
 }
 
@@ -1133,162 +1122,95 @@ bsq_status onehot_chunk_owner(const KParams &k, size_t sz, hipStream_t s) {
     CParams c;
     for (int i = 0; i < 256; ++i) c.lut[i] = k.lut[i];
     if (!chunk_owner_fields(k, sz, c)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    switch (sz) {
-    case 1: return launch_chunks<uint8_t>(c, s);
-    case 2: return launch_chunks<uint16_t>(c, s);
-    case 4: return launch_chunks<uint32_t>(c, s);
-    default: return launch_chunks<uint64_t>(c, s);
-    }
+    return with_elem_size(sz, [&](auto z) { return launch_chunks<decltype(z)>(c, s); });
 }
 
-// Which expansion kernel a (P,B,C) expansion runs, and its occupancy pad (launch_expand, launch_expand_multi).
-struct ExpandChoice {
-    bool rows1;   // k_expand_rows1<NR> (else k_expand_chunks)
-    int nr;
-    bool gated;   // k_expand_chunks<..., GATE>
-    size_t pad;   // unused dynamic LDS
-};
-template <typename ST>
-ExpandChoice expand_choice(const EParams &e) {
-    ExpandChoice c;
-    c.rows1 = false;
-    c.nr = 0;
-    c.gated = false;
-    const int padv = bsq_internal::tuning().expand_pad;
-    const bool big_rows = e.C * int64_t(sizeof(ST)) >= 64;
-    // (nibble ids, rows below 64 bytes: 12 KiB = FIVE workgroups per CU -- 16 KiB + the 16-KiB image + the kernel's few bytes of static LDS
-    //  round up to four; cfg4 f32 with nibbles 714 us at four, 648 at five, 662 at six; byte ids 673 / 690 / 703: profiles/r05/nibble_ids_lab.txt)
-    c.pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : (big_rows ? size_t(36864) : (e.nib ? size_t(12288) : size_t(16384))));
+// Which kernel a (P,B,C) expansion runs and under which occupancy cap -- decided here for launch_expand and launch_expand_multi alike, and
+// handed to `launch` as compile-time constants: launch(NR, NT, GATE, NIB, pad) with NR = std::integral_constant<int, rows per lane> for
+// k_expand_rows1<NT, NR, NIB>, NR = 0 for k_expand_chunks<ST, NT, 0, GATE, NIB>.  Deliberately partial: k_expand_rows1 exists for one-byte
+// elements only, and k_expand_chunks<NIB> for elements of 2 bytes and more.
+//
+// Occupancy cap through unused dynamic LDS (3 x (16 KiB image + 36 KiB) = 156 KiB <= 160 KiB; 37 KiB already
+// rounds up to 2 per CU).  Rows >= 64 B (one token load per lane and chunk): 3 workgroups per CU stream
+// cfg3 at 7.5-7.8 TB/s, 8 at 6.3, 4 at 6.7, 2 at 5.5.  Smaller rows: 16 KiB + the 16-KiB image -- FOUR workgroups per CU, not the five
+// the arithmetic suggests (round 5, profiles/r05/nibble_ids_lab.txt: the step from four to five lies between pads of 16 384 and 15 360
+// bytes; byte ids 673 us at four, 690 at five, 703 at six on cfg4 f32).
+// In round 1 a cap HURT the 1M x 160 x 28-byte batch (0.90 ms at 5 per CU vs 0.78 uncapped) -- because the token pass
+// then fetched every character three times and pushed its own scratch out of the Infinity Cache; with the XCD-aware
+// tile order the token loads of the expansion are cache hits and the cap pays: 0.687 ms at 5, 0.689 at 4, 0.725 at
+// 3, 0.731 uncapped (profiles/r02/pad_lab2.txt, pad_lab3.txt).  12 waves per CU is
+// the optimum also with 2-wave workgroups (16 / 14 / 12 / 10 waves: 0.83 / 0.81 / 0.76 / 0.93 ms), and 3 x 4 waves
+// (0.73 ms) beats 6 x 2.
+// Knob "expand_pad": 0 = this rule, > 0 = that many bytes, < 0 = none.
+// (k_expand_small -- dword token loads -- lost: once the token scratch is written in XCD-aware tile order the byte-load kernel under
+// an occupancy cap is 1-2 % ahead of it, and two or four chunks per wave were 20-40 % slower: profiles/r02/pad_lab*.txt, expand_lab3.txt;
+// its source is csrc/labs/bsq_expand_small.inc.)
+template <typename ST, typename L>
+bsq_status expand_select(const EParams &e, L &&launch) {
+    const auto &tn = bsq_internal::tuning();
+    const int padv = tn.expand_pad;
+    auto pad_of = [&](size_t automatic) { return padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : automatic); };
+    const int64_t rowb = e.C * int64_t(sizeof(ST));
+    const bool nt = bsq_internal::nontemporal_stores();
     // (Scalar 64-bit reciprocal multiplies instead of the double reciprocals for the chunk arithmetic: ~90 SALU instructions instead of
     // ~130 VALU ones, ahead where a wave's latency is exposed (2 workgroups per CU: 0.938 vs 0.969 ms on cfg3) and 1 % BEHIND at the
     // bandwidth optimum (3 per CU: 0.741 vs 0.734 ms) -- profiles/r02/math_lab1.txt; not built any more.)
     // one-byte elements, rows of 3 ... 15 bytes: the LDS-free form (knob "expand_rows1": 0 automatic, 1 never, 2 whenever it applies)
     if constexpr (sizeof(ST) == 1) {
-        const int rk = bsq_internal::tuning().expand_rows1;
-        const int rb = e.C;
-        if (rk != 1 && rb >= 3 && rb <= 15) {
-            c.rows1 = true;
-            c.nr = (rb + 14) / rb + 1;  // rows a lane's 16 bytes can touch: 6, 5, 4, 4, 4, 3 ... 3, 2
-            c.pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(32768));  // (no static LDS here: 5 workgroups per CU)
-            return c;
+        if (tn.expand_rows1 != 1 && rowb >= 3 && rowb <= 15) {
+            const size_t pad = pad_of(32768);  // (no static LDS here: 5 workgroups per CU)
+            auto rows = [&](auto NR) { return with_flags([&](auto NT, auto NIB) { return launch(NR, NT, std::false_type{}, NIB, pad); }, nt, e.nib != 0); };
+            switch ((rowb + 14) / rowb + 1) {  // rows a lane's 16 bytes can touch: 6, 5, 4, 4, 4, 3 ... 3, 2
+            case 2: return rows(std::integral_constant<int, 2>{});
+            case 3: return rows(std::integral_constant<int, 3>{});
+            case 4: return rows(std::integral_constant<int, 4>{});
+            case 5: return rows(std::integral_constant<int, 5>{});
+            case 6: return rows(std::integral_constant<int, 6>{});
+            default: return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "k_expand_rows1: rows per lane");
+            }
         }
     }
+    // (nibble ids, rows below 64 bytes: 12 KiB = FIVE workgroups per CU -- 16 KiB + the 16-KiB image + the kernel's few bytes of static LDS
+    //  round up to four; cfg4 f32 with nibbles 714 us at four, 648 at five, 662 at six; byte ids 673 / 690 / 703: profiles/r05/nibble_ids_lab.txt)
+    const size_t pad = pad_of(rowb >= 64 ? size_t(36864) : (e.nib ? size_t(12288) : size_t(16384)));
     // knob "expand_gate": 0 automatic (rows of 24 ... 63 bytes), 1 never, 2 always (the scratch holds at least 256 bytes: Bp >= 256)
-    const int gk = bsq_internal::tuning().expand_gate;
-    const int64_t rowb = e.C * int64_t(sizeof(ST));
-    c.gated = (gk == 2 || (gk == 0 && rowb >= 24 && rowb < 64)) && e.Bp >= 256;
-    return c;
+    const int gk = tn.expand_gate;
+    const bool gated = (gk == 2 || (gk == 0 && rowb >= 24 && rowb < 64)) && e.Bp >= 256;
+    constexpr std::integral_constant<int, 0> kChunks{};
+    if constexpr (sizeof(ST) >= 2) {
+        if (e.nib)  // ids as nibbles (two_pass_nibbles)
+            return with_flags([&](auto NT, auto GATE) { return launch(kChunks, NT, GATE, std::true_type{}, pad); }, nt, gated);
+    }
+    if (e.nib) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "nibble ids: elements of 2 bytes and more, or one-byte rows of 3 ... 15 bytes");
+    return with_flags([&](auto NT, auto GATE) { return launch(kChunks, NT, GATE, std::false_type{}, pad); }, nt, gated);
 }
+
+// grid of one batch's expansion stream (a multiple of 8 blocks: one chunk per wave, 4 waves per workgroup)
+int64_t expand_grid(const EParams &e) { return ((e.nchunks + 7) / 8 + 3) / 4 * 8; }
 
 template <typename ST>
 bsq_status launch_expand(const EParams &e, hipStream_t s) {
-    const int64_t per_class = (e.nchunks + 7) / 8;
-    const int64_t groups = (per_class + 3) / 4;
-    if (groups * 8 >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    const dim3 grid(unsigned(groups * 8));
-    // Occupancy cap through unused dynamic LDS (3 x (16 KiB image + 36 KiB) = 156 KiB <= 160 KiB; 37 KiB already
-    // rounds up to 2 per CU).  Rows >= 64 B (one token load per lane and chunk): 3 workgroups per CU stream
-    // cfg3 at 7.5-7.8 TB/s, 8 at 6.3, 4 at 6.7, 2 at 5.5.  Smaller rows: 16 KiB + the 16-KiB image -- FOUR workgroups per CU, not the five
-    // the arithmetic suggests (round 5, profiles/r05/nibble_ids_lab.txt: the step from four to five lies between pads of 16 384 and 15 360
-    // bytes; byte ids 673 us at four, 690 at five, 703 at six on cfg4 f32).
-    // In round 1 a cap HURT the 1M x 160 x 28-byte batch (0.90 ms at 5 per CU vs 0.78 uncapped) -- because the token pass
-    // then fetched every character three times and pushed its own scratch out of the Infinity Cache; with the XCD-aware
-    // tile order the token loads of the expansion are cache hits and the cap pays: 0.687 ms at 5, 0.689 at 4, 0.725 at
-    // 3, 0.731 uncapped (profiles/r02/pad_lab2.txt, pad_lab3.txt).  12 waves per CU is
-    // the optimum also with 2-wave workgroups (16 / 14 / 12 / 10 waves: 0.83 / 0.81 / 0.76 / 0.93 ms), and 3 x 4 waves
-    // (0.73 ms) beats 6 x 2.
-    // Knob "expand_pad": 0 = this rule, > 0 = that many bytes, < 0 = none.
-    // (k_expand_small -- dword token loads -- lost: once the token scratch is written in XCD-aware tile order the byte-load kernel under
-    // an occupancy cap is 1-2 % ahead of it, and two or four chunks per wave were 20-40 % slower: profiles/r02/pad_lab*.txt, expand_lab3.txt;
-    // its source is csrc/labs/bsq_expand_small.inc.)
-    const ExpandChoice ch = expand_choice<ST>(e);
-    const size_t pad = ch.pad;
-    if constexpr (sizeof(ST) == 1) {
-        if (ch.rows1) {
-            const size_t rpad = ch.pad;
-            const bool nt = bsq_internal::nontemporal_stores();
-#define BSQ_ROWS1(NRV)                                                                                       \
-    case NRV:                                                                                                \
-        if (e.nib) {                                                                                         \
-            if (nt) hipLaunchKernelGGL((k_expand_rows1<true, NRV, true>), grid, dim3(kThreads), rpad, s, e); \
-            else hipLaunchKernelGGL((k_expand_rows1<false, NRV, true>), grid, dim3(kThreads), rpad, s, e);   \
-        } else {                                                                                             \
-            if (nt) hipLaunchKernelGGL((k_expand_rows1<true, NRV>), grid, dim3(kThreads), rpad, s, e);       \
-            else hipLaunchKernelGGL((k_expand_rows1<false, NRV>), grid, dim3(kThreads), rpad, s, e);         \
-        }                                                                                                    \
-        break;
-            switch (ch.nr) {
-                BSQ_ROWS1(2) BSQ_ROWS1(3) BSQ_ROWS1(4) BSQ_ROWS1(5) BSQ_ROWS1(6)
-            default: return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "k_expand_rows1: rows per lane");
-            }
-#undef BSQ_ROWS1
-            return check_launch(e.nib ? "k_expand_rows1<nibbles>" : "k_expand_rows1");
-        }
-    }
-    const bool gated = ch.gated;
-    if constexpr (sizeof(ST) >= 2) {
-        if (e.nib) {  // ids as nibbles (two_pass_nibbles)
-#define BSQ_EXPN(NTV, GV) hipLaunchKernelGGL((k_expand_chunks<ST, NTV, 0, GV, true>), grid, dim3(kThreads), pad, s, e)
-            if (bsq_internal::nontemporal_stores()) { if (gated) BSQ_EXPN(true, true); else BSQ_EXPN(true, false); }
-            else { if (gated) BSQ_EXPN(false, true); else BSQ_EXPN(false, false); }
-#undef BSQ_EXPN
-            return check_launch("k_expand_chunks<nibbles>");
-        }
-    }
-    if (e.nib) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "nibble ids: elements of 2 bytes and more, or one-byte rows of 3 ... 15 bytes");
-    if (bsq_internal::nontemporal_stores()) {
-        if (gated) hipLaunchKernelGGL((k_expand_chunks<ST, true, 0, true>), grid, dim3(kThreads), pad, s, e);
-        else hipLaunchKernelGGL((k_expand_chunks<ST, true, 0>), grid, dim3(kThreads), pad, s, e);
-    } else {
-        if (gated) hipLaunchKernelGGL((k_expand_chunks<ST, false, 0, true>), grid, dim3(kThreads), pad, s, e);
-        else hipLaunchKernelGGL((k_expand_chunks<ST, false, 0>), grid, dim3(kThreads), pad, s, e);
-    }
-    return check_launch("k_expand_chunks");
+    const int64_t blocks = expand_grid(e);
+    if (blocks >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    const dim3 grid{unsigned(blocks)};
+    return expand_select<ST>(e, [&](auto NR, auto NT, auto GATE, auto NIB, size_t pad) {
+        if constexpr (NR() != 0) hipLaunchKernelGGL((k_expand_rows1<NT(), NR(), NIB()>), grid, dim3(kThreads), pad, s, e);
+        else hipLaunchKernelGGL((k_expand_chunks<ST, NT(), 0, GATE(), NIB()>), grid, dim3(kThreads), pad, s, e);
+        return check_launch(NR() != 0 ? (NIB() ? "k_expand_rows1<nibbles>" : "k_expand_rows1") : (NIB() ? "k_expand_chunks<nibbles>" : "k_expand_chunks"));
+    });
 }
 
-
-// The expansions of several batches (family 2 of bsq_onehot_device_multi) in one launch: the kernel expand_choice picks for m.b[0], which the
+// The expansions of several batches (family 2 of bsq_onehot_device_multi) in one launch: the kernel expand_select picks for m.b[0], which the
 // plan made the same for every batch of the launch.
 template <typename ST>
 bsq_status launch_expand_multi(const OnehotMulti<EParams> &m, int64_t blocks, hipStream_t s) {
-    const EParams &e = m.b[0];
-    const ExpandChoice ch = expand_choice<ST>(e);
     const dim3 grid{unsigned(blocks)};
-    const size_t pad = ch.pad;
-    const bool nt = bsq_internal::nontemporal_stores();
-    if constexpr (sizeof(ST) == 1) {
-        if (ch.rows1) {
-#define BSQ_ROWS1M(NRV)                                                                                           \
-    case NRV:                                                                                                     \
-        if (e.nib) {                                                                                              \
-            if (nt) hipLaunchKernelGGL((k_expand_rows1_multi<true, NRV, true>), grid, dim3(kThreads), pad, s, m); \
-            else hipLaunchKernelGGL((k_expand_rows1_multi<false, NRV, true>), grid, dim3(kThreads), pad, s, m);   \
-        } else {                                                                                                  \
-            if (nt) hipLaunchKernelGGL((k_expand_rows1_multi<true, NRV>), grid, dim3(kThreads), pad, s, m);       \
-            else hipLaunchKernelGGL((k_expand_rows1_multi<false, NRV>), grid, dim3(kThreads), pad, s, m);         \
-        }                                                                                                         \
-        break;
-            switch (ch.nr) {
-                BSQ_ROWS1M(2) BSQ_ROWS1M(3) BSQ_ROWS1M(4) BSQ_ROWS1M(5) BSQ_ROWS1M(6)
-            default: return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "k_expand_rows1_multi: rows per lane");
-            }
-#undef BSQ_ROWS1M
-            return check_launch(e.nib ? "k_expand_rows1_multi<nibbles>" : "k_expand_rows1_multi");
-        }
-    }
-#define BSQ_EXPM(NTV, GV, NIBV) hipLaunchKernelGGL((k_expand_chunks_multi<ST, NTV, 0, GV, NIBV>), grid, dim3(kThreads), pad, s, m)
-    if constexpr (sizeof(ST) >= 2) {
-        if (e.nib) {
-            if (nt) { if (ch.gated) BSQ_EXPM(true, true, true); else BSQ_EXPM(true, false, true); }
-            else { if (ch.gated) BSQ_EXPM(false, true, true); else BSQ_EXPM(false, false, true); }
-            return check_launch("k_expand_chunks_multi<nibbles>");
-        }
-    }
-    if (e.nib) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "nibble ids: elements of 2 bytes and more, or one-byte rows of 3 ... 15 bytes");
-    if (nt) { if (ch.gated) BSQ_EXPM(true, true, false); else BSQ_EXPM(true, false, false); }
-    else { if (ch.gated) BSQ_EXPM(false, true, false); else BSQ_EXPM(false, false, false); }
-#undef BSQ_EXPM
-    return check_launch("k_expand_chunks_multi");
+    return expand_select<ST>(m.b[0], [&](auto NR, auto NT, auto GATE, auto NIB, size_t pad) {
+        if constexpr (NR() != 0) hipLaunchKernelGGL((k_expand_rows1_multi<NT(), NR(), NIB()>), grid, dim3(kThreads), pad, s, m);
+        else hipLaunchKernelGGL((k_expand_chunks_multi<ST, NT(), 0, GATE(), NIB()>), grid, dim3(kThreads), pad, s, m);
+        return check_launch(NR() != 0 ? (NIB() ? "k_expand_rows1_multi<nibbles>" : "k_expand_rows1_multi")
+                                      : (NIB() ? "k_expand_chunks_multi<nibbles>" : "k_expand_chunks_multi"));
+    });
 }
 
 // Two-pass one-hot: raw (P,B) tokens into `workspace` (P*B bytes), then the chunk expansion.
@@ -1359,12 +1281,7 @@ EParams expansion_params(const uint8_t *tokens, int64_t pitch, int64_t B, int64_
 bsq_status launch_expansion(const uint8_t *tokens, int64_t pitch, int64_t B, int64_t P, int32_t C, size_t sz,
                             uint64_t one_bits, void *out, hipStream_t s, int64_t row_gap = 0, bool nib = false) {
     const EParams e = expansion_params(tokens, pitch, B, P, C, sz, one_bits, out, row_gap, nib);
-    switch (sz) {
-    case 1: return launch_expand<uint8_t>(e, s);
-    case 2: return launch_expand<uint16_t>(e, s);
-    case 4: return launch_expand<uint32_t>(e, s);
-    default: return launch_expand<uint64_t>(e, s);
-    }
+    return with_elem_size(sz, [&](auto z) { return launch_expand<decltype(z)>(e, s); });
 }
 
 // How a two-pass one-hot is run (round 5).
@@ -1379,27 +1296,29 @@ bsq_status launch_expansion(const uint8_t *tokens, int64_t pitch, int64_t B, int
 //    Slices of <= 96 MB keep every size at the small batches' rate, for two more launches per slice.  Knob "two_pass_slice_mb".
 struct TwoPassPlan {
     int64_t pitch;            // ids per scratch row
+    bool pb8;                 // the raw pass is the register-transposed k_tokens_pb8_fast (launch_tokens_raw; else k_tokens_raw)
+    bool rows1;               // one-byte rows of 3 ... 15 bytes: the expansion is k_expand_rows1 (expand_select)
     bool nib, nib_ok;         // ids as nibbles; whether they could be
     bool wants_slices;        // the id matrix is too large for one piece (it may still BE one piece: a single position tile cannot be cut)
     int64_t ntt, tiles_per_slice;
     size_t ws_bytes;
 };
-TwoPassPlan two_pass_plan(const KParams &k, size_t sz) {
+TwoPassPlan two_pass_plan(const bsq_desc *d, bool masked, int64_t B, int64_t P, int32_t C, size_t sz) {
     const auto &tn = bsq_internal::tuning();
     TwoPassPlan pl;
-    pl.pitch = two_pass_pitch(k.B);  // padded: every scratch row is aligned, full-width vector stores
-    pl.ntt = (k.P + kTT - 1) / kTT;
-    const int64_t rb = k.C * int64_t(sz);
+    pl.pitch = two_pass_pitch(B);  // padded: every scratch row is aligned, full-width vector stores
+    pl.ntt = (P + kTT - 1) / kTT;
+    const int64_t rb = C * int64_t(sz);
     // the register-transposed raw pass (no mask, foldable or LDS table, ids < 251): what nibbles and slices are built on
-    const bool pb8 = !k.mask && k.desc && tn.raw_mode == 0 &&
-                     bsq_internal::tokens_pb8_applicable(k.desc, k.B, k.P, reinterpret_cast<const void *>(uintptr_t(256)), pl.pitch);
-    const bool rows1 = sz == 1 && rb >= 3 && rb <= 15 && tn.expand_rows1 != 1;  // (launch_expand: one-byte rows expand through k_expand_rows1)
-    const bool nib_ok = pb8 && k.C <= 15 && (sz >= 2 || rows1);
+    const bool pb8 = pl.pb8 = !masked && tn.raw_mode == 0 &&
+                              bsq_internal::tokens_pb8_applicable(d, B, P, reinterpret_cast<const void *>(uintptr_t(256)), pl.pitch);
+    const bool rows1 = pl.rows1 = sz == 1 && rb >= 3 && rb <= 15 && tn.expand_rows1 != 1;
+    const bool nib_ok = pb8 && C <= 15 && (sz >= 2 || rows1);
     // (automatic: rows of 24 ... 31 bytes, and every id matrix beyond 128 MB as bytes -- half the scratch to keep resident, slices of twice the rows)
     pl.nib_ok = nib_ok && tn.raw_nibbles != 1;
     // (one-byte rows through k_expand_rows1<nibbles>: ahead of byte ids on every shape tried, 2-9 % -- profiles/r05/rows1_nib_sweep.txt)
-    pl.nib = nib_ok && (tn.raw_nibbles == 2 || (tn.raw_nibbles == 0 && (rows1 || (rb >= 24 && rb < 32) || pl.pitch * k.P > (int64_t(128) << 20))));
-    const int64_t row_bytes = pl.pitch >> (pl.nib ? 1 : 0), all_bytes = row_bytes * k.P;
+    pl.nib = nib_ok && (tn.raw_nibbles == 2 || (tn.raw_nibbles == 0 && (rows1 || (rb >= 24 && rb < 32) || pl.pitch * P > (int64_t(128) << 20))));
+    const int64_t row_bytes = pl.pitch >> (pl.nib ? 1 : 0), all_bytes = row_bytes * P;
     pl.tiles_per_slice = pl.ntt;
     pl.wants_slices = false;
     const int64_t mb = tn.two_pass_slice_mb;
@@ -1414,8 +1333,8 @@ TwoPassPlan two_pass_plan(const KParams &k, size_t sz) {
             pl.tiles_per_slice = (pl.ntt + nslices - 1) / nslices;  // balanced, none above max_tiles
         }
     }
-    const int64_t rows = pl.tiles_per_slice * kTT < k.P ? pl.tiles_per_slice * kTT : k.P;
-    pl.ws_bytes = size_t(pl.tiles_per_slice == pl.ntt ? pl.pitch * k.P : row_bytes * rows);  // (one slice: the byte-sized scratch as before)
+    const int64_t rows = pl.tiles_per_slice * kTT < P ? pl.tiles_per_slice * kTT : P;
+    pl.ws_bytes = size_t(pl.tiles_per_slice == pl.ntt ? pl.pitch * P : row_bytes * rows);  // (one slice: the byte-sized scratch as before)
     return pl;
 }
 
@@ -1425,14 +1344,11 @@ TwoPassPlan two_pass_plan(const KParams &k, size_t sz) {
 // instead: column blocks of nb sequences (a multiple of 4096 / gcd(row bytes, 4096), so that every block's rows are whole chunks), each a
 // two-pass stream of its own with a gap after every position row (bsq_onehot_block_device) whose ids fit the slice target in one piece.
 // Returns nb, or 0 when the batch is not to be cut this way.
-int64_t two_pass_sequence_block(const KParams &k, size_t sz, const void *out) {
-    const TwoPassPlan pl = two_pass_plan(k, sz);
+int64_t two_pass_sequence_block(const TwoPassPlan &pl, int64_t B, int64_t P, int64_t rb) {
     // (fat position slices are fine; thin ones, and a matrix of a single tile -- padlen <= 64 -- that is too large all the same, are cut here)
     // (any alignment of the result since the ragged block form: a tensor torch placed 2560 bytes off a chunk is cut like an aligned one)
-    (void)out;
     if (!pl.wants_slices || pl.tiles_per_slice >= 4) return 0;
     const int64_t mb = bsq_internal::tuning().two_pass_slice_mb;
-    const int64_t rb = k.C * int64_t(sz);
     int64_t g = rb, h = kChunk;
     while (h) {
         const int64_t r = g % h;
@@ -1441,19 +1357,18 @@ int64_t two_pass_sequence_block(const KParams &k, size_t sz, const void *out) {
     }
     const int64_t m = kChunk / g;  // sequences per period of (b * rb) mod 4096
     const int64_t ids = (((mb > 0 ? mb : 96) << 20)) << (pl.nib_ok ? 1 : 0);  // a block's ids in one slice: 96 MB as bytes or as nibbles
-    int64_t nb = ids / k.P / m * m;
+    int64_t nb = ids / P / m * m;
     if (nb < m) nb = m;
-    if (nb >= k.B) return 0;
+    if (nb >= B) return 0;
     // blocks of equal size (2M reads as 1M + 1M, not 1.26M + 0.74M: the last, short block's launches are no cheaper per sequence)
-    const int64_t nblocks = (k.B + nb - 1) / nb;
-    const int64_t even = ((k.B + nblocks - 1) / nblocks + m - 1) / m * m;
+    const int64_t nblocks = (B + nb - 1) / nb;
+    const int64_t even = ((B + nblocks - 1) / nblocks + m - 1) / m * m;
     return even < nb ? even : nb;
 }
 
 // The caller holds nothing: the scratch is acquired here (shared by the calls of one stream -- workspace cache --, so the launches of a
 // call are enqueued back to back under the workspace mutex).
-bsq_status onehot_two_pass(KParams &k, size_t sz, hipStream_t s, int64_t row_gap = 0) {
-    const TwoPassPlan pl = two_pass_plan(k, sz);
+bsq_status onehot_two_pass(KParams &k, size_t sz, const TwoPassPlan &pl, hipStream_t s, int64_t row_gap) {
     std::lock_guard<std::mutex> two_pass_turn(bsq_internal::workspace_mutex());
     void *ws = nullptr;
     bsq_status st = bsq_internal::workspace_acquire(pl.ws_bytes, s, &ws);
@@ -1494,10 +1409,8 @@ bsq_status launch_expand_bcl(const uint8_t *tokens, int64_t B, int64_t P, int32_
     if (groups * 8 >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
     const int padv = bsq_internal::tuning().bcl_pad;  // unused dynamic LDS = occupancy cap: 0 -> 3 workgroups per CU
     const size_t pad = padv > 0 ? size_t(padv) : (padv < 0 ? size_t(0) : size_t(53248));
-    if (bsq_internal::nontemporal_stores())
-        hipLaunchKernelGGL((k_expand_bcl<T, true>), dim3(unsigned(groups * 8)), dim3(kThreads), pad, s, b);
-    else
-        hipLaunchKernelGGL((k_expand_bcl<T, false>), dim3(unsigned(groups * 8)), dim3(kThreads), pad, s, b);
+    with_flags([&](auto NT) { hipLaunchKernelGGL((k_expand_bcl<T, NT()>), dim3(unsigned(groups * 8)), dim3(kThreads), pad, s, b); },
+               bsq_internal::nontemporal_stores());
     return check_launch("k_expand_bcl");
 }
 
@@ -1566,30 +1479,80 @@ static int choose_onehot_path(int32_t C, size_t sz, int64_t B, int64_t P, bool m
     return path;
 }
 
+// The plan of one (P,B,C) one-hot -- the whole tensor (row_seqs == B) or a column block of a wider one (`out_addr`: its first element): read by
+// bsq_onehot_device, bsq_onehot_block_device, bsq_onehot_kernel_name and the multi-batch planner (multi_candidate).
+struct OnehotPlan {
+    int path;           // 0 the generic element kernel, 1 tiled, 2 two-pass, 3 chunk-owner (a column block: 0, 1 its tiles, 2 its stream)
+    int64_t seq_block;  // path 2: cut into column blocks of this many sequences, each a two-pass stream of its own (0: one stream)
+    TwoPassPlan two;    // path 2
+};
+static OnehotPlan onehot_plan(const bsq_desc *d, bool masked, int64_t B, int64_t P, size_t sz, uintptr_t out_addr, int64_t row_seqs) {
+    OnehotPlan pl{};
+    const int32_t C = bsq_alphabet_size(d);
+    const int64_t rb = C * int64_t(sz);
+    if (row_seqs == B) {
+        // Limits of the LDS kernels: 8-bit token ids, 32-bit tile arithmetic, row images must fit in LDS.
+        // (a result that does not start on a 64-byte boundary -- a view into a larger tensor -- counts as misaligned: the tiled kernel's
+        //  row segments then straddle memory sectors, cfg4 int8 16 bytes off: 225 -> 330 us tiled, 242 us two-pass)
+        pl.path = choose_onehot_path(C, sz, B, P, out_addr % 64 != 0, masked);
+    } else {
+        const int block_path = choose_onehot_path(C, sz, B, P, false, masked);
+        const int64_t block_pitch = B * rb;
+        // (rows that the chunk stream expands well: 16 bytes and more, and -- end of round 5 -- one-byte rows of 3 ... 15 bytes through
+        //  k_expand_rows1; unmasked only: a masked raw pass is k_tokens_raw with byte ids -- such blocks stay with the tiled kernel as before)
+        const bool stream_rows = rb >= 16 || (sz == 1 && rb >= 3 && !masked && bsq_internal::tuning().expand_rows1 != 1);
+        const bool whole_chunks = block_pitch % kChunk == 0 && out_addr % kChunk == 0;
+    // A block whose position rows are whole 4-KiB chunks of memory (B * C * sizeof(T) and the address of its first element multiples of
+    // 4096: e.g. any multiple of 4096 sequences at a 4096-sequence boundary of an aligned tensor) is the two-pass stream with a gap after
+    // every row: no chunk straddles two rows (16 384-sequence blocks of cfg3: 4 x 0.19 ms against 4 x 0.25 ms for the tiles).  Any other block of 128 MB and more -- ragged shards of a sharded job
+    // (sharding.store_shard_into_root), the last piece of a host batch, a tensor whose pitch is no multiple of 4 KiB -- takes the RAGGED
+    // form of the same stream (EParams::ragged: every row cut at the chunk boundaries of memory, its first and last piece partial).
+    // Rounds 4-5 cut such blocks in three calls instead (the sequences up to the first chunk boundary, the run of whole chunks, the
+    // rest): two ~15-us side launches, and only row 0 of the middle run aligned when the tensor's pitch was not.
+    // (knob onehot_path = 2: whatever the size -- tests)
+        // Otherwise the tiled kernel: a workgroup owns (sequence tile x 64 positions) and writes one row SEGMENT per position, so a row
+        // pitch other than B * C is just another stride
+        const bool stream = block_path != 1 && stream_rows &&
+                            (whole_chunks || block_pitch * P >= (int64_t(128) << 20) || bsq_internal::tuning().onehot_path == 2);
+        pl.path = block_path == 0 ? 0 : (stream ? 2 : 1);
+    }
+    if (pl.path == 2) {
+        pl.two = two_pass_plan(d, masked, B, P, C, sz);
+        pl.seq_block = two_pass_sequence_block(pl.two, B, P, rb);
+    }
+    return pl;
+}
+
 const char *bsq_onehot_kernel_name(const bsq_desc *d, int64_t B, int64_t P, bsq_dtype t) {
     if (!d) return "";
-    switch (choose_onehot_path(bsq_alphabet_size(d), bsq_dtype_size(t), B, P)) {
+    const OnehotPlan pl = onehot_plan(d, false, B, P, bsq_dtype_size(t), 0, B);
+    switch (pl.path) {
     case 1: return "k_onehot_tile";
     case 2: {
-        const int64_t rb = bsq_alphabet_size(d) * int64_t(bsq_dtype_size(t));
         // (unmasked: the raw-id pass runs in k_tokens_pb8_fast unless a knob keeps it in k_tokens_raw -- see launch_tokens_raw)
-        const bool rows1 = bsq_dtype_size(t) == 1 && rb >= 3 && rb <= 15 && bsq_internal::tuning().expand_rows1 != 1;
-        if (bsq_internal::tuning().raw_mode == 0 && bsq_internal::tuning().tokens_pb8 != 1) {
-            KParams kp;  // (what two_pass_plan looks at)
-            kp.desc = d;
-            kp.mask = nullptr;
-            kp.B = B;
-            kp.P = P;
-            kp.C = bsq_alphabet_size(d);
-            if (two_pass_plan(kp, bsq_dtype_size(t)).nib)
-                return rows1 ? "k_tokens_pb8_fast<raw, nibbles>+k_expand_rows1<nibbles>" : "k_tokens_pb8_fast<raw, nibbles>+k_expand_chunks<nibbles>";
-            return rows1 ? "k_tokens_pb8_fast<raw>+k_expand_rows1" : "k_tokens_pb8_fast<raw>+k_expand_chunks";
-        }
+        const bool rows1 = pl.two.rows1;
+        if (pl.two.nib) return rows1 ? "k_tokens_pb8_fast<raw, nibbles>+k_expand_rows1<nibbles>" : "k_tokens_pb8_fast<raw, nibbles>+k_expand_chunks<nibbles>";
+        if (pl.two.pb8) return rows1 ? "k_tokens_pb8_fast<raw>+k_expand_rows1" : "k_tokens_pb8_fast<raw>+k_expand_chunks";
         return rows1 ? "k_tokens_raw+k_expand_rows1" : "k_tokens_raw+k_expand_chunks";
     }
     case 3: return "k_onehot_chunks";
     default: return "k_onehot_generic";
     }
+}
+
+// Path 2 of the batch in `k` as planned: one two-pass stream (with a gap after every position row when the batch is a column block), or
+// -- short reads, very many of them -- column blocks of pl.seq_block sequences, each planned and run as a block of its own.
+// (the scratch is shared by the calls of one stream -- workspace cache --: onehot_two_pass enqueues its launches back to back
+//  under the workspace mutex; concurrent host threads take turns there: enqueueing takes microseconds, the GPU work overlaps)
+static bsq_status onehot_two_pass_blocks(KParams &k, size_t sz, const OnehotPlan &pl, bsq_dtype t, int64_t row_seqs, void *hip_stream) {
+    const int64_t rb = k.C * int64_t(sz);
+    if (pl.seq_block == 0) return onehot_two_pass(k, sz, pl.two, static_cast<hipStream_t>(hip_stream), (row_seqs - k.B) * rb);
+    for (int64_t b0 = 0; b0 < k.B; b0 += pl.seq_block) {
+        const int64_t n = k.B - b0 < pl.seq_block ? k.B - b0 : pl.seq_block;
+        const bsq_status st = bsq_onehot_block_device(k.desc, k.chars, k.offsets + b0, k.mask, n, k.P, t, static_cast<uint8_t *>(k.out) + b0 * rb, row_seqs, hip_stream);
+        if (st != BSQ_OK) return st;
+    }
+    return BSQ_OK;
 }
 
 bsq_status bsq_onehot_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets,
@@ -1601,11 +1564,8 @@ bsq_status bsq_onehot_device(const bsq_desc *d, const uint8_t *chars, const int6
     if (B == 0) return BSQ_OK;
     const size_t sz = bsq_dtype_size(t);
     if (sz == 0) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
-    // Limits of the LDS kernels: 8-bit token ids, 32-bit tile arithmetic, row images must fit in LDS.
-    // (a result that does not start on a 64-byte boundary -- a view into a larger tensor -- counts as misaligned: the tiled kernel's
-    //  row segments then straddle memory sectors, cfg4 int8 16 bytes off: 225 -> 330 us tiled, 242 us two-pass)
-    const int path = choose_onehot_path(k.C, sz, B, P, reinterpret_cast<uintptr_t>(out) % 64 != 0, k.mask != nullptr);
-    if (path == 0) return bsq_onehot_device_generic(d, chars, offsets, mask_or_null, B, P, t, out, hip_stream);
+    const OnehotPlan pl = onehot_plan(d, k.mask != nullptr, B, P, sz, reinterpret_cast<uintptr_t>(out), B);
+    if (pl.path == 0) return bsq_onehot_device_generic(d, chars, offsets, mask_or_null, B, P, t, out, hip_stream);
     k.one_bits = one_bits_of(t);
     const int64_t pitch = B * k.C * int64_t(sz);
     k.aligned = (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (pitch % 16 == 0);
@@ -1614,27 +1574,9 @@ bsq_status bsq_onehot_device(const bsq_desc *d, const uint8_t *chars, const int6
     // Measured on MI355X (profiles/r01/sweep_shapes.txt): the chunk-owner kernel streams at ~7 TB/s when a
     // row is >= 48 bytes and its per-position gather set stays L2-resident -- i.e. the row pitch is a
     // multiple of 32 KiB (each XCD then keeps to its own chunk columns) and B is moderate, or B is small.
-    if (path == 3) return onehot_chunk_owner(k, sz, s);
-    if (path == 2) {
-        // (the scratch is shared by the calls of one stream -- workspace cache --: onehot_two_pass enqueues its launches back to back
-        //  under the workspace mutex; concurrent host threads take turns there: enqueueing takes microseconds, the GPU work overlaps)
-        if (const int64_t nb = two_pass_sequence_block(k, sz, out)) {  // short reads, very many of them: column blocks of nb sequences
-            const int64_t rb = k.C * int64_t(sz);
-            for (int64_t b0 = 0; b0 < B; b0 += nb) {
-                const int64_t n = B - b0 < nb ? B - b0 : nb;
-                st = bsq_onehot_block_device(d, chars, offsets + b0, mask_or_null, n, P, t, static_cast<uint8_t *>(out) + b0 * rb, B, hip_stream);
-                if (st != BSQ_OK) return st;
-            }
-            return BSQ_OK;
-        }
-        return onehot_two_pass(k, sz, s);
-    }
-    switch (sz) {
-    case 1: return dispatch_onehot_tile<uint8_t>(k, s);
-    case 2: return dispatch_onehot_tile<uint16_t>(k, s);
-    case 4: return dispatch_onehot_tile<uint32_t>(k, s);
-    default: return dispatch_onehot_tile<uint64_t>(k, s);
-    }
+    if (pl.path == 3) return onehot_chunk_owner(k, sz, s);
+    if (pl.path == 2) return onehot_two_pass_blocks(k, sz, pl, t, B, hip_stream);
+    return with_elem_size(sz, [&](auto z) { return dispatch_onehot_tile<decltype(z)>(k, s); });
 }
 
 bsq_status bsq_onehot_block_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets,
@@ -1649,47 +1591,16 @@ bsq_status bsq_onehot_block_device(const bsq_desc *d, const uint8_t *chars, cons
     const size_t sz = bsq_dtype_size(t);
     if (sz == 0) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
     if (reinterpret_cast<uintptr_t>(out) % sz) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output is not aligned to its element size");
-    const int block_path = choose_onehot_path(k.C, sz, B, P, false);
-    if (block_path == 0) return bsq_internal::onehot_generic_block(d, chars, offsets, mask_or_null, B, P, t, out, row_seqs, hip_stream);
+    const OnehotPlan pl = onehot_plan(d, k.mask != nullptr, B, P, sz, reinterpret_cast<uintptr_t>(out), row_seqs);
+    if (pl.path == 0) return bsq_internal::onehot_generic_block(d, chars, offsets, mask_or_null, B, P, t, out, row_seqs, hip_stream);
     k.one_bits = one_bits_of(t);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int64_t block_pitch = B * k.C * int64_t(sz), rb = k.C * int64_t(sz);
-    // (rows that the chunk stream expands well: 16 bytes and more, and -- end of round 5 -- one-byte rows of 3 ... 15 bytes through
-    //  k_expand_rows1; unmasked only: a masked raw pass is k_tokens_raw with byte ids -- such blocks stay with the tiled kernel as before)
-    const bool stream_rows = rb >= 16 || (sz == 1 && rb >= 3 && !k.mask && bsq_internal::tuning().expand_rows1 != 1);
-    const bool whole_chunks = block_pitch % kChunk == 0 && reinterpret_cast<uintptr_t>(out) % kChunk == 0;
-    // A block whose position rows are whole 4-KiB chunks of memory (B * C * sizeof(T) and the address of its first element multiples of
-    // 4096: e.g. any multiple of 4096 sequences at a 4096-sequence boundary of an aligned tensor) is the two-pass stream with a gap after
-    // every row: no chunk straddles two rows (16 384-sequence blocks of cfg3: 4 x 0.19 ms against 4 x 0.25 ms for the tiles).  Any other block of 128 MB and more -- ragged shards of a sharded job
-    // (sharding.store_shard_into_root), the last piece of a host batch, a tensor whose pitch is no multiple of 4 KiB -- takes the RAGGED
-    // form of the same stream (EParams::ragged: every row cut at the chunk boundaries of memory, its first and last piece partial).
-    // Rounds 4-5 cut such blocks in three calls instead (the sequences up to the first chunk boundary, the run of whole chunks, the
-    // rest): two ~15-us side launches, and only row 0 of the middle run aligned when the tensor's pitch was not.
-    // (knob onehot_path = 2: whatever the size -- tests)
-    if (block_path != 1 && stream_rows && (whole_chunks || block_pitch * P >= (int64_t(128) << 20) || bsq_internal::tuning().onehot_path == 2)) {
-        if (const int64_t nb = two_pass_sequence_block(k, sz, out)) {  // (a block of very many short reads: sub-blocks, see bsq_onehot_device)
-            for (int64_t b0 = 0; b0 < B; b0 += nb) {
-                const int64_t n = B - b0 < nb ? B - b0 : nb;
-                st = bsq_onehot_block_device(d, chars, offsets + b0, mask_or_null, n, P, t, static_cast<uint8_t *>(out) + b0 * rb, row_seqs, hip_stream);
-                if (st != BSQ_OK) return st;
-            }
-            return BSQ_OK;
-        }
-        return onehot_two_pass(k, sz, s, (row_seqs - B) * k.C * int64_t(sz));
-    }
-    // otherwise the tiled kernel: a workgroup owns (sequence tile x 64 positions) and writes one row SEGMENT per position, so a row
-    // pitch other than B * C is just another stride
+    if (pl.path == 2) return onehot_two_pass_blocks(k, sz, pl, t, row_seqs, hip_stream);
     k.row_seqs = row_seqs;
     // 16-byte stores: the block's first element, the row pitch AND the block's own row segment must be multiples of 16 (the last tile's
     // segment ends where the block ends; with the whole tensor that is the pitch, here it is not: a block that started aligned and
     // ended 8 bytes short of a line wrote those 8 bytes of its neighbour -- found in round 4 by the misaligned-result test)
-    k.aligned = (reinterpret_cast<uintptr_t>(out) % 16 == 0) && ((row_seqs * k.C * int64_t(sz)) % 16 == 0) && (block_pitch % 16 == 0);
-    switch (sz) {
-    case 1: return dispatch_onehot_tile<uint8_t>(k, s);
-    case 2: return dispatch_onehot_tile<uint16_t>(k, s);
-    case 4: return dispatch_onehot_tile<uint32_t>(k, s);
-    default: return dispatch_onehot_tile<uint64_t>(k, s);
-    }
+    k.aligned = (reinterpret_cast<uintptr_t>(out) % 16 == 0) && ((row_seqs * k.C * int64_t(sz)) % 16 == 0) && ((B * k.C * int64_t(sz)) % 16 == 0);
+    return with_elem_size(sz, [&](auto z) { return dispatch_onehot_tile<decltype(z)>(k, static_cast<hipStream_t>(hip_stream)); });
 }
 
 bsq_status bsq_raw_tokens_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets,
@@ -1769,12 +1680,7 @@ bsq_status bsq_onehot_bcl_device(const bsq_desc *d, const uint8_t *chars, const 
             uint8_t *dst = static_cast<uint8_t *>(out) + b0 * int64_t(k.C) * P * int64_t(sz);
             wst = bsq_internal::launch_tokens_bp8(d, chars, offsets + b0, nb, P, ws, s, true, mask_or_null);
             if (wst != BSQ_OK) break;
-            switch (sz) {
-            case 1: wst = launch_expand_bcl<uint8_t>(tk, nb, P, k.C, k.one_bits, dst, s); break;
-            case 2: wst = launch_expand_bcl<uint16_t>(tk, nb, P, k.C, k.one_bits, dst, s); break;
-            case 4: wst = launch_expand_bcl<uint32_t>(tk, nb, P, k.C, k.one_bits, dst, s); break;
-            default: wst = launch_expand_bcl<uint64_t>(tk, nb, P, k.C, k.one_bits, dst, s); break;
-            }
+            wst = with_elem_size(sz, [&](auto z) { return launch_expand_bcl<decltype(z)>(tk, nb, P, k.C, k.one_bits, dst, s); });
         }
         bsq_internal::workspace_release(ws, s);
         return wst;
@@ -1797,6 +1703,8 @@ struct MultiItem {
     bool paired;     //   follow from C, the dtype and nib, which the call's batches share)
     int64_t pitch;   // family 2: ids per scratch row; the batch's scratch region (as its single call acquires it); the ids' bytes as stored
     int64_t ws_bytes, stored;
+    CFields owner;   // family 1: the batch's row of k_onehot_chunks_multi's table
+    EParams expand;  // family 2: the batch's row of the expansion's table (`tok`: set once the scratch is acquired)
 };
 
 // The family of one batch by itself (before the group's rules).  Arguments already checked.
@@ -1809,29 +1717,24 @@ MultiItem multi_candidate(const bsq_desc *d, const bsq_onehot_batch &b, int64_t 
         if (choose_bcl_path(d, C, sz, b.B, P, b.out) == 3 && bsq_internal::onehot_bcl_chunks_fusable(b.B, P, C, t, b.out)) it.family = 3;
         return it;
     }
-    const int path = choose_onehot_path(C, sz, b.B, P, reinterpret_cast<uintptr_t>(b.out) % 64 != 0, b.mask != nullptr);
-    KParams k;
-    if (fill_common(k, d, b.chars, b.offsets, b.mask, b.B, P, b.out) != BSQ_OK) return it;
-    k.one_bits = one_bits_of(t);
-    if (path == 3) {
-        CFields c;
-        if (chunk_owner_fields(k, sz, c)) it.family = 1;
+    const OnehotPlan pl = onehot_plan(d, b.mask != nullptr, b.B, P, sz, reinterpret_cast<uintptr_t>(b.out), b.B);
+    if (pl.path == 3) {
+        KParams k;
+        if (fill_common(k, d, b.chars, b.offsets, b.mask, b.B, P, b.out) != BSQ_OK) return it;
+        k.one_bits = one_bits_of(t);
+        if (chunk_owner_fields(k, sz, it.owner)) it.family = 1;
         return it;
     }
     // two-pass: unmasked, one piece (no sequence blocks, no position slices), the raw pass in k_tokens_pb8_fast (launch_tokens_raw)
-    if (path != 2 || b.mask || two_pass_sequence_block(k, sz, b.out) != 0) return it;
-    const TwoPassPlan pl = two_pass_plan(k, sz);
-    if (pl.tiles_per_slice < pl.ntt || bsq_internal::tuning().raw_mode != 0 ||
-        !bsq_internal::tokens_pb8_applicable(d, b.B, P, reinterpret_cast<const void *>(uintptr_t(256)), pl.pitch))
-        return it;
-    const EParams e = expansion_params(nullptr, pl.pitch, b.B, P, C, sz, k.one_bits, b.out, 0, pl.nib);
-    if (((e.nchunks + 7) / 8 + 3) / 4 * 8 >= (int64_t(1) << 31)) return it;
+    if (pl.path != 2 || b.mask || pl.seq_block != 0 || pl.two.tiles_per_slice < pl.two.ntt || !pl.two.pb8) return it;
+    it.expand = expansion_params(nullptr, pl.two.pitch, b.B, P, C, sz, one_bits_of(t), b.out, 0, pl.two.nib);
+    if (expand_grid(it.expand) >= (int64_t(1) << 31)) return it;
     it.family = 2;
-    it.nib = pl.nib;
+    it.nib = pl.two.nib;
     it.paired = bsq_internal::tokens_pb8_raw_paired(b.B, P);
-    it.pitch = pl.pitch;
-    it.ws_bytes = int64_t(pl.ws_bytes);
-    it.stored = (pl.pitch >> (pl.nib ? 1 : 0)) * P;
+    it.pitch = pl.two.pitch;
+    it.ws_bytes = int64_t(pl.two.ws_bytes);
+    it.stored = (pl.two.pitch >> (pl.two.nib ? 1 : 0)) * P;
     return it;
 }
 
@@ -1881,18 +1784,17 @@ bsq_status multi_check(const bsq_desc *d, int32_t n, const bsq_onehot_batch *bat
     return BSQ_OK;
 }
 
-// up to eight non-empty batches from *pos on (B == 0 skipped); returns how many
-int32_t next_group(int32_t n, const bsq_onehot_batch *batches, int32_t *pos, bsq_onehot_batch *grp) {
+// up to eight non-empty batches from *pos on (B == 0 skipped), where[i] = the index of grp[i] in `batches`; returns how many
+int32_t next_group(int32_t n, const bsq_onehot_batch *batches, int32_t *pos, bsq_onehot_batch *grp, int32_t *where) {
     int32_t g = 0;
     while (*pos < n && g < kOnehotMultiMax) {
-        if (batches[*pos].B > 0) grp[g++] = batches[*pos];
+        if (batches[*pos].B > 0) where[g] = *pos, grp[g++] = batches[*pos];
         ++*pos;
     }
     return g;
 }
 
-bsq_status run_family1(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, const MultiItem *it, int64_t P, bsq_dtype t, hipStream_t s) {
-    const size_t sz = bsq_dtype_size(t);
+bsq_status run_family1(const bsq_desc *d, int32_t g, const MultiItem *it, bsq_dtype t, hipStream_t s) {
     CMulti cm;
     for (int i = 0; i < 256; ++i) cm.lut[i] = d->lut[i];
     for (int i = 0; i < kOnehotMultiMax; ++i) cm.m.first_block[i] = 0xFFFFFFFFu;
@@ -1900,22 +1802,13 @@ bsq_status run_family1(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp
     int32_t j = 0;
     for (int32_t i = 0; i < g; ++i) {
         if (it[i].family != 1) continue;
-        KParams k;
-        bsq_status st = fill_common(k, d, grp[i].chars, grp[i].offsets, grp[i].mask, grp[i].B, P, grp[i].out);
-        if (st != BSQ_OK) return st;
-        k.one_bits = one_bits_of(t);
-        if (!chunk_owner_fields(k, sz, cm.m.b[j])) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+        cm.m.b[j] = it[i].owner;
         cm.m.first_block[j++] = uint32_t(blocks);
-        blocks += chunks_grid(cm.m.b[j - 1]);
+        blocks += chunks_grid(it[i].owner);
     }
     if (j == 0) return BSQ_OK;
     if (blocks >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    switch (sz) {
-    case 1: return launch_chunks_multi<uint8_t>(cm, blocks, s);
-    case 2: return launch_chunks_multi<uint16_t>(cm, blocks, s);
-    case 4: return launch_chunks_multi<uint32_t>(cm, blocks, s);
-    default: return launch_chunks_multi<uint64_t>(cm, blocks, s);
-    }
+    return with_elem_size(bsq_dtype_size(t), [&](auto z) { return launch_chunks_multi<decltype(z)>(cm, blocks, s); });
 }
 
 // one family-2 set (the members of key `key`): one raw-id launch into one scratch -- a region per batch, each the size its single call
@@ -1923,8 +1816,6 @@ bsq_status run_family1(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp
 bsq_status run_family2_set(const bsq_desc *d, int32_t g, const bsq_onehot_batch *grp, const MultiItem *it, int key, int64_t P, bsq_dtype t,
                            hipStream_t s) {
     const bool nib = (key & 1) != 0, paired = (key & 2) != 0;
-    const size_t sz = bsq_dtype_size(t);
-    const int32_t C = bsq_alphabet_size(d);
     int32_t idx[kOnehotMultiMax], m = 0;
     size_t total = 0;
     for (int32_t i = 0; i < g; ++i)
@@ -1945,26 +1836,19 @@ bsq_status run_family2_set(const bsq_desc *d, int32_t g, const bsq_onehot_batch 
     for (int i = 0; i < kOnehotMultiMax; ++i) em.first_block[i] = 0xFFFFFFFFu;
     size_t at = 0;
     int64_t blocks = 0;
-    const uint64_t one = one_bits_of(t);
     for (int32_t j = 0; j < m; ++j) {
         const MultiItem &x = it[idx[j]];
         const bsq_onehot_batch &b = grp[idx[j]];
         chars[j] = b.chars, offsets[j] = b.offsets, Bs[j] = b.B, wsp[j] = static_cast<uint8_t *>(ws) + at;
         at += (size_t(x.ws_bytes) + 255) / 256 * 256;
-        em.b[j] = expansion_params(wsp[j], x.pitch, b.B, P, C, sz, one, b.out, 0, nib);
+        em.b[j] = x.expand;
+        em.b[j].tok = wsp[j];
         em.first_block[j] = uint32_t(blocks);
-        blocks += ((em.b[j].nchunks + 7) / 8 + 3) / 4 * 8;
+        blocks += expand_grid(x.expand);
     }
     if (blocks >= (int64_t(1) << 31)) st = bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
     if (st == BSQ_OK) st = bsq_internal::launch_tokens_pb8_raw_multi(d, m, chars, offsets, Bs, P, wsp, nib, s);
-    if (st == BSQ_OK) {
-        switch (sz) {
-        case 1: st = launch_expand_multi<uint8_t>(em, blocks, s); break;
-        case 2: st = launch_expand_multi<uint16_t>(em, blocks, s); break;
-        case 4: st = launch_expand_multi<uint32_t>(em, blocks, s); break;
-        default: st = launch_expand_multi<uint64_t>(em, blocks, s); break;
-        }
-    }
+    if (st == BSQ_OK) st = with_elem_size(bsq_dtype_size(t), [&](auto z) { return launch_expand_multi<decltype(z)>(em, blocks, s); });
     bsq_internal::workspace_release(ws, s);
     return st;
 }
@@ -1987,15 +1871,9 @@ int32_t bsq_onehot_multi_plan(const bsq_desc *d, int32_t n, const bsq_onehot_bat
     if (st != BSQ_OK) return -st;
     if (family)
         for (int32_t i = 0; i < n; ++i) family[i] = 0;
-    int32_t launches = 0, pos = 0;
-    while (pos < n) {
-        bsq_onehot_batch grp[kOnehotMultiMax];
-        int32_t where[kOnehotMultiMax], g = 0;
-        while (pos < n && g < kOnehotMultiMax) {  // (next_group, keeping the batches' indices)
-            if (batches[pos].B > 0) where[g] = pos, grp[g++] = batches[pos];
-            ++pos;
-        }
-        if (g == 0) break;
+    int32_t launches = 0, pos = 0, where[kOnehotMultiMax];
+    bsq_onehot_batch grp[kOnehotMultiMax];
+    while (int32_t g = next_group(n, batches, &pos, grp, where)) {
         MultiItem it[kOnehotMultiMax];
         launches += multi_plan_group(d, g, grp, P, layout, t, it);
         if (family)
@@ -2009,13 +1887,13 @@ bsq_status bsq_onehot_device_multi(const bsq_desc *d, int32_t n, const bsq_oneho
     bsq_status st = multi_check(d, n, batches, P, layout, t);
     if (st != BSQ_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    int32_t pos = 0;
+    int32_t pos = 0, where[kOnehotMultiMax];
     bsq_onehot_batch grp[kOnehotMultiMax];
-    while (int32_t g = next_group(n, batches, &pos, grp)) {
+    while (int32_t g = next_group(n, batches, &pos, grp, where)) {
         MultiItem it[kOnehotMultiMax];
         const int32_t launches = multi_plan_group(d, g, grp, P, layout, t, it);
         if (launches > 0) {
-            st = run_family1(d, g, grp, it, P, t, s);
+            st = run_family1(d, g, it, t, s);
             for (int key = 0; key < 4 && st == BSQ_OK; ++key) st = run_family2_set(d, g, grp, it, key, P, t, s);
             if (st == BSQ_OK) st = run_family3(d, g, grp, it, P, t, s);
             if (st != BSQ_OK) return st;

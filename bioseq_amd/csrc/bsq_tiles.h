@@ -472,11 +472,10 @@ int64_t tile_grid(const KParams &k, int64_t ntt) {
     return (k.order == 2 ? (int64_t(k.ntb) + unit - 1) / unit * unit : int64_t(k.ntb)) * ntt;
 }
 
-bsq_status check_launch(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-    return BSQ_OK;
-}
+using bsq_internal::check_launch;
+using bsq_internal::with_elem_size;
+using bsq_internal::with_flags;
+using bsq_internal::with_value_type;
 
 uint64_t one_bits_of(bsq_dtype t) {
     switch (t) {

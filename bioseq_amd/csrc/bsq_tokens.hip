@@ -774,29 +774,30 @@ void tokenize_chunks_fill(const KParams &k, F &c, bool *ragged_out) {
     c.step_r = 64u % c.ppr;
 }
 
+// grid of one batch's chunk stream (a multiple of 8 blocks).  Chunks per wave: 1.  The software-pipelined 4-chunk form (round 2; not built
+// any more) was 15-20 % SLOWER on cfg2 / cfg5: the kernel is bound by its ~550 VALU instructions per chunk, not by memory latency, and four
+// chunks per wave cost occupancy (102 VGPRs).
+int64_t tokenize_chunks_grid(int64_t nchunks) {
+    const int nch = 1;
+    return ((nchunks + 7) / 8 + int64_t(4) * nch - 1) / (int64_t(4) * nch) * 8;
+}
+// unused dynamic LDS of the chunk-stream kernels = occupancy cap (knob "tokenize_pad": experiments)
+size_t tokenize_chunks_pad() {
+    const int padv = bsq_internal::tuning().tokenize_pad;
+    return padv > 0 ? size_t(padv) : 0;
+}
+
 template <typename T, bool HOT>
 bsq_status launch_tokenize_chunks(const KParams &k, hipStream_t s) {
     TParams c;
     for (int i = 0; i < 256; ++i) c.lut[i] = k.lut[i];
     bool ragged = false;
     tokenize_chunks_fill<T, HOT>(k, c, &ragged);
-    // Chunks per wave: 1.  The software-pipelined 4-chunk form (round 2; not built any more) was 15-20 % SLOWER on cfg2 /
-    // cfg5: the kernel is bound by its ~550 VALU instructions per chunk, not by memory latency, and four chunks
-    // per wave cost occupancy (102 VGPRs).
-    const int nch = 1;
-    const int64_t groups = ((c.nchunks + 7) / 8 + int64_t(4) * nch - 1) / (int64_t(4) * nch);
-    if (groups * 8 >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    const dim3 grid(unsigned(groups * 8));
-    const int padv = bsq_internal::tuning().tokenize_pad;  // unused dynamic LDS = occupancy cap (experiments)
-    const size_t pad = padv > 0 ? size_t(padv) : 0;
-    const bool nt = bsq_internal::nontemporal_stores();
-    if (ragged) {
-        if (nt) hipLaunchKernelGGL((k_tokenize_chunks<T, true, HOT, 1, true>), grid, dim3(kThreads), pad, s, c);
-        else hipLaunchKernelGGL((k_tokenize_chunks<T, false, HOT, 1, true>), grid, dim3(kThreads), pad, s, c);
-    } else {
-        if (nt) hipLaunchKernelGGL((k_tokenize_chunks<T, true, HOT, 1>), grid, dim3(kThreads), pad, s, c);
-        else hipLaunchKernelGGL((k_tokenize_chunks<T, false, HOT, 1>), grid, dim3(kThreads), pad, s, c);
-    }
+    const int64_t blocks = tokenize_chunks_grid(c.nchunks);
+    if (blocks >= (int64_t(1) << 31)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "output too large");
+    with_flags([&](auto NT, auto RG) {
+        hipLaunchKernelGGL((k_tokenize_chunks<T, NT(), HOT, 1, RG()>), dim3(unsigned(blocks)), dim3(kThreads), tokenize_chunks_pad(), s, c);
+    }, bsq_internal::nontemporal_stores(), ragged);
     return check_launch(HOT ? "k_tokenize_chunks<onehot bcl>" : "k_tokenize_chunks");
 }
 
@@ -811,12 +812,7 @@ bsq_status launch_onehot_bcl_chunks(const bsq_desc *d, const uint8_t *chars, con
     const bsq_status st = fill_common(k, d, chars, offsets, mask_or_null, B, P, out);
     if (st != BSQ_OK) return st;
     k.one_bits = one_bits_of(t);
-    switch (bsq_dtype_size(t)) {
-    case 1: return launch_tokenize_chunks<uint8_t, true>(k, s);
-    case 2: return launch_tokenize_chunks<uint16_t, true>(k, s);
-    case 4: return launch_tokenize_chunks<uint32_t, true>(k, s);
-    default: return launch_tokenize_chunks<uint64_t, true>(k, s);
-    }
+    return with_elem_size(bsq_dtype_size(t), [&](auto z) { return launch_tokenize_chunks<decltype(z), true>(k, s); });
 }
 
 // bsq_onehot_device_multi, family 3: k_tokenize_chunks<HOT> runs this batch in its plain form -- a 16-byte aligned output, P % (16 / sizeof(T))
@@ -825,7 +821,7 @@ bool onehot_bcl_chunks_fusable(int64_t B, int64_t P, int32_t C, bsq_dtype t, con
     const int64_t sz = int64_t(bsq_dtype_size(t));
     if (sz == 0 || B <= 0 || C <= 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 || P % (16 / sz) != 0) return false;
     const int64_t nchunks = (B * int64_t(C) * (P / (16 / sz)) + kChunk / 16 - 1) / (kChunk / 16);
-    return ((nchunks + 7) / 8 + 3) / 4 * 8 < (int64_t(1) << 31);
+    return tokenize_chunks_grid(nchunks) < (int64_t(1) << 31);
 }
 
 template <typename T>
@@ -843,34 +839,48 @@ static bsq_status bcl_chunks_multi(const bsq_desc *d, int32_t n, const bsq_oneho
         tokenize_chunks_fill<T, true>(k, m.m.b[i], &ragged);
         if (ragged) return set_error(BSQ_ERR_INVALID_ARG, "k_tokenize_chunks_multi: a batch of the ragged form");
         m.m.first_block[i] = uint32_t(blocks);
-        blocks += ((m.m.b[i].nchunks + 7) / 8 + 3) / 4 * 8;  // (launch_tokenize_chunks: one chunk per wave, 4 waves per workgroup)
+        blocks += tokenize_chunks_grid(m.m.b[i].nchunks);
         if (blocks >= (int64_t(1) << 31)) return set_error(BSQ_ERR_INVALID_ARG, "output too large");
     }
-    const int padv = tuning().tokenize_pad;  // as launch_tokenize_chunks
-    const size_t pad = padv > 0 ? size_t(padv) : 0;
-    if (nontemporal_stores())
-        hipLaunchKernelGGL((k_tokenize_chunks_multi<T, true>), dim3(unsigned(blocks)), dim3(kThreads), pad, s, m);
-    else
-        hipLaunchKernelGGL((k_tokenize_chunks_multi<T, false>), dim3(unsigned(blocks)), dim3(kThreads), pad, s, m);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error("k_tokenize_chunks_multi<onehot bcl>", e);
-    return BSQ_OK;
+    with_flags([&](auto NT) {
+        hipLaunchKernelGGL((k_tokenize_chunks_multi<T, NT()>), dim3(unsigned(blocks)), dim3(kThreads), tokenize_chunks_pad(), s, m);
+    }, nontemporal_stores());
+    return check_launch("k_tokenize_chunks_multi<onehot bcl>");
 }
 
 // n (1 ... 8) channels-first one-hots that onehot_bcl_chunks_fusable accepts, in ONE launch
 bsq_status launch_onehot_bcl_chunks_multi(const bsq_desc *d, int32_t n, const bsq_onehot_batch *batches, int64_t P, bsq_dtype t, hipStream_t s) {
     if (n < 1 || n > kOnehotMultiMax) return set_error(BSQ_ERR_INVALID_ARG, "k_tokenize_chunks_multi: 1 ... 8 batches");
-    switch (bsq_dtype_size(t)) {
-    case 1: return bcl_chunks_multi<uint8_t>(d, n, batches, P, t, s);
-    case 2: return bcl_chunks_multi<uint16_t>(d, n, batches, P, t, s);
-    case 4: return bcl_chunks_multi<uint32_t>(d, n, batches, P, t, s);
-    default: return bcl_chunks_multi<uint64_t>(d, n, batches, P, t, s);
-    }
+    return with_elem_size(bsq_dtype_size(t), [&](auto z) { return bcl_chunks_multi<decltype(z)>(d, n, batches, P, t, s); });
 }
 
 }  // namespace bsq_internal
 
 extern "C" {
+
+// Which kernel tokenizes a batch of this shape into an output at address `addr` (0: any 16-byte aligned, contiguous output) -- the one
+// classification bsq_tokenize_device, bsq_augment_tokenize_device and bsq_tokenize_kernel_name read.  Arguments already checked (B > 0).
+enum TokenPath { kTokGeneric, kTokBp8, kTokChunks, kTokRows, kTokPb8, kTokRawValue, kTokTile };
+static TokenPath tokenize_path_of(const bsq_desc *d, int64_t B, int64_t P, bool batch_first, bsq_dtype t, uintptr_t addr) {
+    const auto &tn = bsq_internal::tuning();
+    const int64_t sz = int64_t(bsq_dtype_size(t));
+    const void *out = reinterpret_cast<const void *>(addr);
+    if (bsq_alphabet_size(d) > 250 || B >= (int64_t(1) << 31) - 1024 || (!batch_first && P > kMaxTiledP)) return kTokGeneric;
+    if (batch_first) {
+        // int8 (B,P): k_tokens_bp8 takes any padlen >= 128 and any alignment (its row-piece form when P % 16 != 0)
+        if (t == BSQ_I8 && tn.tokenize_path != 1 && tn.tokens8 != 1 && bsq_internal::tokens_bp8_applicable(d, B, P, out) &&
+            ((addr % 16 == 0 && P % 16 == 0) || tn.tokens8 != 2))  // knob 2: aligned shapes only (round-2 state)
+            return kTokBp8;
+        // chunk kernel: a lane's 16 output bytes lie inside one row (its row-piece form when P % (16 / sz) != 0 or the output
+        // is not 16-byte aligned; knob "tokenize_path" 2: aligned shapes only, the rest falls to k_tokenize_rows as in round 1)
+        if (tn.tokenize_path != 1 && addr % sz == 0 && ((addr % 16 == 0 && P % (16 / sz) == 0) || tn.tokenize_path != 2)) return kTokChunks;
+        return kTokRows;
+    }
+    // (P,B) with 16-byte aligned rows, any element type: register-transposed 256 x 64 tiles (bsq_tokens8.hip; knob tokens_pb8 = 1: never)
+    if (tn.tokenize_path != 1 && bsq_internal::tokens_pb8_applicable(d, B, P, out, B, t)) return kTokPb8;
+    if (t == BSQ_I8 && tn.tokenize_path != 1) return kTokRawValue;  // int8 (P,B): the raw-token kernel in value mode
+    return kTokTile;
+}
 
 bsq_status bsq_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B,
                                int64_t P, int32_t batch_first, bsq_dtype t, void *out, void *hip_stream) {
@@ -880,50 +890,25 @@ bsq_status bsq_tokenize_device(const bsq_desc *d, const uint8_t *chars, const in
     if (B == 0) return BSQ_OK;
     const size_t sz = bsq_dtype_size(t);
     if (sz == 0) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
-    if (k.C > 250 || B >= (int64_t(1) << 31) - 1024 || (!batch_first && P > kMaxTiledP))
-        return bsq_tokenize_device_generic(d, chars, offsets, B, P, batch_first, t, out, hip_stream);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const uintptr_t addr = reinterpret_cast<uintptr_t>(out);
-    // int8 (B,P): k_tokens_bp8 takes any padlen >= 128 and any alignment (its row-piece form when P % 16 != 0)
-    if (batch_first && t == BSQ_I8 && bsq_internal::tuning().tokenize_path != 1 && bsq_internal::tuning().tokens8 != 1 &&
-        bsq_internal::tokens_bp8_applicable(d, B, P, out) &&
-        ((addr % 16 == 0 && P % 16 == 0) || bsq_internal::tuning().tokens8 != 2))  // knob 2: aligned shapes only (round-2 state)
-        return bsq_internal::launch_tokens_bp8(d, chars, offsets, B, P, out, s);
-    // chunk kernel: a lane's 16 output bytes lie inside one row (its row-piece form when P % (16 / sz) != 0 or the output
-    // is not 16-byte aligned; knob "tokenize_path" 2: aligned shapes only, the rest falls to k_tokenize_rows as in round 1)
-    if (batch_first && bsq_internal::tuning().tokenize_path != 1 && addr % sz == 0 &&
-        ((addr % 16 == 0 && P % int64_t(16 / sz) == 0) || bsq_internal::tuning().tokenize_path != 2)) {
-        switch (t) {
-        case BSQ_I8: return launch_tokenize_chunks<int8_t, false>(k, s);
-        case BSQ_I16: return launch_tokenize_chunks<int16_t, false>(k, s);
-        case BSQ_I32: return launch_tokenize_chunks<int32_t, false>(k, s);
-        case BSQ_U64: return launch_tokenize_chunks<uint64_t, false>(k, s);
-        case BSQ_F32: return launch_tokenize_chunks<float, false>(k, s);
-        case BSQ_F64: return launch_tokenize_chunks<double, false>(k, s);
-        }
-    }
-    if (batch_first) {
+    const TokenPath path = tokenize_path_of(d, B, P, batch_first != 0, t, addr);
+    if (path == kTokGeneric) return bsq_tokenize_device_generic(d, chars, offsets, B, P, batch_first, t, out, hip_stream);
+    if (path == kTokBp8) return bsq_internal::launch_tokens_bp8(d, chars, offsets, B, P, out, s);
+    if (path == kTokChunks) return with_value_type(t, [&](auto z) { return launch_tokenize_chunks<decltype(z), false>(k, s); });
+    if (path == kTokRows) {
         const size_t vec = sz * 4 > 16 ? 16 : sz * 4;  // widest store used by k_tokenize_rows
         k.aligned = (addr % vec == 0) && ((P * int64_t(sz)) % int64_t(vec) == 0);
         const unsigned grid = unsigned((B + 3) / 4);
-#define BSQ_ROWS(T) hipLaunchKernelGGL((k_tokenize_rows<T>), dim3(grid), dim3(kThreads), 0, s, k)
-        switch (t) {
-        case BSQ_I8: BSQ_ROWS(int8_t); break;
-        case BSQ_I16: BSQ_ROWS(int16_t); break;
-        case BSQ_I32: BSQ_ROWS(int32_t); break;
-        case BSQ_U64: BSQ_ROWS(uint64_t); break;
-        case BSQ_F32: BSQ_ROWS(float); break;
-        case BSQ_F64: BSQ_ROWS(double); break;
-        }
-#undef BSQ_ROWS
-        return check_launch("k_tokenize_rows");
+        return with_value_type(t, [&](auto z) {
+            hipLaunchKernelGGL((k_tokenize_rows<decltype(z)>), dim3(grid), dim3(kThreads), 0, s, k);
+            return check_launch("k_tokenize_rows");
+        });
     }
     k.aligned = (addr % 16 == 0) && ((B * int64_t(sz)) % 16 == 0);
     k.vw = (!k.aligned && addr % sz == 0 && bsq_internal::tuning().tokenize_path != 2) ? 2 : 1;  // k_tokenize_tile: 2 = line-aligned slots
-    // (P,B) with 16-byte aligned rows, any element type: register-transposed 256 x 64 tiles (bsq_tokens8.hip; knob tokens_pb8 = 1: never)
-    if (bsq_internal::tuning().tokenize_path != 1 && bsq_internal::tokens_pb8_applicable(d, B, P, out, B, t))
-        return bsq_internal::launch_tokens_pb8(d, chars, offsets, B, P, out, B, s, false, t);
-    if (t == BSQ_I8 && bsq_internal::tuning().tokenize_path != 1) {  // int8 (P,B): the raw-token kernel in value mode
+    if (path == kTokPb8) return bsq_internal::launch_tokens_pb8(d, chars, offsets, B, P, out, B, s, false, t);
+    if (path == kTokRawValue) {
         const uint64_t al = uint64_t(addr) | uint64_t(B);  // every row starts at out + t * B
         k.vw = al % 16 == 0 ? 16 : (al % 8 == 0 ? 8 : (al % 4 == 0 ? 4 : 1));
         // tile order 5 (XCD-contiguous ranges of sequence tiles, their position tiles back to back): the 256-byte row
@@ -959,22 +944,18 @@ bsq_status bsq_tokenize_device(const bsq_desc *d, const uint8_t *chars, const in
     const bool shared_sectors = (B * int64_t(sz)) % 64 != 0 && B >= 16384 && sz < 8;
     const int tbk = shared_sectors && bsq_internal::tuning().tokenize_tb == 0 ? 256 : bsq_internal::tuning().tokenize_tb;
     if (shared_sectors && bsq_internal::tuning().tile_order == 0) k.order = 4;
-#define BSQ_TILE(T, AUTO)                                                        \
-    switch (tbk ? tbk : AUTO) {                                                  \
-    case 64: return launch_tokenize_tile<T, 64>(k, s);                           \
-    case 128: return launch_tokenize_tile<T, 128>(k, s);                         \
-    default: return launch_tokenize_tile<T, 256>(k, s);                          \
-    }
-    switch (t) {
-    case BSQ_I8: return launch_tokenize_tile<int8_t, 256>(k, s);
-    case BSQ_I16: BSQ_TILE(int16_t, 128)
-    case BSQ_I32: BSQ_TILE(int32_t, 64)
-    case BSQ_U64: BSQ_TILE(uint64_t, 64)
-    case BSQ_F32: BSQ_TILE(float, 64)
-    case BSQ_F64: BSQ_TILE(double, 64)
-    }
-#undef BSQ_TILE
-    return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
+    return with_value_type(t, [&](auto z) {
+        using T = decltype(z);
+        if constexpr (sizeof(T) == 1) {  // (int8: one tile shape)
+            return launch_tokenize_tile<T, 256>(k, s);
+        } else {
+            switch (tbk ? tbk : (sizeof(T) == 2 ? 128 : 64)) {  // automatic: 128 sequences for 2-byte elements, 64 for wider ones
+            case 64: return launch_tokenize_tile<T, 64>(k, s);
+            case 128: return launch_tokenize_tile<T, 128>(k, s);
+            default: return launch_tokenize_tile<T, 256>(k, s);
+            }
+        }
+    });
 }
 
 bsq_status bsq_augment_tokenize_device(const bsq_desc *d, uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
@@ -991,8 +972,8 @@ bsq_status bsq_augment_tokenize_device(const bsq_desc *d, uint8_t *chars, const 
     if (B == 0) return BSQ_OK;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     // one launch where bsq_tokenize_device would take the fast form of k_tokens_bp8 (same conditions as there)
-    if (chain_len > 0 && frac > 0.0 && chars && batch_first && t == BSQ_I8 && k.C <= 250 && B < (int64_t(1) << 31) - 1024 &&
-        bsq_internal::tuning().tokenize_path != 1 && bsq_internal::tuning().tokens8 != 1 && bsq_internal::tokens_bp8_applicable(d, B, P, out)) {
+    if (chain_len > 0 && frac > 0.0 && chars && bsq_dtype_size(t) != 0 &&
+        tokenize_path_of(d, B, P, batch_first != 0, t, reinterpret_cast<uintptr_t>(out)) == kTokBp8) {
         bsq_internal::FusedAugRequest fr{chars, chain_len, frac, seed};
         bool taken = false;
         st = bsq_internal::launch_tokens_bp8(d, chars, offsets, B, P, out, s, false, nullptr, &fr, &taken);
@@ -1057,36 +1038,24 @@ bsq_status bsq_augment_tokenize_device_multi(const bsq_desc *d, int32_t n, const
 // Name of the kernel(s) bsq_tokenize_device (augment = 0) / bsq_augment_tokenize_device (augment = chain_len > 0) launch for this shape, for a
 // 16-byte aligned contiguous output: the dispatch above, as a function of the shape alone (profiling / bench labels).
 const char *bsq_tokenize_kernel_name(const bsq_desc *d, int64_t B, int64_t P, int32_t batch_first, bsq_dtype t, int32_t augment) {
-    if (!d || B <= 0 || P <= 0) return "";
-    const size_t sz = bsq_dtype_size(t);
-    if (sz == 0) return "";
-    const int C = bsq_alphabet_size(d);
-    const auto &tn = bsq_internal::tuning();
-    if (C > 250 || B >= (int64_t(1) << 31) - 1024 || (!batch_first && P > kMaxTiledP)) return augment ? "k_augment_groups+k_tokenize_generic" : "k_tokenize_generic";
-    if (batch_first) {
-        const bool bp8 = t == BSQ_I8 && tn.tokenize_path != 1 && tn.tokens8 != 1 && bsq_internal::tokens_bp8_applicable(d, B, P, nullptr) &&
-                         (P % 16 == 0 || tn.tokens8 != 2);
-        if (bp8) {
-            const bool fast = bsq_internal::tokens_bp8_fast_form(d, B, P, true);
-            if (augment && fast && tn.augment_fused != 1)
-                return bsq_internal::tokens_bp8_nowait_form(bsq_internal::tokens_bp8_chunks(B, P))
-                           ? "k_augment_tokens_nowait(k_augment_groups || k_tokens_bp8_fast)+k_patch_tokens"
-                           : "k_augment_tokens_fused(k_augment_groups -> k_tokens_bp8_fast)";
-            if (augment) return fast ? "k_augment_groups+k_tokens_bp8_fast" : "k_augment_groups+k_tokens_bp8";
-            return fast ? "k_tokens_bp8_fast" : "k_tokens_bp8";
-        }
-        const bool chunks = tn.tokenize_path != 1 && (P % int64_t(16 / sz) == 0 || tn.tokenize_path != 2);
-        if (augment) return chunks ? "k_augment_groups+k_tokenize_chunks" : "k_augment_groups+k_tokenize_rows";
-        return chunks ? "k_tokenize_chunks" : "k_tokenize_rows";
+    if (!d || B <= 0 || P <= 0 || bsq_dtype_size(t) == 0) return "";
+    switch (tokenize_path_of(d, B, P, batch_first != 0, t, 0)) {
+    case kTokGeneric: return augment ? "k_augment_groups+k_tokenize_generic" : "k_tokenize_generic";
+    case kTokBp8: {
+        const bool fast = bsq_internal::tokens_bp8_fast_form(d, B, P, true);
+        if (augment && bsq_internal::tokens_bp8_fused_form(d, B, P, true))
+            return bsq_internal::tokens_bp8_nowait_form(bsq_internal::tokens_bp8_chunks(B, P))
+                       ? "k_augment_tokens_nowait(k_augment_groups || k_tokens_bp8_fast)+k_patch_tokens"
+                       : "k_augment_tokens_fused(k_augment_groups -> k_tokens_bp8_fast)";
+        if (augment) return fast ? "k_augment_groups+k_tokens_bp8_fast" : "k_augment_groups+k_tokens_bp8";
+        return fast ? "k_tokens_bp8_fast" : "k_tokens_bp8";
     }
-    const char *name;
-    alignas(64) static const char aligned_dummy[64] = {};
-    if (tn.tokenize_path != 1 && bsq_internal::tokens_pb8_applicable(d, B, P, aligned_dummy, B, t)) name = "k_tokens_pb8_fast";
-    else if (t == BSQ_I8 && tn.tokenize_path != 1) name = "k_tokens_raw<value>";
-    else name = "k_tokenize_tile";
-    if (!augment) return name;
-    return name == std::string("k_tokens_pb8_fast") ? "k_augment_groups+k_tokens_pb8_fast"
-           : (name == std::string("k_tokens_raw<value>") ? "k_augment_groups+k_tokens_raw<value>" : "k_augment_groups+k_tokenize_tile");
+    case kTokChunks: return augment ? "k_augment_groups+k_tokenize_chunks" : "k_tokenize_chunks";
+    case kTokRows: return augment ? "k_augment_groups+k_tokenize_rows" : "k_tokenize_rows";
+    case kTokPb8: return augment ? "k_augment_groups+k_tokens_pb8_fast" : "k_tokens_pb8_fast";
+    case kTokRawValue: return augment ? "k_augment_groups+k_tokens_raw<value>" : "k_tokens_raw<value>";
+    default: return augment ? "k_augment_groups+k_tokenize_tile" : "k_tokenize_tile";
+    }
 }
 
 bsq_status bsq_fused_status(uint32_t *failures) {

@@ -1156,20 +1156,56 @@ static void build_rules(uint32_t fill_v, uint32_t at_len_v, T8Rules &rules) {
     }
 }
 
+// What every fast token kernel takes from (descriptor, padlen, raw): the folded alphabet and the lookup it allows, the BOS / EOS / PAD rule
+// table, the length clamp and the packed word's common bits.  raw = false: token VALUES (an unmapped character and, without padchar, the
+// fill are 0: the memset of tokenize.h:427 stays); raw = true: ids with BSQ_NO_TOKEN (255) where a one-hot row is all zero (packed bit 1).
+struct T8Shared {
+    T8Tab tab;
+    T8Rules rules;
+    int lk;          // 2: the register table (v_perm_b32), else the LDS byte table -- knob "tokens8_lookup": 0 automatic (registers when the
+                     // table folds), 1 LDS byte table, 2 registers
+    uint32_t none_v, fill, at_len, bos_id;
+    int32_t room;
+    uint32_t packed;
+    bool eosv;       // the token at bos + L differs from the fill behind it (see tokens_fast_body)
+};
+static int tokens8_lookup_of(bool foldable) {
+    int lk = tuning().tokens8_lookup;
+    if (lk == 0) lk = foldable ? 2 : 1;
+    if (lk == 2 && !foldable) lk = 1;
+    return lk;
+}
+static void t8_shared_setup(const bsq_desc *d, int64_t P, bool raw, T8Shared &c) {
+    c.none_v = raw ? 0xFFu : 0u;
+    c.lk = tokens8_lookup_of(fold_table(d->lut, c.tab.t, c.none_v));
+    c.fill = d->padchar ? uint32_t(bsq_pad_id(d)) : c.none_v;
+    c.at_len = d->eos ? uint32_t(bsq_eos_id(d)) : c.fill;
+    c.bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
+    build_rules(c.fill, c.at_len, c.rules);
+    const int64_t room = P - d->bos - d->eos;
+    c.room = int32_t(room < 0 ? 0 : room);
+    c.packed = uint32_t(d->bos != 0) | (raw ? 2u : 0u) | (c.bos_id << 8) | ((c.at_len & 0xFFu) << 16) | ((c.fill & 0xFFu) << 24);
+    c.eosv = (c.at_len & 0xFFu) != (c.fill & 0xFFu);
+}
+
 // The decisions of launch_tokens_bp8 as functions of the shape alone -- shared by the launcher and by bsq_tokenize_kernel_name (ADVICE round 5:
 // bench.py used to re-implement them and could report a kernel that was not the one launched).
 int64_t tokens_bp8_chunks(int64_t B, int64_t P) { return (B * ((P + 15) / 16) + kChunk / 16 - 1) / (kChunk / 16); }
-bool tokens_bp8_fast_form(const bsq_desc *d, int64_t B, int64_t P, bool aligned_out) {
-    uint32_t tab[8];
+// the fast form: register table, aligned rows, 32-bit piece indices (knob tokens8_fast = 1: never)
+static bool bp8_fast_form(int lk, int64_t B, int64_t P, bool aligned_out) {
     const Tuning &tn = tuning();
-    int lk = tn.tokens8_lookup;
-    const bool foldable = fold_table(d->lut, tab, 0u);
-    if (lk == 0) lk = foldable ? 2 : 1;
-    if (lk == 2 && !foldable) lk = 1;
     return lk == 2 && P % 16 == 0 && aligned_out && !tn.wide_index && tokens_bp8_chunks(B, P) < (int64_t(1) << 23) && B < (int64_t(1) << 31) &&
            tn.tokens8_fast != 1;
 }
-// fused augmentation + tokens: the no-wait form (k_augment_tokens_nowait + k_patch_tokens) or the flag form (k_augment_tokens_fused)
+bool tokens_bp8_fast_form(const bsq_desc *d, int64_t B, int64_t P, bool aligned_out) {
+    uint32_t tab[8];
+    return bp8_fast_form(tokens8_lookup_of(fold_table(d->lut, tab, 0u)), B, P, aligned_out);
+}
+// fused augmentation + tokens in one launch: where the fast form applies, unless a knob says no ("augment_fused" = 1: never; not under the
+// experiments' occupancy pad "tokens8_pad")
+static bool bp8_fused_allowed() { return tuning().augment_fused != 1 && tuning().tokens8_pad <= 0; }
+bool tokens_bp8_fused_form(const bsq_desc *d, int64_t B, int64_t P, bool aligned_out) { return bp8_fused_allowed() && tokens_bp8_fast_form(d, B, P, aligned_out); }
+// ... its no-wait form (k_augment_tokens_nowait + k_patch_tokens) or the flag form (k_augment_tokens_fused)
 bool tokens_bp8_nowait_form(int64_t nchunks) { return (tuning().augment_fused == 0 && nchunks <= 16384) || tuning().augment_fused == 4; }
 
 bool tokens_bp8_applicable(const bsq_desc *d, int64_t B, int64_t P, const void *out) {
@@ -1277,58 +1313,66 @@ void fused_failures_clear() {
     if (g_fused_failures) __atomic_store_n(g_fused_failures, 0u, __ATOMIC_RELAXED);
 }
 
+// What the launches of the (B,P) int8 kernels take from (descriptor, padlen, raw) -- one batch's (launch_tokens_bp8) or several batches'
+// (launch_tokens_multi): k_tokens_bp8_fast's scalar arguments, and what k_tokens_bp8's parameter block is filled from.
+struct Bp8Shared : T8Shared {
+    uint32_t ppr, magic, shift;  // 16-byte pieces per row and their fast_div() constants in the fast kernel's form
+    bool nt;
+};
+static void bp8_shared_setup(const bsq_desc *d, int64_t P, bool raw, Bp8Shared &c) {
+    t8_shared_setup(d, P, raw, c);
+    c.nt = nontemporal_stores() && !raw;  // (raw ids: plain stores, the expansion re-reads them at once)
+    c.ppr = uint32_t((P + 15) / 16);
+    uint32_t pow2 = 0;
+    div_constants(c.ppr, &c.magic, &c.shift, &pow2);
+    if (pow2) {  // d = 2^s, s >= 3: mulhi(n, 2^(32 - s)) == n >> s
+        c.magic = uint32_t(1) << (32 - c.shift);
+        c.shift = 0;
+    }
+}
+
 bsq_status launch_tokens_bp8(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
                              void *out, hipStream_t s, bool raw, const uint8_t *mask, const FusedAugRequest *fuse, bool *fused_taken) {
     if (fused_taken) *fused_taken = false;
-    if (mask && (!raw || P % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0))
+    const bool aligned_out = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    if (mask && (!raw || P % 16 != 0 || !aligned_out))
         return set_error(BSQ_ERR_INVALID_ARG, "k_tokens_bp8: a mask needs raw-id mode and an aligned shape");
-    T8Params c;
+    Bp8Shared sh;
+    bp8_shared_setup(d, P, raw, sh);
+    T8Params c;  // (k_tokens_bp8's block; the fast forms take its chunk count and output pointer)
     c.mask = mask;
     for (int i = 0; i < 256; ++i) c.lut[i] = d->lut[i];
-    c.none_v = raw ? 0xFFu : 0u;  // raw: ids with BSQ_NO_TOKEN where the one-hot row is all zero (plain stores: re-read at once)
-    const bool foldable = fold_table(d->lut, c.tab, c.none_v);
+    for (int i = 0; i < 8; ++i) c.tab[i] = sh.tab.t[i];
+    c.none_v = sh.none_v;
     c.chars = chars;
     c.offsets = offsets;
     c.out = static_cast<uint8_t *>(out);
     c.B = B;
     c.P = uint32_t(P);
     c.total = B * P;
-    c.ppr = uint32_t((P + 15) / 16);
-    c.nchunks = (B * int64_t(c.ppr) + kChunk / 16 - 1) / (kChunk / 16);  // 256 pieces per wave
+    c.ppr = sh.ppr;
+    c.nchunks = tokens_bp8_chunks(B, P);  // 256 pieces per wave
     c.inv_ppr = 1.0 / double(c.ppr);
     div_constants(c.ppr, &c.magic, &c.shift, &c.pow2);
     c.bos = d->bos;
-    const int64_t room = P - d->bos - d->eos;
-    c.room = int32_t(room < 0 ? 0 : room);
-    c.bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
-    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : c.none_v;  // no padchar: the memset 0 of tokenize.h:427 stays
-    c.fill_v = fill;
-    c.at_len_v = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
+    c.room = sh.room;
+    c.bos_id = sh.bos_id;
+    c.fill_v = sh.fill;
+    c.at_len_v = sh.at_len;
     c.abl = 0;
     c.wide_index = tuning().wide_index;
-    int lk = tuning().tokens8_lookup;  // 0 automatic (registers when the table folds), 1 LDS byte table, 2 registers
-    if (lk == 0) lk = foldable ? 2 : 1;
-    if (lk == 2 && !foldable) lk = 1;
     const int64_t groups = ((c.nchunks + 7) / 8 + 3) / 4;
     if (groups * 8 >= (int64_t(1) << 31)) return set_error(BSQ_ERR_INVALID_ARG, "output too large");
     const dim3 grid(unsigned(groups * 8));
     const int padv = tuning().tokens8_pad;  // unused dynamic LDS = occupancy cap (experiments)
     const size_t pad = padv > 0 ? size_t(padv) : 0;
-    const bool nt = nontemporal_stores() && !raw;
-    // the fast form: register table, aligned rows, no mask, 32-bit piece indices (knob tokens8_fast = 1: never)
-    if (lk == 2 && !mask && c.abl == 0 && P % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && !c.wide_index &&
-        c.nchunks < (int64_t(1) << 23) && B < (int64_t(1) << 31) && tuning().tokens8_fast != 1) {
-        uint32_t magic = c.magic, shift = c.shift;
-        if (c.pow2) {  // d = 2^s, s >= 3: mulhi(n, 2^(32 - s)) == n >> s
-            magic = uint32_t(1) << (32 - c.shift);
-            shift = 0;
-        }
-        const uint32_t packed = uint32_t(c.bos != 0) | (raw ? 2u : 0u) | (c.bos_id << 8) | ((c.at_len_v & 0xFFu) << 16) | ((c.fill_v & 0xFFu) << 24);
-        T8Tab tab;
-        for (int i = 0; i < 8; ++i) tab.t[i] = c.tab[i];
-        T8Rules rules;
-        build_rules(c.fill_v, c.at_len_v, rules);
-        if (fuse && fused_taken && tuning().augment_fused != 1 && pad == 0) {  // augmentation in the same launch (see k_augment_tokens_fused)
+    if (!mask && bp8_fast_form(sh.lk, B, P, aligned_out)) {  // (no masked fast form)
+        // one argument list for the three kernels that run tokens_fast_body on one batch (`extra`: the fused forms' augmentation block)
+        auto launch_fast = [&](auto kernel, dim3 g, size_t lds, auto... extra) {
+            hipLaunchKernelGGL(kernel, g, dim3(kThreads), lds, s, offsets, chars, c.out, uint32_t(c.nchunks), uint32_t(B), sh.ppr, sh.magic, sh.shift,
+                               sh.room, sh.packed, sh.tab, sh.rules, extra...);
+        };
+        if (fuse && fused_taken && bp8_fused_allowed()) {  // augmentation in the same launch (see k_augment_tokens_fused)
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             (void)hipStreamIsCapturing(s, &cap);
             const int64_t aug_blocks = ((B + 255) / 256 + 7) / 8 * 8;
@@ -1358,14 +1402,8 @@ bsq_status launch_tokens_bp8(const bsq_desc *d, const uint8_t *chars, const int6
                     fa.flags = nullptr;
                     fa.wait = FusedWait{};
                     fa.rec = static_cast<uint2 *>(ws);
-                    const bool eosv_f = (c.at_len_v & 0xFFu) != (c.fill_v & 0xFFu);
                     const dim3 fgrid(unsigned(aug_blocks + int64_t(grid.x)));
-#define BSQ_NOWAIT(NTV, EV)                                                                                                              \
-    hipLaunchKernelGGL((k_augment_tokens_nowait<NTV, 4, EV>), fgrid, dim3(kThreads), 0, s, offsets, chars, c.out, uint32_t(c.nchunks),   \
-                       uint32_t(B), c.ppr, magic, shift, c.room, packed, tab, rules, fa)
-                    if (nt) { if (eosv_f) BSQ_NOWAIT(true, true); else BSQ_NOWAIT(true, false); }
-                    else { if (eosv_f) BSQ_NOWAIT(false, true); else BSQ_NOWAIT(false, false); }
-#undef BSQ_NOWAIT
+                    with_flags([&](auto NT, auto EV) { launch_fast(k_augment_tokens_nowait<NT(), 4, EV()>, fgrid, 0, fa); }, sh.nt, sh.eosv);
                     hipError_t en = hipGetLastError();
                     if (en == hipSuccess && fuse->chain_len > 0) {
                         PatchLut pl;
@@ -1419,38 +1457,19 @@ bsq_status launch_tokens_bp8(const bsq_desc *d, const uint8_t *chars, const int6
                 const int64_t nap = c.nchunks / 136;
                 fa.wait.naps = uint32_t(nap < 6 ? 6 : (nap > 60 ? 60 : nap));
                 const dim3 fgrid(unsigned(aug_blocks_x + int64_t(grid.x)));
-#define BSQ_FUSED(NTV, SX)                                                                                                          \
-    hipLaunchKernelGGL((k_augment_tokens_fused<NTV, 4, SX>), fgrid, dim3(kThreads), 0, s, offsets, chars, c.out, uint32_t(c.nchunks), \
-                       uint32_t(B), c.ppr, magic, shift, c.room, packed, tab, rules, fa)
-                if (nt) { if (same_xcd) BSQ_FUSED(true, true); else BSQ_FUSED(true, false); }
-                else { if (same_xcd) BSQ_FUSED(false, true); else BSQ_FUSED(false, false); }
-#undef BSQ_FUSED
-                const hipError_t eff = hipGetLastError();
-                if (eff != hipSuccess) return set_hip_error("k_augment_tokens_fused", eff);
-                *fused_taken = true;
-                return BSQ_OK;
+                with_flags([&](auto NT, auto SX) { launch_fast(k_augment_tokens_fused<NT(), 4, SX()>, fgrid, 0, fa); }, sh.nt, same_xcd);
+                st = check_launch("k_augment_tokens_fused");
+                *fused_taken = st == BSQ_OK;
+                return st;
             }
         }
         if (fuse) return BSQ_OK;  // the caller runs the two launches (fused_taken stays false; nothing was launched)
-        const bool eosv = (c.at_len_v & 0xFFu) != (c.fill_v & 0xFFu);
-#define BSQ_T8F(NTV, EV)                                                                                                                 \
-    hipLaunchKernelGGL((k_tokens_bp8_fast<NTV, EV>), grid, dim3(kThreads), pad, s, offsets, chars, c.out, uint32_t(c.nchunks), uint32_t(B), \
-                       c.ppr, magic, shift, c.room, packed, tab, rules)
-        if (nt) { if (eosv) BSQ_T8F(true, true); else BSQ_T8F(true, false); }
-        else { if (eosv) BSQ_T8F(false, true); else BSQ_T8F(false, false); }
-#undef BSQ_T8F
-        const hipError_t ef = hipGetLastError();
-        if (ef != hipSuccess) return set_hip_error("k_tokens_bp8_fast", ef);
-        return BSQ_OK;
+        with_flags([&](auto NT, auto EV) { launch_fast(k_tokens_bp8_fast<NT(), EV()>, grid, pad); }, sh.nt, sh.eosv);
+        return check_launch("k_tokens_bp8_fast");
     }
     if (fuse) return BSQ_OK;  // no fused form for this shape: the caller runs the two launches
-#define BSQ_T8(NTV, LKV) launch_variant<NTV, LKV>(c, grid, pad, s)
-    if (lk == 2) { if (nt) BSQ_T8(true, 1); else BSQ_T8(false, 1); }
-    else { if (nt) BSQ_T8(true, 0); else BSQ_T8(false, 0); }
-#undef BSQ_T8
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error("k_tokens_bp8", e);
-    return BSQ_OK;
+    with_flags([&](auto NT, auto LK) { launch_variant<NT(), LK() ? 1 : 0>(c, grid, pad, s); }, sh.nt, sh.lk == 2);
+    return check_launch("k_tokens_bp8");
 }
 
 // (P,B) tokens of any element type (pitch = ELEMENTS between two position rows; the final matrix: pitch = B) through
@@ -1476,253 +1495,147 @@ bool tokens_pb8_applicable(const bsq_desc *d, int64_t B, int64_t P, const void *
 // group of 8 sequence tiles (knob "tokens_pb8_pair" = 1: never).  Shared with the raw-id multi launch (tokens_pb8_raw_paired).
 static bool pb8_paired_tail(int64_t ntb, int64_t P) { return P % 64 != 0 && P % 64 <= 32 && ntb > 8 && tuning().tokens_pb8_pair != 1; }
 
-bsq_status launch_tokens_pb8(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, void *out,
-                             int64_t pitch, hipStream_t s, bool raw, bsq_dtype t, bool nib, int64_t tt0, int64_t ntt_count) {
-    const uint32_t none_v = raw ? 0xFFu : 0u;
-    if (raw && t != BSQ_I8) return set_error(BSQ_ERR_INVALID_ARG, "raw ids are bytes");
-    if (nib && (!raw || pitch % 32 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 || bsq_alphabet_size(d) > 15))
-        return set_error(BSQ_ERR_INVALID_ARG, "nibble ids: raw mode, at most 15 classes, rows of a multiple of 32 ids");
-    T8Tab tab;
-    const bool foldable = fold_table(d->lut, tab.t, none_v);
-    // knob "tokens8_lookup": 0 automatic (registers when the table folds), 1 LDS byte table, 2 registers
-    int lk = tuning().tokens8_lookup;
-    if (lk == 0) lk = foldable ? 2 : 1;
-    if (lk == 2 && !foldable) lk = 1;
-    T8Lut lut;
+// The argument block of the k_tokens_pb8_fast family (its one-batch, multi-batch and raw multi-batch kernels) as it follows from the descriptor,
+// padlen and what differs between the launchers: raw (no one = 0xFF, packed bit 1), the divisor of the block index, contig (packed bit 2)
+// and the paired tail (packed bit 3).
+struct Pb8Shared : T8Shared {
+    uint32_t magic, shift;  // fast_div() constants of the block index's divisor; magic = 0 marks a power of two (the kernel shifts)
+    T8Lut lut;              // the LDS byte table's 256 entries, four per word (lk != 2)
+};
+static void pb8_shared_setup(const bsq_desc *d, int64_t P, bool raw, uint32_t divisor, bool contig, bool paired, Pb8Shared &c) {
+    t8_shared_setup(d, P, raw, c);
+    c.packed |= (contig ? 4u : 0u) | (paired ? 8u : 0u);
     for (int w = 0; w < 64; ++w) {
         uint32_t v = 0;
         for (int k = 0; k < 4; ++k) {
-            const int c = 4 * w + k;
-            const uint32_t tkn = (c < 128 && d->lut[c] >= 0) ? uint32_t(uint8_t(d->lut[c])) : none_v;
-            v |= tkn << (8 * k);
+            const int ch = 4 * w + k;
+            v |= ((ch < 128 && d->lut[ch] >= 0) ? uint32_t(uint8_t(d->lut[ch])) : c.none_v) << (8 * k);
         }
-        lut.w[w] = v;
+        c.lut.w[w] = v;
     }
-    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : none_v;  // no padchar: the memset 0 of tokenize.h:427 stays
-    const uint32_t at_len = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
-    const uint32_t bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
-    T8Rules rules;
-    build_rules(fill, at_len, rules);
-    const int64_t room64 = P - d->bos - d->eos;
-    const int32_t room = int32_t(room64 < 0 ? 0 : room64);
+    uint32_t pow2 = 0;
+    div_constants(divisor, &c.magic, &c.shift, &pow2);
+    if (pow2) c.magic = 0;
+}
+// one tile shape: 256 sequences x 64 positions (512 x 64 and 512 x 32 were built and measured slower:
+// profiles/r03/pb8_coalesced_ab.txt, pb8_512x32_tile_lost.txt)
+constexpr int kPb8TB = 256, kPb8TT = 64;
+// blocks of one (P,B) matrix in the class-pinned and the contiguous tile orders alike: its sequence tiles rounded up to 8, times the position tiles
+static int64_t pb8_blocks(int64_t ntb, int64_t ntt) { return (ntb + 7) / 8 * 8 * ntt; }
+
+bsq_status launch_tokens_pb8(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, void *out,
+                             int64_t pitch, hipStream_t s, bool raw, bsq_dtype t, bool nib, int64_t tt0, int64_t ntt_count) {
+    if (raw && t != BSQ_I8) return set_error(BSQ_ERR_INVALID_ARG, "raw ids are bytes");
+    if (nib && (!raw || pitch % 32 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 || bsq_alphabet_size(d) > 15))
+        return set_error(BSQ_ERR_INVALID_ARG, "nibble ids: raw mode, at most 15 classes, rows of a multiple of 32 ids");
+    const int64_t sz = int64_t(bsq_dtype_size(t));
     // bit 2: every XCD walks its own contiguous range of sequence tiles (rows that are not 64-byte aligned: the sectors two
     // neighbouring tiles share are then merged in ONE L2 -- 65 000 x 1024 int16: 49.6 -> 38.9 us, profiles/r03/pb8_unaligned_rows.txt)
     // (also for 4- / 8-byte elements: with the position tiles of a sequence tile back to back they took 53 / 111 us instead of 51 / 100)
-    const bool contig = (pitch * int64_t(bsq_dtype_size(t))) % 64 != 0 || reinterpret_cast<uintptr_t>(out) % 64 != 0 || bsq_dtype_size(t) >= 4;
-    uint32_t packed = uint32_t(d->bos != 0) | (raw ? 2u : 0u) | (contig ? 4u : 0u) | (bos_id << 8) | ((at_len & 0xFFu) << 16) | ((fill & 0xFFu) << 24);
-    const bool nt = nontemporal_stores() && !raw;  // the raw matrix is re-read by the expansion right away
-    // one tile shape: 256 sequences x 64 positions (512 x 64 and 512 x 32 were built and measured slower:
-    // profiles/r03/pb8_coalesced_ab.txt, pb8_512x32_tile_lost.txt)
-    const int TB = 256, TT = 64;
-    const int64_t ntb = (B + TB - 1) / TB, ntt_all = (P + TT - 1) / TT;
+    const bool contig = (pitch * sz) % 64 != 0 || reinterpret_cast<uintptr_t>(out) % 64 != 0 || sz >= 4;
+    const int64_t ntb = (B + kPb8TB - 1) / kPb8TB, ntt_all = (P + kPb8TT - 1) / kPb8TT;
     if (tt0 < 0 || tt0 >= ntt_all || ntt_count < 0 || tt0 + ntt_count > ntt_all) return set_error(BSQ_ERR_INVALID_ARG, "position tiles of the slice");
     const int64_t ntt = ntt_count > 0 ? ntt_count : ntt_all - tt0;  // the launch's position tiles: tt0 .. tt0 + ntt - 1 (`out` = the slice's first row)
     // the address row 0 of the matrix would have (the kernel indexes rows by their absolute position)
-    out = static_cast<uint8_t *>(out) - ((tt0 * TT * pitch * int64_t(bsq_dtype_size(t))) >> (nib ? 1 : 0));
-    const int64_t blocks = (ntb + 7) / 8 * 8 * ntt;
+    uint8_t *out0 = static_cast<uint8_t *>(out) - ((tt0 * kPb8TT * pitch * sz) >> (nib ? 1 : 0));
+    const int64_t blocks = pb8_blocks(ntb, ntt);
     if (blocks >= (int64_t(1) << 31)) return set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    const bool ua = !((pitch * int64_t(bsq_dtype_size(t))) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
-                      (raw || (B * int64_t(bsq_dtype_size(t))) % 16 == 0));
-    uint32_t magic = 0, shift = 0, pow2 = 0;
-    div_constants((contig || ua) ? uint32_t((ntb + 7) / 8) : uint32_t(ntt), &magic, &shift, &pow2);  // the divisor of the block index
-    if (pow2) magic = 0;  // the kernel shifts (magic 0 marks a power of two)
+    const bool ua = !((pitch * sz) % 16 == 0 && reinterpret_cast<uintptr_t>(out0) % 16 == 0 && (raw || (B * sz) % 16 == 0));
     // paired tail (see the kernel): the last position tile holds 1 ... 32 positions, the aligned class-pinned form, more than one group of 8 sequence
     // tiles (knob "tokens_pb8_pair" = 1: never)
-    if (!contig && !ua && pb8_paired_tail(ntb, P)) packed |= 8u;
-#define BSQ_PB8U(NTV, LKV, SZV, FLTV, UAV)                                                                                             \
-    hipLaunchKernelGGL((k_tokens_pb8_fast<NTV, 256, LKV, SZV, FLTV, UAV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, offsets, chars,  \
-                       static_cast<uint8_t *>(out), pitch, uint32_t(B), uint32_t(P), uint32_t(ntb), uint32_t(ntt), magic, shift,    \
-                       room, packed, uint32_t(tt0), tab, rules, lut)
-#define BSQ_PB8(NTV, LKV, SZV, FLTV)                                       \
-    do {                                                                   \
-        if constexpr (SZV <= 2 && !FLTV) {                                 \
-            if (ua) BSQ_PB8U(NTV, LKV, SZV, FLTV, true);                   \
-            else BSQ_PB8U(NTV, LKV, SZV, FLTV, false);                     \
-        } else {                                                           \
-            BSQ_PB8U(NTV, LKV, SZV, FLTV, false);                          \
-        }                                                                  \
-    } while (0)
-#define BSQ_PB8_T(SZV, FLTV)                                                                   \
-    do {                                                                                       \
-        if (lk == 2) { if (nt) BSQ_PB8(true, 1, SZV, FLTV); else BSQ_PB8(false, 1, SZV, FLTV); } \
-        else { if (nt) BSQ_PB8(true, 0, SZV, FLTV); else BSQ_PB8(false, 0, SZV, FLTV); }         \
-    } while (0)
+    Pb8Shared c;
+    pb8_shared_setup(d, P, raw, (contig || ua) ? uint32_t((ntb + 7) / 8) : uint32_t(ntt), contig, !contig && !ua && pb8_paired_tail(ntb, P), c);
+    const bool nt = nontemporal_stores() && !raw;  // the raw matrix is re-read by the expansion right away
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, s, offsets, chars, out0, pitch, uint32_t(B), uint32_t(P), uint32_t(ntb),
+                           uint32_t(ntt), c.magic, c.shift, c.room, c.packed, uint32_t(tt0), c.tab, c.rules, c.lut);
+    };
     if (nib) {  // (raw: plain stores, aligned rows)
-#define BSQ_PB8N(LKV)                                                                                                                     \
-    hipLaunchKernelGGL((k_tokens_pb8_fast<false, 256, LKV, 1, false, false, true>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, offsets, \
-                       chars, static_cast<uint8_t *>(out), pitch, uint32_t(B), uint32_t(P), uint32_t(ntb), uint32_t(ntt), magic, shift,   \
-                       room, packed, uint32_t(tt0), tab, rules, lut)
-        if (lk == 2) BSQ_PB8N(1); else BSQ_PB8N(0);
-#undef BSQ_PB8N
-        const hipError_t en = hipGetLastError();
-        if (en != hipSuccess) return set_hip_error("k_tokens_pb8_fast<nibbles>", en);
-        return BSQ_OK;
+        with_flags([&](auto LK) { launch(k_tokens_pb8_fast<false, kPb8TB, LK() ? 1 : 0, 1, false, false, true>); }, c.lk == 2);
+        return check_launch("k_tokens_pb8_fast<nibbles>");
     }
-    switch (t) {
-    case BSQ_I8: BSQ_PB8_T(1, false); break;
-    case BSQ_I16: BSQ_PB8_T(2, false); break;
-    case BSQ_I32: BSQ_PB8_T(4, false); break;
-    case BSQ_F32: BSQ_PB8_T(4, true); break;
-    case BSQ_U64: BSQ_PB8_T(8, false); break;
-    case BSQ_F64: BSQ_PB8_T(8, true); break;
-    default: return set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
-    }
-#undef BSQ_PB8_T
-#undef BSQ_PB8
-#undef BSQ_PB8U
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error("k_tokens_pb8_fast", e);
-    return BSQ_OK;
+    return with_value_type(t, [&](auto zero) {
+        using T = decltype(zero);
+        constexpr int SZ = int(sizeof(T));
+        constexpr bool FLT = std::is_floating_point<T>::value;
+        constexpr bool kHasUA = SZ <= 2 && !FLT;  // the UA form (rows that are only element-aligned) exists for 1- and 2-byte integers only
+        with_flags([&](auto NT, auto LK, auto UA) {
+            if constexpr (kHasUA || !UA()) launch(k_tokens_pb8_fast<NT(), kPb8TB, LK() ? 1 : 0, SZ, FLT, UA()>);
+        }, nt, c.lk == 2, kHasUA && ua);
+        return check_launch("k_tokens_pb8_fast");
+    });
 }
 
-// What the batches of a multi-batch (B,P) int8 launch share (k_tokens_bp8_fast's scalar arguments), and their per-batch table.
-struct Bp8Shared {
-    uint32_t ppr, magic, shift, packed;
-    int32_t room;
-    T8Tab tab;
-    T8Rules rules;
-    bool eosv, nt;
-};
-// false: the fast (B,P) int8 kernel does not take this tokenizer / padlen (or a knob says no)
-static bool bp8_shared_setup(const bsq_desc *d, int64_t P, Bp8Shared &c) {
-    const Tuning &tn = tuning();
-    if (bsq_alphabet_size(d) > 250 || P < 128 || P % 16 != 0 || P > (int64_t(1) << 30)) return false;
-    if (tn.tokenize_path == 1 || tn.wide_index || tn.tokens8_pad > 0 || tn.tokens8 == 1 || tn.tokens8_fast == 1) return false;
-    const bool foldable = fold_table(d->lut, c.tab.t, 0u);
-    if (!foldable || tn.tokens8_lookup == 1) return false;  // (the LDS byte-table form has no fast kernel)
-    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : 0u;
-    const uint32_t at_len = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
-    const uint32_t bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
-    build_rules(fill, at_len, c.rules);
-    const int64_t room64 = P - d->bos - d->eos;
-    c.room = int32_t(room64 < 0 ? 0 : room64);
-    c.nt = nontemporal_stores();
-    c.ppr = uint32_t(P / 16);
-    uint32_t pow2 = 0;
-    div_constants(c.ppr, &c.magic, &c.shift, &pow2);
-    if (pow2) {  // d = 2^s, s >= 3: mulhi(n, 2^(32 - s)) == n >> s
-        c.magic = uint32_t(1) << (32 - c.shift);
-        c.shift = 0;
-    }
-    c.packed = uint32_t(d->bos != 0) | (bos_id << 8) | ((at_len & 0xFFu) << 16) | ((fill & 0xFFu) << 24);
-    c.eosv = (at_len & 0xFFu) != (fill & 0xFFu);
-    return true;
-}
 static void multi_clear(T8Multi &m) {
     for (int i = 0; i < kMultiMax; ++i) {
         m.offsets[i] = nullptr, m.chars[i] = nullptr, m.out[i] = nullptr;
         m.first_block[i] = 0xFFFFFFFFu, m.units[i] = 0, m.B[i] = 0;
     }
 }
-// false: some batch does not qualify (alignment, size); *blocks = the grid of the n batches' chunk streams
-static bool bp8_multi_table(const bsq_desc *d, int32_t n, const bsq_batch *bt, int64_t P, uint32_t ppr, T8Multi &m, int64_t *blocks) {
-    multi_clear(m);
-    *blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t B = bt[i].B;
-        if (B <= 0 || B >= (int64_t(1) << 31) || !tokens_bp8_applicable(d, B, P, bt[i].out) || reinterpret_cast<uintptr_t>(bt[i].out) % 16 != 0) return false;
-        const int64_t nchunks = (B * int64_t(ppr) + kChunk / 16 - 1) / (kChunk / 16);
-        if (nchunks >= (int64_t(1) << 23)) return false;
-        m.offsets[i] = bt[i].offsets, m.chars[i] = bt[i].chars, m.out[i] = static_cast<uint8_t *>(bt[i].out);
-        m.first_block[i] = uint32_t(*blocks), m.units[i] = uint32_t(nchunks), m.B[i] = uint32_t(B);
-        *blocks += ((nchunks + 7) / 8 + 3) / 4 * 8;
-    }
-    return *blocks < (int64_t(1) << 31);
-}
-static bsq_status launch_bp8_multi(const Bp8Shared &c, const T8Multi &m, int64_t blocks, hipStream_t s) {
-#define BSQ_T8M(NTV, EV) \
-    hipLaunchKernelGGL((k_tokens_bp8_fast_multi<NTV, EV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, c.ppr, c.magic, c.shift, c.room, c.packed, c.tab, c.rules, m)
-    if (c.nt) { if (c.eosv) BSQ_T8M(true, true); else BSQ_T8M(true, false); }
-    else { if (c.eosv) BSQ_T8M(false, true); else BSQ_T8M(false, false); }
-#undef BSQ_T8M
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error("k_tokens_bp8_fast_multi", e);
-    return BSQ_OK;
+static void multi_add(T8Multi &m, int i, const int64_t *offsets, const uint8_t *chars, void *out, int64_t first_block, int64_t units, int64_t B) {
+    m.offsets[i] = offsets, m.chars[i] = chars, m.out[i] = static_cast<uint8_t *>(out);
+    m.first_block[i] = uint32_t(first_block), m.units[i] = uint32_t(units), m.B[i] = uint32_t(B);
 }
 
 // n <= kMultiMax independent batches of one tokenizer, padlen, layout and element type in ONE launch (bsq_tokenize_device_multi).  *taken =
 // false and nothing launched when some batch does not qualify for the fast kernel of its layout (the caller then issues the batches
-// one after the other): (B,P): int8, padlen % 16 == 0 and >= 128, 16-byte aligned outputs, a foldable alphabet; (P,B): 1- / 2-byte
-// integers, B * sz % 64 == 0 and 64-byte aligned outputs (the class-pinned tile order whose block-index divisor the batches share).
+// one after the other): (B,P): int8 and what the single call's fast form asks (padlen % 16 == 0 and >= 128, 16-byte aligned outputs, a
+// foldable alphabet); (P,B): 1- / 2-byte integers, B * sz % 64 == 0 and 64-byte aligned outputs (the class-pinned tile order whose
+// block-index divisor the batches share).
 bsq_status launch_tokens_multi(const bsq_desc *d, int32_t n, const bsq_batch *bt, int64_t P, bool batch_first, bsq_dtype t, hipStream_t s,
                                bool *taken) {
     *taken = false;
     if (n < 1 || n > kMultiMax || bsq_alphabet_size(d) > 250 || P <= 0 || P > (int64_t(1) << 30)) return BSQ_OK;
     const Tuning &tn = tuning();
     if (tn.tokenize_path == 1 || tn.wide_index || tn.tokens8_pad > 0) return BSQ_OK;
-    const size_t sz = bsq_dtype_size(t);
-    if (batch_first) {
-        Bp8Shared c;
-        T8Multi m;
-        int64_t blocks = 0;
-        if (t != BSQ_I8 || !bp8_shared_setup(d, P, c) || !bp8_multi_table(d, n, bt, P, c.ppr, m, &blocks)) return BSQ_OK;
-        const bsq_status st = launch_bp8_multi(c, m, blocks, s);
-        if (st != BSQ_OK) return st;
-        *taken = true;
-        return BSQ_OK;
-    }
-    const uint32_t none_v = 0u;
-    T8Tab tab;
-    const bool foldable = fold_table(d->lut, tab.t, none_v);
-    int lk = tn.tokens8_lookup;  // 0 automatic (registers when the table folds), 1 LDS byte table, 2 registers
-    if (lk == 0) lk = foldable ? 2 : 1;
-    if (lk == 2 && !foldable) lk = 1;
-    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : none_v;
-    const uint32_t at_len = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
-    const uint32_t bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
-    T8Rules rules;
-    build_rules(fill, at_len, rules);
-    const int64_t room64 = P - d->bos - d->eos;
-    const int32_t room = int32_t(room64 < 0 ? 0 : room64);
-    const bool nt = nontemporal_stores();
     T8Multi m;
     multi_clear(m);
     int64_t blocks = 0;
+    if (batch_first) {
+        if (t != BSQ_I8 || tn.tokens8 == 1) return BSQ_OK;
+        Bp8Shared c;
+        bp8_shared_setup(d, P, false, c);
+        for (int i = 0; i < n; ++i) {
+            const int64_t B = bt[i].B;
+            if (!tokens_bp8_applicable(d, B, P, bt[i].out) || !bp8_fast_form(c.lk, B, P, reinterpret_cast<uintptr_t>(bt[i].out) % 16 == 0)) return BSQ_OK;
+            const int64_t nchunks = tokens_bp8_chunks(B, P);
+            multi_add(m, i, bt[i].offsets, bt[i].chars, bt[i].out, blocks, nchunks, B);
+            blocks += ((nchunks + 7) / 8 + 3) / 4 * 8;
+        }
+        if (blocks >= (int64_t(1) << 31)) return BSQ_OK;
+        with_flags([&](auto NT, auto EV) {
+            hipLaunchKernelGGL((k_tokens_bp8_fast_multi<NT(), EV()>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, c.ppr, c.magic, c.shift, c.room,
+                               c.packed, c.tab, c.rules, m);
+        }, c.nt, c.eosv);
+        const bsq_status st = check_launch("k_tokens_bp8_fast_multi");
+        *taken = st == BSQ_OK;
+        return st;
+    }
+    const size_t sz = bsq_dtype_size(t);
     if (sz > 2 || (t != BSQ_I8 && t != BSQ_I16) || tn.tokens_pb8 == 1 || tn.tokens_pb8 == 3) return BSQ_OK;
-    const int TB = 256, TT = 64;
-    const int64_t ntt = (P + TT - 1) / TT;
+    const int64_t ntt = (P + kPb8TT - 1) / kPb8TT;
     for (int i = 0; i < n; ++i) {
         const int64_t B = bt[i].B;
         if (B <= 0 || !tokens_pb8_applicable(d, B, P, bt[i].out, B, t) || (B * int64_t(sz)) % 64 != 0 || reinterpret_cast<uintptr_t>(bt[i].out) % 64 != 0)
             return BSQ_OK;
-        const int64_t ntb = (B + TB - 1) / TB;
-        m.offsets[i] = bt[i].offsets, m.chars[i] = bt[i].chars, m.out[i] = static_cast<uint8_t *>(bt[i].out);
-        m.first_block[i] = uint32_t(blocks), m.units[i] = uint32_t(ntb), m.B[i] = uint32_t(B);
-        blocks += (ntb + 7) / 8 * 8 * ntt;
+        const int64_t ntb = (B + kPb8TB - 1) / kPb8TB;
+        multi_add(m, i, bt[i].offsets, bt[i].chars, bt[i].out, blocks, ntb, B);
+        blocks += pb8_blocks(ntb, ntt);
     }
     if (blocks >= (int64_t(1) << 31)) return BSQ_OK;
-    T8Lut lut;
-    for (int w = 0; w < 64; ++w) {
-        uint32_t v = 0;
-        for (int k = 0; k < 4; ++k) {
-            const int c = 4 * w + k;
-            v |= ((c < 128 && d->lut[c] >= 0) ? uint32_t(uint8_t(d->lut[c])) : none_v) << (8 * k);
-        }
-        lut.w[w] = v;
-    }
-    uint32_t magic = 0, shift = 0, pow2 = 0;
-    div_constants(uint32_t(ntt), &magic, &shift, &pow2);
-    if (pow2) magic = 0;  // the kernel shifts (magic 0 marks a power of two)
-    const uint32_t packed = uint32_t(d->bos != 0) | (bos_id << 8) | ((at_len & 0xFFu) << 16) | ((fill & 0xFFu) << 24);
-#define BSQ_PB8M(NTV, LKV, SZV)                                                                                                            \
-    hipLaunchKernelGGL((k_tokens_pb8_fast_multi<NTV, LKV, SZV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, uint32_t(P), uint32_t(ntt), magic, \
-                       shift, room, packed, tab, rules, lut, m)
-#define BSQ_PB8M_T(SZV)                                                              \
-    do {                                                                             \
-        if (lk == 2) { if (nt) BSQ_PB8M(true, 1, SZV); else BSQ_PB8M(false, 1, SZV); } \
-        else { if (nt) BSQ_PB8M(true, 0, SZV); else BSQ_PB8M(false, 0, SZV); }         \
-    } while (0)
-    if (sz == 1) BSQ_PB8M_T(1); else BSQ_PB8M_T(2);
-#undef BSQ_PB8M_T
-#undef BSQ_PB8M
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error("k_tokens_pb8_fast_multi", e);
-    *taken = true;
-    return BSQ_OK;
+    Pb8Shared c;
+    pb8_shared_setup(d, P, false, uint32_t(ntt), false, false, c);
+    with_flags([&](auto NT, auto LK, auto WIDE) {
+        hipLaunchKernelGGL((k_tokens_pb8_fast_multi<NT(), LK() ? 1 : 0, WIDE() ? 2 : 1>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, uint32_t(P),
+                           uint32_t(ntt), c.magic, c.shift, c.room, c.packed, c.tab, c.rules, c.lut, m);
+    }, nontemporal_stores(), c.lk == 2, sz == 2);
+    const bsq_status st = check_launch("k_tokens_pb8_fast_multi");
+    *taken = st == BSQ_OK;
+    return st;
 }
 
 // The paired-tail flag (packed bit 3) launch_tokens_pb8 sets for the raw pass of a B-sequence batch into an aligned scratch of the two-pass pitch
-bool tokens_pb8_raw_paired(int64_t B, int64_t P) { return pb8_paired_tail((B + 255) / 256, P); }
+bool tokens_pb8_raw_paired(int64_t B, int64_t P) { return pb8_paired_tail((B + kPb8TB - 1) / kPb8TB, P); }
 
 // n (1 ... kMultiMax) raw-id passes -- exactly what launch_tokens_pb8(d, chars, offsets, B, P, ws[i], pitch = B rounded up to 256, raw = true,
 // BSQ_I8, nib) launches for each -- in ONE launch.  Every ws[i] 64-byte aligned; the batches share the paired-tail flag (tokens_pb8_raw_paired).
@@ -1730,58 +1643,26 @@ bsq_status launch_tokens_pb8_raw_multi(const bsq_desc *d, int32_t n, const uint8
                                        int64_t P, uint8_t *const *ws, bool nib, hipStream_t s) {
     if (n < 1 || n > kMultiMax || P <= 0 || P > (int64_t(1) << 30)) return set_error(BSQ_ERR_INVALID_ARG, "raw multi: 1 ... 8 batches, padlen");
     if (nib && bsq_alphabet_size(d) > 15) return set_error(BSQ_ERR_INVALID_ARG, "nibble ids: at most 15 classes");
-    const uint32_t none_v = 0xFFu;
-    T8Tab tab;
-    const bool foldable = fold_table(d->lut, tab.t, none_v);
-    int lk = tuning().tokens8_lookup;  // as launch_tokens_pb8
-    if (lk == 0) lk = foldable ? 2 : 1;
-    if (lk == 2 && !foldable) lk = 1;
-    T8Lut lut;
-    for (int w = 0; w < 64; ++w) {
-        uint32_t v = 0;
-        for (int k = 0; k < 4; ++k) {
-            const int c = 4 * w + k;
-            const uint32_t tkn = (c < 128 && d->lut[c] >= 0) ? uint32_t(uint8_t(d->lut[c])) : none_v;
-            v |= tkn << (8 * k);
-        }
-        lut.w[w] = v;
-    }
-    const uint32_t fill = d->padchar ? uint32_t(bsq_pad_id(d)) : none_v;
-    const uint32_t at_len = d->eos ? uint32_t(bsq_eos_id(d)) : fill;
-    const uint32_t bos_id = uint32_t(bsq_bos_id(d)) & 0xFFu;
-    T8Rules rules;
-    build_rules(fill, at_len, rules);
-    const int64_t room64 = P - d->bos - d->eos;
-    const int32_t room = int32_t(room64 < 0 ? 0 : room64);
-    const int TT = 64;
-    const int64_t ntt = (P + TT - 1) / TT;
+    const int64_t ntt = (P + kPb8TT - 1) / kPb8TT;
     const bool paired = tokens_pb8_raw_paired(Bs[0], P);
-    uint32_t packed = uint32_t(d->bos != 0) | 2u | (paired ? 8u : 0u) | (bos_id << 8) | ((at_len & 0xFFu) << 16) | ((fill & 0xFFu) << 24);
     T8Multi m;
     multi_clear(m);
     int64_t blocks = 0;
     for (int32_t i = 0; i < n; ++i) {
-        const int64_t B = Bs[i], pitch = (B + 255) / 256 * 256;
+        const int64_t B = Bs[i], ntb = (B + kPb8TB - 1) / kPb8TB, pitch = ntb * kPb8TB;
         if (!tokens_pb8_applicable(d, B, P, ws[i], pitch) || reinterpret_cast<uintptr_t>(ws[i]) % 64 != 0 || tokens_pb8_raw_paired(B, P) != paired)
             return set_error(BSQ_ERR_INVALID_ARG, "raw multi: a batch the one-piece raw pass does not take alike");
-        const int64_t ntb = (B + 255) / 256;
-        m.offsets[i] = offsets[i], m.chars[i] = chars[i], m.out[i] = ws[i];
-        m.first_block[i] = uint32_t(blocks), m.units[i] = uint32_t(ntb), m.B[i] = uint32_t(B);
-        blocks += (ntb + 7) / 8 * 8 * ntt;
+        multi_add(m, i, offsets[i], chars[i], ws[i], blocks, ntb, B);
+        blocks += pb8_blocks(ntb, ntt);
     }
     if (blocks >= (int64_t(1) << 31)) return set_error(BSQ_ERR_INVALID_ARG, "output too large");
-    uint32_t magic = 0, shift = 0, pow2 = 0;
-    div_constants(uint32_t(ntt), &magic, &shift, &pow2);
-    if (pow2) magic = 0;  // the kernel shifts (magic 0 marks a power of two)
-#define BSQ_PB8RM(LKV, NIBV)                                                                                                                   \
-    hipLaunchKernelGGL((k_tokens_pb8_fast_raw_multi<LKV, NIBV>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, uint32_t(P), uint32_t(ntt), magic, \
-                       shift, room, packed, tab, rules, lut, m)
-    if (nib) { if (lk == 2) BSQ_PB8RM(1, true); else BSQ_PB8RM(0, true); }
-    else { if (lk == 2) BSQ_PB8RM(1, false); else BSQ_PB8RM(0, false); }
-#undef BSQ_PB8RM
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_hip_error(nib ? "k_tokens_pb8_fast_raw_multi<nibbles>" : "k_tokens_pb8_fast_raw_multi", e);
-    return BSQ_OK;
+    Pb8Shared c;
+    pb8_shared_setup(d, P, true, uint32_t(ntt), false, paired, c);
+    with_flags([&](auto LK, auto NIB) {
+        hipLaunchKernelGGL((k_tokens_pb8_fast_raw_multi<LK() ? 1 : 0, NIB()>), dim3(unsigned(blocks)), dim3(kThreads), 0, s, uint32_t(P), uint32_t(ntt),
+                           c.magic, c.shift, c.room, c.packed, c.tab, c.rules, c.lut, m);
+    }, c.lk == 2, nib);
+    return check_launch(nib ? "k_tokens_pb8_fast_raw_multi<nibbles>" : "k_tokens_pb8_fast_raw_multi");
 }
 
 }  // namespace bsq_internal
