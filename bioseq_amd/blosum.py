@@ -67,16 +67,10 @@ def augment_packed(chars, offsets, chain_len=1, augment_frac=1.0, seed=0):
     loaders.py:35) by `chain_len` BLOSUM62-weighted point substitutions; unknown residues use the X row.
     Deterministic in (seed, sequence index).  Runs on torch's current stream.
     """
-    import torch
-    if not (chars.is_cuda and offsets.is_cuda):
-        raise ValueError("augment_packed works on device tensors (use .to('cuda'))")
-    if chars.dtype != torch.uint8 or offsets.dtype != torch.int64 or not chars.is_contiguous() or not offsets.is_contiguous():
-        raise ValueError("chars must be contiguous uint8 and offsets contiguous int64")
-    B = offsets.numel() - 1
+    B = capi.packed_on_device(chars, offsets, "augment_packed works on device tensors (use .to('cuda'))")
     if chars.numel() == 0:
         return chars  # a batch of empty sequences: nothing to mutate
-    with capi.on_device(chars.device):
-        stream = capi.raw_stream(chars.device)
+    with capi.launching(chars.device) as stream:
         capi.check(_lib.bsq_augment_device(chars.data_ptr(), offsets.data_ptr(), B, int(chain_len), float(augment_frac),
                                            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), stream))
     return chars
@@ -106,26 +100,15 @@ def augment_tokenize_packed(tokenizer, chars, offsets, padlen, destchar="b", bat
     padlen - bos - eos must have been rejected by the caller (as `tokenize_packed(validate=True)` does).
     Raises RuntimeError (here, at the next call, or from `check_fused`) if an earlier one-launch call failed inside the kernel."""
     import torch
-    if not (chars.is_cuda and offsets.is_cuda):
-        raise ValueError("augment_tokenize_packed works on device tensors (use .to('cuda'))")
-    if chars.dtype != torch.uint8 or offsets.dtype != torch.int64 or not chars.is_contiguous() or not offsets.is_contiguous():
-        raise ValueError("chars must be contiguous uint8 and offsets contiguous int64")
-    B = offsets.numel() - 1
-    dt = ctypes.c_int(0)
-    capi.check(_lib.bsq_dtype_from_destchar(destchar.encode(), ctypes.byref(dt)))
-    tdt = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[_lib.bsq_dtype_size(dt)]
-    if destchar[0].lower() == "f":
-        tdt = torch.float32
-    elif destchar[0].lower() == "d":
-        tdt = torch.float64
+    B = capi.packed_on_device(chars, offsets, "augment_tokenize_packed works on device tensors (use .to('cuda'))")
+    dt, tdt = capi.dtype_of(destchar)
     shape = (B, padlen) if batch_first else (padlen, B)
     if out is None:
         out = torch.empty(shape, dtype=tdt, device=chars.device)
     elif tuple(out.shape) != shape or out.dtype != tdt or not out.is_contiguous() or out.device != chars.device:
         raise ValueError("out must be a contiguous %s tensor of shape %r on the device of chars" % (tdt, shape))
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
-    with capi.on_device(chars.device):
-        stream = capi.raw_stream(chars.device)
+    desc = capi.desc_of(tokenizer)
+    with capi.launching(chars.device) as stream:
         capi.check(_lib.bsq_augment_tokenize_device(ctypes.byref(desc), chars.data_ptr(), offsets.data_ptr(), B, int(padlen),
                                                     int(bool(batch_first)), dt, out.data_ptr(), int(chain_len) if chars.numel() else 0, float(augment_frac),
                                                     ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), stream))

@@ -23,6 +23,7 @@ EXT = os.path.join(HERE, "cbioseq" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 LIB_SRCS = ["bsq_onehot.hip", "bsq_tokens.hip", "bsq_generic.hip", "bsq_tokens8.hip", "bsq_decode.hip", "bsq_augment.hip", "bsq_mlm.hip", "bsq_gather.hip", "bsq_views.hip", "bsq_diag.hip", "bsq_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
 EXT_SRCS = ["cbioseq_module.cpp"]
+EXT_HDRS = ["bsq_worker_pool.h"]
 
 
 def _newer(target, deps):
@@ -96,7 +97,8 @@ def build_lib(force=False):
 def build_ext(force=False):
     import pybind11
     import glob
-    deps = [os.path.join(CSRC, f) for f in EXT_SRCS] + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + [LIB]
+    # the headers the module includes: the public ones and, from csrc/, the worker pool (everything else there belongs to the library)
+    deps = [os.path.join(CSRC, f) for f in EXT_SRCS + EXT_HDRS] + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + [LIB]
     if force or _newer(EXT, deps):
         _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wextra",
               "-I" + INCLUDE, "-I" + pybind11.get_include(), "-I" + sysconfig.get_paths()["include"],

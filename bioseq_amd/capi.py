@@ -198,3 +198,95 @@ def raw_stream(device=None):
     if fast is not None:
         return fast(idx)
     return torch.cuda.current_stream(idx).cuda_stream
+
+
+class launching:
+    """`with launching(device) as stream:` -- `on_device(device)`, yielding the current stream of `device` as the `void *` a launch takes."""
+    __slots__ = ("_device", "_guard")
+
+    def __init__(self, device):
+        self._device, self._guard = device, on_device(device)
+
+    def __enter__(self):
+        if self._guard is not _NO_CONTEXT:
+            self._guard.__enter__()
+        return ctypes.c_void_p(raw_stream(self._device))
+
+    def __exit__(self, *a):
+        return self._guard.__exit__(*a)
+
+
+# ---- what every wrapper of the package derives before a call: descriptor, element type, checked arguments, the reference's errors ----
+
+_descs = {}
+
+
+def desc_of(tokenizer) -> Desc:
+    """The bsq_desc of a `Tokenizer`, built once per (key, eos, bos, padchar): no call of the library writes to a descriptor."""
+    key = (tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
+    d = _descs.get(key)
+    if d is None:
+        d = _descs[key] = make_desc(*key)
+    return d
+
+
+_torch_dtypes = None
+_dtypes = {}
+
+
+def torch_dtype(code: int):
+    """bsq_dtype code -> torch dtype.  U64 ('l' / 'q') results are uint64 in numpy (the reference's type) and torch.int64 on the device:
+    same bits for token ids and 0/1, and torch.uint64 supports almost no ops."""
+    global _torch_dtypes
+    if _torch_dtypes is None:
+        import torch
+        _torch_dtypes = {I8: torch.int8, I16: torch.int16, I32: torch.int32, U64: torch.int64, F32: torch.float32, F64: torch.float64}
+    return _torch_dtypes[code]
+
+
+def dtype_of(destchar):
+    """(bsq_dtype code, torch dtype) of a `destchar` as `bsq_dtype_from_destchar` reads it; a character it refuses raises as `check` does."""
+    got = _dtypes.get(destchar)
+    if got is None:
+        dt = ctypes.c_int(0)
+        check(load().bsq_dtype_from_destchar(str(destchar).encode(), ctypes.byref(dt)))
+        got = _dtypes[destchar] = (dt.value, torch_dtype(dt.value))
+    return got
+
+
+def parse_layout(layout) -> bool:
+    """True for the channels-first one-hot (B, C, padlen), False for the reference's (padlen, B, C) -- the names `onehot_packed` takes."""
+    if layout in ("tbc", "seq_first", ""):
+        return False
+    if layout in ("bcl", "channels_first"):
+        return True
+    raise ValueError("layout must be 'tbc' (padlen, batch, channels) or 'bcl' (batch, channels, padlen)")
+
+
+def packed_on_device(chars, offsets, what, exact=True, apart="chars and offsets must live on one device") -> int:
+    """B of a packed batch (chars, offsets) that is resident on ONE device -- ValueError `what` / `apart` otherwise -- and, with `exact`,
+    already what the C ABI reads: contiguous uint8 characters and contiguous int64 offsets (a caller that converts passes exact=False)."""
+    import torch
+    if not (isinstance(chars, torch.Tensor) and isinstance(offsets, torch.Tensor) and chars.is_cuda and offsets.is_cuda):
+        raise ValueError(what)
+    if chars.device != offsets.device:
+        raise ValueError(apart)
+    if exact and (chars.dtype != torch.uint8 or offsets.dtype != torch.int64 or not chars.is_contiguous() or not offsets.is_contiguous()):
+        raise ValueError("chars must be contiguous uint8 and offsets contiguous int64")
+    return int(offsets.numel()) - 1
+
+
+def readable_chars(chars, device):
+    """`chars`, or a 16-byte stand-in for an empty tensor: torch hands out a null data_ptr for a tensor without elements, which the entry
+    points refuse for B > 0 (include/bsq.h) -- no kernel reads a character of an empty sequence, so any valid address will do."""
+    if chars.numel():
+        return chars
+    import torch
+    return torch.zeros(16, dtype=torch.uint8, device=device)
+
+
+def raise_too_long(tokenizer, length, padlen, onehot):
+    """The reference's error for an over-long sequence, type and text (RuntimeError from batch_tokenize, tokenize.h:456-459;
+    ValueError from batch_onehot_encode, :359-362) -- as `Tokenizer.batch_tokenize` / `batch_onehot_encode` raise it here."""
+    tl = int(length) + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
+    raise (ValueError if onehot else RuntimeError)("seq len + bos + eos > padlen: %d, vs padlen %d" % (tl, int(padlen)))

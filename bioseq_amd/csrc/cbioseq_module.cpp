@@ -409,16 +409,13 @@ Packed pack(const Gathered &g, int nthreads) {
     return p;
 }
 
-const char *numpy_dtype_name(bsq_dtype t) {
-    switch (t) {
-    case BSQ_I8: return "int8";
-    case BSQ_I16: return "int16";
-    case BSQ_I32: return "int32";
-    case BSQ_U64: return "uint64";
-    case BSQ_F32: return "float32";
-    default: return "float64";
-    }
-}
+// Element types of the batch results, in bsq_dtype order (I8, I16, I32, U64, F32, F64): the numpy dtype of a host result and the torch dtype
+// of a device result.  'l' / 'q' results are uint64 in numpy (the reference's type); as device tensors they are torch.int64 -- same bits for
+// token ids and 0/1, and torch.uint64 does not exist before torch 2.3 and supports almost no ops after.
+struct DtypeNames {
+    const char *numpy, *torch;
+};
+const DtypeNames kDtypes[6] = {{"int8", "int8"}, {"int16", "int16"}, {"int32", "int32"}, {"uint64", "int64"}, {"float32", "float32"}, {"float64", "float64"}};
 
 bsq_dtype parse_dtype(const std::string &dt) {
     bsq_dtype t;
@@ -427,32 +424,16 @@ bsq_dtype parse_dtype(const std::string &dt) {
     return t;
 }
 
-// Result buffer: a numpy array (host) or a torch tensor on `device`.
-struct OutBuf {
-    py::object obj;
-    void *ptr = nullptr;
-    bsq_space space = BSQ_SPACE_HOST;
-    void *stream = nullptr;
-    py::object guard;  // torch.cuda.device(...) context, entered
-    ~OutBuf() {
-        if (guard) {
-            try {
-                guard.attr("__exit__")(py::none(), py::none(), py::none());
-            } catch (...) {
-            }
-        }
-    }
-};
-
 // torch, looked up once (a call of BASELINE config 1's size is ~70 us of fixed costs; module / attribute lookups and the
 // torch.cuda.device context manager were ~15 of them).  Leaked on purpose: destroying py::objects at interpreter exit is not safe.
 struct TorchApi {
+    py::module_ torch;  // for what the rare paths need (decode, single-sequence one-hot)
     py::object device, empty, current_stream, current_device, cuda_device, raw_stream, dtypes[6];  // raw_stream: None when torch has none
 };
 const TorchApi &torch_api() {
     static const TorchApi *api = [] {
-        py::module_ torch = py::module_::import("torch");
         TorchApi *a = new TorchApi();
+        const py::module_ &torch = a->torch = py::module_::import("torch");
         a->device = torch.attr("device");
         a->empty = torch.attr("empty");
         a->current_stream = torch.attr("cuda").attr("current_stream");
@@ -460,40 +441,80 @@ const TorchApi &torch_api() {
         a->cuda_device = torch.attr("cuda").attr("device");
         // torch._C._cuda_getCurrentRawStream(device_index) -> int: what torch.cuda.current_stream() wraps in ~9 us of Python
         a->raw_stream = py::getattr(torch.attr("_C"), "_cuda_getCurrentRawStream", py::none());
-        const char *names[6] = {"int8", "int16", "int32", "int64", "float32", "float64"};  // (BSQ_U64 -> int64: see below)
-        for (int i = 0; i < 6; ++i) a->dtypes[i] = torch.attr(names[i]);
+        for (int i = 0; i < 6; ++i) a->dtypes[i] = torch.attr(kDtypes[i].torch);
         return a;
     }();
     return *api;
 }
 
+// `torch.device(device)`, which must be a HIP device
+py::object hip_device(const py::object &device) {
+    py::object dev = torch_api().device(device);
+    if (dev.attr("type").cast<std::string>() != "cuda")
+        throw std::invalid_argument("device= must be a HIP ('cuda') device; omit it for a numpy result");
+    return dev;
+}
+
+// Makes a torch device the current one for its lifetime (the staging buffers and the launches of a call belong to the current device) --
+// through torch's context manager only when it is not the current one already (the common case) -- and yields that device's current stream.
+class DeviceScope {
+    py::object guard;  // torch.cuda.device(...) context, entered
+    int index;
+
+  public:
+    explicit DeviceScope(const py::object &dev) {
+        const TorchApi &T = torch_api();
+        const py::object idx = dev.attr("index");
+        const int current = T.current_device().cast<int>();
+        index = idx.is_none() ? current : idx.cast<int>();
+        if (index != current) {
+            py::object g = T.cuda_device(dev);
+            g.attr("__enter__")();
+            guard = g;
+        }
+    }
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+    ~DeviceScope() {
+        if (guard) {
+            try {
+                guard.attr("__exit__")(py::none(), py::none(), py::none());
+            } catch (...) {
+            }
+        }
+    }
+    void *stream() const {
+        const TorchApi &T = torch_api();
+        return reinterpret_cast<void *>(T.raw_stream.is_none() ? T.current_stream().attr("cuda_stream").cast<uintptr_t>()
+                                                               : T.raw_stream(index).cast<uintptr_t>());
+    }
+};
+
+void *data_ptr(const py::object &tensor) { return reinterpret_cast<void *>(tensor.attr("data_ptr")().cast<uintptr_t>()); }
+
+// Result buffer: a numpy array (host) or a torch tensor on `device`.
+struct OutBuf {
+    py::object obj;
+    void *ptr = nullptr;
+    bsq_space space = BSQ_SPACE_HOST;
+    void *stream = nullptr;
+    std::unique_ptr<DeviceScope> scope;  // `device=` stays the current device while the buffer is in use
+};
+
 void make_out(OutBuf &o, const std::vector<py::ssize_t> &shape, bsq_dtype t, const py::object &device) {
     if (device.is_none()) {
-        py::array a(py::dtype(numpy_dtype_name(t)), shape);
+        py::array a(py::dtype(kDtypes[int(t)].numpy), shape);
         o.ptr = a.mutable_data();
         o.obj = a;
         o.space = BSQ_SPACE_HOST;
         return;
     }
+    const py::object dev = hip_device(device);
+    o.scope = std::make_unique<DeviceScope>(dev);
     const TorchApi &T = torch_api();
-    py::object dev = T.device(device);
-    if (dev.attr("type").cast<std::string>() != "cuda")
-        throw std::invalid_argument("device= must be a HIP ('cuda') device; omit it for a numpy result");
-    // make `device=` the current device for the staging buffers and the launch -- through torch's context manager only when it
-    // is not the current one already (the common case)
-    const py::object index = dev.attr("index");
-    const int current = T.current_device().cast<int>(), want = index.is_none() ? current : index.cast<int>();
-    if (want != current) {
-        o.guard = T.cuda_device(dev);
-        o.guard.attr("__enter__")();
-    }
-    // 'l' / 'q' results are uint64 in numpy (the reference's type); as device tensors they are torch.int64 -- same
-    // bits for token ids and 0/1, and torch.uint64 does not exist before torch 2.3 and supports almost no ops after
-    static const int dtype_index[6] = {0, 1, 2, 3, 4, 5};  // bsq_dtype order: I8, I16, I32, U64, F32, F64
-    py::object ten = T.empty(py::cast(shape), py::arg("dtype") = T.dtypes[dtype_index[int(t)]], py::arg("device") = dev);
-    o.ptr = reinterpret_cast<void *>(ten.attr("data_ptr")().cast<uintptr_t>());
-    o.stream = reinterpret_cast<void *>(T.raw_stream.is_none() ? T.current_stream().attr("cuda_stream").cast<uintptr_t>()
-                                                               : T.raw_stream(want).cast<uintptr_t>());
+    py::object ten = T.empty(py::cast(shape), py::arg("dtype") = T.dtypes[int(t)], py::arg("device") = dev);
+    o.ptr = data_ptr(ten);
+    o.stream = o.scope->stream();
     o.obj = ten;
     o.space = BSQ_SPACE_DEVICE;
 }
@@ -534,6 +555,117 @@ ArrayArg as_array(const py::object &o, const char *np_dtype, size_t itemsize, co
     a.keep = arr;
     return a;
 }
+
+// offsets[i + 1] = offsets[i] + length of item i for items [lo, hi) (offsets[lo] is there on entry).  Returns the first item longer than
+// maxlen, or -1; the offsets behind such an item are written all the same (its own end is what the error message needs).
+int64_t fill_offsets(const Gathered &g, int64_t *offsets, int64_t lo, int64_t hi, int64_t maxlen) {
+    int64_t bad = -1;
+    for (int64_t i = lo; i < hi; ++i) {
+        const int64_t len = int64_t(g.items[size_t(i)].len);
+        if (len > maxlen && bad < 0) bad = i;
+        offsets[i + 1] = offsets[i] + len;
+    }
+    return bad;
+}
+
+// Items [lo, hi) of a list into `p` (offsets[lo + 1 .. hi] and the characters), as a staged batch produces its pieces: ONE pool job where
+// scan_pack_fast takes the piece, the general passes (mask list / other item types) where it declines.  Returns whether the fast job ran.
+// *bad: the first item longer than maxlen (no character of the piece need have been copied then), or -1.  Throws StageOverflow when the
+// piece does not fit behind p.chars.
+bool produce_piece(const Scan &sc, Gathered &g, const Packed &p, int64_t lo, int64_t hi, int nthreads, int64_t maxlen, int64_t *bad) {
+    if (scan_pack_fast(sc, g, p, lo, hi, nthreads, maxlen, bad)) return true;
+    scan_range(sc, g, lo, hi, nthreads);
+    *bad = fill_offsets(g, p.offsets, lo, hi, maxlen);
+    if (*bad >= 0) return false;
+    if (size_t(p.offsets[hi]) > p.cap) throw StageOverflow{};
+    pack_range(g, p, lo, hi, nthreads);
+    return false;
+}
+
+// When a batch goes through the staged path (include/bsq.h, "staged batches") instead of one pack + one call:
+constexpr int64_t kStageMinSeqs = 16384;                    // fewer sequences: the pieces would not pay for themselves
+constexpr size_t kStageMaxHostResult = size_t(256) << 20;   // a numpy result above this is not mirrored in pinned memory
+constexpr size_t kStageMaxChars = size_t(1) << 30;          // characters the staging areas are ever sized for
+
+bool host_result_stages(int64_t n, size_t per_seq_bytes) { return n >= kStageMinSeqs && size_t(n) * per_seq_bytes <= kStageMaxHostResult; }
+
+// An open staged batch (bsq_stage_begin ... bsq_stage_end): its pinned area `p` and how it is cut into pieces.
+struct Stage {
+    bsq_stage *s = nullptr;
+    Packed p;
+    int64_t head = 0;  // sequences in front of the first piece boundary (column blocks of a result that is not 4-KiB aligned)
+    int64_t seqs = 0;  // sequences per piece
+    Stage() = default;
+    Stage(const Stage &) = delete;
+    Stage &operator=(const Stage &) = delete;
+    ~Stage() {
+        if (s) (void)bsq_stage_end(s);
+    }
+    // false = not applicable (small batch, too many characters, knob host_pieces = 1): nothing has been opened.  n sequences of likely_chars
+    // characters (at most max_chars: the areas are sized for that); `split` = the result may be written in pieces -- blocks of
+    // block_row_bytes-wide rows of `out` (0: contiguous slabs) on `stream`.
+    bool open(int64_t n, size_t likely_chars, size_t max_chars, bool has_mask, bool split, size_t block_row_bytes, void *out, void *stream) {
+        if (n < kStageMinSeqs || max_chars > kStageMaxChars) return false;
+        seqs = split ? bsq_stage_piece_hint(n, likely_chars, block_row_bytes, out, stream, &head) : 0;
+        if (seqs < 0) return false;             // knob host_pieces = 1: the whole-batch path of rounds 1-3
+        if (seqs == 0 || seqs > n) seqs = n;    // one piece (busy stream, misaligned result, ...): still one scan + pack job
+        p.B = n;
+        p.cap = max_chars;
+        const bsq_status st = bsq_stage_begin(n, max_chars, has_mask ? 1 : 0, stream, &s, &p.offsets, &p.chars, &p.mask);
+        if (st != BSQ_OK) throw_status(st);
+        return true;
+    }
+};
+
+// One encode: tokens or one-hot, its layout, element type and sizes -- everything the batch methods and the packed entry points derive from
+// them: the result's shape, how pieces of it are laid out, and which entry point of the C ABI writes the whole of it, a block of it, or
+// encodes it from host memory.
+struct EncodeOp {
+    const bsq_desc *desc;
+    bool onehot;
+    bool rows_first;  // a sequence is a contiguous slab of the result: batch_first tokens (B, P), channels-first one-hot (B, C, P)
+    bsq_dtype t;
+    int64_t padlen, B, C;
+    size_t tsz;
+
+    EncodeOp(const bsq_desc *d, bool onehot_, bool rows_first_, bsq_dtype t_, int64_t padlen_, int64_t B_)
+        : desc(d), onehot(onehot_), rows_first(rows_first_), t(t_), padlen(padlen_), B(B_), C(bsq_alphabet_size(d)), tsz(bsq_dtype_size(t_)) {}
+
+    int64_t maxlen() const { return padlen - desc->bos - desc->eos; }  // a longer sequence is an error
+    std::vector<py::ssize_t> shape() const {
+        if (!onehot) return rows_first ? std::vector<py::ssize_t>{B, padlen} : std::vector<py::ssize_t>{padlen, B};
+        return rows_first ? std::vector<py::ssize_t>{B, C, padlen} : std::vector<py::ssize_t>{padlen, B, C};
+    }
+    size_t cell_bytes() const { return onehot ? size_t(C) * tsz : tsz; }  // one position of one sequence
+    size_t per_seq_bytes() const { return size_t(padlen) * cell_bytes(); }
+    // how pieces of n sequences, each encoded as a result of its own, land in the whole result (fetch_and_land): straight (rows == 0: a
+    // piece is a contiguous slab) or row by row (a piece is rows x n x col_bytes of a (rows, B, col_bytes) result)
+    size_t rows() const { return rows_first ? 0 : size_t(padlen); }
+    size_t col_bytes() const { return cell_bytes(); }
+    // device results in pieces: rows-first results split anywhere; the seq-first one-hot in column blocks of (P, B, C); seq-first tokens in
+    // column blocks of (P, B) only for the types that run through k_tokens_pb8_fast as a block (1, 2, 8 bytes -- 8-byte: whole 16-byte
+    // lines --, ids < 251), one piece otherwise
+    bool splittable() const { return onehot || rows_first || ((tsz == 1 || tsz == 2 || (tsz == 8 && B % 2 == 0)) && C <= 250); }
+    size_t block_row_bytes() const { return onehot && !rows_first ? cell_bytes() : 0; }
+
+    // n sequences as a result of their own at dst (device memory)
+    bsq_status whole(const uint8_t *chars, const int64_t *offsets, const uint8_t *mask, int64_t n, void *dst, void *stream) const {
+        if (!onehot) return bsq_tokenize_device(desc, chars, offsets, n, padlen, rows_first, t, dst, stream);
+        return (rows_first ? bsq_onehot_bcl_device : bsq_onehot_device)(desc, chars, offsets, mask, n, padlen, t, dst, stream);
+    }
+    // sequences [lo, lo + n) of the B-sequence result at out (device memory): a row slab, or a column block of pitch B
+    bsq_status block(const uint8_t *chars, const int64_t *offsets, const uint8_t *mask, int64_t lo, int64_t n, void *out, void *stream) const {
+        if (rows_first) return whole(chars, offsets, mask, n, static_cast<char *>(out) + size_t(lo) * per_seq_bytes(), stream);
+        char *dst = static_cast<char *>(out) + size_t(lo) * cell_bytes();
+        if (!onehot) return bsq_tokenize_block_device(desc, chars, offsets, n, padlen, t, dst, B, stream);
+        return bsq_onehot_block_device(desc, chars, offsets, mask, n, padlen, t, dst, B, stream);
+    }
+    // the whole batch from host memory (one upload, one call)
+    bsq_status from_host(const uint8_t *chars, const int64_t *offsets, const uint8_t *mask, void *out, bsq_space space, void *stream, int64_t *bad) const {
+        if (!onehot) return bsq_tokenize_host(desc, chars, offsets, B, padlen, rows_first, t, out, space, stream, bad);
+        return (rows_first ? bsq_onehot_bcl_host : bsq_onehot_host)(desc, chars, offsets, mask, B, padlen, t, out, space, stream, bad);
+    }
+};
 
 class Tokenizer {
   public:
@@ -578,80 +710,67 @@ class Tokenizer {
         throw std::runtime_error(msg);
     }
 
+    EncodeOp encode_op(bool onehot, bool rows_first, bsq_dtype t, py::ssize_t padlen, int64_t B) const {
+        return EncodeOp(&desc, onehot, rows_first, t, int64_t(padlen), B);
+    }
+
+    // The piece loop of every staged path: `produce(lo, hi)` puts offsets[lo + 1 .. hi] and the characters of [lo, hi) into the pinned
+    // staging area (may throw), the piece is uploaded, then `per_piece(lo, hi, d_chars, d_offsets, d_mask)` (device pointers of the whole
+    // batch; d_offsets at sequence lo).
+    template <typename Produce, typename PerPiece>
+    static void piece_loop(const Stage &sg, Produce produce, PerPiece per_piece) {
+        const int64_t n = sg.p.B;
+        for (int64_t lo = 0, want = sg.head + sg.seqs; lo < n; lo += want, want = sg.seqs) {  // (head: 0 unless the result is cut in column blocks)
+            const int64_t hi = std::min<int64_t>(n, lo + want);
+            produce(lo, hi);
+            const int64_t *d_offsets = nullptr;
+            const uint8_t *d_chars = nullptr, *d_mask = nullptr;
+            bsq_status st = bsq_stage_upload(sg.s, lo, hi, &d_offsets, &d_chars, &d_mask);
+            if (st == BSQ_OK) st = per_piece(lo, hi, d_chars, d_offsets, d_mask);
+            if (st != BSQ_OK) throw_status(st);
+        }
+    }
+    // ... of a list: items [lo, hi) scanned + packed by produce_piece
+    template <typename PerPiece>
+    void list_pieces(const Scan &sc, Gathered &g, const Stage &sg, const EncodeOp &op, int nthreads, PerPiece per_piece) const {
+        piece_loop(sg,
+                   [&](int64_t lo, int64_t hi) {
+                       int64_t bad = -1;
+                       produce_piece(sc, g, sg.p, lo, hi, nthreads, op.maxlen(), &bad);
+                       if (bad >= 0) throw_too_long(sg.p.offsets, bad, op.padlen, op.onehot);
+                   },
+                   per_piece);
+    }
+
+    // Opens the staged batch of a list whose result lives in `space` of `out`; false = not applicable, nothing has been scanned.  The
+    // staging areas are sized from an estimate of the characters (see StageOverflow).
+    bool open_list_stage(Stage &sg, const Scan &sc, const Gathered &g, const EncodeOp &op, const OutBuf &out, bsq_space space) const {
+        if (out.space != space || sc.n < kStageMinSeqs || op.maxlen() <= 0) return false;
+        if (space == BSQ_SPACE_HOST && !host_result_stages(sc.n, op.per_seq_bytes())) return false;
+        size_t likely = 0;
+        const size_t max_chars = estimate_chars(sc, op.maxlen(), &likely);
+        if (space == BSQ_SPACE_HOST) return sg.open(sc.n, likely, max_chars, g.has_mask, true, 0, nullptr, nullptr);
+        return sg.open(sc.n, likely, max_chars, g.has_mask, op.splittable(), op.block_row_bytes(), out.ptr, out.stream);
+    }
+
     // A list -> DEVICE result in pieces (include/bsq.h, "staged batches"): items [lo, hi) are scanned, packed into the pinned staging
     // area, sent on their way and encoded as a block of the result while the next piece is scanned and packed -- the call costs
     // one piece of host work + the upload + one piece of kernel instead of the sum of the three.  false = not applicable (small
     // batch, numpy result, knob host_pieces = 1): nothing has been scanned, the caller goes on with the whole-batch path.
     // The GIL stays held as it is during every pack (the items must stay alive and unchanged); nothing in here blocks on the
     // GPU except the wait for the staging slot used three calls ago.
-    // The piece loop of both staged paths: items [lo, hi) scanned + packed (one pool job, or the general passes), uploaded, then
-    // `per_piece(lo, hi, d_chars, d_offsets, d_mask)` (device pointers of the whole batch; d_offsets at sequence lo).
-    template <typename Produce, typename PerPiece>
-    static void piece_loop(int64_t n, bsq_stage *stage, int64_t head, int64_t seqs, Produce produce, PerPiece per_piece) {
-        for (int64_t lo = 0, want = head + seqs; lo < n; lo += want, want = seqs) {
-            const int64_t hi = std::min<int64_t>(n, lo + want);
-            produce(lo, hi);  // offsets[lo + 1 .. hi] and the characters of [lo, hi) into the pinned staging area (may throw)
-            const int64_t *d_offsets = nullptr;
-            const uint8_t *d_chars = nullptr, *d_mask = nullptr;
-            bsq_status st = bsq_stage_upload(stage, lo, hi, &d_offsets, &d_chars, &d_mask);
-            if (st == BSQ_OK) st = per_piece(lo, hi, d_chars, d_offsets, d_mask);
-            if (st != BSQ_OK) throw_status(st);
-        }
-    }
-    template <typename PerPiece>
-    void staged_pieces(const Scan &sc, Gathered &g, const Packed &p, bsq_stage *stage, int64_t head, int64_t seqs, py::ssize_t padlen, int nthreads,
-                       bool onehot, PerPiece per_piece) const {
-        const int64_t maxlen = int64_t(padlen) - desc.bos - desc.eos;
-        piece_loop(sc.n, stage, head, seqs,
-                   [&](int64_t lo, int64_t hi) {
-                       int64_t bad = -1;
-                       if (!scan_pack_fast(sc, g, p, lo, hi, nthreads, maxlen, &bad)) {  // mask list / other item types: the general passes
-                           scan_range(sc, g, lo, hi, nthreads);
-                           for (int64_t i = lo; i < hi; ++i) {
-                               p.offsets[i + 1] = p.offsets[i] + int64_t(g.items[size_t(i)].len);
-                               if (int64_t(g.items[size_t(i)].len) > maxlen) throw_too_long(p.offsets, i, padlen, onehot);
-                           }
-                           if (size_t(p.offsets[hi]) > p.cap) throw StageOverflow{};
-                           pack_range(g, p, lo, hi, nthreads);
-                       }
-                       if (bad >= 0) throw_too_long(p.offsets, bad, padlen, onehot);
-                   },
-                   per_piece);
-    }
-
-    struct StageEnd {
-        bsq_stage *s;
-        ~StageEnd() { (void)bsq_stage_end(s); }
-    };
-
-    template <typename BlockFn>
-    bool staged(const Scan &sc, Gathered &g, py::ssize_t padlen, int nthreads, const OutBuf &out, bool splittable, size_t block_row_bytes,
-                bool onehot, BlockFn block) const {
-        const int64_t maxlen = int64_t(padlen) - desc.bos - desc.eos;  // a longer item is an error anyway
-        if (out.space != BSQ_SPACE_DEVICE || sc.n < 16384 || maxlen <= 0) return false;
-        size_t likely = 0;
-        const size_t max_chars = estimate_chars(sc, maxlen, &likely);  // (an estimate: see StageOverflow)
-        if (max_chars > (size_t(1) << 30)) return false;
-        int64_t head = 0;  // sequences in front of the first piece boundary (column blocks of a result that is not 4-KiB aligned)
-        int64_t seqs = splittable ? bsq_stage_piece_hint(sc.n, likely, block_row_bytes, out.ptr, out.stream, &head) : 0;
-        if (seqs < 0) return false;                  // knob host_pieces = 1: the whole-batch path of rounds 1-3
-        if (seqs == 0 || seqs > sc.n) seqs = sc.n;   // one piece (busy stream, misaligned result, ...): still one scan + pack job
-        bsq_stage *stage = nullptr;
-        Packed p;
-        p.B = sc.n;
-        p.cap = max_chars;
-        const bsq_status st0 = bsq_stage_begin(sc.n, max_chars, g.has_mask ? 1 : 0, out.stream, &stage, &p.offsets, &p.chars, &p.mask);
-        if (st0 != BSQ_OK) throw_status(st0);
-        StageEnd end{stage};
+    bool staged(const Scan &sc, Gathered &g, int nthreads, const OutBuf &out, const EncodeOp &op) const {
+        Stage sg;
+        if (!open_list_stage(sg, sc, g, op, out, BSQ_SPACE_DEVICE)) return false;
         try {
-            staged_pieces(sc, g, p, stage, head, seqs, padlen, nthreads, onehot,
-                          [&](int64_t lo, int64_t hi, const uint8_t *d_chars, const int64_t *d_offsets, const uint8_t *d_mask) {
-                              const int64_t lead = lo == 0 && head < hi ? head : 0;
-                              bsq_status st = BSQ_OK;
-                              if (lead) st = block(d_chars, d_offsets, d_mask, 0, lead);
-                              if (st == BSQ_OK) st = block(d_chars, d_offsets + lead, d_mask, lo + lead, hi - lo - lead);
-                              return st;
-                          });
+            list_pieces(sc, g, sg, op, nthreads,
+                        [&](int64_t lo, int64_t hi, const uint8_t *d_chars, const int64_t *d_offsets, const uint8_t *d_mask) {
+                            const int64_t lead = lo == 0 && sg.head < hi ? sg.head : 0;
+                            bsq_status st = BSQ_OK;
+                            if (lead) st = op.block(d_chars, d_offsets, d_mask, 0, lead, out.ptr, out.stream);
+                            if (st == BSQ_OK) st = op.block(d_chars, d_offsets + lead, d_mask, lo + lead, hi - lo - lead, out.ptr, out.stream);
+                            return st;
+                        });
         } catch (const StageOverflow &) {
             // more characters than the sampled estimate allowed for: the blocks encoded so far are valid and will simply be written
             // again, in stream order, by the whole-batch path the caller goes on with (it scans everything before it allocates)
@@ -665,17 +784,15 @@ class Tokenizer {
         g.total = 0;
     }
 
-    // The same for a NUMPY result (the reference's default return) of up to 256 MB -- token matrices, small one-hots: every piece
-    // is encoded as a matrix of its own (`piece(d_chars, d_offsets, d_mask, n, dst)`: n sequences, per_seq_bytes each) in the staging
-    // area's device scratch and fetched into its pinned mirror while the next piece is packed and uploaded (PCIe runs both ways);
-    // at the end the pool copies the pinned pieces into the array -- straight (rows == 0: a piece is a contiguous slab of the result:
-    // (B, P), (B, C, P)) or row by row (a piece is `rows` x n x col_bytes of a (rows, B, col_bytes) result: (P, B), (P, B, C)).
-    // Host results of a staged batch: `loop(per_piece)` runs the piece loop; every piece is encoded by `piece(...)` as a matrix of its
-    // own (n sequences of per_seq_bytes) in the staging area's device scratch and fetched into its pinned mirror; the pieces land in
-    // `dst` as their fetches complete -- straight (rows == 0) or row by row (`rows` x n x col_bytes pieces of a (rows, B, col_bytes) result).
-    template <typename Loop, typename PieceFn>
-    static void fetch_and_land(bsq_stage *stage, int64_t B, size_t per_seq_bytes, size_t rows, size_t col_bytes, int nthreads, char *dst, Loop loop,
-                               PieceFn piece, bool gil_held) {
+    // Host results of a staged batch (a NUMPY result -- the reference's default return -- of up to 256 MB: token matrices, small one-hots):
+    // `loop(per_piece)` runs the piece loop; every piece is encoded as a result of its own (op.whole) in the staging area's device scratch and
+    // fetched into its pinned mirror while the next piece is packed and uploaded (PCIe runs both ways); the pieces land in `dst` as their
+    // fetches complete, the pool copying them -- straight or row by row (EncodeOp::rows).
+    template <typename Loop>
+    static void fetch_and_land(const Stage &sg, const EncodeOp &op, int nthreads, char *dst, Loop loop, bool gil_held) {
+        bsq_stage *stage = sg.s;
+        const int64_t B = sg.p.B;
+        const size_t per_seq_bytes = op.per_seq_bytes(), rows = op.rows(), col_bytes = op.col_bytes();
         void *d_res = nullptr, *h_res = nullptr;
         bsq_status st = bsq_stage_result(stage, size_t(B) * per_seq_bytes, &d_res, &h_res);
         if (st != BSQ_OK) throw_status(st);
@@ -703,7 +820,7 @@ class Tokenizer {
         };
         std::vector<Pending> pending;
         loop([&](int64_t lo, int64_t hi, const uint8_t *d_chars, const int64_t *d_offsets, const uint8_t *d_mask) {
-            bsq_status s1 = piece(d_chars, d_offsets, d_mask, hi - lo, static_cast<char *>(d_res) + size_t(lo) * per_seq_bytes);
+            bsq_status s1 = op.whole(d_chars, d_offsets, d_mask, hi - lo, static_cast<char *>(d_res) + size_t(lo) * per_seq_bytes, nullptr);
             int32_t ticket = -1;
             if (s1 == BSQ_OK) s1 = bsq_stage_fetch(stage, size_t(lo) * per_seq_bytes, size_t(hi - lo) * per_seq_bytes, &ticket);
             pending.push_back(Pending{lo, hi, ticket});
@@ -733,30 +850,13 @@ class Tokenizer {
         }
     }
 
-    // A NUMPY result (the reference's default return) of up to 256 MB -- token matrices, small one-hots -- from a list: see fetch_and_land.
-    template <typename PieceFn>
-    bool staged_host(const Scan &sc, Gathered &g, py::ssize_t padlen, int nthreads, const OutBuf &out, size_t per_seq_bytes, size_t rows,
-                     size_t col_bytes, bool onehot, PieceFn piece) const {
-        const int64_t maxlen = int64_t(padlen) - desc.bos - desc.eos;
-        const size_t total = size_t(sc.n) * per_seq_bytes;
-        if (out.space != BSQ_SPACE_HOST || sc.n < 16384 || maxlen <= 0 || total > (size_t(256) << 20)) return false;
-        size_t likely = 0;
-        const size_t max_chars = estimate_chars(sc, maxlen, &likely);
-        if (max_chars > (size_t(1) << 30)) return false;
-        int64_t head = 0;
-        int64_t seqs = bsq_stage_piece_hint(sc.n, likely, 0, nullptr, nullptr, &head);
-        if (seqs < 0) return false;
-        if (seqs == 0 || seqs > sc.n) seqs = sc.n;
-        bsq_stage *stage = nullptr;
-        Packed p;
-        p.B = sc.n;
-        p.cap = max_chars;
-        const bsq_status st = bsq_stage_begin(sc.n, max_chars, g.has_mask ? 1 : 0, nullptr, &stage, &p.offsets, &p.chars, &p.mask);
-        if (st != BSQ_OK) throw_status(st);
-        StageEnd end{stage};
+    // A NUMPY result of up to 256 MB from a list: see fetch_and_land.
+    bool staged_host(const Scan &sc, Gathered &g, int nthreads, const OutBuf &out, const EncodeOp &op) const {
+        Stage sg;
+        if (!open_list_stage(sg, sc, g, op, out, BSQ_SPACE_HOST)) return false;
         try {
-            fetch_and_land(stage, sc.n, per_seq_bytes, rows, col_bytes, nthreads, static_cast<char *>(out.ptr),
-                           [&](auto per_piece) { staged_pieces(sc, g, p, stage, 0, seqs, padlen, nthreads, onehot, per_piece); }, piece, true);
+            fetch_and_land(sg, op, nthreads, static_cast<char *>(out.ptr),
+                           [&](auto per_piece) { list_pieces(sc, g, sg, op, nthreads, per_piece); }, true);
         } catch (const StageOverflow &) {  // (nothing has landed in the array yet: pieces land after the loop)
             reset_scan(g);
             return false;
@@ -766,21 +866,12 @@ class Tokenizer {
 
     // The same for a PACKED batch in host memory (numpy arrays, a memory-mapped FlatFile): the pieces are copied into the pinned
     // staging area (no Python object involved: the GIL is released by the caller).  Lengths have been validated.
-    template <typename PieceFn>
-    bool staged_host_packed(const uint8_t *chars, const int64_t *offs, const uint8_t *mask, int64_t B, int nthreads, char *dst, size_t per_seq_bytes,
-                            size_t rows, size_t col_bytes, PieceFn piece) const {
-        const size_t total = size_t(B) * per_seq_bytes, nchars = size_t(offs[B] - offs[0]);
-        if (B < 16384 || total > (size_t(256) << 20) || nchars > (size_t(1) << 30)) return false;
-        int64_t head = 0;
-        int64_t seqs = bsq_stage_piece_hint(B, nchars, 0, nullptr, nullptr, &head);
-        if (seqs < 0) return false;
-        if (seqs == 0 || seqs > B) seqs = B;
-        bsq_stage *stage = nullptr;
-        Packed p;
-        p.B = B;
-        const bsq_status st = bsq_stage_begin(B, nchars, mask ? 1 : 0, nullptr, &stage, &p.offsets, &p.chars, &p.mask);
-        if (st != BSQ_OK) throw_status(st);
-        StageEnd end{stage};
+    static bool staged_host_packed(const uint8_t *chars, const int64_t *offs, const uint8_t *mask, int nthreads, char *dst, const EncodeOp &op) {
+        const int64_t B = op.B;
+        const size_t nchars = size_t(offs[B] - offs[0]);
+        Stage sg;
+        if (!host_result_stages(B, op.per_seq_bytes()) || !sg.open(B, nchars, nchars, mask != nullptr, true, 0, nullptr, nullptr)) return false;
+        const Packed &p = sg.p;
         const int nt = std::max(1, std::min(nthreads, 64));
         const int64_t base = offs[0];
         auto produce = [&](int64_t lo, int64_t hi) {
@@ -795,66 +886,66 @@ class Tokenizer {
                 }
             });
         };
-        fetch_and_land(stage, B, per_seq_bytes, rows, col_bytes, nthreads, dst,
-                       [&](auto per_piece) { piece_loop(B, stage, 0, seqs, produce, per_piece); }, piece, false);
+        fetch_and_land(sg, op, nthreads, dst, [&](auto per_piece) { piece_loop(sg, produce, per_piece); }, false);
         return true;
     }
 
-    // batch_tokenize (tokenize.cpp:82-98 -> tokenize.h:381-485)
-    py::object batch_tokenize(py::sequence batch, py::ssize_t padlen, const std::string &dt, bool batch_first,
-                              int nthreads, const py::object &device) const {
+    // batch_tokenize (tokenize.cpp:82-98 -> tokenize.h:381-485) and batch_onehot_encode (tokenize.cpp:65-81 -> tokenize.h:283-371) of a
+    // list: `rows_first` is batch_first for tokens, the channels-first layout (B, C, P) for the one-hot.
+    py::object batch_encode(bool onehot, bool rows_first, py::sequence batch, py::ssize_t padlen, const std::string &dt, int nthreads,
+                            const py::object &mask, const py::object &device) const {
         const bsq_dtype t = parse_dtype(dt);
         check_padlen(padlen);
+        static const bool prof = std::getenv("BSQ_PROFILE_HOST") != nullptr;  // per-phase host times on stderr
+        const auto t0 = std::chrono::steady_clock::now();
         Gathered g;
-        const Scan sc = scan_begin(batch, py::none(), g, nthreads);  // (resolves nthreads = 0 to the automatic count)
+        const Scan sc = scan_begin(batch, mask, g, nthreads);  // (resolves nthreads = 0 to the automatic count)
+        const EncodeOp op = encode_op(onehot, rows_first, t, padlen, sc.n);
         // numpy results: small batches scan first (item errors before the result is allocated, as ever); large ones that fit the
         // staged path (<= 256 MB of result) are scanned piece by piece in staged_host
-        const size_t row_bytes = size_t(padlen) * bsq_dtype_size(t);
-        const bool host_stage = device.is_none() && sc.n >= 16384 && size_t(sc.n) * row_bytes <= (size_t(256) << 20);
+        const bool host_stage = device.is_none() && host_result_stages(sc.n, op.per_seq_bytes());
         bool scanned = false;
         if (device.is_none() && !host_stage) {
             scan_range(sc, g, 0, sc.n, nthreads);
             scanned = true;
         }
+        const auto t1 = std::chrono::steady_clock::now();
         PackLock lock;
         OutBuf out;  // first: it makes `device=` the current device, so the pinned scratch and the staging
                      // buffers used by pack() and by the encode call belong to the same device
-        const py::ssize_t nb = py::ssize_t(sc.n);
-        make_out(out, batch_first ? std::vector<py::ssize_t>{nb, padlen} : std::vector<py::ssize_t>{padlen, nb}, t, device);
-        const size_t row = size_t(padlen) * bsq_dtype_size(t);
-        // batch-first: a piece is rows [lo, lo + n) of (B, P); seq-first: a column block of (P, B) -- split only for the types that
-        // run through k_tokens_pb8_fast as a block (1, 2, 8 bytes, ids < 251), one piece otherwise
-        const size_t tsz = bsq_dtype_size(t);
-        const bool sf_blocks = (tsz == 1 || tsz == 2 || (tsz == 8 && nb % 2 == 0)) && bsq_alphabet_size(&desc) <= 250;  // (8-byte: whole 16-byte lines)
-        if (staged(sc, g, padlen, nthreads, out, batch_first || sf_blocks, 0, false,
-                   [&](const uint8_t *chars, const int64_t *offsets, const uint8_t *, int64_t lo, int64_t n) {
-                       if (batch_first)
-                           return bsq_tokenize_device(&desc, chars, offsets, n, padlen, 1, t, static_cast<char *>(out.ptr) + size_t(lo) * row, out.stream);
-                       return bsq_tokenize_block_device(&desc, chars, offsets, n, padlen, t, static_cast<char *>(out.ptr) + size_t(lo) * tsz, int64_t(nb),
-                                                        out.stream);
-                   }))
+        make_out(out, op.shape(), t, device);
+        const auto t2 = std::chrono::steady_clock::now();
+        auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
+        // device result: the pieces are encoded as blocks of it while the next ones are scanned, packed and uploaded
+        if (staged(sc, g, nthreads, out, op)) {
+            if (prof) std::fprintf(stderr, "[bsq host] list setup %ld us, output alloc %ld us (address %% 4096 = %lu), scan + pack + upload + launch in pieces %ld us\n",
+                                   us(t0, t1), us(t1, t2), (unsigned long)(reinterpret_cast<uintptr_t>(out.ptr) % 4096), us(t2, std::chrono::steady_clock::now()));
             return out.obj;
+        }
         // numpy result of up to 256 MB: the pieces are encoded on the device and fetched while the next one is packed and uploaded
-        if (host_stage && staged_host(sc, g, padlen, nthreads, out, row, batch_first ? 0 : size_t(padlen), tsz, false,
-                                            [&](const uint8_t *chars, const int64_t *offsets, const uint8_t *, int64_t n, void *dst) {
-                                                return bsq_tokenize_device(&desc, chars, offsets, n, padlen, batch_first, t, dst, nullptr);
-                                            }))
-            return out.obj;
+        if (host_stage && staged_host(sc, g, nthreads, out, op)) return out.obj;
         if (!scanned) scan_range(sc, g, 0, sc.n, nthreads);
         const Packed p = pack(g, nthreads);
+        const auto t3 = std::chrono::steady_clock::now();
         int64_t bad = -1;
         bsq_status st;
         {
             py::gil_scoped_release nogil;
-            st = bsq_tokenize_host(&desc, p.chars, p.offsets, p.B, padlen, batch_first, t, out.ptr, out.space,
-                                   out.stream, &bad);
+            st = op.from_host(p.chars, p.offsets, p.mask, out.ptr, out.space, out.stream, &bad);
         }
-        if (st == BSQ_ERR_SEQ_TOO_LONG) throw_too_long(p.offsets, bad, padlen, false);
+        if (prof)
+            std::fprintf(stderr, "[bsq host] gather %ld us, output alloc %ld us, scan (device results) + pack %ld us, upload+launch %ld us\n", us(t0, t1),
+                         us(t1, t2), us(t2, t3), us(t3, std::chrono::steady_clock::now()));
+        if (st == BSQ_ERR_SEQ_TOO_LONG) throw_too_long(p.offsets, bad, padlen, onehot);
         if (st != BSQ_OK) throw_status(st);
         return out.obj;
     }
 
-    // batch_onehot_encode (tokenize.cpp:65-81 -> tokenize.h:283-371); always (P, B, C)
+    py::object batch_tokenize(py::sequence batch, py::ssize_t padlen, const std::string &dt, bool batch_first, int nthreads,
+                              const py::object &device) const {
+        return batch_encode(false, batch_first, batch, padlen, dt, nthreads, py::none(), device);
+    }
+
     static bool parse_layout(const std::string &layout) {  // true: channels-first (B, C, P)
         if (layout == "tbc" || layout == "seq_first" || layout.empty()) return false;
         if (layout == "bcl" || layout == "channels_first") return true;
@@ -864,66 +955,7 @@ class Tokenizer {
     py::object batch_onehot_encode(py::sequence batch, py::ssize_t padlen, const std::string &dt, int nthreads,
                                    const py::object &mask, const py::object &device, const std::string &layout) const {
         const bool bcl = parse_layout(layout);
-        const bsq_dtype t = parse_dtype(dt);
-        check_padlen(padlen);
-        static const bool prof = std::getenv("BSQ_PROFILE_HOST") != nullptr;  // per-phase host times on stderr
-        const auto t0 = std::chrono::steady_clock::now();
-        Gathered g;
-        const Scan sc = scan_begin(batch, mask, g, nthreads);
-        const size_t per_seq = size_t(padlen) * size_t(bsq_alphabet_size(&desc)) * bsq_dtype_size(t);
-        const bool host_stage = device.is_none() && sc.n >= 16384 && size_t(sc.n) * per_seq <= (size_t(256) << 20);  // (see batch_tokenize)
-        bool scanned = false;
-        if (device.is_none() && !host_stage) {
-            scan_range(sc, g, 0, sc.n, nthreads);
-            scanned = true;
-        }
-        const auto t1 = std::chrono::steady_clock::now();
-        PackLock lock;
-        OutBuf out;  // before pack(): see batch_tokenize
-        const py::ssize_t C = py::ssize_t(bsq_alphabet_size(&desc)), nb = py::ssize_t(sc.n);
-        make_out(out, bcl ? std::vector<py::ssize_t>{nb, C, padlen} : std::vector<py::ssize_t>{padlen, nb, C}, t, device);
-        const auto t2 = std::chrono::steady_clock::now();
-        auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-        // seq-first: piece = a column block of (P, B, C); channels-first: piece = rows [lo, lo + n) of (B, C, P)
-        const size_t row = size_t(C) * bsq_dtype_size(t);
-        const bool done =
-            bcl ? staged(sc, g, padlen, nthreads, out, true, 0, true,
-                         [&](const uint8_t *chars, const int64_t *offsets, const uint8_t *m, int64_t lo, int64_t n) {
-                             return bsq_onehot_bcl_device(&desc, chars, offsets, m, n, padlen, t,
-                                                          static_cast<char *>(out.ptr) + size_t(lo) * row * size_t(padlen), out.stream);
-                         })
-                : staged(sc, g, padlen, nthreads, out, true, row, true,
-                         [&](const uint8_t *chars, const int64_t *offsets, const uint8_t *m, int64_t lo, int64_t n) {
-                             return bsq_onehot_block_device(&desc, chars, offsets, m, n, padlen, t, static_cast<char *>(out.ptr) + size_t(lo) * row,
-                                                            int64_t(nb), out.stream);
-                         });
-        if (done) {
-            if (prof) std::fprintf(stderr, "[bsq host] list setup %ld us, output alloc %ld us (address %% 4096 = %lu), scan + pack + upload + launch in pieces %ld us\n",
-                                   us(t0, t1), us(t1, t2), (unsigned long)(reinterpret_cast<uintptr_t>(out.ptr) % 4096), us(t2, std::chrono::steady_clock::now()));
-            return out.obj;
-        }
-        if (host_stage && staged_host(sc, g, padlen, nthreads, out, per_seq, bcl ? 0 : size_t(padlen), row, true,
-                                      [&](const uint8_t *chars, const int64_t *offsets, const uint8_t *m, int64_t n, void *dst) {
-                                          return bcl ? bsq_onehot_bcl_device(&desc, chars, offsets, m, n, padlen, t, dst, nullptr)
-                                                     : bsq_onehot_device(&desc, chars, offsets, m, n, padlen, t, dst, nullptr);
-                                      }))
-            return out.obj;
-        if (!scanned) scan_range(sc, g, 0, sc.n, nthreads);
-        const Packed p = pack(g, nthreads);
-        const auto t3 = std::chrono::steady_clock::now();
-        int64_t bad = -1;
-        bsq_status st;
-        {
-            py::gil_scoped_release nogil;
-            st = (bcl ? bsq_onehot_bcl_host : bsq_onehot_host)(&desc, p.chars, p.offsets, p.mask, p.B, padlen, t, out.ptr,
-                                                               out.space, out.stream, &bad);
-        }
-        if (prof)
-            std::fprintf(stderr, "[bsq host] gather %ld us, output alloc %ld us, scan (device results) + pack %ld us, upload+launch %ld us\n", us(t0, t1),
-                         us(t1, t2), us(t2, t3), us(t3, std::chrono::steady_clock::now()));
-        if (st == BSQ_ERR_SEQ_TOO_LONG) throw_too_long(p.offsets, bad, padlen, true);
-        if (st != BSQ_OK) throw_status(st);
-        return out.obj;
+        return batch_encode(true, bcl, batch, padlen, dt, nthreads, mask, device);
     }
 
     // Packed-batch entry points (additive): chars uint8[total] + offsets int64[B+1] (+ mask uint8[total]),
@@ -946,23 +978,17 @@ class Tokenizer {
         if (has_mask && mask.n < chars.n) throw std::invalid_argument("mask must have one byte per character");
         py::object device = device_o;
         if (chars.on_device && device.is_none()) device = chars.keep.attr("device");
-        if (chars.on_device && !device.is_none()) {
-            py::module_ torch = py::module_::import("torch");
-            if (!torch.attr("device")(device).equal(chars.keep.attr("device")))
-                throw std::invalid_argument("device= differs from the device of the packed batch");
-        }
-        const py::ssize_t C = bsq_alphabet_size(&desc);
-        std::vector<py::ssize_t> shape = onehot ? (bcl ? std::vector<py::ssize_t>{B, C, padlen} : std::vector<py::ssize_t>{padlen, B, C})
-                                                : (batch_first ? std::vector<py::ssize_t>{B, padlen}
-                                                               : std::vector<py::ssize_t>{padlen, B});
+        if (chars.on_device && !device.is_none() && !torch_api().device(device).equal(chars.keep.attr("device")))
+            throw std::invalid_argument("device= differs from the device of the packed batch");
+        const EncodeOp op = encode_op(onehot, onehot ? bcl : batch_first, t, padlen, B);
         PackLock lock;
         OutBuf out;
-        make_out(out, shape, t, device);
+        make_out(out, op.shape(), t, device);
         int64_t bad = -1;
         bsq_status st;
-        std::vector<int64_t> bad_pair(2, 0);
+        const int64_t *offs = static_cast<const int64_t *>(offsets.ptr);
+        const uint8_t *cp = static_cast<const uint8_t *>(chars.ptr), *mp = has_mask ? static_cast<const uint8_t *>(mask.ptr) : nullptr;
         if (chars.on_device) {
-            const int64_t *offs = static_cast<const int64_t *>(offsets.ptr);
             {
                 py::gil_scoped_release nogil;
                 st = BSQ_OK;
@@ -970,47 +996,27 @@ class Tokenizer {
                 // kernels bound their reads by offsets[B], not by the real size of the buffer.  validate=False is an
                 // unchecked contract: the caller vouches for well-formed offsets and lengths <= padlen - bos - eos.
                 if (validate) st = bsq_validate_packed_device(offs, B, padlen, desc.bos, desc.eos, chars.n, &bad, out.stream);
-                if (st == BSQ_OK)
-                    st = onehot ? (bcl ? bsq_onehot_bcl_device : bsq_onehot_device)(
-                                      &desc, static_cast<const uint8_t *>(chars.ptr), offs,
-                                      has_mask ? static_cast<const uint8_t *>(mask.ptr) : nullptr, B, padlen, t, out.ptr,
-                                      out.stream)
-                                : bsq_tokenize_device(&desc, static_cast<const uint8_t *>(chars.ptr), offs, B, padlen,
-                                                      batch_first, t, out.ptr, out.stream);
+                if (st == BSQ_OK) st = op.whole(cp, offs, mp, B, out.ptr, out.stream);
             }
             if (st == BSQ_ERR_INVALID_ARG && bad >= 0)
                 throw std::invalid_argument("offsets must be non-negative, non-decreasing and end inside chars (first bad entry: " +
                                             std::to_string(bad) + ")");
             if (st == BSQ_ERR_SEQ_TOO_LONG) {
                 py::object pair = offsets.keep.attr("__getitem__")(py::slice(bad, bad + 2, 1)).attr("tolist")();
-                bad_pair = pair.cast<std::vector<int64_t>>();
+                const std::vector<int64_t> bad_pair = pair.cast<std::vector<int64_t>>();
                 throw_too_long(bad_pair.data(), 0, padlen, onehot);
             }
         } else {
-            const int64_t *offs = static_cast<const int64_t *>(offsets.ptr);
             if (B > 0 && (offs[0] < 0 || offs[B] > chars.n)) throw std::invalid_argument("offsets exceed chars");
             for (int64_t i = 0; i < B; ++i)
                 if (offs[i + 1] < offs[i]) throw std::invalid_argument("offsets must be non-decreasing");
             {
                 py::gil_scoped_release nogil;
-                const uint8_t *cp = static_cast<const uint8_t *>(chars.ptr), *mp = has_mask ? static_cast<const uint8_t *>(mask.ptr) : nullptr;
                 st = bsq_validate_lengths(offs, B, padlen, desc.bos, desc.eos, &bad);
-                bool done = false;
                 // a numpy result of up to 256 MB: pieces go up, are encoded and fetched back while the next ones go up (staged_host_packed)
-                if (st == BSQ_OK && out.space == BSQ_SPACE_HOST && B >= 16384) {
-                    const size_t sz = bsq_dtype_size(t), per_seq = size_t(padlen) * sz * (onehot ? size_t(C) : 1);
-                    const bool columns = onehot ? !bcl : !batch_first;
-                    done = staged_host_packed(cp, offs, mp, B, resolve_threads(0, B), static_cast<char *>(out.ptr), per_seq, columns ? size_t(padlen) : 0,
-                                              onehot ? size_t(C) * sz : sz,
-                                              [&](const uint8_t *dc, const int64_t *dof, const uint8_t *dm, int64_t n, void *dst) {
-                                                  if (!onehot) return bsq_tokenize_device(&desc, dc, dof, n, padlen, batch_first, t, dst, nullptr);
-                                                  return bcl ? bsq_onehot_bcl_device(&desc, dc, dof, dm, n, padlen, t, dst, nullptr)
-                                                             : bsq_onehot_device(&desc, dc, dof, dm, n, padlen, t, dst, nullptr);
-                                              });
-                }
-                if (st == BSQ_OK && !done)
-                    st = onehot ? (bcl ? bsq_onehot_bcl_host : bsq_onehot_host)(&desc, cp, offs, mp, B, padlen, t, out.ptr, out.space, out.stream, &bad)
-                                : bsq_tokenize_host(&desc, cp, offs, B, padlen, batch_first, t, out.ptr, out.space, out.stream, &bad);
+                const bool done = st == BSQ_OK && out.space == BSQ_SPACE_HOST &&
+                                  staged_host_packed(cp, offs, mp, resolve_threads(0, B), static_cast<char *>(out.ptr), op);
+                if (st == BSQ_OK && !done) st = op.from_host(cp, offs, mp, out.ptr, out.space, out.stream, &bad);
             }
             if (st == BSQ_ERR_SEQ_TOO_LONG) throw_too_long(offs, bad, padlen, onehot);
         }
@@ -1043,44 +1049,51 @@ class Tokenizer {
             for (; r < padlen; ++r) ptr[r * C + bsq_pad_id(&desc)] = T(1);
         return ret;
     }
+    // The element types of the single-sequence one-hot: the dtype character is case-masked; unsigned numpy types on the host (the reference's),
+    // and on the device the torch dtype of the same bits (the 16- and 32-bit unsigned types have no usable torch dtype).
+    struct SingleDtype {
+        char letter;
+        bsq_dtype t;
+        const char *torch_name;
+        py::array (Tokenizer::*host)(const char *, py::ssize_t, py::ssize_t) const;
+    };
+    static const SingleDtype &single_dtype(const std::string &dt) {
+        static const SingleDtype table[] = {{'B', BSQ_I8, "uint8", &Tokenizer::onehot_single_t<uint8_t>},
+                                            {'H', BSQ_I16, "int16", &Tokenizer::onehot_single_t<uint16_t>},
+                                            {'I', BSQ_I32, "int32", &Tokenizer::onehot_single_t<uint32_t>},
+                                            {'F', BSQ_F32, "float32", &Tokenizer::onehot_single_t<float>},
+                                            {'D', BSQ_F64, "float64", &Tokenizer::onehot_single_t<double>}};
+        const char c = dt.empty() ? char(0) : char(dt[0] & 223);
+        for (const SingleDtype &row : table)
+            if (row.letter == c) return row;
+        throw std::invalid_argument(std::string("Unsupported dtype: ") + dt);
+    }
     // Single-sequence one-hot ON THE DEVICE (device=...): the batch kernel with B = 1 and P = rows writes BOS, the
     // residues, EOS and PAD rows; the reference pads only the rows below `padlen` (tokenize.h:208-212), so the rows
-    // from max(padlen, L + bos + eos) on are zeroed again.  Returns a torch tensor (rows, C) of uint8 / int16 / int32 /
-    // float32 / float64 (the 16- and 32-bit unsigned types of the host path have no usable torch dtype: same bits).
+    // from max(padlen, L + bos + eos) on are zeroed again.  Returns a torch tensor (rows, C).
     py::object onehot_single_device(const char *s, py::ssize_t L, py::ssize_t padlen, const std::string &dt,
                                     const py::object &device) const {
         if (padlen > 0 && L > padlen) throw std::runtime_error("padlen is too short to accommodate sequence\n");
-        bsq_dtype t;
-        const char *tname;
-        switch (dt.empty() ? 0 : (dt[0] & 223)) {
-        case 'B': t = BSQ_I8, tname = "uint8"; break;
-        case 'H': t = BSQ_I16, tname = "int16"; break;
-        case 'I': t = BSQ_I32, tname = "int32"; break;
-        case 'F': t = BSQ_F32, tname = "float32"; break;
-        case 'D': t = BSQ_F64, tname = "float64"; break;
-        default: throw std::invalid_argument(std::string("Unsupported dtype: ") + dt);
-        }
-        py::module_ torch = py::module_::import("torch");
-        py::object dev = torch.attr("device")(device);
-        if (dev.attr("type").cast<std::string>() != "cuda")
-            throw std::invalid_argument("device= must be a HIP ('cuda') device; omit it for a numpy result");
+        const SingleDtype &sd = single_dtype(dt);
+        const TorchApi &T = torch_api();
+        const py::object dev = hip_device(device);
         const py::ssize_t C = bsq_alphabet_size(&desc);
         const py::ssize_t rows = std::max(L, padlen) + desc.bos + desc.eos;
-        py::object out = torch.attr("empty")(py::make_tuple(rows, C), py::arg("dtype") = torch.attr(tname), py::arg("device") = dev);
+        py::object out = T.empty(py::make_tuple(rows, C), py::arg("dtype") = T.torch.attr(sd.torch_name), py::arg("device") = dev);
         if (rows == 0) return out;
         // packed batch of one sequence: offsets | chars in one small host tensor -> device
         py::array_t<uint8_t> host(py::ssize_t(16 + L));
         int64_t offs[2] = {0, int64_t(L)};
         std::memcpy(host.mutable_data(), offs, 16);
         if (L) std::memcpy(host.mutable_data() + 16, s, size_t(L));
-        py::object packed = torch.attr("from_numpy")(host).attr("to")(dev);
-        const uintptr_t base = packed.attr("data_ptr")().cast<uintptr_t>();
-        py::object guard = torch.attr("cuda").attr("device")(dev);
-        guard.attr("__enter__")();
-        void *stream = reinterpret_cast<void *>(torch.attr("cuda").attr("current_stream")().attr("cuda_stream").cast<uintptr_t>());
-        const bsq_status st = bsq_onehot_device(&desc, reinterpret_cast<const uint8_t *>(base + 16), reinterpret_cast<const int64_t *>(base),
-                                                nullptr, 1, rows, t, reinterpret_cast<void *>(out.attr("data_ptr")().cast<uintptr_t>()), stream);
-        guard.attr("__exit__")(py::none(), py::none(), py::none());
+        py::object packed = T.torch.attr("from_numpy")(host).attr("to")(dev);
+        const char *base = static_cast<const char *>(data_ptr(packed));
+        bsq_status st;
+        {
+            const DeviceScope scope(dev);
+            st = bsq_onehot_device(&desc, reinterpret_cast<const uint8_t *>(base + 16), reinterpret_cast<const int64_t *>(base), nullptr, 1, rows,
+                                   sd.t, data_ptr(out), scope.stream());
+        }
         if (st != BSQ_OK) throw_status(st);
         const py::ssize_t first_zero = std::max(padlen, L + desc.bos + desc.eos);
         if (desc.padchar && first_zero < rows) out.attr("__getitem__")(py::slice(first_zero, rows, 1)).attr("zero_")();
@@ -1089,21 +1102,15 @@ class Tokenizer {
     py::object onehot_single(const char *s, py::ssize_t L, py::ssize_t padlen, const std::string &dt,
                              const py::object &device = py::none()) const {
         if (!device.is_none()) return onehot_single_device(s, L, padlen, dt, device);
-        switch (dt.empty() ? 0 : (dt[0] & 223)) {
-        case 'B': return onehot_single_t<uint8_t>(s, L, padlen);
-        case 'H': return onehot_single_t<uint16_t>(s, L, padlen);
-        case 'I': return onehot_single_t<uint32_t>(s, L, padlen);
-        case 'F': return onehot_single_t<float>(s, L, padlen);
-        case 'D': return onehot_single_t<double>(s, L, padlen);
-        default: throw std::invalid_argument(std::string("Unsupported dtype: ") + dt);
-        }
+        return (this->*single_dtype(dt).host)(s, L, padlen);
     }
 
     // decode_tokens (tokenize.h:131-183): 1-D -> str, 2-D -> list of str.
     // Token matrices that live on a HIP device are decoded THERE (bsq_decode.hip: per-row wave prefix sums of the
     // piece widths; only the decoded text is copied back), host arrays here.
     py::object decode_device(py::object t) const {
-        py::module_ torch = py::module_::import("torch");
+        const TorchApi &T = torch_api();
+        const py::module_ &torch = T.torch;
         t = t.attr("detach")();
         const int64_t ndim = t.attr("dim")().cast<int64_t>();
         if (ndim > 2 || ndim == 0)
@@ -1123,21 +1130,11 @@ class Tokenizer {
             return empty;
         }
         py::object dev = t.attr("device");
-        py::object guard = torch.attr("cuda").attr("device")(dev);
-        guard.attr("__enter__")();
-        struct Exit {
-            py::object g;
-            ~Exit() {
-                try {
-                    g.attr("__exit__")(py::none(), py::none(), py::none());
-                } catch (...) {
-                }
-            }
-        } exit_guard{guard};
-        void *stream = reinterpret_cast<void *>(torch.attr("cuda").attr("current_stream")().attr("cuda_stream").cast<uintptr_t>());
-        const void *tok = reinterpret_cast<const void *>(t.attr("data_ptr")().cast<uintptr_t>());
-        py::object offs = torch.attr("empty")(py::make_tuple(nrows + 1), py::arg("dtype") = torch.attr("int64"), py::arg("device") = dev);
-        int64_t *offs_p = reinterpret_cast<int64_t *>(offs.attr("data_ptr")().cast<uintptr_t>());
+        const DeviceScope scope(dev);
+        void *stream = scope.stream();
+        const void *tok = data_ptr(t);
+        py::object offs = T.empty(py::make_tuple(nrows + 1), py::arg("dtype") = torch.attr("int64"), py::arg("device") = dev);
+        int64_t *offs_p = static_cast<int64_t *>(data_ptr(offs));
         int64_t total = 0, bad = -1;
         bsq_status st;
         {
@@ -1151,9 +1148,9 @@ class Tokenizer {
             throw std::runtime_error("Unexpected/invalid token " + std::to_string(v));
         }
         if (st != BSQ_OK) throw_status(st);
-        py::object out = torch.attr("empty")(py::make_tuple(total), py::arg("dtype") = torch.attr("uint8"), py::arg("device") = dev);
+        py::object out = T.empty(py::make_tuple(total), py::arg("dtype") = torch.attr("uint8"), py::arg("device") = dev);
         {
-            uint8_t *out_p = reinterpret_cast<uint8_t *>(out.attr("data_ptr")().cast<uintptr_t>());
+            uint8_t *out_p = static_cast<uint8_t *>(data_ptr(out));
             py::gil_scoped_release nogil;
             st = bsq_decode_write_device(&desc, tok, itemsize, nrows, ncols, rs, cs, offs_p, out_p, stream);
         }
@@ -1171,7 +1168,7 @@ class Tokenizer {
     // decode_logits (addition; README.md:48): argmax over the last (channel) axis on the device, then decode_device.
     // logits: float tensor on a HIP device, (L, C) -> str, (B, L, C) -> list of B str (batch_first) or (L, B, C).
     py::object decode_logits(py::object logits, bool batch_first) const {
-        py::module_ torch = py::module_::import("torch");
+        const TorchApi &T = torch_api();
         if (!py::hasattr(logits, "is_cuda") || !logits.attr("is_cuda").cast<bool>())
             throw std::invalid_argument("decode_logits expects a float tensor on a HIP ('cuda') device");
         logits = logits.attr("detach")();
@@ -1193,19 +1190,13 @@ class Tokenizer {
         std::vector<int64_t> tshape(shape.begin(), shape.end() - 1);
         for (int64_t v : tshape) n *= v;
         py::object dev = logits.attr("device");
-        py::object tokens = torch.attr("empty")(py::cast(tshape), py::arg("dtype") = torch.attr(C <= 256 ? "uint8" : "int32"),
-                                                py::arg("device") = dev);
+        py::object tokens = T.empty(py::cast(tshape), py::arg("dtype") = T.torch.attr(C <= 256 ? "uint8" : "int32"), py::arg("device") = dev);
+        bsq_status st;
         {
-            py::object guard = torch.attr("cuda").attr("device")(dev);
-            guard.attr("__enter__")();
-            void *stream = reinterpret_cast<void *>(torch.attr("cuda").attr("current_stream")().attr("cuda_stream").cast<uintptr_t>());
-            const bsq_status st = bsq_argmax_tokens_device(reinterpret_cast<const void *>(logits.attr("data_ptr")().cast<uintptr_t>()),
-                                                           kind, n, int32_t(C), C,
-                                                           reinterpret_cast<void *>(tokens.attr("data_ptr")().cast<uintptr_t>()),
-                                                           C <= 256 ? 1 : 4, stream);
-            guard.attr("__exit__")(py::none(), py::none(), py::none());
-            if (st != BSQ_OK) throw_status(st);
+            const DeviceScope scope(dev);
+            st = bsq_argmax_tokens_device(data_ptr(logits), kind, n, int32_t(C), C, data_ptr(tokens), C <= 256 ? 1 : 4, scope.stream());
         }
+        if (st != BSQ_OK) throw_status(st);
         if (ndim == 3 && !batch_first) tokens = tokens.attr("t")();  // a strided view: the decoder takes any strides
         return decode_device(tokens);
     }
@@ -1278,6 +1269,28 @@ struct ListScan {
     py::array_t<int64_t> offsets;
     int64_t n = 0, bad = -1;
     int nthreads = 1;
+
+    ListScan(py::sequence batch, int64_t maxlen, int nthreads_) : nthreads(nthreads_) {
+        const Scan scan = scan_begin(batch, py::none(), g, nthreads);
+        scan_range(scan, g, 0, scan.n, nthreads);
+        n = scan.n;
+        offsets = py::array_t<int64_t>(n + 1);
+        offsets.mutable_data()[0] = 0;
+        bad = fill_offsets(g, offsets.mutable_data(), 0, n, maxlen);
+    }
+    // items [lo, hi) -> dst[offsets[lo] : offsets[hi]] (dst = the whole batch's buffer: writable, contiguous bytes)
+    void pack(int64_t lo, int64_t hi, const py::buffer &dst, const char *refusal) {
+        if (lo < 0 || hi < lo || hi > n) throw py::index_error("_ListScan.pack: range outside the list");
+        py::buffer_info info = dst.request(true);
+        const int64_t *o = offsets.data();
+        if (info.itemsize != 1 || info.ndim != 1 || int64_t(info.shape[0]) < o[hi] || (info.strides[0] != 1 && info.shape[0] > 1))
+            throw std::invalid_argument(refusal);
+        Packed p;
+        p.B = n;
+        p.offsets = const_cast<int64_t *>(o);
+        p.chars = static_cast<uint8_t *>(info.ptr);
+        pack_range(g, p, lo, hi, nthreads);
+    }
 };
 
 // devices=[...] of Tokenizer.batch_tokenize / batch_onehot_encode (keyword-only; not in the reference): the same validation, in the same
@@ -1308,8 +1321,8 @@ PYBIND11_MODULE(cbioseq, m) {
         py::gil_scoped_release nogil;
         bsq_release_staging();
     });
-    // The host half of the staged path without a device (tests, sanitizer runs): scan + pack `batch` piece by piece exactly as
-    // Tokenizer::staged does -- scan_pack_fast per piece, the general passes where it declines -- into ordinary memory.
+    // The host half of the staged path without a device (tests, sanitizer runs): scan + pack `batch` piece by piece through the
+    // produce_piece the staged paths run -- scan_pack_fast per piece, the general passes where it declines -- into ordinary memory.
     // Returns (offsets int64[n + 1], chars uint8[total], first item longer than maxlen or -1, pieces that took the fast job).
     m.def("_pack_list_in_pieces", [](py::sequence batch, int64_t piece, int64_t maxlen, int nthreads) {
         Gathered g;
@@ -1322,19 +1335,8 @@ PYBIND11_MODULE(cbioseq, m) {
         p.offsets = offsets.data();
         p.chars = chars.data();
         int64_t bad = -1, fast = 0;
-        for (int64_t lo = 0; lo < sc.n && bad < 0; lo += piece) {
-            const int64_t hi = std::min<int64_t>(sc.n, lo + piece);
-            if (scan_pack_fast(sc, g, p, lo, hi, nthreads, maxlen, &bad)) {
-                ++fast;
-                continue;
-            }
-            scan_range(sc, g, lo, hi, nthreads);
-            for (int64_t i = lo; i < hi && bad < 0; ++i) {
-                offsets[size_t(i) + 1] = offsets[size_t(i)] + int64_t(g.items[size_t(i)].len);
-                if (int64_t(g.items[size_t(i)].len) > maxlen) bad = i;
-            }
-            if (bad < 0) pack_range(g, p, lo, hi, nthreads);
-        }
+        for (int64_t lo = 0; lo < sc.n && bad < 0; lo += piece)
+            fast += produce_piece(sc, g, p, lo, std::min<int64_t>(sc.n, lo + piece), nthreads, maxlen, &bad);
         const int64_t upto = bad >= 0 ? bad : sc.n;
         py::array_t<int64_t> o(upto + 1);
         std::memcpy(o.mutable_data(), offsets.data(), size_t(upto + 1) * 8);
@@ -1347,66 +1349,20 @@ PYBIND11_MODULE(cbioseq, m) {
     // of a PINNED torch tensor: the slices of the N devices then go up as asynchronous copies on N copy streams).  Returns (offsets
     // int64[n + 1], the buffer alloc returned, index of the first item longer than maxlen or -1).  Nothing is packed when an item is too long.
     m.def("_pack_list_into", [](py::sequence batch, int64_t maxlen, int nthreads, py::function alloc) -> py::tuple {
-        Gathered g;
-        const Scan sc = scan_begin(batch, py::none(), g, nthreads);
-        scan_range(sc, g, 0, sc.n, nthreads);
-        py::array_t<int64_t> offsets(sc.n + 1);
-        int64_t *o = offsets.mutable_data();
-        int64_t bad = -1, acc = 0;
-        o[0] = 0;
-        for (Py_ssize_t i = 0; i < sc.n; ++i) {
-            const int64_t len = int64_t(g.items[size_t(i)].len);
-            if (len > maxlen && bad < 0) bad = i;
-            acc += len;
-            o[i + 1] = acc;
-        }
-        if (bad >= 0) return py::make_tuple(offsets, py::object(py::none()), bad);
-        py::object buf = alloc(py::int_(size_t(acc) + 16));  // (+16: the kernels' unaligned 16-byte loads never leave the allocation)
-        py::buffer_info info = py::reinterpret_borrow<py::buffer>(buf).request(true);
-        if (info.itemsize != 1 || info.ndim != 1 || size_t(info.shape[0]) < size_t(acc) || (info.strides[0] != 1 && info.shape[0] > 1))
-            throw std::invalid_argument("_pack_list_into: alloc() must return a writable, contiguous buffer of bytes of the requested size");
-        Packed p;
-        p.B = sc.n;
-        p.offsets = o;
-        p.chars = static_cast<uint8_t *>(info.ptr);
-        pack_range(g, p, 0, sc.n, nthreads);
-        return py::make_tuple(offsets, buf, bad);
+        ListScan sc(batch, maxlen, nthreads);
+        if (sc.bad >= 0) return py::make_tuple(sc.offsets, py::object(py::none()), sc.bad);
+        py::object buf = alloc(py::int_(size_t(sc.offsets.data()[sc.n]) + 16));  // (+16: the kernels' unaligned 16-byte loads never leave the allocation)
+        sc.pack(0, sc.n, py::reinterpret_borrow<py::buffer>(buf),
+                "_pack_list_into: alloc() must return a writable, contiguous buffer of bytes of the requested size");
+        return py::make_tuple(sc.offsets, buf, sc.bad);
     }, py::arg("batch"), py::arg("maxlen"), py::arg("nthreads"), py::arg("alloc"));
     py::class_<ListScan>(m, "_ListScan")
-        .def(py::init([](py::sequence batch, int64_t maxlen, int nthreads) {
-                 auto sc = std::make_unique<ListScan>();
-                 const Scan scan = scan_begin(batch, py::none(), sc->g, nthreads);
-                 scan_range(scan, sc->g, 0, scan.n, nthreads);
-                 sc->n = scan.n;
-                 sc->nthreads = nthreads;
-                 sc->offsets = py::array_t<int64_t>(scan.n + 1);
-                 int64_t *o = sc->offsets.mutable_data();
-                 int64_t acc = 0;
-                 o[0] = 0;
-                 for (Py_ssize_t i = 0; i < scan.n; ++i) {
-                     const int64_t len = int64_t(sc->g.items[size_t(i)].len);
-                     if (len > maxlen && sc->bad < 0) sc->bad = i;
-                     acc += len;
-                     o[i + 1] = acc;
-                 }
-                 return sc;
-             }),
-             py::arg("batch"), py::arg("maxlen"), py::arg("nthreads") = 0)
+        .def(py::init<py::sequence, int64_t, int>(), py::arg("batch"), py::arg("maxlen"), py::arg("nthreads") = 0)
         .def_readonly("offsets", &ListScan::offsets)
         .def_readonly("bad", &ListScan::bad)
         .def_readonly("n", &ListScan::n)
         .def("pack", [](ListScan &sc, int64_t lo, int64_t hi, py::buffer dst) {
-            // items [lo, hi) -> dst[offsets[lo] : offsets[hi]] (dst = the whole batch's buffer: writable, contiguous bytes)
-            if (lo < 0 || hi < lo || hi > sc.n) throw py::index_error("_ListScan.pack: range outside the list");
-            py::buffer_info info = dst.request(true);
-            const int64_t *o = sc.offsets.data();
-            if (info.itemsize != 1 || info.ndim != 1 || int64_t(info.shape[0]) < o[hi] || (info.strides[0] != 1 && info.shape[0] > 1))
-                throw std::invalid_argument("_ListScan.pack: dst must be a writable, contiguous buffer of at least offsets[hi] bytes");
-            Packed p;
-            p.B = sc.n;
-            p.offsets = const_cast<int64_t *>(o);
-            p.chars = static_cast<uint8_t *>(info.ptr);
-            pack_range(sc.g, p, lo, hi, sc.nthreads);
+            sc.pack(lo, hi, dst, "_ListScan.pack: dst must be a writable, contiguous buffer of at least offsets[hi] bytes");
         }, py::arg("lo"), py::arg("hi"), py::arg("dst"));
     m.def("alphabet_keys", [] {
         std::vector<std::string> k;

@@ -212,7 +212,6 @@ class FlatFile:
         validate=False: a device index tensor the caller vouches for (in range) -- nothing is read back, the call never
         synchronises; with distinct=True (no index twice: a sampler's permutation) the buffer is sized by the n longest
         sequences of the store instead of n times the longest."""
-        import ctypes
         import torch
         from . import capi
         lib = capi.load()
@@ -243,8 +242,7 @@ class FlatFile:
         status = torch.empty(1, dtype=torch.int64, device=dev) if (on_device and validate) else None
         while True:
             out_chars = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
-            with capi.on_device(dev):
-                stream = ctypes.c_void_p(capi.raw_stream(dev))
+            with capi.launching(dev) as stream:
                 capi.check(lib.bsq_gather_packed_device(chars.data_ptr(), offs.data_ptr(), self._n, idx.data_ptr(), n,
                                                         out_chars.data_ptr(), capacity, out_offs.data_ptr(),
                                                         status.data_ptr() if status is not None else None, stream))

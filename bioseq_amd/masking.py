@@ -18,20 +18,13 @@ from __future__ import annotations
 import ctypes
 
 from . import capi
-from .multi import _dtype, validate_packed_multi
+from .multi import validate_packed_multi
 
 _lib = capi.load()
 
 
 def _check_packed(chars, offsets):
-    import torch
-    if not (isinstance(chars, torch.Tensor) and isinstance(offsets, torch.Tensor) and chars.is_cuda and offsets.is_cuda):
-        raise ValueError("the masked-LM calls work on packed batches resident on the device (chars, offsets tensors)")
-    if chars.device != offsets.device:
-        raise ValueError("chars and offsets must live on one device")
-    if chars.dtype != torch.uint8 or offsets.dtype != torch.int64 or not chars.is_contiguous() or not offsets.is_contiguous():
-        raise ValueError("chars must be contiguous uint8 and offsets contiguous int64")
-    return int(offsets.numel()) - 1
+    return capi.packed_on_device(chars, offsets, "the masked-LM calls work on packed batches resident on the device (chars, offsets tensors)")
 
 
 def _params(frac, mask_prob, random_prob, mask_token, ignore_index, seed, first_row):
@@ -48,28 +41,15 @@ def _params(frac, mask_prob, random_prob, mask_token, ignore_index, seed, first_
                     int(first_row))
 
 
-def _dtype_code(destchar):
-    dt = ctypes.c_int(0)
-    capi.check(_lib.bsq_dtype_from_destchar(str(destchar).encode(), ctypes.byref(dt)))
-    return dt
-
-
-def _desc(tok):
-    return capi.make_desc(tok.key, tok.includes_eos(), tok.includes_bos(), tok.is_padded())
-
-
 def _launch_mlm(tok, chars, offsets, B, padlen, batch_first, m, in_dt, inputs, label_dt, labels):
-    desc = _desc(tok)
+    desc = capi.desc_of(tok)
     if B == 0:
         return
-    if chars.numel() == 0:  # every sequence is empty: torch hands out a null data_ptr for it, and no kernel reads a character
-        import torch
-        chars = torch.zeros(16, dtype=torch.uint8, device=offsets.device)
-    with capi.on_device(chars.device):
+    chars = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+    with capi.launching(chars.device) as stream:
         capi.check(_lib.bsq_mlm_tokenize_device(ctypes.byref(desc), chars.data_ptr(), offsets.data_ptr(), B, int(padlen), int(bool(batch_first)),
                                                 ctypes.byref(m), in_dt, inputs.data_ptr() if inputs is not None else None, label_dt,
-                                                labels.data_ptr() if labels is not None else None,
-                                                ctypes.c_void_p(capi.raw_stream(chars.device))))
+                                                labels.data_ptr() if labels is not None else None, stream))
 
 
 def mlm_tokenize_packed(tok, chars, offsets, padlen, destchar="b", batch_first=True, *, frac=0.15, mask_prob=0.8, random_prob=0.1,
@@ -85,13 +65,13 @@ def mlm_tokenize_packed(tok, chars, offsets, padlen, destchar="b", batch_first=T
     m = _params(frac, mask_prob, random_prob, tok.alphabet_size() if mask_token is None else mask_token, ignore_index, seed, first_row)
     if int(padlen) <= 0:
         raise ValueError("padlen must be positive")
-    in_dt, label_dt = _dtype_code(destchar), _dtype_code(label_dtype)
+    (in_dt, in_tdt), (label_dt, label_tdt) = capi.dtype_of(destchar), capi.dtype_of(label_dtype)
     B = _check_packed(chars, offsets)
     if validate and B > 0:
         validate_packed_multi(tok, [(chars, offsets)], int(padlen))
     shape = (B, int(padlen)) if batch_first else (int(padlen), B)
-    inputs = torch.empty(shape, dtype=_dtype(in_dt.value), device=chars.device)
-    labels = torch.empty(shape, dtype=_dtype(label_dt.value), device=chars.device)
+    inputs = torch.empty(shape, dtype=in_tdt, device=chars.device)
+    labels = torch.empty(shape, dtype=label_tdt, device=chars.device)
     _launch_mlm(tok, chars, offsets, B, padlen, batch_first, m, in_dt, inputs, label_dt, labels)
     return inputs, labels
 
@@ -104,10 +84,9 @@ def random_mask_packed(tok, chars, offsets, *, frac, seed, first_row=0):
     B = _check_packed(chars, offsets)
     mask = torch.ones(chars.numel(), dtype=torch.uint8, device=chars.device)
     if B > 0 and chars.numel() > 0:
-        desc = _desc(tok)
-        with capi.on_device(chars.device):
-            capi.check(_lib.bsq_random_mask_device(ctypes.byref(desc), chars.data_ptr(), offsets.data_ptr(), B, ctypes.byref(m), mask.data_ptr(),
-                                                   ctypes.c_void_p(capi.raw_stream(chars.device))))
+        desc = capi.desc_of(tok)
+        with capi.launching(chars.device) as stream:
+            capi.check(_lib.bsq_random_mask_device(ctypes.byref(desc), chars.data_ptr(), offsets.data_ptr(), B, ctypes.byref(m), mask.data_ptr(), stream))
     return mask
 
 
@@ -120,11 +99,11 @@ def onehot_masked_packed(tok, chars, offsets, padlen, destchar="f", layout="bcl"
     m = _params(frac, 0.0, 0.0, 0, ignore_index, seed, first_row)
     if int(padlen) <= 0:
         raise ValueError("padlen must be positive")
-    label_dt = _dtype_code(label_dtype)
+    label_dt, label_tdt = capi.dtype_of(label_dtype)
     B = _check_packed(chars, offsets)
     mask = random_mask_packed(tok, chars, offsets, frac=frac, seed=seed, first_row=first_row)
     onehot = tok.onehot_packed(chars, offsets, int(padlen), destchar, mask=mask, validate=validate, layout=layout)
-    labels = torch.empty((B, int(padlen)), dtype=_dtype(label_dt.value), device=chars.device)
+    labels = torch.empty((B, int(padlen)), dtype=label_tdt, device=chars.device)
     _launch_mlm(tok, chars, offsets, B, padlen, True, m, label_dt, None, label_dt, labels)
     return onehot, labels
 

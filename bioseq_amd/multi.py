@@ -13,15 +13,8 @@ import ctypes
 
 from . import capi
 
-_TORCH_DTYPES = None
-
-
-def _dtype(code):
-    import torch
-    global _TORCH_DTYPES
-    if _TORCH_DTYPES is None:
-        _TORCH_DTYPES = {0: torch.int8, 1: torch.int16, 2: torch.int32, 3: torch.int64, 4: torch.float32, 5: torch.float64}
-    return _TORCH_DTYPES[code]
+_RESIDENT = "the multi-batch calls work on packed batches resident on the device (chars, offsets tensors)"
+_ONE_DEVICE = "every batch of a multi-batch call lives on one device"
 
 
 def _convert(batches):
@@ -30,12 +23,11 @@ def _convert(batches):
     import torch
     out, dev = [], None
     for chars, offsets in batches:
-        if not (isinstance(chars, torch.Tensor) and chars.is_cuda and isinstance(offsets, torch.Tensor) and offsets.is_cuda):
-            raise ValueError("the multi-batch calls work on packed batches resident on the device (chars, offsets tensors)")
+        capi.packed_on_device(chars, offsets, _RESIDENT, exact=False, apart=_ONE_DEVICE)
         if dev is None:
             dev = chars.device
-        if chars.device != dev or offsets.device != dev:
-            raise ValueError("every batch of a multi-batch call lives on one device")
+        if chars.device != dev:
+            raise ValueError(_ONE_DEVICE)
         out.append((chars.contiguous(), offsets.to(torch.int64).contiguous()))
     return out
 
@@ -44,15 +36,12 @@ def _prepare(tokenizer, batches, padlen, destchar, batch_first, outs, onehot=Fal
     """batches: the output of _convert.  onehot: the table is of bsq_onehot_batch and the results are (padlen, B, C) / (B, C, padlen)."""
     import torch
     lib = capi.load()
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
-    dt = ctypes.c_int(0)
-    capi.check(lib.bsq_dtype_from_destchar(destchar.encode(), ctypes.byref(dt)))
-    tdt = _dtype(dt.value)
+    desc = capi.desc_of(tokenizer)
+    dt, tdt = capi.dtype_of(destchar)
     n = len(batches)
     arr = ((capi.OnehotBatch if onehot else capi.Batch) * max(n, 1))()
     results, keep = [], []
     dev = batches[0][0].device if batches else None
-    room = int(padlen) - int(tokenizer.includes_bos()) - int(tokenizer.includes_eos())
     C = lib.bsq_alphabet_size(ctypes.byref(desc))
     for i, (chars, offsets) in enumerate(batches):
         B = int(offsets.shape[0]) - 1
@@ -66,33 +55,29 @@ def _prepare(tokenizer, batches, padlen, destchar, batch_first, outs, onehot=Fal
                 raise ValueError("outs[%d] must be a contiguous %s tensor of shape %r on %s" % (i, tdt, shape, dev))
         else:
             out = torch.empty(shape, dtype=tdt, device=dev)
-        if chars.numel() == 0 and B > 0:
-            # every sequence of this batch is empty: torch hands out a null data_ptr for a tensor without elements, which the augmentation entry
-            # points refuse for B > 0 (include/bsq.h) -- no kernel reads a character of an empty sequence, so any valid address will do
-            chars = torch.zeros(16, dtype=torch.uint8, device=dev)
+        if B > 0:
+            chars = capi.readable_chars(chars, dev)  # (every sequence of this batch may be empty)
         keep.append((chars, offsets))
         results.append(out)
         arr[i].chars, arr[i].offsets, arr[i].B, arr[i].out = chars.data_ptr(), offsets.data_ptr(), B, out.data_ptr()
-    return lib, desc, dt, arr, results, keep, dev, room
+    return lib, desc, dt, arr, results, keep, dev
 
 
 def validate_packed_multi(tokenizer, batches, padlen):
     """The reference's over-long-sequence error for every batch (one synchronising check per batch: `tokenize_packed(validate=True)`'s).
     batches: the output of _convert (the offsets are read as contiguous int64)."""
     lib = capi.load()
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
+    desc = capi.desc_of(tokenizer)
     for chars, offsets in batches:
         B = int(offsets.shape[0]) - 1
         if B <= 0:
             continue
         bad = ctypes.c_int64(-1)
-        with capi.on_device(chars.device):
-            st = lib.bsq_validate_packed_device(offsets.data_ptr(), B, padlen, desc.bos, desc.eos, chars.numel(), ctypes.byref(bad),
-                                                ctypes.c_void_p(capi.raw_stream(chars.device)))
+        with capi.launching(chars.device) as stream:
+            st = lib.bsq_validate_packed_device(offsets.data_ptr(), B, padlen, desc.bos, desc.eos, chars.numel(), ctypes.byref(bad), stream)
         if st == capi.ERR_SEQ_TOO_LONG:  # the reference's error of batch_tokenize (tokenize.h:456-459), as tokenize_packed raises it
             i = int(bad.value)
-            length = int(offsets[i + 1] - offsets[i]) + int(desc.bos) + int(desc.eos)
-            raise RuntimeError("seq len + bos + eos > padlen: %d, vs padlen %d" % (length, int(padlen)))
+            capi.raise_too_long(tokenizer, int(offsets[i + 1] - offsets[i]), padlen, False)
         capi.check(st)
 
 
@@ -102,10 +87,10 @@ def tokenize_packed_multi(tokenizer, batches, padlen, destchar="B", batch_first=
     batches = _convert(batches)
     if validate:
         validate_packed_multi(tokenizer, batches, padlen)
-    lib, desc, dt, arr, results, keep, dev, _ = _prepare(tokenizer, batches, padlen, destchar, batch_first, outs)
+    lib, desc, dt, arr, results, keep, dev = _prepare(tokenizer, batches, padlen, destchar, batch_first, outs)
     if batches:
-        with capi.on_device(dev):
-            capi.check(lib.bsq_tokenize_device_multi(ctypes.byref(desc), len(batches), arr, padlen, int(batch_first), dt, ctypes.c_void_p(capi.raw_stream(dev))))
+        with capi.launching(dev) as stream:
+            capi.check(lib.bsq_tokenize_device_multi(ctypes.byref(desc), len(batches), arr, padlen, int(batch_first), dt, stream))
     return results
 
 
@@ -121,12 +106,12 @@ def augment_tokenize_packed_multi(tokenizer, batches, padlen, destchar="b", batc
     batches = _convert(batches)
     if validate:
         validate_packed_multi(tokenizer, batches, padlen)
-    lib, desc, dt, arr, results, keep, dev, _ = _prepare(tokenizer, batches, padlen, destchar, batch_first, outs)
+    lib, desc, dt, arr, results, keep, dev = _prepare(tokenizer, batches, padlen, destchar, batch_first, outs)
     if batches:
         sd = (ctypes.c_uint64 * n)(*[s & ((1 << 64) - 1) for s in seeds])
-        with capi.on_device(dev):
+        with capi.launching(dev) as stream:
             capi.check(lib.bsq_augment_tokenize_device_multi(ctypes.byref(desc), n, arr, padlen, int(batch_first), dt, int(chain_len), float(augment_frac),
-                                                             sd, ctypes.c_void_p(capi.raw_stream(dev))))
+                                                             sd, stream))
     return results
 
 
@@ -135,12 +120,7 @@ def onehot_packed_multi(tokenizer, batches, padlen, destchar="B", layout="tbc", 
     launches (`bsq_onehot_device_multi`).  batches: list of (chars uint8, offsets) device tensors; masks: None, or a list of None / uint8 device
     tensors of chars_i.numel() bytes (0 = masked, as `onehot_packed(mask=...)`); layout "tbc" -> (padlen, B_i, C), "bcl" -> (B_i, C, padlen)."""
     import torch
-    if layout in ("tbc", "seq_first", ""):
-        bcl = False
-    elif layout in ("bcl", "channels_first"):
-        bcl = True
-    else:
-        raise ValueError("layout must be 'tbc' (padlen, batch, channels) or 'bcl' (batch, channels, padlen)")
+    bcl = capi.parse_layout(layout)
     n = len(batches)
     masks = [None] * n if masks is None else list(masks)
     if len(masks) != n:
@@ -155,10 +135,10 @@ def onehot_packed_multi(tokenizer, batches, padlen, destchar="B", layout="tbc", 
         masks[i] = m.contiguous()
     if validate:
         validate_packed_multi(tokenizer, batches, padlen)
-    lib, desc, dt, arr, results, keep, dev, _ = _prepare(tokenizer, batches, padlen, destchar, bcl, outs, onehot=True)
+    lib, desc, dt, arr, results, keep, dev = _prepare(tokenizer, batches, padlen, destchar, bcl, outs, onehot=True)
     for i, m in enumerate(masks):
         arr[i].mask = m.data_ptr() if m is not None and m.numel() > 0 else None
     if batches:
-        with capi.on_device(dev):
-            capi.check(lib.bsq_onehot_device_multi(ctypes.byref(desc), n, arr, padlen, int(bcl), dt, ctypes.c_void_p(capi.raw_stream(dev))))
+        with capi.launching(dev) as stream:
+            capi.check(lib.bsq_onehot_device_multi(ctypes.byref(desc), n, arr, padlen, int(bcl), dt, stream))
     return results

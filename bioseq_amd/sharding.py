@@ -37,7 +37,11 @@ from __future__ import annotations
 
 from typing import Callable, Optional, Tuple
 
+import ctypes
+
 import numpy as np
+
+from . import capi
 
 
 def shard_bounds(B: int, world: int, rank: int) -> Tuple[int, int]:
@@ -248,17 +252,11 @@ def onehot_gathered(raw_tokens: Callable, expand: Callable, chars, offsets, grou
 
 def device_passes(tokenizer, padlen: int, destchar: str, device):
     """(raw_tokens, expand) for `onehot_gathered`, running the library's two passes on `device` through the C ABI."""
-    import ctypes
-
     import torch
-
-    from . import capi
     lib = capi.load()
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
+    desc = capi.desc_of(tokenizer)
     C = int(tokenizer.alphabet_size())
-    dt = ctypes.c_int(0)
-    capi.check(lib.bsq_dtype_from_destchar(destchar.encode(), ctypes.byref(dt)))
-    tdt = {0: torch.int8, 1: torch.int16, 2: torch.int32, 3: torch.int64, 4: torch.float32, 5: torch.float64}[dt.value]
+    dt, tdt = capi.dtype_of(destchar)
     dev = torch.device(device)
 
     def raw_tokens(chars, offsets):
@@ -268,17 +266,15 @@ def device_passes(tokenizer, padlen: int, destchar: str, device):
         out = torch.empty((padlen, Bg), dtype=torch.uint8, device=dev)
         if Bg == 0:
             return out
-        with capi.on_device(dev):
-            capi.check(lib.bsq_raw_tokens_device(ctypes.byref(desc), ch.data_ptr(), of.data_ptr(), None, Bg, padlen,
-                                                 out.data_ptr(), Bg, capi.raw_stream()))
+        with capi.launching(dev) as stream:
+            capi.check(lib.bsq_raw_tokens_device(ctypes.byref(desc), ch.data_ptr(), of.data_ptr(), None, Bg, padlen, out.data_ptr(), Bg, stream))
         return out
 
     def expand(tokens):
         P, B = int(tokens.shape[0]), int(tokens.shape[1])
         out = torch.empty((P, B, C), dtype=tdt, device=tokens.device)
-        with capi.on_device(tokens.device):
-            capi.check(lib.bsq_onehot_from_raw_tokens_device(tokens.data_ptr(), B, B, P, C, dt, out.data_ptr(),
-                                                             capi.raw_stream()))
+        with capi.launching(tokens.device) as stream:
+            capi.check(lib.bsq_onehot_from_raw_tokens_device(tokens.data_ptr(), B, B, P, C, dt, out.data_ptr(), stream))
         return out
 
     return raw_tokens, expand
@@ -343,21 +339,15 @@ def store_shard_into_root(tokenizer, shard_chars, shard_offsets, b0: int, B: int
     row, every row of the shard cut at the 4-KiB boundaries of the root's memory -- any first sequence, any pitch --; the tiled
     kernel with the root tensor's row pitch for shards below 128 MB; the xGMI links, not HBM, bound a remote store).  Returns the whole-batch tensor on `root`,
     None elsewhere."""
-    import ctypes
-
     import torch
-
-    from . import capi
     dist = _dist()
     rank = dist.get_rank(group)
     if layout not in ("tokens_bf", "tokens_sf", "bcl", "tbc"):
         raise ValueError("layout must be 'tokens_bf', 'tokens_sf', 'bcl' or 'tbc'")
     lib = capi.load()
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
+    desc = capi.desc_of(tokenizer)
     C = int(tokenizer.alphabet_size())
-    dt = ctypes.c_int(0)
-    capi.check(lib.bsq_dtype_from_destchar(destchar.encode(), ctypes.byref(dt)))
-    tdt = {0: torch.int8, 1: torch.int16, 2: torch.int32, 3: torch.int64, 4: torch.float32, 5: torch.float64}[dt.value]
+    dt, tdt = capi.dtype_of(destchar)
     dev = torch.device(device)
     shape = {"tokens_bf": (int(B), padlen), "tokens_sf": (padlen, int(B)), "bcl": (int(B), C, padlen), "tbc": (padlen, int(B), C)}[layout]
     # Everything a rank can fail at on its own (mapping the root's memory, an invalid shard, an encode error) is caught and
@@ -391,11 +381,7 @@ def store_shard_into_root(tokenizer, shard_chars, shard_offsets, b0: int, B: int
 
 def _store_shard(lib, desc, dt, full, shard_chars, shard_offsets, b0, B, padlen, layout, dev, validate):
     """This rank's part of `store_shard_into_root`: the ordinary encode kernels with the root's (mapped) slab as their output."""
-    import ctypes
-
     import torch
-
-    from . import capi
     ch = torch.as_tensor(shard_chars).to(dev)
     of = torch.as_tensor(shard_offsets).to(dev).to(torch.int64).contiguous()
     nb = int(of.shape[0]) - 1
@@ -403,8 +389,7 @@ def _store_shard(lib, desc, dt, full, shard_chars, shard_offsets, b0, B, padlen,
         # 'tbc': this rank's sequences are a COLUMN BLOCK of every position row of the (P, B, C) tensor
         slab = full[:, b0:b0 + nb] if layout in ("tbc", "tokens_sf") else full[b0:b0 + nb]
         assert layout in ("tbc", "tokens_sf") or (slab.is_contiguous() and slab.shape[0] == nb)
-        with capi.on_device(dev):
-            stream = ctypes.c_void_p(capi.raw_stream())
+        with capi.launching(dev) as stream:
             if validate:
                 bad = ctypes.c_int64(-1)
                 capi.check(lib.bsq_validate_packed_device(of.data_ptr(), nb, padlen, desc.bos, desc.eos, ch.numel(), ctypes.byref(bad), stream))
@@ -494,22 +479,14 @@ def pack_once(tokenizer, batch, padlen: int, nthreads: int = 0, onehot: bool = F
         lens = offsets[1:] - offsets[:-1]
         if lens.numel() and int(lens.max()) > room:
             first = int((lens > room).nonzero()[0])
-            _raise_too_long(tokenizer, int(lens[first]), padlen, onehot)
+            capi.raise_too_long(tokenizer, int(lens[first]), padlen, onehot)
         if not chars.is_pinned():
             chars = chars.contiguous().pin_memory()
         return chars, offsets
     offs, buf, bad = cbioseq._pack_list_into(batch, max(room, 0), int(nthreads), _pinned_alloc)
     if bad >= 0:
-        _raise_too_long(tokenizer, int(offs[bad + 1] - offs[bad]), padlen, onehot)
+        capi.raise_too_long(tokenizer, int(offs[bad + 1] - offs[bad]), padlen, onehot)
     return torch.from_numpy(buf), torch.from_numpy(offs)
-
-
-def _raise_too_long(tokenizer, length, padlen, onehot):
-    """The reference's error for an over-long sequence, type and text (RuntimeError from batch_tokenize, tokenize.h:456-459;
-    ValueError from batch_onehot_encode, :359-362) -- as `Tokenizer.batch_tokenize` / `batch_onehot_encode` raise it here."""
-    tl = int(length) + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
-    msg = "seq len + bos + eos > padlen: %d, vs padlen %d" % (tl, int(padlen))
-    raise (ValueError if onehot else RuntimeError)(msg)
 
 
 class _DeviceSlot:
@@ -604,11 +581,7 @@ def encode_on_devices(tokenizer, batch, padlen: int, destchar: str = "B", device
 
 
 def _encode_on_devices(tokenizer, batch, padlen, destchar, devices, op, batch_first, layout, root, nthreads):
-    import ctypes
-
     import torch
-
-    from . import capi
     if op not in ("tokenize", "onehot"):
         raise ValueError("op must be 'tokenize' or 'onehot'")
     if op == "onehot" and layout not in ("tbc", "bcl"):
@@ -618,11 +591,9 @@ def _encode_on_devices(tokenizer, batch, padlen, destchar, devices, op, batch_fi
         raise ValueError("encode_on_devices needs a non-empty list of HIP devices")
     devs = [torch.device("cuda", torch.cuda.current_device() if d.index is None else d.index) for d in devs]
     lib = capi.load()
-    desc = capi.make_desc(tokenizer.key, tokenizer.includes_eos(), tokenizer.includes_bos(), tokenizer.is_padded())
+    desc = capi.desc_of(tokenizer)
     C = int(tokenizer.alphabet_size())
-    dt = ctypes.c_int(0)
-    capi.check(lib.bsq_dtype_from_destchar(destchar.encode(), ctypes.byref(dt)))
-    tdt = {0: torch.int8, 1: torch.int16, 2: torch.int32, 3: torch.int64, 4: torch.float32, 5: torch.float64}[dt.value]
+    dt, tdt = capi.dtype_of(destchar)
     seq_first = (op == "onehot" and layout == "tbc") or (op == "tokenize" and not batch_first)
     G = len(devs)
     scan = user_chars = None
@@ -636,7 +607,7 @@ def _encode_on_devices(tokenizer, batch, padlen, destchar, devices, op, batch_fi
         scan = cbioseq._ListScan(batch, max(room, 0), int(nthreads))
         offsets = torch.from_numpy(scan.offsets)
         if scan.bad >= 0:
-            _raise_too_long(tokenizer, int(offsets[scan.bad + 1] - offsets[scan.bad]), padlen, op == "onehot")
+            capi.raise_too_long(tokenizer, int(offsets[scan.bad + 1] - offsets[scan.bad]), padlen, op == "onehot")
     B = int(offsets.shape[0]) - 1
     o_np = offsets.numpy()
     total = int(o_np[-1])

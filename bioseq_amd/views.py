@@ -44,20 +44,7 @@ def _crop(window, mode, revcomp_frac, seed, first_row):
 
 
 def _check_store(chars, offsets):
-    import torch
-    if not (isinstance(chars, torch.Tensor) and isinstance(offsets, torch.Tensor) and chars.is_cuda and offsets.is_cuda):
-        raise ValueError("views are cut from packed stores resident on the device (chars, offsets tensors)")
-    if chars.device != offsets.device:
-        raise ValueError("chars and offsets must live on one device")
-    if chars.dtype != torch.uint8 or offsets.dtype != torch.int64 or not chars.is_contiguous() or not offsets.is_contiguous():
-        raise ValueError("chars must be contiguous uint8 and offsets contiguous int64")
-    return int(offsets.numel()) - 1
-
-
-def _nonempty(t, dev):
-    """`t`, or a 16-byte stand-in for an empty tensor (torch hands out a null data_ptr for it; no kernel reads a byte of it)."""
-    import torch
-    return t if t.numel() else torch.zeros(16, dtype=torch.uint8, device=dev)
+    return capi.packed_on_device(chars, offsets, "views are cut from packed stores resident on the device (chars, offsets tensors)")
 
 
 def _index_arg(index, n_store, dev):
@@ -129,12 +116,12 @@ def _launch_crop(chars, offsets, n_store, idx, n, c, capacity, origin=False, che
     starts = torch.empty(n, dtype=torch.int64, device=dev) if origin else None
     strand = torch.empty(n, dtype=torch.uint8, device=dev) if origin else None
     status = torch.empty(1, dtype=torch.int64, device=dev) if check else None
-    with capi.on_device(dev):
-        capi.check(_lib.bsq_crop_packed_device(_nonempty(chars, dev).data_ptr(), offsets.data_ptr(), n_store,
+    with capi.launching(dev) as stream:
+        capi.check(_lib.bsq_crop_packed_device(capi.readable_chars(chars, dev).data_ptr(), offsets.data_ptr(), n_store,
                                                idx.data_ptr() if idx is not None else None, n, ctypes.byref(c), out_chars.data_ptr(), capacity,
                                                out_offs.data_ptr(), starts.data_ptr() if starts is not None and n else None,
                                                strand.data_ptr() if strand is not None and n else None,
-                                               status.data_ptr() if status is not None else None, ctypes.c_void_p(capi.raw_stream(dev))))
+                                               status.data_ptr() if status is not None else None, stream))
     return out_chars, out_offs, starts, strand, status
 
 
@@ -168,12 +155,11 @@ def gather_views(chars, offsets, seq, start, length, strand=None, validate=True)
     out_chars = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
     out_offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(1, dtype=torch.int64, device=dev) if validate else None
-    with capi.on_device(dev):
-        capi.check(_lib.bsq_views_packed_device(_nonempty(chars, dev).data_ptr(), offsets.data_ptr(), n_store, d_seq.data_ptr(),
+    with capi.launching(dev) as stream:
+        capi.check(_lib.bsq_views_packed_device(capi.readable_chars(chars, dev).data_ptr(), offsets.data_ptr(), n_store, d_seq.data_ptr(),
                                                 d_start.data_ptr(), d_len.data_ptr(),
                                                 d_strand.data_ptr() if d_strand is not None and n else None, n, out_chars.data_ptr(),
-                                                capacity, out_offs.data_ptr(), status.data_ptr() if status is not None else None,
-                                                ctypes.c_void_p(capi.raw_stream(dev))))
+                                                capacity, out_offs.data_ptr(), status.data_ptr() if status is not None else None, stream))
     if status is not None:
         _raise_status(int(status.item()), n, "gather_views")
     return out_chars, out_offs

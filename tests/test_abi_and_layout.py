@@ -180,3 +180,27 @@ def test_onehot_path_rule_for_one_byte_rows():
     assert nm("DNA", (0, 0, 0), 4096, 512, capi.F32) == b"k_onehot_chunks" and nm("DNA", (0, 0, 0), 8192, 512, capi.F32) == b"k_onehot_tile"
     assert nm("DNA", (0, 0, 0), 16384, 512, capi.F32) == b"k_tokens_pb8_fast<raw>+k_expand_chunks"
     assert nm("DNA4", (1, 1, 1), 1000000, 160, capi.I16).startswith(b"k_tokens_pb8_fast<raw") and nm("DNA4", (0, 0, 0), 1000000, 160, capi.I16) == b"k_onehot_tile"
+
+
+def test_destchar_table_agrees_with_the_element_size_derivation():
+    """capi.dtype_of (one code -> torch dtype table) gives, for every byte `bsq_dtype_from_destchar` accepts, the torch dtype that
+    `blosum.augment_tokenize_packed` used to derive from the element size (1/2/4/8 bytes -> int8/16/32/64, then 'f' / 'd' by hand)."""
+    import torch
+    from bioseq_amd import capi
+    lib = capi.load()
+    accepted = 0
+    for byte in range(256):
+        ch = bytes([byte])
+        dt = ctypes.c_int(0)
+        if lib.bsq_dtype_from_destchar(ch, ctypes.byref(dt)) != capi.OK:
+            continue
+        accepted += 1
+        by_size = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[lib.bsq_dtype_size(dt)]
+        if ch.lower() == b"f":
+            by_size = torch.float32
+        elif ch.lower() == b"d":
+            by_size = torch.float64
+        assert capi.torch_dtype(dt.value) == by_size, (ch, dt.value)
+        if byte < 128:
+            assert capi.dtype_of(ch.decode()) == (dt.value, by_size), ch
+    assert accepted == 14  # b h i l q f d in either case (bsq_dtype_from_destchar)
