@@ -38,6 +38,11 @@ class Crop(ctypes.Structure):
                 ("first_row", ctypes.c_int64)]
 
 
+class Kmer(ctypes.Structure):
+    """struct bsq_kmer"""
+    _fields_ = [("k", ctypes.c_int32), ("stride", ctypes.c_int32)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -127,6 +132,15 @@ def load():
         "bsq_crop_plan_host": (i32, [vp, i64, vp, i64, ctypes.POINTER(Crop), vp, vp, vp]),
         "bsq_views_packed_device": (i32, [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp]),
         "bsq_complement_table": (i32, [vp]),
+        "bsq_kmer_vocab_size": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_unk_id": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_bos_id": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_eos_id": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_pad_id": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_count": (i64, [ctypes.POINTER(Kmer), i64]),
+        "bsq_kmer_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp, vp]),
+        "bsq_kmer_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp]),
+        "bsq_kmer_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(Kmer), i64, i64, i32, c_int]),
         "bsq_blosum62_normrows": (i32, [vp]),
         "bsq_augment_device": (i32, [vp, vp, i64, i32, ctypes.c_double, ctypes.c_uint64, vp]),
         "bsq_augment_tokenize_device": (i32, [vp, vp, vp, i64, i64, i32, i32, vp, i32, ctypes.c_double, ctypes.c_uint64, vp]),

@@ -1,0 +1,180 @@
+"""k-mer ids of packed batches on the device (`bsq_kmer_tokenize_device`): the vocabulary DNA language models are trained on.
+
+Every other encode path of the package stops at one token per character.  Here a token is a window of `k` characters -- overlapping
+(stride 1: DNABERT's 3- to 6-mers), non-overlapping (stride k: 6-mers as the Nucleotide Transformer reads them) or any other stride,
+over any alphabet of the package whose `nchars ** k` stays within 2 ** 24 -- written in ONE launch from the packed batch, instead of
+tokens + `unfold` + weighted sum + `where` in torch.
+
+With A = the alphabet's classes and V = A ** k: plain ids are 0 .. V - 1 in lexicographic order (first character most significant),
+UNK = V marks a window with any unmapped character (an N under DNA4), then BOS, EOS and PAD follow in the tokenizer's own order of
+its specials.  A tail shorter than k is dropped.  include/bsq.h (`bsq_kmer`) has the full rules.
+
+* `kmer_tokenize_packed`  the ids of a packed batch resident on the device, (B, padlen) or (padlen, B);
+* `kmer_vocab_size`, `kmer_special_ids`, `kmer_padlen`, `kmer_count`  the sizes an embedding table and a batch need;
+* `kmer_decode`           ids -> words (host code: what one needs to write a vocabulary file);
+* `kmer_tokenize_host`    the library's CPU twin of the ids (numpy in, numpy out; no device).
+
+The crops and reverse-complement views of `views` hand this module packed batches as they are:
+`kmer_tokenize_packed(tok, *views.crop_packed(chars, offsets, 1000, revcomp_frac=0.5), k=6, padlen=...)`.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import capi
+
+_lib = capi.load()
+
+_NUMPY = {capi.I8: np.int8, capi.I16: np.int16, capi.I32: np.int32, capi.U64: np.uint64, capi.F32: np.float32, capi.F64: np.float64}
+
+
+def _kmer(tok, k, stride=1):
+    """(bsq_desc, bsq_kmer) with the library's argument rules applied (ValueError; no device is touched for a bad argument)."""
+    desc = capi.desc_of(tok)
+    km = capi.Kmer(int(k), int(stride))
+    if km.stride < 1:
+        raise ValueError("stride must be >= 1, got %r" % (stride,))
+    if _lib.bsq_kmer_vocab_size(ctypes.byref(desc), ctypes.byref(km)) < 0:
+        raise ValueError("k = %r with %d classes: %s" % (k, desc.nchars, _lib.bsq_last_error().decode()))
+    return desc, km
+
+
+def _dtype(desc, km, destchar):
+    """capi.dtype_of, refusing an element type the vocabulary does not fit (the library's BSQ_ERR_DTYPE) as a ValueError."""
+    dt, tdt = capi.dtype_of(destchar)
+    vocab = _lib.bsq_kmer_vocab_size(ctypes.byref(desc), ctypes.byref(km))
+    limit = {capi.I8: 128, capi.I16: 32768}.get(dt)
+    if limit is not None and vocab > limit:
+        raise ValueError("a vocabulary of %d ids does not fit destchar %r (at most %d)" % (vocab, destchar, limit))
+    return dt, tdt
+
+
+def kmer_vocab_size(tok, k):
+    """Ids of the k-mer vocabulary of `tok`: nchars ** k plain words, UNK, and BOS / EOS / PAD where the tokenizer has them."""
+    desc, km = _kmer(tok, k)
+    return int(_lib.bsq_kmer_vocab_size(ctypes.byref(desc), ctypes.byref(km)))
+
+
+def kmer_special_ids(tok, k):
+    """{"unk", "bos", "eos", "pad"}: bos / eos are -1 where the tokenizer has none; pad is the id whether or not the tokenizer pads
+    with it (an unpadded tokenizer stores 0 at pad positions, as `tokenize_packed` does)."""
+    desc, km = _kmer(tok, k)
+    d, m = ctypes.byref(desc), ctypes.byref(km)
+    return {"unk": int(_lib.bsq_kmer_unk_id(d, m)), "bos": int(_lib.bsq_kmer_bos_id(d, m)), "eos": int(_lib.bsq_kmer_eos_id(d, m)),
+            "pad": int(_lib.bsq_kmer_pad_id(d, m))}
+
+
+def kmer_count(k, length, stride=1):
+    """Whole windows of k characters at multiples of `stride` in a sequence of `length` characters (0 below k)."""
+    km = capi.Kmer(int(k), int(stride))
+    n = int(_lib.bsq_kmer_count(ctypes.byref(km), int(length)))
+    if n < 0:
+        raise ValueError("k and stride must be >= 1")
+    return n
+
+
+def kmer_padlen(tok, k, max_seq_len, stride=1):
+    """The padlen that holds every sequence of up to `max_seq_len` characters: its windows + BOS + EOS."""
+    _kmer(tok, k, stride)
+    return kmer_count(k, max_seq_len, stride) + int(tok.includes_bos()) + int(tok.includes_eos())
+
+
+def kmer_max_length(tok, k, padlen, stride=1):
+    """The longest sequence whose windows all fit into `padlen` positions (a longer one is clamped by the kernels)."""
+    room = int(padlen) - int(tok.includes_bos()) - int(tok.includes_eos())
+    return max(room, 0) * int(stride) + int(k) - 1
+
+
+def kmer_decode(tok, k, ids):
+    """The words of k-mer ids, as a list of str (nested like `ids`): the first byte of each class for a plain id, `<UNK>`, `<BOS>`,
+    `<EOS>`, `<PAD>` for the specials.  Host code over a numpy / CPU array or a list."""
+    desc, km = _kmer(tok, k)
+    sp = kmer_special_ids(tok, k)
+    lut = np.frombuffer(bytes(desc.lut), dtype=np.int8)
+    letters = [chr(int(np.flatnonzero(lut == c)[0])) for c in range(desc.nchars)]
+    names = {sp["unk"]: "<UNK>", sp["pad"]: "<PAD>"}
+    if sp["bos"] >= 0:
+        names[sp["bos"]] = "<BOS>"
+    if sp["eos"] >= 0:
+        names[sp["eos"]] = "<EOS>"
+    arr = np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids)
+    V = desc.nchars ** km.k
+
+    def word(v):
+        v = int(v)
+        if v in names:
+            return names[v]
+        if not 0 <= v < V:
+            raise ValueError("%d is not an id of this vocabulary" % v)
+        out = []
+        for _ in range(km.k):
+            v, r = divmod(v, desc.nchars)
+            out.append(letters[r])
+        return "".join(reversed(out))
+
+    def walk(a):
+        return [walk(x) for x in a] if a.ndim > 1 else [word(v) for v in a]
+
+    return word(arr) if arr.ndim == 0 else walk(arr)
+
+
+def kmer_kernel_name(tok, k, B, padlen, destchar="q", batch_first=True, *, stride=1):
+    """The kernel `kmer_tokenize_packed` takes for this shape (host only: profiling labels, tests)."""
+    desc, km = _kmer(tok, k, stride)
+    dt, _ = _dtype(desc, km, destchar)
+    return _lib.bsq_kmer_kernel_name(ctypes.byref(desc), ctypes.byref(km), int(B), int(padlen), int(bool(batch_first)), dt).decode()
+
+
+def kmer_tokenize_host(tok, chars, offsets, k, padlen, destchar="q", batch_first=True, *, stride=1):
+    """The library's CPU twin (`bsq_kmer_tokenize_host`, the same id code as the kernels) on numpy arrays: a numpy matrix."""
+    desc, km = _kmer(tok, k, stride)
+    dt, _ = _dtype(desc, km, destchar)
+    if int(padlen) <= 0:
+        raise ValueError("padlen must be positive")
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    B = offsets.size - 1
+    out = np.empty((B, int(padlen)) if batch_first else (int(padlen), B), dtype=_NUMPY[dt])
+    keep = chars if chars.size else np.zeros(16, np.uint8)
+    capi.check(_lib.bsq_kmer_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
+                                           ctypes.byref(km), dt, out.ctypes.data))
+    return out
+
+
+def kmer_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch_first=True, *, stride=1, validate=True):
+    """k-mer ids of a packed batch on the device (chars uint8[total], offsets int64[B + 1]): a device tensor (B, padlen) when
+    batch_first else (padlen, B), on torch's current stream, one launch.
+
+    Row = [BOS] id_0 .. id_{n-1} [EOS] PAD ..., window j = characters [j * stride, j * stride + k).  validate: the over-long-sequence
+    check of `tokenize_packed` with the k-mer bound -- a sequence longer than `kmer_max_length(tok, k, padlen, stride)` raises the
+    library's over-long error instead of being clamped; malformed offsets raise too."""
+    import torch
+    desc, km = _kmer(tok, k, stride)
+    dt, tdt = _dtype(desc, km, destchar)
+    padlen = int(padlen)
+    if padlen <= 0:
+        raise ValueError("padlen must be positive")
+    B = capi.packed_on_device(chars, offsets, "kmer_tokenize_packed works on packed batches resident on the device (chars, offsets tensors)")
+    if validate and B > 0:
+        bound = kmer_max_length(tok, k, padlen, stride)
+        bad = ctypes.c_int64(-1)
+        with capi.launching(chars.device) as stream:
+            st = _lib.bsq_validate_packed_device(offsets.data_ptr(), B, bound, 0, 0, chars.numel(), ctypes.byref(bad), stream)
+        if st == capi.ERR_SEQ_TOO_LONG:
+            i = int(bad.value)
+            raise RuntimeError("seq len %d holds more than padlen %d k-mers (k %d, stride %d, bos + eos %d): at most %d characters fit"
+                               % (int(offsets[i + 1] - offsets[i]), padlen, km.k, km.stride, desc.bos + desc.eos, bound))
+        capi.check(st)
+    out = torch.empty((B, padlen) if batch_first else (padlen, B), dtype=tdt, device=chars.device)
+    if B > 0:
+        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_kmer_tokenize_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, padlen, int(bool(batch_first)),
+                                                     ctypes.byref(km), dt, out.data_ptr(), stream))
+    return out
+
+
+__all__ = ["kmer_tokenize_packed", "kmer_tokenize_host", "kmer_vocab_size", "kmer_special_ids", "kmer_count", "kmer_padlen",
+           "kmer_max_length", "kmer_decode", "kmer_kernel_name"]

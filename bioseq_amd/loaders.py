@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import blosum, masking, views
+from . import blosum, kmers, masking, views
 from .flatfile import FlatFile
 
 
@@ -57,12 +57,18 @@ class FlatFileDataset(torch.utils.data.Dataset):
     then the augmentation, then the mask and the encode.  Their draw is keyed like the masks, by a counter of its own (enabling crop
     changes no mask): a fresh key per get_batch / __getitems__ / __getitem__ / fetch call and per `batches()` epoch, a row keyed by
     its index in the epoch's order.
+
+    kmer=k (keyword; off by default; token rows only): a token is a window of k characters, `kmer_stride` characters apart
+    (kmers.kmer_tokenize_packed: 1 = overlapping, k = non-overlapping), so max_seq_len = kmers.kmer_padlen of the longest stored
+    sequence, or of `crop` when cropping.  It composes with crop, revcomp_frac, shuffle, group and prefetch -- they all hand the encode
+    a packed batch.  With cnn=True, augment > 0 or masked=True it raises ValueError: a k-mer one-hot and protein mutations under
+    k-mers are not provided, and masking overlapping windows needs span masks, which this draw is not.
     """
 
     NUCLEOTIDE_KEYS = ("DNA", "DNA4", "DNA5")
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
-                 crop=None, crop_mode="random", revcomp_frac=0.0):
+                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -98,6 +104,14 @@ class FlatFileDataset(torch.utils.data.Dataset):
         if self.crop is not None:  # every view fits: nothing to validate
             self.max_seq_len = self.maxseqlen = self.crop + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
             self._trusted_lengths = True
+        self.kmer = None if kmer is None else int(kmer)
+        self.kmer_stride = int(kmer_stride)
+        if self.kmer is not None:
+            if cnn or augment or masked:
+                raise ValueError("kmer= gives token rows of the plain batch: it cannot be combined with cnn=True, augment > 0 or masked=True")
+            # (k, stride and nchars ** k are checked here); at least one position, so that a store of sequences shorter than k still encodes
+            longest = self.crop if self.crop is not None else ff.maxseqlen
+            self.max_seq_len = self.maxseqlen = max(1, kmers.kmer_padlen(tokenizer, self.kmer, longest, self.kmer_stride))
 
     def __len__(self):
         return self.ff.nseqs()
@@ -168,6 +182,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
         one-call entry `blosum.augment_tokenize_packed` (one launch for int8 rows; the entry runs the two launches for the
         other types); the one-hot form augments, then encodes."""
         trusted = self._trusted_lengths
+        if self.kmer is not None:
+            return kmers.kmer_tokenize_packed(self.tokenizer, chars, offs, self.kmer, self.max_seq_len, self.token_dtype, True,
+                                              stride=self.kmer_stride, validate=not trusted)
         if self.augment:
             self._calls += 1
             seed = self._seed + self._calls

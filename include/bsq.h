@@ -33,7 +33,9 @@ extern "C" {
 #define BSQ_ABI_VERSION 7 /* 7 (round 6): bsq_tokenize_device_multi, bsq_augment_device_multi, bsq_augment_tokenize_device_multi, bsq_enable_peer_access, bsq_tokenize_kernel_name; nothing removed.
                            * Added since, without a version bump (nothing changed or removed): bsq_mlm, bsq_mlm_tokenize_device,
                            * bsq_random_mask_device, bsq_random_mask_host, bsq_onehot_device_multi, bsq_onehot_multi_plan,
-                           * bsq_crop_packed_device, bsq_crop_plan_host, bsq_views_packed_device, bsq_complement_table; nothing removed */
+                           * bsq_crop_packed_device, bsq_crop_plan_host, bsq_views_packed_device, bsq_complement_table, bsq_kmer, bsq_kmer_vocab_size,
+                           * bsq_kmer_unk_id, bsq_kmer_bos_id, bsq_kmer_eos_id, bsq_kmer_pad_id, bsq_kmer_count, bsq_kmer_tokenize_device,
+                           * bsq_kmer_tokenize_host, bsq_kmer_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -390,6 +392,57 @@ bsq_status bsq_views_packed_device(const uint8_t *chars, const int64_t *offsets,
                                    int64_t *out_offsets, int64_t *status_dev, void *hip_stream);
 /* out[c] <- comp(c) for every byte c: the library's own complement table. */
 bsq_status bsq_complement_table(uint8_t out[256]);
+
+/* ---- k-mer ids of a packed batch: the vocabulary DNA language models are trained on -- overlapping 3- to 6-mers (stride 1),
+ * non-overlapping 6-mers (stride k), and the same over reduced protein alphabets -- in ONE launch instead of tokens + unfold +
+ * weighted sum + where in the framework.
+ *
+ * THE IDS.  For a tokenizer description d with A = d->nchars classes, a word length k >= 1 and a stride s >= 1:
+ *     V        = A^k                                    plain k-mer ids are 0 .. V - 1
+ *     id(w)    = sum_{i<k} lut[w[i]] * A^(k-1-i)         first character most significant (lexicographic order)
+ *     UNK      = V                                      a window with ANY unmapped character (lut < 0: N under DNA4, '*', bytes >= 0x80)
+ *     BOS      = V + 1                  (if d->bos)     the order of the single-residue specials, shifted behind UNK
+ *     EOS      = V + 1 + bos            (if d->eos)
+ *     PAD      = V + 1 + bos + eos      (stored at pad positions when d->padchar, else 0 is stored, as bsq_tokenize_device does)
+ *     vocab    = V + 1 + bos + eos + padchar
+ *     n_tok(L) = 0 if L < k else (L - k) / s + 1        window j covers characters [j*s, j*s + k); a tail shorter than k is dropped
+ *     row      = [BOS] id_0 .. id_{n-1} [EOS] PAD ...   n = min(n_tok(L), max(P - bos - eos, 0)): over-long rows are clamped, memory-safe
+ * (a row is cut at P positions: P = 1 with BOS and EOS holds the BOS alone).  Output (B, P) when batch_first else (P, B), C-contiguous,
+ * every element written exactly once; all six bsq_dtypes, values converted as bsq_tokenize_device converts tokens.
+ *
+ * Limits, checked before anything is launched: 1 <= k <= 16, s >= 1, A >= 1, A^k <= 2^24 (every id is exact in f32: DNA4 up to
+ * k = 12, AMINO20 up to k = 5) -- otherwise BSQ_ERR_INVALID_ARG; BSQ_I8 needs vocab <= 128, BSQ_I16 vocab <= 32768 -- otherwise
+ * BSQ_ERR_DTYPE.  A row fits (nothing is clamped) iff L <= (P - bos - eos) * s + k - 1: for the reference-style length check call
+ * bsq_validate_packed_device with that bound as its P and bos = eos = 0.
+ *
+ * Known answers (DNA4, k = 3, s = 1, P = 8, no flags): ACGTAC -> 6 27 44 49 0 0 0 0; ACGNACGT -> 6 64 64 64 6 27 0 0; TTTTTTT -> 63 63 63 63 63 0 0 0;
+ * with BOS, EOS and PAD: ACGTAC -> 65 6 27 44 49 66 67 67.
+ *
+ * Conventions of the neighbouring entry points: stream-ordered, never synchronises, B == 0 is BSQ_OK with nothing launched, null /
+ * negative arguments BSQ_ERR_INVALID_ARG.  Kernels: (B, P) with stride 1 -> k_kmer_bp<s1> (a lane owns 16 positions of a row: two
+ * 16-byte character loads, a rolling id, stores in whole 1-KiB runs), (B, P) with stride k, 2 <= k <= 8 -> k_kmer_bp<sk>, everything
+ * else ((P, B), other strides, stride k > 8) -> k_kmer_generic (one thread per element: correct, not tuned). */
+typedef struct bsq_kmer {
+    int32_t k;      /* characters per token, 1 .. 16 */
+    int32_t stride; /* characters between the starts of two consecutive windows, >= 1 (1: overlapping, k: non-overlapping) */
+} bsq_kmer;
+/* vocab / the ids above; a negative bsq_status (-BSQ_ERR_INVALID_ARG) for a null pointer, a bad k or A^k > 2^24.  bos / eos: -1 where
+ * the flag is off; pad: the id, whether or not padchar is set (as bsq_pad_id). */
+int64_t bsq_kmer_vocab_size(const bsq_desc *d, const bsq_kmer *km);
+int64_t bsq_kmer_unk_id(const bsq_desc *d, const bsq_kmer *km);
+int64_t bsq_kmer_bos_id(const bsq_desc *d, const bsq_kmer *km);
+int64_t bsq_kmer_eos_id(const bsq_desc *d, const bsq_kmer *km);
+int64_t bsq_kmer_pad_id(const bsq_desc *d, const bsq_kmer *km);
+/* n_tok(L) (0 for L < k); a negative bsq_status for a null km, k < 1 or stride < 1. */
+int64_t bsq_kmer_count(const bsq_kmer *km, int64_t L);
+bsq_status bsq_kmer_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                    int32_t batch_first, const bsq_kmer *km, bsq_dtype t, void *out, void *hip_stream);
+/* CPU twin on host buffers (the same id code; no device is needed). */
+bsq_status bsq_kmer_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                  int32_t batch_first, const bsq_kmer *km, bsq_dtype t, void *out);
+/* Host only: the kernel bsq_kmer_tokenize_device takes for this shape ("k_kmer_bp<s1>", "k_kmer_bp<sk>", "k_kmer_generic"), from the
+ * predicate the launch uses; "" for arguments the device call refuses. */
+const char *bsq_kmer_kernel_name(const bsq_desc *d, const bsq_kmer *km, int64_t B, int64_t P, int32_t batch_first, bsq_dtype t);
 
 /* ---- FASTA / FASTQ (plain or gzip) -> FlatFile on the host: replaces FlatFile::make (fxstats.cpp:33-64) and getlens /
  * getstats (:12-23, :202-219).  Same record grammar as the reference's kseq loop (bsq_fastx.cpp lists it), but streaming:

@@ -1,0 +1,351 @@
+"""CPU: the k-mer ids (include/bsq.h, bsq_kmer) -- the library's host twin bsq_kmer_tokenize_host against the numpy twin
+(tests/kmer_twin.py) byte for byte, the known answers of the specification, the tie to the single-residue tokens, the argument rules,
+the id helpers and the Python helpers of bioseq_amd.kmers.  No device is needed."""
+import ctypes
+import itertools
+
+import numpy as np
+import pytest
+
+import kmer_twin as twin
+
+SEQS = [b"ACGTAC", b"ACGNACGT", b"AC", b"", b"TTTTTTT"]
+FLAGS = list(itertools.product((0, 1), repeat=3))  # (bos, eos, padchar)
+PADLENS = (1, 15, 16, 17, 100, 1000)
+GUARD = 64
+
+
+def _lib():
+    from bioseq_amd import capi
+    return capi, capi.load()
+
+
+def _pack(seqs, lead=b"", tail=b""):
+    chars = np.frombuffer(lead + b"".join(seqs) + tail, dtype=np.uint8).copy()
+    offs = np.zeros(len(seqs) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in seqs], out=offs[1:])
+    return chars, offs + len(lead)
+
+
+def _lut(key):
+    capi, L = _lib()
+    lut = (ctypes.c_int8 * 256)()
+    n = ctypes.c_int32(0)
+    assert L.bsq_lut_get(key.encode(), lut, ctypes.byref(n)) == capi.OK
+    return np.array(lut, dtype=np.int8), n.value
+
+
+def _host(key, flags, chars, offs, k, s, P, dt, batch_first=True, B=None, first=0):
+    """bsq_kmer_tokenize_host on rows [first, first + B) into a buffer with guard bytes on both sides: (status, matrix, guards intact)."""
+    capi, L = _lib()
+    bos, eos, pad = flags
+    d = capi.make_desc(key, eos=eos, bos=bos, padchar=pad)
+    km = capi.Kmer(k, s)
+    B = len(offs) - 1 - first if B is None else B
+    np_t = twin.NP_DTYPES[dt]
+    nbytes = B * P * np.dtype(np_t).itemsize
+    raw = np.full(nbytes + 2 * GUARD, 0xAB, dtype=np.uint8)
+    st = L.bsq_kmer_tokenize_host(ctypes.byref(d), chars.ctypes.data, offs[first:].ctypes.data, B, P, int(batch_first), ctypes.byref(km), dt,
+                                  raw.ctypes.data + GUARD)
+    intact = bool((raw[:GUARD] == 0xAB).all() and (raw[GUARD + nbytes:] == 0xAB).all())
+    out = raw[GUARD:GUARD + nbytes].view(np_t).reshape((B, P) if batch_first else (P, B))
+    return st, out, intact
+
+
+def test_new_symbols_are_declared_and_exported():
+    capi, L = _lib()
+    names = capi.declared_symbols(capi.HEADER_PATH)
+    for n in ("bsq_kmer_vocab_size", "bsq_kmer_unk_id", "bsq_kmer_bos_id", "bsq_kmer_eos_id", "bsq_kmer_pad_id", "bsq_kmer_count",
+              "bsq_kmer_tokenize_device", "bsq_kmer_tokenize_host", "bsq_kmer_kernel_name"):
+        assert n in names and hasattr(L, n), n
+    assert "typedef struct bsq_kmer" in open(capi.HEADER_PATH).read()
+    assert L.bsq_abi_version() == 7
+    import bioseq_amd
+    assert bioseq_amd.kmers.kmer_tokenize_packed and "kmers" in bioseq_amd.__all__
+
+
+KNOWN = [
+    (3, 1, 8, (0, 0, 0), ["6 27 44 49 0 0 0 0", "6 64 64 64 6 27 0 0", "0 0 0 0 0 0 0 0", "0 0 0 0 0 0 0 0", "63 63 63 63 63 0 0 0"]),
+    (3, 1, 8, (1, 1, 1), ["65 6 27 44 49 66 67 67", "65 6 64 64 64 6 27 66", "65 66 67 67 67 67 67 67", "65 66 67 67 67 67 67 67",
+                          "65 63 63 63 63 63 66 67"]),
+    (3, 3, 4, (1, 1, 1), ["65 6 49 66", "65 6 64 66", "65 66 67 67", "65 66 67 67", "65 63 63 66"]),
+    (2, 2, 5, (0, 1, 1), ["1 11 1 17 18", "1 16 1 11 17", "1 17 18 18 18", "17 18 18 18 18", "15 15 15 17 18"]),
+]
+
+
+@pytest.mark.parametrize("k, s, P, flags, rows", KNOWN)
+def test_known_answers_of_the_specification(k, s, P, flags, rows):
+    capi, _ = _lib()
+    want = np.array([[int(x) for x in r.split()] for r in rows], dtype=np.int64)
+    chars, offs = _pack(SEQS)
+    st, got, intact = _host("DNA4", flags, chars, offs, k, s, P, capi.U64)
+    assert st == capi.OK and intact
+    assert np.array_equal(got.astype(np.int64), want), got
+    lut, A = _lut("DNA4")
+    assert np.array_equal(twin.rows(lut, A, chars, offs, k, s, P, *flags), want)
+    assert np.array_equal(twin.rows_fast(lut, A, chars, offs, k, s, P, *flags), want)
+
+
+def _random_batch(rng, lut, k, dirty=True):
+    """Lengths 0, < k, == k, random ones; characters mostly mapped, with runs of unmapped bytes and bytes >= 0x80 when dirty."""
+    mapped = np.flatnonzero(lut >= 0).astype(np.uint8)
+    unmapped = np.flatnonzero(lut < 0).astype(np.uint8)
+    lens = [0, max(k - 1, 0), k, k + 1, 60] + [int(x) for x in rng.integers(0, 70, 5)]
+    seqs = []
+    for n in lens:
+        s = mapped[rng.integers(0, mapped.size, n)]
+        if dirty and unmapped.size and n:
+            for _ in range(int(rng.integers(0, 3))):
+                a = int(rng.integers(0, n))
+                s[a:a + int(rng.integers(1, 4))] = unmapped[rng.integers(0, unmapped.size)]
+            if rng.integers(0, 2):
+                s[int(rng.integers(0, n))] = 0x80 + int(rng.integers(0, 128)) if lut[0x80:].max() < 0 else s[0]
+        seqs.append(bytes(s))
+    order = rng.permutation(len(seqs))
+    return [seqs[i] for i in order]
+
+
+ALPHABETS = ["DNA4", "DNA5", "AMINO20", "SEB8", "PURPYR", "BYTES"]
+CASES = [(key, k) for key in ALPHABETS for k in (1, 2, 3, 4, 5, 6, 7, 8, 12)
+         if _lut(key)[1] ** k <= 2 ** 24 and (k <= 8 or key == "DNA4")]
+
+
+@pytest.mark.parametrize("key, k", CASES)
+def test_host_twin_equals_numpy_twin(key, k):
+    capi, _ = _lib()
+    lut, A = _lut(key)
+    rng = np.random.default_rng(1000 * k + len(key) + A)
+    seqs = _random_batch(rng, lut, k)
+    # the batch sits inside a larger buffer: offsets[0] = 5, junk before and after
+    chars, offs = _pack(seqs, lead=b"\xffGGGG", tail=b"TTTT\xff")
+    n = 0
+    for s in sorted({1, k, 2, 5, k + 3}):
+        for flags in FLAGS:
+            vocab = twin.specials(A, k, *flags)["vocab"]
+            for P in PADLENS:
+                want = twin.rows(lut, A, chars, offs, k, s, P, *flags)
+                for dt in range(6):
+                    for bf in (True, False):
+                        st, got, intact = _host(key, flags, chars, offs, k, s, P, dt, bf)
+                        if (dt == capi.I8 and vocab > 128) or (dt == capi.I16 and vocab > 32768):
+                            assert st == capi.ERR_DTYPE and intact and (got.view(np.uint8) == 0xAB).all()
+                            continue
+                        exp = np.ascontiguousarray(want if bf else want.T).astype(twin.NP_DTYPES[dt])
+                        assert st == capi.OK and intact, (s, flags, P, dt, bf)
+                        assert got.tobytes() == exp.tobytes(), (s, flags, P, dt, bf)
+                        n += 1
+    assert n > 0
+    # P = 15 clamps the longer rows (over-long rows are cut, memory-safe) and every row holds at most P - bos - eos ids
+    body = twin.rows(lut, A, chars, offs, k, 1, 15, 1, 1, 1)
+    sp = twin.specials(A, k, 1, 1, 1)
+    assert ((body[:, 1:-1] <= sp["unk"]) | (body[:, 1:-1] >= sp["eos"])).all() and (body[:, 0] == sp["bos"]).all()
+    assert any(len(q) - k + 1 > 13 for q in seqs) and (body[:, -1] >= sp["eos"]).all()
+
+
+@pytest.mark.parametrize("key", ["DNA4", "AMINO20", "SEB8"])
+def test_vectorised_twin_equals_the_plain_twin(key):
+    capi, _ = _lib()
+    lut, A = _lut(key)
+    rng = np.random.default_rng(7)
+    k = 3
+    chars, offs = _pack(_random_batch(rng, lut, k), lead=b"AC")
+    for s, flags, P in itertools.product((1, 3, 2), FLAGS, (1, 2, 16, 40, 100)):
+        a, b = twin.rows(lut, A, chars, offs, k, s, P, *flags), twin.rows_fast(lut, A, chars, offs, k, s, P, *flags)
+        assert np.array_equal(a, b), (s, flags, P)
+        st, got, _ = _host(key, flags, chars, offs, k, s, P, capi.I32)
+        assert st == capi.OK and np.array_equal(got, b)
+
+
+@pytest.mark.parametrize("key", ["DNA4", "DNA5", "AMINO20", "SEB8"])
+def test_one_mers_are_the_single_residue_tokens(key):
+    """k = 1, stride 1, no flags, mapped characters only: the ids are the existing token semantics -- the alphabet table looked up per
+    character, zeros behind the sequence (the restatement the other host tests use)."""
+    capi, _ = _lib()
+    lut, A = _lut(key)
+    rng = np.random.default_rng(3)
+    seqs = _random_batch(rng, lut, 1, dirty=False)
+    chars, offs = _pack(seqs)
+    P = 80
+    want = np.zeros((len(seqs), P), dtype=np.int64)
+    for b, q in enumerate(seqs):
+        want[b, :len(q)] = lut[np.frombuffer(q, dtype=np.uint8)]
+    st, got, intact = _host(key, (0, 0, 0), chars, offs, 1, 1, P, capi.I8)
+    assert st == capi.OK and intact and np.array_equal(got.astype(np.int64), want)
+
+
+def test_a_sub_batch_equals_its_slice_of_the_whole():
+    capi, _ = _lib()
+    lut, _ = _lut("DNA5")
+    chars, offs = _pack(_random_batch(np.random.default_rng(11), lut, 4), lead=b"NNN")
+    for s, P, flags in ((1, 33, (1, 1, 1)), (4, 16, (0, 1, 0)), (3, 20, (1, 0, 1))):
+        _, whole, _ = _host("DNA5", flags, chars, offs, 4, s, P, capi.I16)
+        for b0, b1 in ((0, 3), (3, 10), (4, 5), (9, 10)):
+            st, part, intact = _host("DNA5", flags, chars, offs, 4, s, P, capi.I16, B=b1 - b0, first=b0)
+            assert st == capi.OK and intact and np.array_equal(part, whole[b0:b1]), (s, P, b0, b1)
+
+
+def test_argument_rules_nothing_written():
+    capi, L = _lib()
+    chars, offs = _pack(SEQS)
+    bad_shape = [("DNA4", 0, 1), ("DNA4", 17, 1), ("DNA4", -1, 1), ("DNA4", 13, 1), ("AMINO20", 6, 1), ("BYTES", 4, 1), ("DNA4", 3, 0),
+                 ("DNA4", 3, -2)]
+    for key, k, s in bad_shape:
+        st, got, intact = _host(key, (0, 0, 0), chars, offs, k, s, 8, capi.U64)
+        assert st == capi.ERR_INVALID_ARG and intact and (got.view(np.uint8) == 0xAB).all(), (key, k, s)
+        assert L.bsq_last_error() != b""
+        d, km = capi.make_desc(key), capi.Kmer(k, s)
+        assert L.bsq_kmer_kernel_name(ctypes.byref(d), ctypes.byref(km), 5, 8, 1, capi.U64) == b""
+        # the device call refuses the same arguments before it touches a device (host pointers are never read)
+        out = np.full(64, 0xAB, dtype=np.uint8)
+        assert L.bsq_kmer_tokenize_device(ctypes.byref(d), chars.ctypes.data, offs.ctypes.data, 5, 8, 1, ctypes.byref(km), capi.I8,
+                                          out.ctypes.data, None) == capi.ERR_INVALID_ARG
+        assert (out == 0xAB).all()
+    # the largest plain vocabularies that are allowed
+    for key, k in (("DNA4", 12), ("AMINO20", 5), ("BYTES", 3), ("PURPYR", 16)):
+        st, _, intact = _host(key, (1, 1, 1), chars, offs, k, 1, 8, capi.F32)
+        assert st == capi.OK and intact, (key, k)
+    # element types: int8 holds 128 ids, int16 32768
+    for key, flags, k, dt, want in (("PURPYR", (0, 0, 0), 7, capi.I8, capi.ERR_DTYPE),      # vocab 129
+                                    ("PURPYR", (1, 1, 1), 6, capi.I8, capi.OK),             # vocab 68
+                                    ("DNA4", (0, 0, 0), 3, capi.I8, capi.OK),               # vocab 65
+                                    ("PURPYR", (0, 0, 0), 15, capi.I16, capi.ERR_DTYPE),    # vocab 32769
+                                    ("DNA4", (1, 1, 1), 7, capi.I16, capi.OK),              # vocab 16388
+                                    ("DNA4", (0, 0, 0), 8, capi.I16, capi.ERR_DTYPE),
+                                    ("DNA4", (0, 0, 0), 8, capi.I32, capi.OK),
+                                    ("DNA4", (0, 0, 0), 3, 6, capi.ERR_DTYPE), ("DNA4", (0, 0, 0), 3, -1, capi.ERR_DTYPE)):
+        capi_d = capi.make_desc(key, eos=flags[1], bos=flags[0], padchar=flags[2])
+        km = capi.Kmer(k, 1)
+        raw = np.full(5 * 8 * 8 + 2 * GUARD, 0xAB, dtype=np.uint8)
+        st = L.bsq_kmer_tokenize_host(ctypes.byref(capi_d), chars.ctypes.data, offs.ctypes.data, 5, 8, 1, ctypes.byref(km), dt,
+                                      raw.ctypes.data + GUARD)
+        assert st == want, (key, flags, k, dt)
+        if want != capi.OK:
+            assert (raw == 0xAB).all()
+    # null pointers, negative sizes
+    d, km = capi.make_desc("DNA4"), capi.Kmer(3, 1)
+    out = np.full(5 * 8, 0xAB, dtype=np.uint8)
+    args = dict(d=ctypes.byref(d), chars=chars.ctypes.data, offs=offs.ctypes.data, B=5, P=8, km=ctypes.byref(km), out=out.ctypes.data)
+
+    def call(fn_device=False, **kw):
+        a = dict(args, **kw)
+        if fn_device:
+            return L.bsq_kmer_tokenize_device(a["d"], a["chars"], a["offs"], a["B"], a["P"], 1, a["km"], capi.I8, a["out"], None)
+        return L.bsq_kmer_tokenize_host(a["d"], a["chars"], a["offs"], a["B"], a["P"], 1, a["km"], capi.I8, a["out"])
+
+    for dev in (False, True):
+        for kw in ({"d": None}, {"km": None}, {"chars": None}, {"offs": None}, {"out": None}, {"B": -1}, {"P": 0}, {"P": -3}):
+            assert call(dev, **kw) == capi.ERR_INVALID_ARG, (dev, kw)
+        assert (out == 0xAB).all()
+        assert call(dev, B=0) == capi.OK and call(dev, B=0, chars=None, offs=None, out=None) == capi.OK  # nothing to do, nothing launched
+        assert (out == 0xAB).all()
+    if L.bsq_device_count() == 0:  # the device call alone needs a device
+        assert call(True) == capi.ERR_NO_DEVICE
+    assert call(False) == capi.OK
+
+
+def test_id_helpers_follow_the_formulas():
+    capi, L = _lib()
+    for key, k, flags in itertools.product(("DNA4", "DNA5", "AMINO20", "PURPYR"), (1, 2, 3, 5), FLAGS):
+        bos, eos, pad = flags
+        _, A = _lut(key)
+        d, km = capi.make_desc(key, eos=eos, bos=bos, padchar=pad), capi.Kmer(k, 1)
+        dp, kp = ctypes.byref(d), ctypes.byref(km)
+        V = A ** k
+        assert L.bsq_kmer_vocab_size(dp, kp) == V + 1 + bos + eos + pad
+        assert L.bsq_kmer_unk_id(dp, kp) == V
+        assert L.bsq_kmer_bos_id(dp, kp) == (V + 1 if bos else -1)
+        assert L.bsq_kmer_eos_id(dp, kp) == (V + 1 + bos if eos else -1)
+        assert L.bsq_kmer_pad_id(dp, kp) == V + 1 + bos + eos
+        sp = twin.specials(A, k, *flags)
+        assert (sp["unk"], sp["bos"], sp["eos"], sp["pad"], sp["vocab"]) == (V, L.bsq_kmer_bos_id(dp, kp), L.bsq_kmer_eos_id(dp, kp),
+                                                                            L.bsq_kmer_pad_id(dp, kp), L.bsq_kmer_vocab_size(dp, kp))
+    d = capi.make_desc("DNA4")
+    for bad in (capi.Kmer(0, 1), capi.Kmer(17, 1), capi.Kmer(13, 1)):
+        for fn in (L.bsq_kmer_vocab_size, L.bsq_kmer_unk_id, L.bsq_kmer_bos_id, L.bsq_kmer_eos_id, L.bsq_kmer_pad_id):
+            assert fn(ctypes.byref(d), ctypes.byref(bad)) == -capi.ERR_INVALID_ARG
+    assert L.bsq_kmer_vocab_size(None, ctypes.byref(capi.Kmer(3, 1))) == -capi.ERR_INVALID_ARG
+    assert L.bsq_kmer_vocab_size(ctypes.byref(d), None) == -capi.ERR_INVALID_ARG
+    for k, s, Ls in itertools.product((1, 2, 3, 6, 7), (1, 2, 3, 6, 8), range(0, 70)):
+        want = 0 if Ls < k else (Ls - k) // s + 1
+        assert L.bsq_kmer_count(ctypes.byref(capi.Kmer(k, s)), Ls) == want == twin.count(Ls, k, s)
+        # a row fits iff L <= room * s + k - 1 (the bound the Python layer validates with)
+        for room in (0, 1, 5):
+            assert (want <= room) == (Ls <= room * s + k - 1)
+    assert L.bsq_kmer_count(ctypes.byref(capi.Kmer(3, 1)), -5) == 0
+    assert L.bsq_kmer_count(ctypes.byref(capi.Kmer(0, 1)), 5) == -capi.ERR_INVALID_ARG
+    assert L.bsq_kmer_count(ctypes.byref(capi.Kmer(3, 0)), 5) == -capi.ERR_INVALID_ARG
+    assert L.bsq_kmer_count(None, 5) == -capi.ERR_INVALID_ARG
+
+
+def test_kernel_name_for_one_shape_per_kernel():
+    capi, L = _lib()
+    d = capi.make_desc("DNA4", 1, 1, 1)
+    name = lambda k, s, B, P, bf, t: L.bsq_kmer_kernel_name(ctypes.byref(d), ctypes.byref(capi.Kmer(k, s)), B, P, bf, t)
+    assert name(6, 1, 262144, 512, 1, capi.I16) == b"k_kmer_bp<s1>"
+    assert name(1, 1, 100, 17, 1, capi.I8) == b"k_kmer_bp<s1>"      # (stride 1 == k: the rolling form)
+    assert name(6, 6, 262144, 87, 1, capi.U64) == b"k_kmer_bp<sk>"
+    assert name(8, 8, 1000, 64, 1, capi.I32) == b"k_kmer_bp<sk>"
+    assert name(9, 9, 1000, 64, 1, capi.I32) == b"k_kmer_generic"   # (a window of more than 8 bytes)
+    assert name(6, 2, 1000, 64, 1, capi.I16) == b"k_kmer_generic"
+    assert name(6, 1, 1000, 64, 0, capi.I16) == b"k_kmer_generic"   # (P, B)
+    assert name(6, 6, 1000, 64, 0, capi.I16) == b"k_kmer_generic"
+    assert name(6, 1, 4, 2 ** 24 + 16, 1, capi.I16) == b"k_kmer_generic"
+    assert name(6, 1, 1000, 64, 1, capi.I8) == b""                  # (vocab 4100 does not fit int8)
+
+
+def test_python_helpers_round_trip_on_the_known_answers():
+    import bioseq_amd
+    from bioseq_amd import kmers
+    tok = bioseq_amd.Tokenizer("DNA4", True, True, True)  # (eos, bos, padchar)
+    plain = bioseq_amd.Tokenizer("DNA4")
+    assert kmers.kmer_vocab_size(tok, 3) == 68 and kmers.kmer_vocab_size(plain, 3) == 65
+    assert kmers.kmer_special_ids(tok, 3) == {"unk": 64, "bos": 65, "eos": 66, "pad": 67}
+    assert kmers.kmer_special_ids(plain, 3) == {"unk": 64, "bos": -1, "eos": -1, "pad": 65}
+    assert kmers.kmer_padlen(tok, 3, 8) == 8 and kmers.kmer_padlen(tok, 3, 7, stride=3) == 4 and kmers.kmer_padlen(plain, 6, 512) == 507
+    assert kmers.kmer_padlen(plain, 6, 512, stride=6) == 85 and kmers.kmer_padlen(plain, 6, 3) == 0
+    assert kmers.kmer_count(3, 7, 3) == 2 and kmers.kmer_count(3, 2) == 0
+    assert kmers.kmer_max_length(tok, 3, 8) == 8 and kmers.kmer_max_length(tok, 3, 4, 3) == 8
+    chars, offs = _pack(SEQS)
+    got = kmers.kmer_tokenize_host(tok, chars, offs, 3, 8)
+    assert got.dtype == np.uint64 and got.shape == (5, 8)
+    assert got[0].tolist() == [65, 6, 27, 44, 49, 66, 67, 67]
+    assert kmers.kmer_decode(tok, 3, got[0]) == ["<BOS>", "ACG", "CGT", "GTA", "TAC", "<EOS>", "<PAD>", "<PAD>"]
+    assert kmers.kmer_decode(tok, 3, got[1])[:4] == ["<BOS>", "ACG", "<UNK>", "<UNK>"]
+    assert kmers.kmer_decode(tok, 3, 6) == "ACG" and kmers.kmer_decode(tok, 3, 64) == "<UNK>"
+    assert kmers.kmer_decode(plain, 2, [[1, 11], [15, 0]]) == [["AC", "GT"], ["TT", "AA"]]
+    # the whole plain vocabulary decodes to distinct words in lexicographic order, and encodes back to its ids
+    words = kmers.kmer_decode(plain, 3, np.arange(64))
+    assert words == sorted(words) and len(set(words)) == 64
+    c2, o2 = _pack([w.encode() for w in words])
+    assert kmers.kmer_tokenize_host(plain, c2, o2, 3, 1, "i")[:, 0].tolist() == list(range(64))
+    assert kmers.kmer_tokenize_host(tok, chars, offs, 3, 8, "h", batch_first=False).shape == (8, 5)
+    assert kmers.kmer_kernel_name(tok, 6, 1000, 512, "h") == "k_kmer_bp<s1>"
+    for bad in (dict(k=0), dict(k=17), dict(k=13), dict(k=3, stride=0)):
+        with pytest.raises(ValueError):
+            kmers.kmer_tokenize_host(tok, chars, offs, bad["k"], 8, stride=bad.get("stride", 1))
+    with pytest.raises(ValueError):
+        kmers.kmer_decode(tok, 3, [68])
+    with pytest.raises(ValueError):
+        kmers.kmer_tokenize_host(tok, chars, offs, 4, 8, "b")  # (260 ids do not fit int8; the 68 of k = 3 do)
+    assert kmers.kmer_tokenize_host(tok, chars, offs, 3, 8, "b").dtype == np.int8
+    with pytest.raises(ValueError):
+        kmers.kmer_tokenize_host(tok, chars, offs, 3, 0)
+
+
+def test_dataset_keywords_without_a_device(tmp_path):
+    import bioseq_amd
+    from bioseq_amd.flatfile import FlatFile, write_flatfile
+    from bioseq_amd.loaders import FlatFileDataset
+    ff = FlatFile(write_flatfile([b"ACGTACGTACGT", b"ACG", b""], str(tmp_path / "k.ff")))
+    tok = bioseq_amd.Tokenizer("DNA4", True, True, True)
+    for kw in ({"cnn": True}, {"augment": 1}, {"masked": True}):
+        with pytest.raises(ValueError):
+            FlatFileDataset(ff, tok, device="cpu", kmer=6, **kw)
+    for kw in ({"kmer": 0}, {"kmer": 13}, {"kmer": 3, "kmer_stride": 0}):
+        with pytest.raises(ValueError):
+            FlatFileDataset(ff, tok, device="cpu", **kw)
+    assert FlatFileDataset(ff, tok, device="cpu", kmer=6).max_seq_len == 7 + 2
+    assert FlatFileDataset(ff, tok, device="cpu", kmer=6, kmer_stride=6).max_seq_len == 2 + 2
+    assert FlatFileDataset(ff, tok, device="cpu", kmer=3, crop=8, revcomp_frac=0.5).max_seq_len == 6 + 2
+    assert FlatFileDataset(ff, bioseq_amd.Tokenizer("DNA4"), device="cpu", kmer=6, crop=4).max_seq_len == 1
+    assert FlatFileDataset(ff, tok, device="cpu").max_seq_len == 14  # (off by default)
