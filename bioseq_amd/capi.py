@@ -17,6 +17,7 @@ DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bsq_diag.h")
 I8, I16, I32, U64, F32, F64 = range(6)
 SPACE_HOST, SPACE_DEVICE = 0, 1
 CROP_RANDOM, CROP_HEAD, CROP_CENTER = range(3)
+PACK_STREAM, PACK_NEXTFIT = range(2)
 OK, ERR_INVALID_KEY, ERR_INVALID_ARG, ERR_DTYPE, ERR_SEQ_TOO_LONG, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = range(8)
 
 
@@ -141,6 +142,12 @@ def load():
         "bsq_kmer_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp, vp]),
         "bsq_kmer_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp]),
         "bsq_kmer_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(Kmer), i64, i64, i32, c_int]),
+        "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
+        "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
+        "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
+        "bsq_pack_tokenize_device": (i32, [dp, vp, vp, i64, vp, i64, i64, c_int, vp, vp, vp, vp]),
+        "bsq_pack_tokenize_host": (i32, [dp, vp, vp, i64, vp, i64, i64, c_int, vp, vp, vp]),
+        "bsq_pack_kernel_name": (ctypes.c_char_p, [dp, i64, i64, i64, c_int]),
         "bsq_blosum62_normrows": (i32, [vp]),
         "bsq_augment_device": (i32, [vp, vp, i64, i32, ctypes.c_double, ctypes.c_uint64, vp]),
         "bsq_augment_tokenize_device": (i32, [vp, vp, vp, i64, i64, i32, i32, vp, i32, ctypes.c_double, ctypes.c_uint64, vp]),

@@ -187,3 +187,14 @@ bsq_status tokenize_generic_block(const bsq_desc *d, const uint8_t *chars, const
                                   int32_t batch_first, bsq_dtype t, void *out, int64_t row_seqs, void *hip_stream);
 
 }  // namespace bsq_internal
+
+// bsq_pack_host.cpp: the argument rules of the packing family, shared by its device entry points (bsq_pack.hip) and its CPU twins
+namespace bsq_pack_host {
+constexpr int64_t kMaxP = int64_t(1) << 30;
+constexpr int64_t kMaxRows = int64_t(1) << 31;
+constexpr int64_t kMaxPositions = int64_t(1) << 40;  // rows * padlen of one encode: its grid of 4096-position blocks stays far inside 32 bits
+bsq_status check_plan(const int64_t *offsets, int64_t B, int64_t P, int32_t bos, int32_t eos, int32_t mode, int64_t max_rows,
+                      const int64_t *starts, const int64_t *n_rows);
+bsq_status check_encode(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts, int64_t rows,
+                        int64_t P, bsq_dtype t, const void *tokens);
+}  // namespace bsq_pack_host

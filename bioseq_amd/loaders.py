@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import blosum, kmers, masking, views
+from . import blosum, kmers, masking, packing, views
 from .flatfile import FlatFile
 
 
@@ -63,12 +63,21 @@ class FlatFileDataset(torch.utils.data.Dataset):
     sequence, or of `crop` when cropping.  It composes with crop, revcomp_frac, shuffle, group and prefetch -- they all hand the encode
     a packed batch.  With cnn=True, augment > 0 or masked=True it raises ValueError: a k-mer one-hot and protein mutations under
     k-mers are not provided, and masking overlapping windows needs span masks, which this draw is not.
+
+    pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
+    of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
+    (tokens, segment_ids, position_ids), each (rows, max_seq_len), rows being what the batch needs (one 8-byte read-back per batch:
+    the host waits for the batch's plan before it issues the encode, also under `prefetch`, where that wait falls into the issue of the
+    NEXT batch -- the encode still runs under the consumer's kernels, the host-side overlap of the issue is what is lost).
+    It composes with crop, revcomp_frac, shuffle and prefetch.  With cnn=True, augment > 0, masked=True, kmer= or group > 1 it raises
+    ValueError: a super-batch's row blocks are not the batches' own packings, and the mask draw is keyed by row and index in the
+    sequence, which a packed row is not.
     """
 
     NUCLEOTIDE_KEYS = ("DNA", "DNA4", "DNA5")
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
-                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1):
+                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -112,6 +121,13 @@ class FlatFileDataset(torch.utils.data.Dataset):
             # (k, stride and nchars ** k are checked here); at least one position, so that a store of sequences shorter than k still encodes
             longest = self.crop if self.crop is not None else ff.maxseqlen
             self.max_seq_len = self.maxseqlen = max(1, kmers.kmer_padlen(tokenizer, self.kmer, longest, self.kmer_stride))
+        self.pack = pack
+        if pack is not None:
+            if pack not in ("nextfit", "stream"):
+                raise ValueError("pack must be 'nextfit' or 'stream', got %r" % (pack,))
+            if cnn or augment or masked or kmer is not None:
+                raise ValueError("pack= gives packed token rows of the plain batch: it cannot be combined with cnn=True, augment > 0, "
+                                 "masked=True or kmer=")
 
     def __len__(self):
         return self.ff.nseqs()
@@ -182,6 +198,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
         one-call entry `blosum.augment_tokenize_packed` (one launch for int8 rows; the entry runs the two launches for the
         other types); the one-hot form augments, then encodes."""
         trusted = self._trusted_lengths
+        if self.pack is not None:
+            return tuple(packing.pack_tokenize_packed(self.tokenizer, chars, offs, self.max_seq_len, self.token_dtype, mode=self.pack,
+                                                      validate=not trusted)[:3])
         if self.kmer is not None:
             return kmers.kmer_tokenize_packed(self.tokenizer, chars, offs, self.kmer, self.max_seq_len, self.token_dtype, True,
                                               stride=self.kmer_stride, validate=not trusted)
@@ -261,6 +280,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
         batch_size = int(batch_size)
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
+        if self.pack is not None and int(group) > 1:
+            raise ValueError("group > 1 cannot be combined with pack=: a super-batch's row blocks are not the batches' own packings")
+        pairs = self.masked or self.pack is not None  # a batch is a tuple of tensors
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
@@ -277,8 +299,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode(*packed)
 
         def hand_out(big):
-            rows = big[0].shape[0] if self.masked else big.shape[0]
-            if rows <= batch_size:
+            rows = big[0].shape[0] if pairs else big.shape[0]
+            if rows <= batch_size or self.pack is not None:
                 yield big
             elif self.masked:
                 for r in range(0, rows, batch_size):
@@ -331,7 +353,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
                     issue()  # the next one goes out BEFORE this one is handed over: it runs under whatever the consumer does with it
                     now = torch.cuda.current_stream()
                     now.wait_event(ready)
-                    for t in (big if self.masked else (big,)):
+                    for t in (big if pairs else (big,)):
                         t.record_stream(now)
                     if fused:
                         blosum.check_fused()
@@ -345,9 +367,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             s, e, st = index.indices(len(self))
             return self.__getitems__(list(range(s, e, st)))
         index = self._index(index)
-        if self.masked:
-            inputs, labels = self.get_batch(index, index + 1)
-            return inputs[0], labels[0]
+        if self.masked or self.pack is not None:
+            return tuple(t[0] for t in self.get_batch(index, index + 1))
         return self.get_batch(index, index + 1)[0]
 
     def fetch(self, index, return_items=False):

@@ -35,7 +35,8 @@ extern "C" {
                            * bsq_random_mask_device, bsq_random_mask_host, bsq_onehot_device_multi, bsq_onehot_multi_plan,
                            * bsq_crop_packed_device, bsq_crop_plan_host, bsq_views_packed_device, bsq_complement_table, bsq_kmer, bsq_kmer_vocab_size,
                            * bsq_kmer_unk_id, bsq_kmer_bos_id, bsq_kmer_eos_id, bsq_kmer_pad_id, bsq_kmer_count, bsq_kmer_tokenize_device,
-                           * bsq_kmer_tokenize_host, bsq_kmer_kernel_name; nothing removed */
+                           * bsq_kmer_tokenize_host, bsq_kmer_kernel_name, bsq_pack_plan_device, bsq_pack_plan_host, bsq_pack_plan_parallel_host,
+                           * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -443,6 +444,80 @@ bsq_status bsq_kmer_tokenize_host(const bsq_desc *d, const uint8_t *chars, const
 /* Host only: the kernel bsq_kmer_tokenize_device takes for this shape ("k_kmer_bp<s1>", "k_kmer_bp<sk>", "k_kmer_generic"), from the
  * predicate the launch uses; "" for arguments the device call refuses. */
 const char *bsq_kmer_kernel_name(const bsq_desc *d, const bsq_kmer *km, int64_t B, int64_t P, int32_t batch_first, bsq_dtype t);
+
+/* ---- sequence packing: several sequences per token row.  Every other encode path writes one sequence per row and fills the rest with
+ * PAD; a transformer pays for every position of the matrix, and at protein-like or read-like length distributions most of them are
+ * PAD.  Here the runs of a packed batch are laid out back to back in a (R, P) matrix, with segment ids and position ids so that
+ * attention and position embeddings stay per sequence.
+ *
+ * RUNS AND PREFIX.  For sequence i of a packed batch with length L_i and the tokenizer's bos / eos flags (0 / 1):
+ *     run_i = [BOS] t_0 .. t_{L-1} [EOS]                    the w_i = L_i + bos + eos tokens bsq_tokenize_device writes for it
+ *                                                           (an unmapped character is 0, as there)
+ *     S_i   = sum_{j<i} w_j = offsets[i] - offsets[0] + i * (bos + eos)             a closed form: no scan
+ * OUTPUT.  (R, P), batch-first, C-contiguous, read as ONE flat array of R * P positions.  starts[i] (int64, B + 1 entries) is the flat
+ * position of run i's first token, starts[B] the end of the last run.
+ *     BSQ_PACK_STREAM   starts[i] = S_i: the flat output is the concatenation of the runs followed by PAD; runs may cross row
+ *                       boundaries; R = ceil(S_B / P), and 1 when S_B = 0 and B > 0.
+ *     BSQ_PACK_NEXTFIT  the plain sequential loop: with (row, col) = (0, 0), for i = 0 .. B - 1: if i > 0 and col + w_i > P then
+ *                       (row, col) = (row + 1, 0); starts[i] = row * P + col; col += w_i.  R = row + 1.  No run is split:
+ *                       starts[i] / P == (starts[i] + w_i - 1) / P for every 0 < w_i <= P.  A run wider than P is what the length
+ *                       validation refuses; without validation it has its row to itself and is cut at P positions (memory-safe, as
+ *                       over-long rows are everywhere else).
+ *     B = 0: R = 0, starts[0] = 0.
+ * tokens        flat[starts[i] .. starts[i] + w_i) = run_i (cut as above); every other position holds the PAD id, or 0 for a tokenizer
+ *               without padchar, as bsq_tokenize_device stores.  All six bsq_dtypes, converted as everywhere else.
+ * segment_ids   int32: 0 at positions outside every run; elsewhere 1 + (i - i_first(r)), i the sequence whose run covers the position
+ *               and i_first(r) the one covering column 0 of its row r.  One rule for both modes: a sequence continued from the
+ *               previous row in stream mode is segment 1 of its new row.  (Sequences with w_i = 0 cover nothing and still count.)
+ * position_ids  int32: the index of the token inside its run (it continues across a row cut in stream mode); 0 outside every run.
+ * Every element of every requested output is written exactly once; segment_ids and position_ids are each optional.
+ *
+ * A MATRIX OF A FIXED NUMBER OF ROWS (max_rows = N > 0; 0 = as many rows as the batch needs).  Only the prefix of the sequences whose
+ * runs end inside the N rows (starts[i] + w_i <= N * P, w_i cut at P in next-fit rows) is placed: *n_placed (nullable) <- their number, starts
+ * of every other sequence <- -1, starts[B] <- the end of the last run placed (0: none).  *n_rows still reports the rows the WHOLE batch
+ * needs.  Rows behind the placed runs are all PAD.  A caller resumes at sequence n_placed.
+ *
+ * Known answers (DNA4: A C G T = 0 1 2 3; the batch ACG, "", AC, ACGTAC, T; P = 8; no BOS, EOS or padchar), next-fit:
+ *     starts 0 3 3 8 14 | 15, R = 2, tokens 0 1 2 0 1 0 0 0 / 0 1 2 3 0 1 3 0, segment_ids 1 1 1 3 3 0 0 0 / 1 1 1 1 1 1 2 0,
+ *     position_ids 0 1 2 0 1 0 0 0 / 0 1 2 3 4 5 0 0;
+ * stream: starts 0 3 3 5 11 | 12, R = 2, tokens 0 1 2 0 1 0 1 2 / 3 0 1 3 0 0 0 0, segment_ids 1 1 1 3 3 4 4 4 / 1 1 1 2 0 0 0 0,
+ *     position_ids 0 1 2 0 1 0 1 2 / 3 4 5 0 0 0 0 0.  With BOS = 4, EOS = 5, PAD = 6, next-fit: starts 0 5 8 16 24 | 27, R = 4,
+ *     tokens 4 0 1 2 5 4 5 6 / 4 0 1 5 6 6 6 6 / 4 0 1 2 3 0 1 5 / 4 3 5 6 6 6 6 6.
+ *
+ * bsq_pack_plan_device: offsets (device, B + 1) -> starts (device int64[B + 1]), n_rows (device int64), n_placed (device int64, nullable).
+ *   Stream-ordered, never synchronises, no host loop over sequences.  The sequential loop has a parallel form: next(s) = the largest
+ *   e > s with S_e - S_s <= P (and s + 1 for a run wider than P) is one binary search over the closed-form S; the row heads are the
+ *   chain 0 -> next(0) -> next(next(0)) -> ...; chain membership comes from pointer jumping (ceil(log4 B) small launches); an
+ *   inclusive scan of the marks gives a sequence its row and its head, and column = S_i - S_head.  B <= 2^31 - 2, P <= 2^30.
+ * bsq_pack_plan_host: the CPU twin on host buffers -- the plain loop above.  bsq_pack_plan_parallel_host: the device plan's own
+ *   arithmetic (csrc/bsq_pack_dev.h) run round by round on the CPU; it exists so that the parallel form is checked against the loop
+ *   without a device.
+ * bsq_pack_tokenize_device: the encode, ONE launch, output-driven: a wave owns 1024 consecutive positions of the flat output, finds its
+ *   first sequence by a binary search in the monotone `starts` and walks forward, so the stores are whole, aligned and coalesced
+ *   whatever the lengths are and the PAD gaps fall out of the same loop.  `starts` is a plan of bsq_pack_plan_* (entries < 0 = not
+ *   placed); rows * P positions are written whatever the plan says (rows = 0: nothing is launched).  A run ends where the next one
+ *   starts and at starts[B] at the latest.  Stream-ordered, never synchronises.  rows <= 2^31, rows * P <= 2^40.
+ * bsq_pack_tokenize_host: its CPU twin on host buffers (the same cursor and id code).
+ * bsq_pack_kernel_name: host only, the kernel bsq_pack_tokenize_device takes ("k_pack_flat<perm>": the register-table lookup, an alphabet
+ *   whose mapped bytes are letters with both cases alike; "k_pack_flat<lut>": any other alphabet); "" for arguments the call refuses.
+ * Argument errors (BSQ_ERR_INVALID_ARG, nothing launched, nothing written): null pointers, B < 0, P <= 0, an unknown mode, bos / eos
+ * other than 0 / 1, max_rows < 0, rows < 0, a size beyond the limits above; a bad dtype: BSQ_ERR_DTYPE.  The device plan and its CPU
+ * twins agree on well-formed offsets (what bsq_validate_packed_device accepts); on offsets it would refuse every entry point stays
+ * memory-safe, but the rows = N prefix of the device plan may differ from the twins'. */
+enum { BSQ_PACK_STREAM = 0, BSQ_PACK_NEXTFIT = 1 };
+bsq_status bsq_pack_plan_device(const int64_t *offsets, int64_t B, int64_t P, int32_t bos, int32_t eos, int32_t mode, int64_t max_rows,
+                                int64_t *starts, int64_t *n_rows, int64_t *n_placed_or_null, void *hip_stream);
+bsq_status bsq_pack_plan_host(const int64_t *offsets, int64_t B, int64_t P, int32_t bos, int32_t eos, int32_t mode, int64_t max_rows,
+                              int64_t *starts, int64_t *n_rows, int64_t *n_placed_or_null);
+bsq_status bsq_pack_plan_parallel_host(const int64_t *offsets, int64_t B, int64_t P, int32_t bos, int32_t eos, int32_t mode, int64_t max_rows,
+                                       int64_t *starts, int64_t *n_rows, int64_t *n_placed_or_null);
+bsq_status bsq_pack_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts,
+                                    int64_t rows, int64_t P, bsq_dtype t, void *tokens, int32_t *segment_ids_or_null,
+                                    int32_t *position_ids_or_null, void *hip_stream);
+bsq_status bsq_pack_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts,
+                                  int64_t rows, int64_t P, bsq_dtype t, void *tokens, int32_t *segment_ids_or_null,
+                                  int32_t *position_ids_or_null);
+const char *bsq_pack_kernel_name(const bsq_desc *d, int64_t B, int64_t rows, int64_t P, bsq_dtype t);
 
 /* ---- FASTA / FASTQ (plain or gzip) -> FlatFile on the host: replaces FlatFile::make (fxstats.cpp:33-64) and getlens /
  * getstats (:12-23, :202-219).  Same record grammar as the reference's kseq loop (bsq_fastx.cpp lists it), but streaming:
