@@ -148,6 +148,9 @@ def load():
         "bsq_pack_tokenize_device": (i32, [dp, vp, vp, i64, vp, i64, i64, c_int, vp, vp, vp, vp]),
         "bsq_pack_tokenize_host": (i32, [dp, vp, vp, i64, vp, i64, i64, c_int, vp, vp, vp]),
         "bsq_pack_kernel_name": (ctypes.c_char_p, [dp, i64, i64, i64, c_int]),
+        "bsq_pack_mlm_tokenize_device": (i32, [dp, vp, vp, i64, vp, i64, i64, ctypes.POINTER(Mlm), c_int, vp, c_int, vp, vp, vp, vp]),
+        "bsq_pack_mlm_tokenize_host": (i32, [dp, vp, vp, i64, vp, i64, i64, ctypes.POINTER(Mlm), c_int, vp, c_int, vp, vp, vp]),
+        "bsq_pack_mlm_kernel_name": (ctypes.c_char_p, [dp, i64, i64, i64, c_int]),
         "bsq_blosum62_normrows": (i32, [vp]),
         "bsq_augment_device": (i32, [vp, vp, i64, i32, ctypes.c_double, ctypes.c_uint64, vp]),
         "bsq_augment_tokenize_device": (i32, [vp, vp, vp, i64, i64, i32, i32, vp, i32, ctypes.c_double, ctypes.c_uint64, vp]),

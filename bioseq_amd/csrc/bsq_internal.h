@@ -188,7 +188,10 @@ bsq_status tokenize_generic_block(const bsq_desc *d, const uint8_t *chars, const
 
 }  // namespace bsq_internal
 
-// bsq_pack_host.cpp: the argument rules of the packing family, shared by its device entry points (bsq_pack.hip) and its CPU twins
+namespace bsq_packd {
+struct MlmDraw;  // bsq_pack_dev.h
+}
+// bsq_pack_host.cpp: the argument rules of the packing family, shared by its device entry points (bsq_pack.hip, bsq_pack_mlm.hip) and its CPU twins
 namespace bsq_pack_host {
 constexpr int64_t kMaxP = int64_t(1) << 30;
 constexpr int64_t kMaxRows = int64_t(1) << 31;
@@ -197,4 +200,8 @@ bsq_status check_plan(const int64_t *offsets, int64_t B, int64_t P, int32_t bos,
                       const int64_t *starts, const int64_t *n_rows);
 bsq_status check_encode(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts, int64_t rows,
                         int64_t P, bsq_dtype t, const void *tokens);
+// the masked encode: check_encode (on whichever output is given) and the rules of the MLM family (make_thresholds); *draw <- the draw
+bsq_status check_encode_mlm(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts, int64_t rows,
+                            int64_t P, const bsq_mlm *m, bsq_dtype in_dtype, const void *inputs, bsq_dtype label_dtype, const void *labels,
+                            bsq_packd::MlmDraw *draw);
 }  // namespace bsq_pack_host

@@ -1,5 +1,5 @@
 // Sequence packing (include/bsq.h, "sequence packing"): the arithmetic of the row plan and the value of ONE output position, as plain
-// host + device code.  The kernels of bsq_pack.hip and the CPU twins of bsq_pack_host.cpp are loops around these functions.
+// host + device code.  The kernels of bsq_pack.hip / bsq_pack_mlm.hip and the CPU twins of bsq_pack_host.cpp are loops around these functions.
 //
 // The plan.  S_i = offsets[i] - offsets[0] + i * (bos + eos) is a closed form, so "which sequence opens the row after the one that s
 // opens" is one binary search (next_head), the row heads are the chain 0 -> next_head(0) -> ..., and chain membership comes from
@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "bsq.h"
+#include "bsq_mlm_dev.h"
 
 #if defined(__HIPCC__)
 #define BSQ_PACK_HD __host__ __device__ __forceinline__
@@ -147,6 +148,53 @@ BSQ_PACK_HD int32_t run_token(const Ids &x, const Lut &lut, const uint8_t *chars
     if (a < 0 || a >= nchars) return 0;
     const int32_t v = lut[chars[a]];
     return v < 0 ? 0 : v;
+}
+
+// ---- the masked encode (bsq_pack_mlm_tokenize_*) --------------------------------------------------------------------------------
+// The draw of a packed masked batch: the thresholds and constants of a bsq_mlm (bsq_mlm_dev.h), made on the host.
+struct MlmDraw {
+    bsq_mlmd::Thresholds th;
+    uint64_t seed;
+    int64_t first_row, mask_token, ignore;
+    int32_t nchars;  // size of the alphabet a random id is drawn from
+};
+// BSQ_OK and the draw, or BSQ_ERR_INVALID_ARG (message in *why): make_thresholds of the MLM family
+inline bsq_status make_draw(const bsq_desc *d, const bsq_mlm *m, MlmDraw *x, const char **why) {
+    const bsq_status st = bsq_mlmd::make_thresholds(m, &x->th, why);
+    if (st != BSQ_OK) return st;
+    x->seed = m->seed;
+    x->first_row = m->first_row;
+    x->mask_token = m->mask_token;
+    x->ignore = m->ignore_index;
+    x->nchars = d->nchars;
+    return BSQ_OK;
+}
+
+// Token k of the run of sequence i under the masked-LM draw: the plain id of run_token, whether the draw selects it (characters only,
+// and only mapped ones: character j = k - bos of row first_row + i, keyed by h = row_key(seed, first_row + i)), and the masked input.
+struct MlmToken {
+    int64_t input;
+    int32_t plain;
+    bool sel;
+};
+template <typename Lut>
+BSQ_PACK_HD MlmToken run_mlm_token(const Ids &x, const Lut &lut, const uint8_t *chars, int64_t off, int64_t L, int64_t nchars, int64_t k,
+                                   uint64_t h, const MlmDraw &m) {
+    MlmToken t;
+    t.sel = false;
+    const int64_t j = k - x.bos;
+    if (j < 0) {
+        t.plain = x.bos_id;
+    } else if (j >= L) {
+        t.plain = x.eos_id;
+    } else {
+        const int64_t a = off + j;
+        const int32_t v = a < 0 || a >= nchars ? -1 : lut[chars[a]];
+        t.plain = v < 0 ? 0 : v;
+        t.sel = v >= 0 && bsq_mlmd::lane16(bsq_mlmd::select_word(h, static_cast<uint64_t>(j >> 2)), static_cast<uint32_t>(j)) < m.th.sel;
+    }
+    t.input = t.sel ? bsq_mlmd::replace(bsq_mlmd::replace_word(h, static_cast<uint64_t>(j)), m.th, m.mask_token, m.nchars, t.plain) : t.plain;
+    return t;
 }
 
 }  // namespace bsq_packd

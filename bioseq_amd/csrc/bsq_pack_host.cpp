@@ -1,7 +1,7 @@
 // Sequence packing, the CPU side (include/bsq.h, "sequence packing"): the argument rules every entry point of the family shares, the
 // plan as the plain sequential loop (bsq_pack_plan_host), the device plan's rounds run on the CPU (bsq_pack_plan_parallel_host: the
-// arithmetic of bsq_pack_dev.h in the order the kernels of bsq_pack.hip apply it) and the encode twin (bsq_pack_tokenize_host: the
-// cursor and the id code of the kernel).  Plain C++: this file is part of the sanitizer build of the host code.
+// arithmetic of bsq_pack_dev.h in the order the kernels of bsq_pack.hip apply it) and the encode twins (bsq_pack_tokenize_host,
+// bsq_pack_mlm_tokenize_host: the cursor and the id code of the kernels).  Plain C++: this file is part of the sanitizer build of the host code.
 #include <cstdint>
 #include <vector>
 
@@ -31,6 +31,18 @@ bsq_status check_encode(const bsq_desc *d, const uint8_t *chars, const int64_t *
     if (t < BSQ_I8 || t > BSQ_F64) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
     if (rows > 0 && (!tokens || !starts)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "tokens or starts is null");
     if (rows > 0 && B > 0 && (!offsets || !chars)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "chars or offsets is null");
+    return BSQ_OK;
+}
+
+bsq_status check_encode_mlm(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts, int64_t rows,
+                            int64_t P, const bsq_mlm *m, bsq_dtype in_dtype, const void *inputs, bsq_dtype label_dtype, const void *labels,
+                            bsq_packd::MlmDraw *draw) {
+    if (!inputs && !labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "both outputs are null");
+    if (label_dtype < BSQ_I8 || label_dtype > BSQ_F64) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
+    const bsq_status st = check_encode(d, chars, offsets, B, starts, rows, P, in_dtype, inputs ? inputs : labels);
+    if (st != BSQ_OK) return st;
+    const char *why = "";
+    if (bsq_packd::make_draw(d, m, draw, &why) != BSQ_OK) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, why);
     return BSQ_OK;
 }
 
@@ -126,6 +138,45 @@ bsq_status bsq_pack_tokenize_host(const bsq_desc *d, const uint8_t *chars, const
             if (position_ids_or_null) position_ids_or_null[q] = in ? static_cast<int32_t>(q - c.s) : 0;
         }
         return BSQ_OK;
+    });
+}
+
+bsq_status bsq_pack_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts,
+                                      int64_t rows, int64_t P, const bsq_mlm *m, bsq_dtype in_dtype, void *inputs_or_null,
+                                      bsq_dtype label_dtype, void *labels_or_null, int32_t *segment_ids_or_null,
+                                      int32_t *position_ids_or_null) {
+    bsq_packd::MlmDraw draw;
+    const bsq_status st = check_encode_mlm(d, chars, offsets, B, starts, rows, P, m, in_dtype, inputs_or_null, label_dtype, labels_or_null, &draw);
+    if (st != BSQ_OK || rows == 0 || B == 0) return st;
+    const bsq_packd::Ids ids = bsq_packd::make_ids(d);
+    const int64_t be = ids.bos + ids.eos, total = rows * P, nchars = offsets[B];
+    return bsq_internal::with_value_type(in_dtype, [&](auto ti) {
+        using TI = decltype(ti);
+        return bsq_internal::with_value_type(label_dtype, [&](auto tl) {
+            using TL = decltype(tl);
+            TI *in = static_cast<TI *>(inputs_or_null);
+            TL *lab = static_cast<TL *>(labels_or_null);
+            const TL ign = static_cast<TL>(draw.ignore);
+            bsq_packd::Cursor c = bsq_packd::cursor_at(offsets, starts, B, be, -1);
+            uint64_t h = 0;
+            int64_t i_first = -1;
+            for (int64_t q = 0; q < total; ++q) {
+                if (static_cast<uint64_t>(q) >= c.next) {
+                    c = bsq_packd::cursor_at(offsets, starts, B, be, bsq_packd::find(starts, B, c.i, static_cast<uint64_t>(q)));
+                    h = bsq_mlmd::row_key(draw.seed, static_cast<uint64_t>(draw.first_row + c.i));
+                }
+                if (q % P == 0) i_first = c.i;
+                const bool inside = c.i >= 0 && static_cast<uint64_t>(q) < c.e;
+                bsq_packd::MlmToken t;
+                t.input = t.plain = ids.pad_store, t.sel = false;
+                if (inside) t = bsq_packd::run_mlm_token(ids, d->lut, chars, c.off, c.L, nchars, q - c.s, h, draw);
+                if (in) in[q] = static_cast<TI>(t.input);
+                if (lab) lab[q] = t.sel ? static_cast<TL>(static_cast<int64_t>(t.plain)) : ign;
+                if (segment_ids_or_null) segment_ids_or_null[q] = inside ? static_cast<int32_t>(1 + c.i - i_first) : 0;
+                if (position_ids_or_null) position_ids_or_null[q] = inside ? static_cast<int32_t>(q - c.s) : 0;
+            }
+            return BSQ_OK;
+        });
     });
 }
 

@@ -70,14 +70,21 @@ class FlatFileDataset(torch.utils.data.Dataset):
     the host waits for the batch's plan before it issues the encode, also under `prefetch`, where that wait falls into the issue of the
     NEXT batch -- the encode still runs under the consumer's kernels, the host-side overlap of the issue is what is lost).
     It composes with crop, revcomp_frac, shuffle and prefetch.  With cnn=True, augment > 0, masked=True, kmer= or group > 1 it raises
-    ValueError: a super-batch's row blocks are not the batches' own packings, and the mask draw is keyed by row and index in the
-    sequence, which a packed row is not.
+    ValueError: a super-batch's row blocks are not the batches' own packings, and the masked form of a packed batch has a keyword
+    of its own:
+
+    pack_mlm=True (keyword; off by default; only with pack=): the packed batches are masked-LM batches drawn on the device at rate
+    `maskfrac` (packing.pack_mlm_tokenize_packed, one encode launch) -- `get_batch`, `__getitems__` and `batches()` hand out
+    (inputs, labels, segment_ids, position_ids).  The mask draw is keyed by a sequence's row in the draw and a character's index in
+    its sequence, which the packed encode carries for every position: the masks are those masked=True gives the same sequences,
+    keyed the same way (a fresh key per call and per `batches()` epoch, a row keyed by its index in the epoch's order; `prefetch`
+    hands out the same masks).  The exclusions of pack= hold.
     """
 
     NUCLEOTIDE_KEYS = ("DNA", "DNA4", "DNA5")
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
-                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None):
+                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -127,7 +134,10 @@ class FlatFileDataset(torch.utils.data.Dataset):
                 raise ValueError("pack must be 'nextfit' or 'stream', got %r" % (pack,))
             if cnn or augment or masked or kmer is not None:
                 raise ValueError("pack= gives packed token rows of the plain batch: it cannot be combined with cnn=True, augment > 0, "
-                                 "masked=True or kmer=")
+                                 "masked=True or kmer= (masked-LM batches over packed rows: pack_mlm=True)")
+        self.pack_mlm = bool(pack_mlm)
+        if self.pack_mlm and pack is None:
+            raise ValueError("pack_mlm=True masks the packed batches of pack=: give pack='nextfit' or pack='stream' with it")
 
     def __len__(self):
         return self.ff.nseqs()
@@ -193,6 +203,11 @@ class FlatFileDataset(torch.utils.data.Dataset):
         return masking.mlm_tokenize_packed(self.tokenizer, chars, offs, self.max_seq_len, self.token_dtype, True, frac=self.maskfrac,
                                            seed=mask_seed, first_row=first_row, validate=not trusted)
 
+    def _encode_pack_mlm(self, chars, offs, mask_seed, first_row):
+        return tuple(packing.pack_mlm_tokenize_packed(self.tokenizer, chars, offs, self.max_seq_len, self.token_dtype, mode=self.pack,
+                                                      frac=self.maskfrac, seed=mask_seed, first_row=first_row,
+                                                      validate=not self._trusted_lengths)[:4])
+
     def _encode(self, chars, offs):
         """augment_seq, then encode (bioseq/loaders.py:83-84, :102-103) on the batch's own copy.  Token rows go through the
         one-call entry `blosum.augment_tokenize_packed` (one launch for int8 rows; the entry runs the two launches for the
@@ -223,6 +238,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
         """Sequences [start, stop) as one encoded batch on the device."""
         if self.masked:
             return self._encode_masked(*self._packed_device(start, stop), self._mask_key(), 0)
+        if self.pack_mlm:
+            return self._encode_pack_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
         return self._encode(*self._packed_device(start, stop))
 
     def _index(self, i):
@@ -248,6 +265,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             packed = self._packed_device(0, 0, idx)
         if self.masked:
             return self._encode_masked(*packed, self._mask_key(), 0)
+        if self.pack_mlm:
+            return self._encode_pack_mlm(*packed, self._mask_key(), 0)
         return self._encode(*packed)
 
     def batches(self, batch_size, shuffle=True, drop_last=False, generator=None, prefetch=None, group=1):
@@ -286,7 +305,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
-        mask_seed = self._mask_key() if self.masked else None
+        mask_seed = self._mask_key() if self.masked or self.pack_mlm else None
         crop_seed = self._crop_key() if self._views else None
 
         def encode(first):
@@ -296,6 +315,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
                       else self._packed_device(first, stop, view=view))
             if self.masked:
                 return self._encode_masked(*packed, mask_seed, first)
+            if self.pack_mlm:
+                return self._encode_pack_mlm(*packed, mask_seed, first)
             return self._encode(*packed)
 
         def hand_out(big):

@@ -14,7 +14,9 @@ packing") has the full rules.
 * `pack_plan`             starts and row count alone;
 * `pack_rows_bound`       a safe `rows=` from the sizes of a batch, with no device work;
 * `pack_cu_seqlens`       int32 sequence boundaries for varlen attention (stream mode);
-* `pack_plan_host`, `pack_tokenize_host`  the library's CPU twins (numpy in, numpy out; no device).
+* `pack_mlm_tokenize_packed`  the masked-LM form of a packed batch (`bsq_pack_mlm_tokenize_device`): masked inputs, labels, segment_ids,
+                          position_ids in one launch, the draw of `masking.mlm_tokenize_packed` per sequence;
+* `pack_plan_host`, `pack_tokenize_host`, `pack_mlm_tokenize_host`  the library's CPU twins (numpy in, numpy out; no device).
 
 The crops and reverse-complement views of `views` hand this module packed batches as they are.
 """
@@ -26,6 +28,7 @@ import ctypes
 import numpy as np
 
 from . import capi
+from .masking import _params as _mlm_params
 
 _lib = capi.load()
 
@@ -37,6 +40,12 @@ Packed.__doc__ = """Result of `pack_tokenize_packed`: tokens (rows, padlen); seg
 not requested); starts int64[B + 1]; n_rows (0-d int64 tensor on the device, an int from the host twin)."""
 PackedRows = collections.namedtuple("PackedRows", "tokens segment_ids position_ids starts n_rows n_placed")
 PackedRows.__doc__ = """`Packed` of a call with `rows=N`, plus n_placed: how many sequences of the batch were placed."""
+
+PackedMlm = collections.namedtuple("PackedMlm", "inputs labels segment_ids position_ids starts n_rows")
+PackedMlm.__doc__ = """Result of `pack_mlm_tokenize_packed`: masked inputs and labels (rows, padlen); segment_ids, position_ids int32 of the same
+shape (None when not requested); starts int64[B + 1]; n_rows (0-d int64 tensor on the device, an int from the host twin)."""
+PackedMlmRows = collections.namedtuple("PackedMlmRows", "inputs labels segment_ids position_ids starts n_rows n_placed")
+PackedMlmRows.__doc__ = """`PackedMlm` of a call with `rows=N`, plus n_placed: how many sequences of the batch were placed."""
 
 
 def _args(tok, padlen, mode, rows=None):
@@ -87,6 +96,13 @@ def pack_kernel_name(tok, B, rows, padlen, destchar="q"):
     return _lib.bsq_pack_kernel_name(ctypes.byref(desc), int(B), int(rows), int(padlen), dt).decode()
 
 
+def pack_mlm_kernel_name(tok, B, rows, padlen, destchar="q"):
+    """The kernel `pack_mlm_tokenize_packed` takes (host only: profiling labels, tests)."""
+    dt, _ = capi.dtype_of(destchar)
+    desc = capi.desc_of(tok)
+    return _lib.bsq_pack_mlm_kernel_name(ctypes.byref(desc), int(B), int(rows), int(padlen), dt).decode()
+
+
 def _host_offsets(offsets):
     offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     if offsets.ndim != 1 or offsets.size < 1:
@@ -128,6 +144,33 @@ def pack_tokenize_host(tok, chars, offsets, padlen, destchar="q", *, mode="nextf
     if rows is None:
         return Packed(tokens, seg, pos, starts, n_rows)
     return PackedRows(tokens, seg, pos, starts, n_rows, n_placed)
+
+
+def pack_mlm_tokenize_host(tok, chars, offsets, padlen, destchar="q", *, mode="nextfit", rows=None, frac=0.15, mask_prob=0.8, random_prob=0.1,
+                           mask_token=None, ignore_index=-100, label_dtype="q", seed=0, first_row=0, segment_ids=True, position_ids=True):
+    """The library's CPU twin of `pack_mlm_tokenize_packed` on numpy arrays: the same named tuple, of numpy arrays and Python ints."""
+    desc, code, padlen, rows = _args(tok, padlen, mode, rows)
+    m = _mlm_params(frac, mask_prob, random_prob, tok.alphabet_size() if mask_token is None else mask_token, ignore_index, seed, first_row)
+    (dt, _), (ldt, _) = capi.dtype_of(destchar), capi.dtype_of(label_dtype)
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
+    offsets = _host_offsets(offsets)
+    B = offsets.size - 1
+    starts, n_rows, n_placed = pack_plan_host(tok, offsets, padlen, mode, rows)
+    R = n_rows if rows is None else rows
+    pad = tok.pad() if tok.is_padded() else 0
+    # (the entry writes nothing for a batch without sequences: such a matrix is all PAD / ignore_index / 0 / 0)
+    inputs = np.full((R, padlen), pad, dtype=_NUMPY[dt])
+    labels = np.full((R, padlen), np.int64(ignore_index)).astype(_NUMPY[ldt])
+    seg = np.zeros((R, padlen), dtype=np.int32) if segment_ids else None
+    pos = np.zeros((R, padlen), dtype=np.int32) if position_ids else None
+    keep = chars if chars.size else np.zeros(16, np.uint8)
+    if R > 0 and B > 0:
+        capi.check(_lib.bsq_pack_mlm_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, starts.ctypes.data, R, padlen,
+                                                   ctypes.byref(m), dt, inputs.ctypes.data, ldt, labels.ctypes.data,
+                                                   seg.ctypes.data if segment_ids else None, pos.ctypes.data if position_ids else None))
+    if rows is None:
+        return PackedMlm(inputs, labels, seg, pos, starts, n_rows)
+    return PackedMlmRows(inputs, labels, seg, pos, starts, n_rows, n_placed)
 
 
 def _validate(chars, offsets, B, desc, code, padlen):
@@ -209,5 +252,52 @@ def pack_tokenize_packed(tok, chars, offsets, padlen, destchar="q", *, mode="nex
     return PackedRows(tokens, seg, pos, starts, n_rows, n_placed)
 
 
+def pack_mlm_tokenize_packed(tok, chars, offsets, padlen, destchar="q", *, mode="nextfit", rows=None, frac=0.15, mask_prob=0.8, random_prob=0.1,
+                             mask_token=None, ignore_index=-100, label_dtype="q", seed=0, first_row=0, segment_ids=True, position_ids=True,
+                             validate=True):
+    """The masked-LM batch of a packed batch resident on the device, sequence-packed: the named tuple (inputs, labels, segment_ids,
+    position_ids, starts, n_rows) -- `pack_tokenize_packed` with its tokens replaced by the masked inputs and the labels of
+    `masking.mlm_tokenize_packed`, in ONE encode launch.
+
+    A character's fate depends on (seed, first_row + its sequence's index in the batch, its index in the sequence) only -- never on the
+    layout: the run of sequence i at `starts[i]` equals the head of row i of `mlm_tokenize_packed` with the same arguments, in either
+    mode and at any padlen; a batch packed in pieces (`rows=N`, resumed at `n_placed` with `first_row` advanced by as much) or in
+    shards gives every sequence the same run.  Positions outside every run hold PAD (0 for an unpadded tokenizer) and `ignore_index`;
+    BOS / EOS are never selected.  `frac`, `mask_prob`, `random_prob`, `mask_token`, `ignore_index`, `label_dtype`, `seed`, `first_row`
+    as in `mlm_tokenize_packed`; everything else -- `rows`, the one read-back of rows=None, `validate`, ValueError before any device
+    work -- as in `pack_tokenize_packed`."""
+    import torch
+    desc, code, padlen, rows = _args(tok, padlen, mode, rows)
+    m = _mlm_params(frac, mask_prob, random_prob, tok.alphabet_size() if mask_token is None else mask_token, ignore_index, seed, first_row)
+    (dt, tdt), (ldt, ltdt) = capi.dtype_of(destchar), capi.dtype_of(label_dtype)
+    B = capi.packed_on_device(chars, offsets, "pack_mlm_tokenize_packed works on packed batches resident on the device (chars, offsets tensors)")
+    if validate and B > 0:
+        _validate(chars, offsets, B, desc, code, padlen)
+    starts, n_rows, n_placed = _plan(offsets, B, desc, code, padlen, rows)
+    R = int(n_rows) if rows is None else rows  # (rows=None: the one read-back)
+    dev = offsets.device
+    if B > 0:
+        inputs = torch.empty((R, padlen), dtype=tdt, device=dev)
+        labels = torch.empty((R, padlen), dtype=ltdt, device=dev)
+        seg = torch.empty((R, padlen), dtype=torch.int32, device=dev) if segment_ids else None
+        pos = torch.empty((R, padlen), dtype=torch.int32, device=dev) if position_ids else None
+    else:  # (the entry writes nothing for a batch without sequences: such a matrix is all PAD / ignore_index / 0 / 0)
+        inputs = torch.full((R, padlen), tok.pad() if tok.is_padded() else 0, dtype=tdt, device=dev)
+        labels = torch.full((R, padlen), int(ignore_index), dtype=ltdt, device=dev)
+        seg = torch.zeros((R, padlen), dtype=torch.int32, device=dev) if segment_ids else None
+        pos = torch.zeros((R, padlen), dtype=torch.int32, device=dev) if position_ids else None
+    if R > 0 and B > 0:
+        src = capi.readable_chars(chars, dev)
+        with capi.launching(dev) as stream:
+            capi.check(_lib.bsq_pack_mlm_tokenize_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, starts.data_ptr(), R, padlen,
+                                                         ctypes.byref(m), dt, inputs.data_ptr(), ldt, labels.data_ptr(),
+                                                         seg.data_ptr() if segment_ids else None, pos.data_ptr() if position_ids else None,
+                                                         stream))
+    if rows is None:
+        return PackedMlm(inputs, labels, seg, pos, starts, n_rows)
+    return PackedMlmRows(inputs, labels, seg, pos, starts, n_rows, n_placed)
+
+
 __all__ = ["pack_tokenize_packed", "pack_plan", "pack_plan_host", "pack_tokenize_host", "pack_rows_bound", "pack_cu_seqlens",
-           "pack_kernel_name", "Packed", "PackedRows"]
+           "pack_kernel_name", "Packed", "PackedRows", "pack_mlm_tokenize_packed", "pack_mlm_tokenize_host", "pack_mlm_kernel_name",
+           "PackedMlm", "PackedMlmRows"]

@@ -36,7 +36,8 @@ extern "C" {
                            * bsq_crop_packed_device, bsq_crop_plan_host, bsq_views_packed_device, bsq_complement_table, bsq_kmer, bsq_kmer_vocab_size,
                            * bsq_kmer_unk_id, bsq_kmer_bos_id, bsq_kmer_eos_id, bsq_kmer_pad_id, bsq_kmer_count, bsq_kmer_tokenize_device,
                            * bsq_kmer_tokenize_host, bsq_kmer_kernel_name, bsq_pack_plan_device, bsq_pack_plan_host, bsq_pack_plan_parallel_host,
-                           * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name; nothing removed */
+                           * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name, bsq_pack_mlm_tokenize_device,
+                           * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -518,6 +519,37 @@ bsq_status bsq_pack_tokenize_host(const bsq_desc *d, const uint8_t *chars, const
                                   int64_t rows, int64_t P, bsq_dtype t, void *tokens, int32_t *segment_ids_or_null,
                                   int32_t *position_ids_or_null);
 const char *bsq_pack_kernel_name(const bsq_desc *d, int64_t B, int64_t rows, int64_t P, bsq_dtype t);
+
+/* MASKED-LM BATCHES OVER PACKED ROWS: the masked inputs and the labels of bsq_mlm (above: THE DRAW) in the layout of
+ * bsq_pack_tokenize_device, with its segment_ids and position_ids, in ONE launch.  Position q of the flat (rows, P) output lies either
+ * in the run of a placed sequence i at index k (q = starts[i] + k) or outside every run.
+ *     outside every run        input = the PAD id (0 for a tokenizer without padchar), label = ignore_index
+ *     BOS / EOS of a run       input = their ids, label = ignore_index
+ *     character j = k - bos    exactly the fate THE DRAW gives character j of row first_row + i: h_row of that row, the selection word
+ *     of sequence i            of quad j >> 2, its 16 bits at 16 (j & 3), and for a selected character the replacement word of j.  An
+ *                              unmapped character is never selected and stores 0; a selected character's label is its plain id and
+ *                              its input the mask token, a uniform alphabet id, or itself.
+ * The draw never sees the layout: the run of sequence i in the packed matrix equals the head of row i of bsq_mlm_tokenize_device for
+ * the same bsq_mlm, in either mode and at any width, and a batch packed in pieces (rows = N, resumed at n_placed with first_row advanced
+ * by as much; shards) gives every sequence the run of the whole-batch call.
+ * The plan (`starts`), the rows = N rule, the next-fit cut of an unvalidated over-wide run, segment_ids and position_ids are those of
+ * bsq_pack_tokenize_device, bit for bit.  inputs and labels take all six bsq_dtypes each, converted as bsq_mlm_tokenize_device converts
+ * them; either may be NULL, not both; segment_ids and position_ids are each optional.  rows = 0 or B = 0: BSQ_OK, nothing is written.
+ * Argument errors (nothing launched, nothing written): everything bsq_pack_tokenize_device refuses (the output it checks is whichever
+ * of inputs / labels is given), everything bsq_mlm_tokenize_device refuses about a bsq_mlm, both outputs NULL, a bad dtype on either
+ * side (BSQ_ERR_DTYPE).
+ * bsq_pack_mlm_tokenize_host: the CPU twin on host buffers (the same cursor, id and draw code).
+ * bsq_pack_mlm_kernel_name: host only, the kernel the device call takes ("k_pack_mlm_flat<perm>" / "k_pack_mlm_flat<lut>", by the rule of
+ * bsq_pack_kernel_name); "" for arguments the call refuses. */
+bsq_status bsq_pack_mlm_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts,
+                                        int64_t rows, int64_t P, const bsq_mlm *m, bsq_dtype in_dtype, void *inputs_or_null,
+                                        bsq_dtype label_dtype, void *labels_or_null, int32_t *segment_ids_or_null,
+                                        int32_t *position_ids_or_null, void *hip_stream);
+bsq_status bsq_pack_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const int64_t *starts,
+                                      int64_t rows, int64_t P, const bsq_mlm *m, bsq_dtype in_dtype, void *inputs_or_null,
+                                      bsq_dtype label_dtype, void *labels_or_null, int32_t *segment_ids_or_null,
+                                      int32_t *position_ids_or_null);
+const char *bsq_pack_mlm_kernel_name(const bsq_desc *d, int64_t B, int64_t rows, int64_t P, bsq_dtype in_dtype);
 
 /* ---- FASTA / FASTQ (plain or gzip) -> FlatFile on the host: replaces FlatFile::make (fxstats.cpp:33-64) and getlens /
  * getstats (:12-23, :202-219).  Same record grammar as the reference's kseq loop (bsq_fastx.cpp lists it), but streaming:
