@@ -21,7 +21,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libbsq_hip.so")
 EXT = os.path.join(HERE, "cbioseq" + sysconfig.get_config_var("EXT_SUFFIX"))
 
-LIB_SRCS = ["bsq_onehot.hip", "bsq_tokens.hip", "bsq_generic.hip", "bsq_tokens8.hip", "bsq_decode.hip", "bsq_augment.hip", "bsq_mlm.hip", "bsq_kmer.hip", "bsq_pack.hip", "bsq_pack_mlm.hip", "bsq_gather.hip", "bsq_views.hip", "bsq_diag.hip", "bsq_host.cpp", "bsq_pack_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
+LIB_SRCS = ["bsq_onehot.hip", "bsq_tokens.hip", "bsq_generic.hip", "bsq_tokens8.hip", "bsq_decode.hip", "bsq_augment.hip", "bsq_mlm.hip", "bsq_kmer.hip", "bsq_kmer_mlm.hip", "bsq_pack.hip", "bsq_pack_mlm.hip", "bsq_gather.hip", "bsq_views.hip", "bsq_diag.hip", "bsq_host.cpp", "bsq_pack_host.cpp", "bsq_kmer_mlm_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
 EXT_SRCS = ["cbioseq_module.cpp"]
 EXT_HDRS = ["bsq_worker_pool.h"]
 
@@ -107,9 +107,14 @@ def build_ext(force=False):
     return EXT
 
 
+# the host sources scripts/asan_host.sh rebuilds itself with g++ under the sanitizers
+ASAN_HOST_SRCS = ["bsq_host.cpp", "bsq_pack_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
+
+
 def kernel_objects():
-    """The hipcc-built objects of the library's .hip sources, in link order (scripts/asan_host.sh links exactly these)."""
-    return [os.path.join(CSRC, "_obj", f + ".o") for f in LIB_SRCS if f.endswith(".hip")]
+    """The hipcc-built objects scripts/asan_host.sh links as they are, in link order: the library's .hip sources and every host
+    source the script does not rebuild itself (bsq_kmer_mlm_host.cpp: its sanitizer pass is a stand-alone program, not this script)."""
+    return [os.path.join(CSRC, "_obj", f + ".o") for f in LIB_SRCS if f not in ASAN_HOST_SRCS]
 
 
 def build_all(force=False):

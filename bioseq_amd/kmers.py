@@ -12,7 +12,10 @@ its specials.  A tail shorter than k is dropped.  include/bsq.h (`bsq_kmer`) has
 * `kmer_tokenize_packed`  the ids of a packed batch resident on the device, (B, padlen) or (padlen, B);
 * `kmer_vocab_size`, `kmer_special_ids`, `kmer_padlen`, `kmer_count`  the sizes an embedding table and a batch need;
 * `kmer_decode`           ids -> words (host code: what one needs to write a vocabulary file);
-* `kmer_tokenize_host`    the library's CPU twin of the ids (numpy in, numpy out; no device).
+* `kmer_tokenize_host`    the library's CPU twin of the ids (numpy in, numpy out; no device);
+* `kmer_mlm_tokenize_packed`  span-masked masked-LM pairs (inputs, labels) over the k-mer ids, drawn in the encode launch (DNABERT's
+                          objective: contiguous runs of `span` windows are selected, then BERT's 80/10/10 replacement);
+* `kmer_mlm_tokenize_host`, `span_anchor_prob`, `kmer_mlm_kernel_name`  its CPU twin, the share -> anchor rate helper, the kernel taken.
 
 The crops and reverse-complement views of `views` hand this module packed batches as they are:
 `kmer_tokenize_packed(tok, *views.crop_packed(chars, offsets, 1000, revcomp_frac=0.5), k=6, padlen=...)`.
@@ -143,6 +146,19 @@ def kmer_tokenize_host(tok, chars, offsets, k, padlen, destchar="q", batch_first
     return out
 
 
+def _validate(tok, chars, offsets, B, desc, km, padlen):
+    """The over-long-sequence check of `tokenize_packed` with the k-mer bound (the library's error), and malformed offsets."""
+    bound = kmer_max_length(tok, km.k, padlen, km.stride)
+    bad = ctypes.c_int64(-1)
+    with capi.launching(chars.device) as stream:
+        st = _lib.bsq_validate_packed_device(offsets.data_ptr(), B, bound, 0, 0, chars.numel(), ctypes.byref(bad), stream)
+    if st == capi.ERR_SEQ_TOO_LONG:
+        i = int(bad.value)
+        raise RuntimeError("seq len %d holds more than padlen %d k-mers (k %d, stride %d, bos + eos %d): at most %d characters fit"
+                           % (int(offsets[i + 1] - offsets[i]), padlen, km.k, km.stride, desc.bos + desc.eos, bound))
+    capi.check(st)
+
+
 def kmer_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch_first=True, *, stride=1, validate=True):
     """k-mer ids of a packed batch on the device (chars uint8[total], offsets int64[B + 1]): a device tensor (B, padlen) when
     batch_first else (padlen, B), on torch's current stream, one launch.
@@ -158,15 +174,7 @@ def kmer_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch_fir
         raise ValueError("padlen must be positive")
     B = capi.packed_on_device(chars, offsets, "kmer_tokenize_packed works on packed batches resident on the device (chars, offsets tensors)")
     if validate and B > 0:
-        bound = kmer_max_length(tok, k, padlen, stride)
-        bad = ctypes.c_int64(-1)
-        with capi.launching(chars.device) as stream:
-            st = _lib.bsq_validate_packed_device(offsets.data_ptr(), B, bound, 0, 0, chars.numel(), ctypes.byref(bad), stream)
-        if st == capi.ERR_SEQ_TOO_LONG:
-            i = int(bad.value)
-            raise RuntimeError("seq len %d holds more than padlen %d k-mers (k %d, stride %d, bos + eos %d): at most %d characters fit"
-                               % (int(offsets[i + 1] - offsets[i]), padlen, km.k, km.stride, desc.bos + desc.eos, bound))
-        capi.check(st)
+        _validate(tok, chars, offsets, B, desc, km, padlen)
     out = torch.empty((B, padlen) if batch_first else (padlen, B), dtype=tdt, device=chars.device)
     if B > 0:
         src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
@@ -176,5 +184,104 @@ def kmer_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch_fir
     return out
 
 
+def span_anchor_prob(frac, span):
+    """The anchor rate at which a share `frac` of the windows of a long row is covered by spans of `span` windows:
+    1 - (1 - frac) ** (1 / span) (`bsq_kmer_mlm_anchor_prob`)."""
+    p = float(_lib.bsq_kmer_mlm_anchor_prob(float(frac), int(span)))
+    if p < 0:
+        raise ValueError("frac must lie in [0, 1] and span in 1 .. 16, got %r and %r" % (frac, span))
+    return p
+
+
+def _kmer_mlm(tok, k, stride, destchar, label_destchar, frac, span, anchor_prob, mask_prob, random_prob, mask_token, ignore_index, seed, first_row):
+    """(desc, km, bsq_kmer_mlm, input dtype, label dtype, torch dtypes) with the library's argument rules applied as ValueError."""
+    desc, km = _kmer(tok, k, stride)
+    span = -(-km.k // km.stride) if span is None else int(span)
+    if not 1 <= span <= 16:
+        raise ValueError("span must lie in 1 .. 16, got %r" % (span,))
+    if anchor_prob is None:
+        anchor_prob = span_anchor_prob(frac, span)
+    elif frac != 0.15:
+        raise ValueError("give frac or anchor_prob, not both")
+    vocab = int(_lib.bsq_kmer_vocab_size(ctypes.byref(desc), ctypes.byref(km)))
+    m = capi.KmerMlm(float(anchor_prob), float(mask_prob), float(random_prob), span, vocab if mask_token is None else int(mask_token),
+                     int(ignore_index), int(seed) & (2 ** 64 - 1), int(first_row))
+    for name, p in (("anchor_prob", m.anchor_prob), ("mask_prob", m.mask_prob), ("random_prob", m.random_prob)):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("%s must lie in [0, 1], got %r" % (name, p))
+    if m.mask_prob + m.random_prob > 1.0 + 1e-12:
+        raise ValueError("mask_prob + random_prob > 1")
+    if m.first_row < 0 or m.mask_token < 0:
+        raise ValueError("first_row and mask_token must be >= 0")
+    dt, tdt = capi.dtype_of(destchar)
+    ldt, ltdt = capi.dtype_of(label_destchar)
+    top = max(vocab - 1, m.mask_token)
+    limit = {capi.I8: 127, capi.I16: 32767}
+    if top > limit.get(dt, top):
+        raise ValueError("ids up to %d (vocabulary and mask token) do not fit destchar %r" % (top, destchar))
+    if desc.nchars ** km.k - 1 > limit.get(ldt, 2 ** 24):
+        raise ValueError("plain ids up to %d do not fit label_destchar %r" % (desc.nchars ** km.k - 1, label_destchar))
+    return desc, km, m, dt, ldt, tdt, ltdt
+
+
+def kmer_mlm_kernel_name(tok, k, B, padlen, destchar="q", batch_first=True, *, stride=1, label_destchar="q"):
+    """The kernel `kmer_mlm_tokenize_packed` takes for this shape (host only: profiling labels, tests)."""
+    desc, km, m, dt, ldt, _, _ = _kmer_mlm(tok, k, stride, destchar, label_destchar, 0.15, None, None, 0.8, 0.1, None, -100, 0, 0)
+    return _lib.bsq_kmer_mlm_kernel_name(ctypes.byref(desc), ctypes.byref(km), ctypes.byref(m), int(B), int(padlen), int(bool(batch_first)),
+                                         dt, ldt).decode()
+
+
+def kmer_mlm_tokenize_host(tok, chars, offsets, k, padlen, destchar="q", batch_first=True, *, stride=1, frac=0.15, span=None, anchor_prob=None,
+                           mask_prob=0.8, random_prob=0.1, mask_token=None, ignore_index=-100, label_destchar="q", seed=0, first_row=0):
+    """The library's CPU twin (`bsq_kmer_mlm_tokenize_host`, the element code of the kernels) on numpy arrays: (inputs, labels)."""
+    desc, km, m, dt, ldt, _, _ = _kmer_mlm(tok, k, stride, destchar, label_destchar, frac, span, anchor_prob, mask_prob, random_prob, mask_token,
+                                           ignore_index, seed, first_row)
+    if int(padlen) <= 0:
+        raise ValueError("padlen must be positive")
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    B = offsets.size - 1
+    shape = (B, int(padlen)) if batch_first else (int(padlen), B)
+    inputs, labels = np.empty(shape, dtype=_NUMPY[dt]), np.empty(shape, dtype=_NUMPY[ldt])
+    keep = chars if chars.size else np.zeros(16, np.uint8)
+    if B > 0:
+        capi.check(_lib.bsq_kmer_mlm_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
+                                                   ctypes.byref(km), ctypes.byref(m), dt, inputs.ctypes.data, ldt, labels.ctypes.data))
+    return inputs, labels
+
+
+def kmer_mlm_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch_first=True, *, stride=1, frac=0.15, span=None, anchor_prob=None,
+                             mask_prob=0.8, random_prob=0.1, mask_token=None, ignore_index=-100, label_destchar="q", seed=0, first_row=0,
+                             validate=True):
+    """Span-masked masked-LM pairs over the k-mer ids of a packed batch on the device: (inputs, labels) device tensors, (B, padlen) when
+    batch_first else (padlen, B), on torch's current stream, one launch (`bsq_kmer_mlm_tokenize_device`; include/bsq.h has the draw).
+
+    Anchors open runs of `span` consecutive windows (None: ceil(k / stride), the windows that share a character -- k at stride 1, 1 at
+    stride k); a selected window becomes `mask_token` (None: `kmer_vocab_size`) with probability mask_prob, a uniform plain id with
+    random_prob, else keeps its id; labels hold the plain id at selected windows and ignore_index elsewhere.  UNK windows and BOS / EOS /
+    PAD are never selected.  `frac` is the share of windows covered in a long row (`anchor_prob` = `span_anchor_prob(frac, span)`);
+    give `anchor_prob` instead to set the anchor rate itself -- both is a ValueError.  A window's fate depends on (seed, first_row + its
+    row, its index) only.  validate: as `kmer_tokenize_packed`."""
+    import torch
+    desc, km, m, dt, ldt, tdt, ltdt = _kmer_mlm(tok, k, stride, destchar, label_destchar, frac, span, anchor_prob, mask_prob, random_prob,
+                                                mask_token, ignore_index, seed, first_row)
+    padlen = int(padlen)
+    if padlen <= 0:
+        raise ValueError("padlen must be positive")
+    B = capi.packed_on_device(chars, offsets, "kmer_mlm_tokenize_packed works on packed batches resident on the device (chars, offsets tensors)")
+    if validate and B > 0:
+        _validate(tok, chars, offsets, B, desc, km, padlen)
+    shape = (B, padlen) if batch_first else (padlen, B)
+    inputs = torch.empty(shape, dtype=tdt, device=chars.device)
+    labels = torch.empty(shape, dtype=ltdt, device=chars.device)
+    if B > 0:
+        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_kmer_mlm_tokenize_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, padlen, int(bool(batch_first)),
+                                                         ctypes.byref(km), ctypes.byref(m), dt, inputs.data_ptr(), ldt, labels.data_ptr(), stream))
+    return inputs, labels
+
+
 __all__ = ["kmer_tokenize_packed", "kmer_tokenize_host", "kmer_vocab_size", "kmer_special_ids", "kmer_count", "kmer_padlen",
-           "kmer_max_length", "kmer_decode", "kmer_kernel_name"]
+           "kmer_max_length", "kmer_decode", "kmer_kernel_name", "kmer_mlm_tokenize_packed", "kmer_mlm_tokenize_host", "span_anchor_prob",
+           "kmer_mlm_kernel_name"]

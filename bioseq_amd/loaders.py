@@ -62,7 +62,16 @@ class FlatFileDataset(torch.utils.data.Dataset):
     (kmers.kmer_tokenize_packed: 1 = overlapping, k = non-overlapping), so max_seq_len = kmers.kmer_padlen of the longest stored
     sequence, or of `crop` when cropping.  It composes with crop, revcomp_frac, shuffle, group and prefetch -- they all hand the encode
     a packed batch.  With cnn=True, augment > 0 or masked=True it raises ValueError: a k-mer one-hot and protein mutations under
-    k-mers are not provided, and masking overlapping windows needs span masks, which this draw is not.
+    k-mers are not provided, and masking overlapping windows needs span masks, which this draw is not -- the span-masked form has a
+    keyword of its own:
+
+    kmer_mlm=True (keyword; off by default; only with kmer=): the k-mer batches are span-masked masked-LM batches drawn on the device
+    (kmers.kmer_mlm_tokenize_packed, one launch) -- `get_batch`, `__getitems__` and `batches()` hand out (inputs, labels): anchors open
+    runs of `kmer_span` consecutive windows (None: ceil(kmer / kmer_stride), the windows that share a character) so that a share
+    `maskfrac` of the windows is selected, then BERT's 80/10/10 replacement with mask token = kmers.kmer_vocab_size; labels int64 with
+    ignore_index -100.  Keyed like masked=True: a fresh key per call and per `batches()` epoch, a row keyed by its index in the epoch's
+    order -- crop, revcomp_frac, shuffle, `group` and `prefetch` compose and hand out the same masks.  With cnn=True, augment > 0,
+    masked=True or pack= it raises ValueError, and so it does without kmer=.
 
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
@@ -84,7 +93,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
     NUCLEOTIDE_KEYS = ("DNA", "DNA4", "DNA5")
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
-                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False):
+                 crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False,
+                 kmer_mlm=False, kmer_span=None):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -135,6 +145,14 @@ class FlatFileDataset(torch.utils.data.Dataset):
             if cnn or augment or masked or kmer is not None:
                 raise ValueError("pack= gives packed token rows of the plain batch: it cannot be combined with cnn=True, augment > 0, "
                                  "masked=True or kmer= (masked-LM batches over packed rows: pack_mlm=True)")
+        self.kmer_mlm = bool(kmer_mlm)
+        self.kmer_span = None if kmer_span is None else int(kmer_span)
+        if self.kmer_mlm:
+            if self.kmer is None:
+                raise ValueError("kmer_mlm=True masks the k-mer batches of kmer=: give kmer=k with it")
+            if cnn or augment or masked or pack is not None:  # (the first three are refused by kmer= above)
+                raise ValueError("kmer_mlm=True cannot be combined with cnn=True, augment > 0, masked=True or pack=")
+            kmers.span_anchor_prob(maskfrac, -(-self.kmer // self.kmer_stride) if self.kmer_span is None else self.kmer_span)  # (checked here)
         self.pack_mlm = bool(pack_mlm)
         if self.pack_mlm and pack is None:
             raise ValueError("pack_mlm=True masks the packed batches of pack=: give pack='nextfit' or pack='stream' with it")
@@ -208,6 +226,11 @@ class FlatFileDataset(torch.utils.data.Dataset):
                                                       frac=self.maskfrac, seed=mask_seed, first_row=first_row,
                                                       validate=not self._trusted_lengths)[:4])
 
+    def _encode_kmer_mlm(self, chars, offs, mask_seed, first_row):
+        return kmers.kmer_mlm_tokenize_packed(self.tokenizer, chars, offs, self.kmer, self.max_seq_len, self.token_dtype, True,
+                                              stride=self.kmer_stride, frac=self.maskfrac, span=self.kmer_span, seed=mask_seed,
+                                              first_row=first_row, validate=not self._trusted_lengths)
+
     def _encode(self, chars, offs):
         """augment_seq, then encode (bioseq/loaders.py:83-84, :102-103) on the batch's own copy.  Token rows go through the
         one-call entry `blosum.augment_tokenize_packed` (one launch for int8 rows; the entry runs the two launches for the
@@ -240,6 +263,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_masked(*self._packed_device(start, stop), self._mask_key(), 0)
         if self.pack_mlm:
             return self._encode_pack_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
+        if self.kmer_mlm:
+            return self._encode_kmer_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
         return self._encode(*self._packed_device(start, stop))
 
     def _index(self, i):
@@ -267,6 +292,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_masked(*packed, self._mask_key(), 0)
         if self.pack_mlm:
             return self._encode_pack_mlm(*packed, self._mask_key(), 0)
+        if self.kmer_mlm:
+            return self._encode_kmer_mlm(*packed, self._mask_key(), 0)
         return self._encode(*packed)
 
     def batches(self, batch_size, shuffle=True, drop_last=False, generator=None, prefetch=None, group=1):
@@ -301,11 +328,11 @@ class FlatFileDataset(torch.utils.data.Dataset):
             raise ValueError("batch_size must be positive")
         if self.pack is not None and int(group) > 1:
             raise ValueError("group > 1 cannot be combined with pack=: a super-batch's row blocks are not the batches' own packings")
-        pairs = self.masked or self.pack is not None  # a batch is a tuple of tensors
+        pairs = self.masked or self.pack is not None or self.kmer_mlm  # a batch is a tuple of tensors
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
-        mask_seed = self._mask_key() if self.masked or self.pack_mlm else None
+        mask_seed = self._mask_key() if self.masked or self.pack_mlm or self.kmer_mlm else None
         crop_seed = self._crop_key() if self._views else None
 
         def encode(first):
@@ -317,13 +344,15 @@ class FlatFileDataset(torch.utils.data.Dataset):
                 return self._encode_masked(*packed, mask_seed, first)
             if self.pack_mlm:
                 return self._encode_pack_mlm(*packed, mask_seed, first)
+            if self.kmer_mlm:
+                return self._encode_kmer_mlm(*packed, mask_seed, first)
             return self._encode(*packed)
 
         def hand_out(big):
             rows = big[0].shape[0] if pairs else big.shape[0]
             if rows <= batch_size or self.pack is not None:
                 yield big
-            elif self.masked:
+            elif self.masked or self.kmer_mlm:
                 for r in range(0, rows, batch_size):
                     yield big[0][r:r + batch_size], big[1][r:r + batch_size]
             else:
@@ -388,7 +417,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
             s, e, st = index.indices(len(self))
             return self.__getitems__(list(range(s, e, st)))
         index = self._index(index)
-        if self.masked or self.pack is not None:
+        if self.masked or self.pack is not None or self.kmer_mlm:
             return tuple(t[0] for t in self.get_batch(index, index + 1))
         return self.get_batch(index, index + 1)[0]
 

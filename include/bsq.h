@@ -37,7 +37,8 @@ extern "C" {
                            * bsq_kmer_unk_id, bsq_kmer_bos_id, bsq_kmer_eos_id, bsq_kmer_pad_id, bsq_kmer_count, bsq_kmer_tokenize_device,
                            * bsq_kmer_tokenize_host, bsq_kmer_kernel_name, bsq_pack_plan_device, bsq_pack_plan_host, bsq_pack_plan_parallel_host,
                            * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name, bsq_pack_mlm_tokenize_device,
-                           * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name; nothing removed */
+                           * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name, bsq_kmer_mlm, bsq_kmer_mlm_anchor_prob,
+                           * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -445,6 +446,72 @@ bsq_status bsq_kmer_tokenize_host(const bsq_desc *d, const uint8_t *chars, const
 /* Host only: the kernel bsq_kmer_tokenize_device takes for this shape ("k_kmer_bp<s1>", "k_kmer_bp<sk>", "k_kmer_generic"), from the
  * predicate the launch uses; "" for arguments the device call refuses. */
 const char *bsq_kmer_kernel_name(const bsq_desc *d, const bsq_kmer *km, int64_t B, int64_t P, int32_t batch_first, bsq_dtype t);
+
+/* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
+ * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
+ * selection is made of contiguous runs of `span` windows, each opened by an anchor.  Inputs and labels of a packed batch in ONE launch,
+ * with bsq_kmer's ids and positions.
+ *
+ * THE DRAW.  n is the number of windows the row holds (bsq_kmer's rule, clamp included), id_j the plain id of window j, V = A^k,
+ * UNK = V; row = first_row + i for sequence i of the batch.  With mix64 the splitmix64 finalizer and T_x = floor(p_x * 65536 + 0.5):
+ *     h_row       = mix64((seed ^ 0x4B4D45524D4C4D53) + 0x9E3779B97F4A7C15 * (row + 1))    a domain of its own: not bsq_mlm's stream
+ *     w(q)        = mix64(h_row + 0xD1342543DE82EF95 * (q + 1))                             one word per 4 window indices
+ *     anchor(a)   <=>  a >= 0  and  ((w(a >> 2) >> (16 * (a & 3))) & 0xFFFF) < T_anchor       independent of the characters
+ *     covered(j)  <=>  some a in [max(0, j - span + 1), j] has anchor(a)                     an anchor opens the span [a, a + span)
+ *     selected(j) <=>  covered(j) and 0 <= j < n and id_j != UNK
+ *     v           = mix64(~h_row + 0xD1342543DE82EF95 * (j + 1))                            selected windows only
+ *     cat16 = v & 0xFFFF,  rnd32 = (v >> 16) & 0xFFFFFFFF
+ *     input       = mask_token                 if cat16 < T_mask
+ *                   (rnd32 * V) >> 32          if cat16 < T_mask + T_random    (a uniform plain id; 32 bits because V reaches 2^24)
+ *                   id_j                       otherwise
+ *     label       = id_j if selected(j) else ignore_index
+ * BOS, EOS, PAD and UNK positions are never selected: they carry bsq_kmer's value in the inputs and ignore_index in the labels.  A
+ * window's fate depends on (seed, row, j, span, the thresholds) and its own id only -- never on padlen, layout, element types, batch
+ * size, shards, pieces or the stream.  anchor_prob = 0: the inputs are bsq_kmer_tokenize_device's output, bit for bit, and no label is
+ * set; anchor_prob = 1: every non-UNK window is selected.  The struct carries the anchor probability, not the share of selected
+ * windows (no pow() between this rule and a bit-exact twin): bsq_kmer_mlm_anchor_prob(frac, span) = 1 - (1 - frac)^(1 / span) is the
+ * anchor rate at which a share `frac` of the windows of a long row is covered (a negative bsq_status, as a double, for frac outside
+ * [0, 1] or span outside 1 .. 16).
+ *
+ * Known answers (DNA4, k = 3, s = 1, P = 8, span = 3, anchor_prob = 0.5, mask_prob = 0.8, random_prob = 0.1, mask_token = vocab,
+ * ignore_index = -100 written as "-", seed = 7, first_row = 0; the batch ACGTAC, ACGNACGT, AC, "", TTTTTTT of bsq_kmer's known answers,
+ * rows 0, 1 and 4), no flags (mask_token 65):
+ *     ACGTAC   -> inputs 65 65 47 65 0 0 0 0     labels 6 27 44 49 - - - -
+ *     ACGNACGT -> inputs 6 64 64 64 65 65 0 0    labels - - - - 6 27 - -
+ *     TTTTTTT  -> inputs 65 38 63 63 65 0 0 0    labels 63 63 63 63 63 - - -
+ * with BOS, EOS and PAD (mask_token 68): ACGTAC -> inputs 65 68 68 47 68 66 67 67, labels - 6 27 44 49 - - -; with anchor_prob = 0.3
+ * and no flags: TTTTTTT -> inputs 63 38 63 63 63 0 0 0, labels - 63 63 63 - - - -.
+ *
+ * Refused before anything is launched, BSQ_ERR_INVALID_ARG: everything bsq_kmer_tokenize_device refuses, a probability outside [0, 1]
+ * or NaN, mask_prob + random_prob > 1, span outside 1 .. 16, first_row < 0, mask_token < 0, both outputs NULL; BSQ_ERR_DTYPE: an
+ * input type that cannot hold max(vocab - 1, mask_token) (BSQ_I8: 127, BSQ_I16: 32767), a label type that cannot hold V - 1.
+ * Conventions of the neighbouring entry points: stream-ordered, never synchronises, B == 0 is BSQ_OK with nothing launched, either
+ * output may be NULL (not both); all six bsq_dtypes for each output, values converted as bsq_mlm_tokenize_device converts them.
+ * Kernels: (B, P) with stride 1 -> k_kmer_mlm_bp<s1>, (B, P) with stride k, 2 <= k <= 8 -> k_kmer_mlm_bp<sk> (k_kmer_bp's lanes: 16
+ * positions each, their anchor bits as one 32-bit mask, at most nine selection hashes, one replacement hash per selected window),
+ * everything else -> k_kmer_mlm_generic (one thread per element: correct, not tuned). */
+typedef struct bsq_kmer_mlm {
+    double anchor_prob;   /* share of the window indices that open a span, in [0, 1] */
+    double mask_prob;     /* of the selected: replaced by mask_token (BERT: 0.8) */
+    double random_prob;   /* of the selected: replaced by a uniform plain id (BERT: 0.1); the rest keep their id */
+    int32_t span;         /* consecutive windows an anchor selects, 1 .. 16 */
+    int64_t mask_token;   /* usually bsq_kmer_vocab_size(): one past the last id */
+    int64_t ignore_index; /* label of every position that is not selected (torch: -100) */
+    uint64_t seed;
+    int64_t first_row;    /* row key of the batch's first sequence (a shard or a piece of a larger batch: its first row there) */
+} bsq_kmer_mlm;
+double bsq_kmer_mlm_anchor_prob(double frac, int32_t span);
+bsq_status bsq_kmer_mlm_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                        int32_t batch_first, const bsq_kmer *km, const bsq_kmer_mlm *m, bsq_dtype in_dtype,
+                                        void *inputs_or_null, bsq_dtype label_dtype, void *labels_or_null, void *hip_stream);
+/* CPU twin on host buffers (the same element code; no device is needed). */
+bsq_status bsq_kmer_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                      int32_t batch_first, const bsq_kmer *km, const bsq_kmer_mlm *m, bsq_dtype in_dtype,
+                                      void *inputs_or_null, bsq_dtype label_dtype, void *labels_or_null);
+/* Host only: the kernel bsq_kmer_mlm_tokenize_device takes for this shape ("k_kmer_mlm_bp<s1>", "k_kmer_mlm_bp<sk>",
+ * "k_kmer_mlm_generic"), from the predicate the launch uses; "" for arguments the device call refuses. */
+const char *bsq_kmer_mlm_kernel_name(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_mlm *m, int64_t B, int64_t P,
+                                     int32_t batch_first, bsq_dtype in_dtype, bsq_dtype label_dtype);
 
 /* ---- sequence packing: several sequences per token row.  Every other encode path writes one sequence per row and fills the rest with
  * PAD; a transformer pays for every position of the matrix, and at protein-like or read-like length distributions most of them are
