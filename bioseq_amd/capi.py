@@ -144,6 +144,7 @@ def load():
         "bsq_kmer_bos_id": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_eos_id": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_pad_id": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_dtype_holds": (i32, [c_int, i64, i64]),
         "bsq_kmer_count": (i64, [ctypes.POINTER(Kmer), i64]),
         "bsq_kmer_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp, vp]),
         "bsq_kmer_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), c_int, vp]),

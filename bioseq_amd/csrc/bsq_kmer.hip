@@ -187,8 +187,8 @@ bsq_status check_shape(const bsq_desc *d, const bsq_kmer *km, int64_t B, int64_t
     const char *why = "";
     if (bsq_kmerd::make_geometry(d, km, g, &why) != BSQ_OK) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, why);
     if (t < BSQ_I8 || t > BSQ_F64) return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
-    if (t == BSQ_I8 && g->vocab > 128) return bsq_internal::set_error(BSQ_ERR_DTYPE, "the k-mer vocabulary does not fit int8 (vocab > 128)");
-    if (t == BSQ_I16 && g->vocab > 32768) return bsq_internal::set_error(BSQ_ERR_DTYPE, "the k-mer vocabulary does not fit int16 (vocab > 32768)");
+    if (!bsq_kmerd::holds(t, 0, static_cast<int64_t>(g->vocab) - 1))
+        return bsq_internal::set_error(BSQ_ERR_DTYPE, "the element type cannot hold every id of the k-mer vocabulary (0 .. vocab - 1)");
     return BSQ_OK;
 }
 
@@ -233,6 +233,8 @@ int64_t bsq_kmer_unk_id(const bsq_desc *d, const bsq_kmer *km) { return geometry
 int64_t bsq_kmer_bos_id(const bsq_desc *d, const bsq_kmer *km) { return geometry_value(d, km, 2); }
 int64_t bsq_kmer_eos_id(const bsq_desc *d, const bsq_kmer *km) { return geometry_value(d, km, 3); }
 int64_t bsq_kmer_pad_id(const bsq_desc *d, const bsq_kmer *km) { return geometry_value(d, km, 4); }
+
+int32_t bsq_dtype_holds(bsq_dtype t, int64_t lo, int64_t hi) { return bsq_kmerd::holds(t, lo, hi) ? 1 : 0; }
 
 int64_t bsq_kmer_count(const bsq_kmer *km, int64_t L) {
     if (!km || km->k < 1 || km->stride < 1)

@@ -15,7 +15,24 @@
 namespace bsq_kmerd {
 
 constexpr int32_t kMaxK = 16;
-constexpr int64_t kMaxPlain = int64_t(1) << 24;  // A^k: every id is exact in f32
+constexpr int64_t kMaxPlain = int64_t(1) << 24;  // A^k: every PLAIN id and UNK (= A^k) is exact in f32; BOS / EOS / PAD behind it need not be
+
+// THE RULE of the element types of both k-mer families (include/bsq.h, "what an element type holds"; bsq_dtype_holds is this function):
+// every integer of [lo, hi] converts to `t` and back unchanged.  The integer types hold their own range, BSQ_U64 every int64 as its bits,
+// the float types the integers up to 2^mantissa (2^24 + 1 is the first one f32 rounds).
+inline bool holds(bsq_dtype t, int64_t lo, int64_t hi) {
+    int64_t mag;  // the type holds [-mag - (two's complement ? 1 : 0), mag]
+    switch (t) {
+    case BSQ_I8: mag = 127; break;
+    case BSQ_I16: mag = 32767; break;
+    case BSQ_I32: mag = 2147483647; break;
+    case BSQ_U64: return true;
+    case BSQ_F32: return lo >= -(int64_t(1) << 24) && hi <= (int64_t(1) << 24);
+    case BSQ_F64: return lo >= -(int64_t(1) << 53) && hi <= (int64_t(1) << 53);
+    default: return false;
+    }
+    return lo >= -mag - 1 && hi <= mag;
+}
 
 struct Geometry {
     int64_t V;    // A^k: plain ids are 0 .. V - 1, UNK = V

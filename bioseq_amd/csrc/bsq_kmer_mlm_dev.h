@@ -89,10 +89,10 @@ inline bsq_status check_args(const bsq_desc *d, const uint8_t *chars, const int6
     if (buffers && !inputs && !labels) return set_error(BSQ_ERR_INVALID_ARG, "both outputs are null");
     if (in_dtype < BSQ_I8 || in_dtype > BSQ_F64 || label_dtype < BSQ_I8 || label_dtype > BSQ_F64) return set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
     const int64_t top = m->mask_token > g->vocab - 1 ? m->mask_token : g->vocab - 1;
-    if ((in_dtype == BSQ_I8 && top > 127) || (in_dtype == BSQ_I16 && top > 32767))
-        return set_error(BSQ_ERR_DTYPE, "the input type cannot hold the k-mer vocabulary and mask_token");
-    if ((label_dtype == BSQ_I8 && g->V - 1 > 127) || (label_dtype == BSQ_I16 && g->V - 1 > 32767))
-        return set_error(BSQ_ERR_DTYPE, "the label type cannot hold the plain k-mer ids");
+    if (!bsq_kmerd::holds(in_dtype, 0, top)) return set_error(BSQ_ERR_DTYPE, "the input type cannot hold the k-mer vocabulary and mask_token");
+    const int64_t ign = m->ignore_index;
+    if (!bsq_kmerd::holds(label_dtype, ign < 0 ? ign : 0, ign > g->V - 1 ? ign : g->V - 1))
+        return set_error(BSQ_ERR_DTYPE, "the label type cannot hold the plain k-mer ids and ignore_index");
     if (buffers && B > 0 && (!offsets || !chars)) return set_error(BSQ_ERR_INVALID_ARG, "chars or offsets is null");
     dr->th.anchor = bsq_mlmd::threshold(m->anchor_prob);
     dr->th.mask = bsq_mlmd::threshold(m->mask_prob);

@@ -45,12 +45,12 @@ def _kmer(tok, k, stride=1):
 
 
 def _dtype(desc, km, destchar):
-    """capi.dtype_of, refusing an element type the vocabulary does not fit (the library's BSQ_ERR_DTYPE) as a ValueError."""
+    """capi.dtype_of, refusing an element type that cannot hold every id of the vocabulary (the library's BSQ_ERR_DTYPE, by its own
+    rule `bsq_dtype_holds`) as a ValueError."""
     dt, tdt = capi.dtype_of(destchar)
     vocab = _lib.bsq_kmer_vocab_size(ctypes.byref(desc), ctypes.byref(km))
-    limit = {capi.I8: 128, capi.I16: 32768}.get(dt)
-    if limit is not None and vocab > limit:
-        raise ValueError("a vocabulary of %d ids does not fit destchar %r (at most %d)" % (vocab, destchar, limit))
+    if not _lib.bsq_dtype_holds(dt, 0, vocab - 1):
+        raise ValueError("destchar %r cannot hold every id of a vocabulary of %d (the rule is in include/bsq.h, bsq_dtype_holds)" % (destchar, vocab))
     return dt, tdt
 
 
@@ -216,17 +216,18 @@ def _kmer_mlm(tok, k, stride, destchar, label_destchar, frac, span, anchor_prob,
     dt, tdt = capi.dtype_of(destchar)
     ldt, ltdt = capi.dtype_of(label_destchar)
     top = max(vocab - 1, m.mask_token)
-    limit = {capi.I8: 127, capi.I16: 32767}
-    if top > limit.get(dt, top):
-        raise ValueError("ids up to %d (vocabulary and mask token) do not fit destchar %r" % (top, destchar))
-    if desc.nchars ** km.k - 1 > limit.get(ldt, 2 ** 24):
-        raise ValueError("plain ids up to %d do not fit label_destchar %r" % (desc.nchars ** km.k - 1, label_destchar))
+    if not _lib.bsq_dtype_holds(dt, 0, top):
+        raise ValueError("destchar %r cannot hold ids up to %d (vocabulary and mask token)" % (destchar, top))
+    last = desc.nchars ** km.k - 1
+    if not _lib.bsq_dtype_holds(ldt, min(m.ignore_index, 0), max(m.ignore_index, last)):
+        raise ValueError("label_destchar %r cannot hold plain ids up to %d and ignore_index %d" % (label_destchar, last, m.ignore_index))
     return desc, km, m, dt, ldt, tdt, ltdt
 
 
-def kmer_mlm_kernel_name(tok, k, B, padlen, destchar="q", batch_first=True, *, stride=1, label_destchar="q"):
-    """The kernel `kmer_mlm_tokenize_packed` takes for this shape (host only: profiling labels, tests)."""
-    desc, km, m, dt, ldt, _, _ = _kmer_mlm(tok, k, stride, destchar, label_destchar, 0.15, None, None, 0.8, 0.1, None, -100, 0, 0)
+def kmer_mlm_kernel_name(tok, k, B, padlen, destchar="q", batch_first=True, *, stride=1, label_destchar="q", mask_token=None, ignore_index=-100):
+    """The kernel `kmer_mlm_tokenize_packed` takes for this shape (host only: profiling labels, tests).  mask_token and ignore_index
+    matter only to the element-type rule: a call the encode would refuse is a ValueError here too."""
+    desc, km, m, dt, ldt, _, _ = _kmer_mlm(tok, k, stride, destchar, label_destchar, 0.15, None, None, 0.8, 0.1, mask_token, ignore_index, 0, 0)
     return _lib.bsq_kmer_mlm_kernel_name(ctypes.byref(desc), ctypes.byref(km), ctypes.byref(m), int(B), int(padlen), int(bool(batch_first)),
                                          dt, ldt).decode()
 

@@ -71,7 +71,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
     `maskfrac` of the windows is selected, then BERT's 80/10/10 replacement with mask token = kmers.kmer_vocab_size; labels int64 with
     ignore_index -100.  Keyed like masked=True: a fresh key per call and per `batches()` epoch, a row keyed by its index in the epoch's
     order -- crop, revcomp_frac, shuffle, `group` and `prefetch` compose and hand out the same masks.  With cnn=True, augment > 0,
-    masked=True or pack= it raises ValueError, and so it does without kmer=.
+    masked=True or pack= it raises ValueError, and so it does without kmer=.  `token_dtype` must hold every id and the mask token
+    (the rule of include/bsq.h): 'f' at nchars ** kmer = 2 ** 24 (DNA4 kmer=12) cannot, and the first batch raises ValueError.
 
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out

@@ -38,7 +38,7 @@ extern "C" {
                            * bsq_kmer_tokenize_host, bsq_kmer_kernel_name, bsq_pack_plan_device, bsq_pack_plan_host, bsq_pack_plan_parallel_host,
                            * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name, bsq_pack_mlm_tokenize_device,
                            * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name, bsq_kmer_mlm, bsq_kmer_mlm_anchor_prob,
-                           * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name; nothing removed */
+                           * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -411,11 +411,22 @@ bsq_status bsq_complement_table(uint8_t out[256]);
  *     n_tok(L) = 0 if L < k else (L - k) / s + 1        window j covers characters [j*s, j*s + k); a tail shorter than k is dropped
  *     row      = [BOS] id_0 .. id_{n-1} [EOS] PAD ...   n = min(n_tok(L), max(P - bos - eos, 0)): over-long rows are clamped, memory-safe
  * (a row is cut at P positions: P = 1 with BOS and EOS holds the BOS alone).  Output (B, P) when batch_first else (P, B), C-contiguous,
- * every element written exactly once; all six bsq_dtypes, values converted as bsq_tokenize_device converts tokens.
+ * every element written exactly once; all six bsq_dtypes, and every stored value is exact in its type (the rule below).
  *
- * Limits, checked before anything is launched: 1 <= k <= 16, s >= 1, A >= 1, A^k <= 2^24 (every id is exact in f32: DNA4 up to
- * k = 12, AMINO20 up to k = 5) -- otherwise BSQ_ERR_INVALID_ARG; BSQ_I8 needs vocab <= 128, BSQ_I16 vocab <= 32768 -- otherwise
- * BSQ_ERR_DTYPE.  A row fits (nothing is clamped) iff L <= (P - bos - eos) * s + k - 1: for the reference-style length check call
+ * Limits, checked before anything is launched: 1 <= k <= 16, s >= 1, A >= 1, A^k <= 2^24 (every plain id and UNK = A^k is exact in
+ * f32: DNA4 up to k = 12, AMINO20 up to k = 5) -- otherwise BSQ_ERR_INVALID_ARG; an element type that cannot hold every id it may
+ * store, [0, vocab - 1] -- otherwise BSQ_ERR_DTYPE.
+ *
+ * WHAT AN ELEMENT TYPE HOLDS (bsq_dtype_holds; the one rule of this family and of the k-mer masked-LM): a type holds [lo, hi] when
+ * every integer in it converts to the type and back unchanged --
+ *     BSQ_I8  [-128, 127]     BSQ_I16  [-32768, 32767]     BSQ_I32  [-2^31, 2^31 - 1]     BSQ_U64  every int64 (its bits)
+ *     BSQ_F32 |x| <= 2^24     BSQ_F64  |x| <= 2^53
+ * So BSQ_I8 needs vocab <= 128 and BSQ_I16 vocab <= 32768, and at V = 2^24 (DNA4 k = 12, SEB8 k = 8, BYTES k = 3) BSQ_F32 is
+ * accepted only without BOS, EOS and PAD (the top id is then UNK = 2^24): BOS = 2^24 + 1 would store as 2^24, which is UNK, and
+ * PAD = 2^24 + 3 as 2^24 + 4, one past the embedding table.  Every smaller vocabulary (AMINO20 k = 5, PURPYR k = 16) fits BSQ_F32 with
+ * every flag; BSQ_I32, BSQ_U64 and BSQ_F64 hold every vocabulary that is allowed.
+ *
+ * A row fits (nothing is clamped) iff L <= (P - bos - eos) * s + k - 1: for the reference-style length check call
  * bsq_validate_packed_device with that bound as its P and bos = eos = 0.
  *
  * Known answers (DNA4, k = 3, s = 1, P = 8, no flags): ACGTAC -> 6 27 44 49 0 0 0 0; ACGNACGT -> 6 64 64 64 6 27 0 0; TTTTTTT -> 63 63 63 63 63 0 0 0;
@@ -436,6 +447,8 @@ int64_t bsq_kmer_unk_id(const bsq_desc *d, const bsq_kmer *km);
 int64_t bsq_kmer_bos_id(const bsq_desc *d, const bsq_kmer *km);
 int64_t bsq_kmer_eos_id(const bsq_desc *d, const bsq_kmer *km);
 int64_t bsq_kmer_pad_id(const bsq_desc *d, const bsq_kmer *km);
+/* 1 when `t` holds every integer of [lo, hi] (the table above), else 0 (an unknown bsq_dtype: 0). */
+int32_t bsq_dtype_holds(bsq_dtype t, int64_t lo, int64_t hi);
 /* n_tok(L) (0 for L < k); a negative bsq_status for a null km, k < 1 or stride < 1. */
 int64_t bsq_kmer_count(const bsq_kmer *km, int64_t L);
 bsq_status bsq_kmer_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
@@ -483,10 +496,12 @@ const char *bsq_kmer_kernel_name(const bsq_desc *d, const bsq_kmer *km, int64_t 
  * and no flags: TTTTTTT -> inputs 63 38 63 63 63 0 0 0, labels - 63 63 63 - - - -.
  *
  * Refused before anything is launched, BSQ_ERR_INVALID_ARG: everything bsq_kmer_tokenize_device refuses, a probability outside [0, 1]
- * or NaN, mask_prob + random_prob > 1, span outside 1 .. 16, first_row < 0, mask_token < 0, both outputs NULL; BSQ_ERR_DTYPE: an
- * input type that cannot hold max(vocab - 1, mask_token) (BSQ_I8: 127, BSQ_I16: 32767), a label type that cannot hold V - 1.
+ * or NaN, mask_prob + random_prob > 1, span outside 1 .. 16, first_row < 0, mask_token < 0, both outputs NULL; BSQ_ERR_DTYPE, by
+ * bsq_kmer's rule of what an element type holds (bsq_dtype_holds): an input type that does not hold [0, max(vocab - 1, mask_token)],
+ * a label type that does not hold [min(ignore_index, 0), max(ignore_index, V - 1)] -- ignore_index = -1000 into BSQ_I8 labels would
+ * read as the plain id 24, and the default mask_token = vocab does not fit BSQ_F32 at V = 2^24.
  * Conventions of the neighbouring entry points: stream-ordered, never synchronises, B == 0 is BSQ_OK with nothing launched, either
- * output may be NULL (not both); all six bsq_dtypes for each output, values converted as bsq_mlm_tokenize_device converts them.
+ * output may be NULL (not both); all six bsq_dtypes for each output, every stored value exact in its type.
  * Kernels: (B, P) with stride 1 -> k_kmer_mlm_bp<s1>, (B, P) with stride k, 2 <= k <= 8 -> k_kmer_mlm_bp<sk> (k_kmer_bp's lanes: 16
  * positions each, their anchor bits as one 32-bit mask, at most nine selection hashes, one replacement hash per selected window),
  * everything else -> k_kmer_mlm_generic (one thread per element: correct, not tuned). */

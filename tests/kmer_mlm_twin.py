@@ -83,6 +83,18 @@ def mlm(lut, A, chars, offsets, k, s, P, bos=False, eos=False, padchar=False, *,
     return inputs, labels
 
 
+def fates(seed, row, sel, mask_prob, random_prob):
+    """int8[n] per window of batch row `row` (first_row included): 0 not selected, 1 mask token, 2 random id, 3 keeps its id -- the
+    category of the replacement word, for the tests that look at one branch (sel: the row's `selected` of mlm()'s details)."""
+    h = row_key(seed, row)
+    tm, tr = threshold(mask_prob), threshold(mask_prob) + threshold(random_prob)
+    out = np.zeros(len(sel), dtype=np.int8)
+    for j in np.flatnonzero(sel):
+        cat = mix64((~h & M64) + STEP * (int(j) + 1)) & 0xFFFF
+        out[j] = 1 if cat < tm else (2 if cat < tr else 3)
+    return out
+
+
 def matrices(*a, batch_first=True, in_dtype=np.int64, label_dtype=np.int64, **kw):
     """What bsq_kmer_mlm_tokenize_* writes: (B, P) or (P, B), C-contiguous, in the element types (int64 -> uint64 keeps the bits)."""
     inputs, labels = mlm(*a, **kw)

@@ -74,3 +74,39 @@ def rows_fast(lut, A, chars, offsets, k, s, P, bos=False, eos=False, padchar=Fal
         ok = at < P
         out[np.arange(B)[ok], at[ok]] = sp["eos"]
     return out
+
+
+# What an element type holds (include/bsq.h, "what an element type holds"), restated as a table: bsq_dtype code -> [lo, hi], the integers
+# that survive the conversion to the type and back.  The host tests check the table itself by doing that conversion with numpy.
+HOLDS = {0: (-2 ** 7, 2 ** 7 - 1), 1: (-2 ** 15, 2 ** 15 - 1), 2: (-2 ** 31, 2 ** 31 - 1), 3: (-2 ** 63, 2 ** 63 - 1), 4: (-2 ** 24, 2 ** 24),
+         5: (-2 ** 53, 2 ** 53)}
+
+
+def holds(dt, lo, hi):
+    r = HOLDS.get(dt)
+    return r is not None and r[0] <= lo and hi <= r[1]
+
+
+def back(a):
+    """A matrix the library wrote, as int64 values (uint64 holds an int64's bits): the comparison that does not pass through the
+    element type on the expected side."""
+    a = np.asarray(a)
+    return a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64)
+
+
+def edge_bytes(lut, A, k):
+    """(first, last, unmapped, top): a byte of class 0, a byte of the highest class the table maps, an unmapped byte, and the id of k
+    copies of `last` -- V - 1, except under BYTES, whose int8 table maps the bytes below 0x80 only (its top id is 127 * (V - 1) / 255)."""
+    lut = np.asarray(lut, dtype=np.int64)
+    A_top = int(lut.max())
+    first, last = int(np.flatnonzero(lut == 0)[0]), int(np.flatnonzero(lut == A_top)[0])
+    return first, last, int(np.flatnonzero(lut < 0)[-1]), sum(A_top * A ** i for i in range(k))
+
+
+def edge_pool(lut):
+    """Bytes to draw random sequences from: the first byte of every mapped class, about one unmapped byte in 25."""
+    lut = np.asarray(lut, dtype=np.int64)
+    firsts = np.array([np.flatnonzero(lut == c)[0] for c in range(int(lut.max()) + 1)], dtype=np.uint8)
+    unmapped = np.flatnonzero(lut < 0).astype(np.uint8)
+    body = np.tile(firsts, -(-48 // firsts.size))
+    return np.concatenate([body, unmapped[[0, -1] * max(1, body.size // 48)]])

@@ -27,20 +27,25 @@ def _lut(key):
     return np.array(lut, dtype=np.int8), n.value
 
 
-def _batch(rng, B, k, s, room, pool=DNA_POOL):
+def _batch(rng, B, k, s, room, pool=DNA_POOL, unmapped=ord("N"), pins=()):
     """Packed batch: rows with no window (lengths 0 and k - 1), one window, exactly `room` windows, more (clamped), random ones; a run of N
-    in the middle of some rows; the LAST row is full and ends at the last byte of chars (the guarded loads)."""
+    (`unmapped`) in the middle of some rows; the LAST row is full and ends at the last byte of chars (the guarded loads).
+    pins: (length, byte) for rows 7, 8, ...: rows of that length filled with that byte."""
     fill = (max(room, 1) - 1) * s + k
     lens = rng.integers(0, fill + 1, B).astype(np.int64)
     lens[:6] = (0, max(k - 1, 0), k, fill, fill + 2 * s + 3, 0)
     lens[-1] = fill
+    for r, (n, _) in enumerate(pins):
+        lens[7 + r] = n
     chars = rng.choice(pool, int(lens.sum())).astype(np.uint8)
     offs = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(lens, out=offs[1:])
     for b in range(6, B, 3):  # N runs of 1 .. 3 characters (inside a span, and where a span would end)
         if lens[b] > 8:
             a = int(offs[b] + rng.integers(0, lens[b] - 3))
-            chars[a:a + int(rng.integers(1, 4))] = ord("N")
+            chars[a:a + int(rng.integers(1, 4))] = unmapped
+    for r, (_, byte) in enumerate(pins):
+        chars[offs[7 + r]:offs[8 + r]] = byte
     chars[offs[-1] - 1] = ord("A")
     return chars, offs
 
@@ -97,6 +102,74 @@ def test_device_equals_the_twin_on_every_form(gpu, bsq, P):
             assert ((plain == V) & (tl != -100)).sum() == 0
     # the batch reached what it is meant to reach
     assert last_anchor > 0 and unk_in_span > 0 and rows_n0 > 0 and clamped > 0
+
+
+CODE = {"b": 0, "h": 1, "i": 2, "q": 3, "f": 4, "d": 5}
+# (kernel, key, k, stride, batch_first): the rolling-id code and the uniform replacement (rnd32 * V) >> 32 beyond DNA4 -- an alphabet
+# that is no power of two, and V = 2^24 through each of its three alphabets
+WIDE_FORMS = [(S1, "AMINO20", 5, 1, True), (SK, "AMINO20", 5, 5, True), (GEN, "AMINO20", 5, 2, True), (S1, "SEB8", 8, 1, True),
+              (SK, "SEB8", 8, 8, True), (S1, "BYTES", 3, 1, True), (SK, "BYTES", 3, 3, True), (S1, "DNA4", 12, 1, True),
+              (GEN, "AMINO20", 5, 1, False), (GEN, "DNA4", 12, 12, True)]
+
+
+@pytest.mark.parametrize("kernel, key, k, s, bf", WIDE_FORMS)
+def test_device_equals_the_twin_beyond_dna4(gpu, bsq, kernel, key, k, s, bf):
+    """The loop of test_device_equals_the_twin_on_every_form over the other alphabets, with float and int32 element types: inputs and
+    labels cast back to int64 equal the twin's int64 (never the twin through the element type).  f32 inputs run where the rule of
+    include/bsq.h accepts them -- at V = 2^24 without flags and with mask_token = 2^24 -- and f64 inputs with every flag.  Every random
+    replacement is a plain id, and over an alphabet that is no power of two the batch holds replacements from the upper half of [0, V)."""
+    import torch
+    from bioseq_amd import kmers
+    lut, A = _lut(key)
+    V, B = A ** k, 37
+    first, last, unmapped, top = kmer_twin.edge_bytes(lut, A, k)
+    pool = kmer_twin.edge_pool(lut)
+    # (flags, input type, label type): 'f' inputs only where the type holds the ids; mask_token None = the vocabulary size
+    plans = [((0, 0, 0), "f", "i"), ((1, 1, 1), "d", "f"), ((1, 0, 1), "i", "d")]
+    lab_seen, upper, n_rand, changed = set(), 0, 0, 0
+    for P, (flags, dc, ldc), span in itertools.product((40, 272), plans, (1, 16)):
+        rng = np.random.default_rng(1000 * P + 10 * k + s + span)
+        room = P - flags[0] - flags[1]
+        chars, offs = _batch(rng, B, k, s, room, pool, unmapped, pins=((k + 15 * s, last), (k + 15 * s, first)))
+        assert offs[-1] == chars.size
+        tok = _tok(bsq, key, flags)
+        sp = kmer_twin.specials(A, k, *flags)
+        mask_token = V if dc == "f" and V == 2 ** 24 else sp["vocab"]
+        assert kmer_twin.holds(CODE[dc], 0, max(sp["vocab"] - 1, mask_token)) and kmer_twin.holds(CODE[ldc], -100, V - 1)
+        kw = dict(span=span, anchor_prob=0.2, mask_prob=0.5, random_prob=0.3, mask_token=mask_token, seed=77 + span, first_row=3)
+        assert kmers.kmer_mlm_kernel_name(tok, k, B, P, dc, bf, stride=s, label_destchar=ldc, mask_token=mask_token) == kernel
+        gi, gl = kmers.kmer_mlm_tokenize_packed(tok, _dev(chars, gpu), _dev(offs, gpu), k, P, dc, bf, stride=s, label_destchar=ldc,
+                                                validate=False, **kw)
+        torch.cuda.synchronize()
+        det = []
+        ti, tl = twin.mlm(lut, A, chars, offs, k, s, P, *flags, details=det, fast=True, **kw)
+        gi, gl = gi.cpu().numpy(), gl.cpu().numpy()
+        assert gi.dtype == NP_OF[dc] and gl.dtype == NP_OF[ldc] and gi.shape == ((B, P) if bf else (P, B))
+        gi, gl = (x.astype(np.int64) if bf else x.astype(np.int64).T for x in (gi, gl))
+        assert np.array_equal(gi, ti), (kernel, P, flags, dc, span)
+        assert np.array_equal(gl, tl), (kernel, P, flags, ldc, span)
+        # the random branch, recovered from the twin's selection: plain ids only, on the device and in the twin
+        for i, (n, anch, cov, sel) in enumerate(det):
+            at = flags[0] + np.flatnonzero(twin.fates(kw["seed"], 3 + i, sel, 0.5, 0.3) == 2)
+            assert (gi[i, at] >= 0).all() and (gi[i, at] < V).all() and (tl[i, at] != -100).all()
+            upper += int((ti[i, at] >= V // 2).sum())
+            n_rand += at.size
+            changed += int((gi[i, at] != tl[i, at]).sum())
+        plain = kmer_twin.rows_fast(lut, A, chars, offs, k, s, P, *flags)
+        assert ((plain == V) & (tl != -100)).sum() == 0
+        lab_seen |= {0, top} & set(tl.reshape(-1).tolist())
+        stored = [0, top, sp["unk"], mask_token] + [sp[n] for n, on in zip(("bos", "eos", "pad"), flags) if on]
+        assert set(stored) <= set(ti.reshape(-1).tolist()), (P, flags, span)
+    assert lab_seen == {0, top} and n_rand > 200  # both ends of the plain ids were labels; the random branch is well populated
+    # a uniform draw meets the window's own id with probability 1 / V <= 20 ** -5: positions that kept their id are not in `at`
+    assert changed >= 0.99 * n_rand
+    assert upper > 20  # (replacements from the upper half of the plain ids: a product (rnd32 * V) cut to 32 bits would not get there)
+    if V == 2 ** 24:  # what the rule refuses for f32 inputs is a ValueError before any launch
+        chars, offs = _batch(np.random.default_rng(1), B, k, s, 38, pool, unmapped)
+        dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+        for flags, mt in (((0, 0, 0), None), ((1, 1, 1), V), ((0, 0, 1), V)):
+            with pytest.raises(ValueError):
+                kmers.kmer_mlm_tokenize_packed(_tok(bsq, key, flags), dch, dof, k, 40, "f", bf, stride=s, mask_token=mt, validate=False)
 
 
 @pytest.mark.parametrize("P", [4128, 4124])
@@ -176,6 +249,31 @@ def test_all_type_pairs_either_output_and_a_side_stream(gpu, bsq):
     assert call(capi.I16, bi.data_ptr(), capi.I16, None) == capi.OK
     m.mask_token = 32768
     assert call(capi.I16, bi.data_ptr(), capi.U64, None) == capi.ERR_DTYPE
+    # mask_token and ignore_index against the rule of the element types: each refusal, then its neighbour at the boundary.  The int8
+    # labels run with k = 3 (V - 1 = 63, vocab 68), where the type holds every plain id and ignore_index alone decides
+    bl = torch.full((n,), -77, dtype=torch.int64, device=gpu)
+    for kk, it, lt, mt, ign, want in ((4, capi.I32, capi.U64, 2 ** 31, -100, capi.ERR_DTYPE), (4, capi.I32, capi.U64, 2 ** 31 - 1, -100, capi.OK),
+                                      (4, capi.F32, capi.U64, 2 ** 24 + 1, -100, capi.ERR_DTYPE), (4, capi.F32, capi.U64, 2 ** 24, -100, capi.OK),
+                                      (4, capi.F64, capi.U64, 2 ** 53 + 1, -100, capi.ERR_DTYPE),
+                                      (3, capi.U64, capi.I8, 68, -129, capi.ERR_DTYPE), (3, capi.U64, capi.I8, 68, -128, capi.OK),
+                                      (3, capi.U64, capi.I8, 68, -1000, capi.ERR_DTYPE),  # (would read as the plain id 24)
+                                      (4, capi.U64, capi.I16, 260, -32769, capi.ERR_DTYPE), (4, capi.U64, capi.I16, 260, -32768, capi.OK),
+                                      (4, capi.U64, capi.F32, 260, -2 ** 24 - 1, capi.ERR_DTYPE), (4, capi.U64, capi.F32, 260, -2 ** 24, capi.OK)):
+        km.k, m.mask_token, m.ignore_index = kk, mt, ign
+        assert kmer_twin.holds(lt, 0, 4 ** kk - 1) and kmer_twin.holds(it, 0, 4 ** kk + 3)  # (so mask_token or ignore_index decides)
+        bi.fill_(-77), bl.fill_(-77)
+        assert call(it, bi.data_ptr(), lt, bl.data_ptr()) == want, (kk, it, lt, mt, ign)
+        torch.cuda.synchronize()
+        if want != capi.OK:
+            assert bool((bi == -77).all()) and bool((bl == -77).all()), (kk, it, lt, mt, ign)
+        else:  # (the buffers are int64 elements wide: a narrower type fills their first bytes)
+            ti, tl = twin.mlm(*_lut("DNA4"), big, offs, kk, 1, P, *flags, anchor_prob=0.25, span=4, mask_token=mt, ignore_index=ign, seed=11, fast=True)
+            assert (tl != ign).any() and (tl == ign).any()
+            for buf, t, exp in ((bi, it, ti), (bl, lt, tl)):
+                got = buf.cpu().numpy().view(kmer_twin.NP_DTYPES[t])[:n]
+                assert np.array_equal(kmer_twin.back(got).reshape(B, P), exp), (kk, it, lt, mt, ign)
+    km.k = 4
+    m.mask_token, m.ignore_index = 260, -100
     torch.cuda.synchronize()
     tok = _tok(bsq, "DNA4", flags)
     with pytest.raises(ValueError):

@@ -169,6 +169,7 @@ def test_every_type_pair_on_the_host():
         for got, want, t in ((gi, ti, it), (gl, tl, lt)):
             exp = want.view(np.uint64) if t == capi.U64 else want.astype(twin.NP_DTYPES[t])
             assert got.tobytes() == exp.tobytes(), (it, lt)
+            assert np.array_equal(kmer_twin.back(got), want), (it, lt)  # the values, not the twin through the type
 
 
 def test_probabilities_at_their_ends():
@@ -270,6 +271,91 @@ def test_refusals_with_their_statuses_nothing_written():
     st3, gi3, gl3, _ = _host("DNA4", (0, 0, 0), chars, offs, 3, 1, 8, _m(capi))
     assert st == st2 == st3 == capi.OK and intact and intact2 and _untouched(gl) and _untouched(gi2)
     assert np.array_equal(gi, gi3) and np.array_equal(gl2, gl3)
+
+
+# (input type, label type, mask_token, ignore_index, accepted): each refusal next to its neighbour at the boundary.  DNA4, k = 3, no flags
+# (vocab 65, V - 1 = 63), so only mask_token and ignore_index decide.
+EDGE_RULES = [
+    ("i", "q", 2 ** 31, -100, False), ("i", "q", 2 ** 31 - 1, -100, True),
+    ("f", "q", 2 ** 24 + 1, -100, False), ("f", "q", 2 ** 24, -100, True),
+    ("d", "q", 2 ** 53 + 1, -100, False), ("d", "q", 2 ** 53, -100, True),
+    ("q", "b", 65, -129, False), ("q", "b", 65, -128, True),
+    ("q", "h", 65, -32769, False), ("q", "h", 65, -32768, True),
+    ("q", "f", 65, -2 ** 24 - 1, False), ("q", "f", 65, -2 ** 24, True),
+    ("q", "b", 65, -1000, False),                                    # (would read as the plain id 24)
+    ("q", "b", 65, 128, False), ("q", "b", 65, 127, True),           # a positive ignore_index is bounded too
+    ("q", "d", 65, -2 ** 53 - 1, False), ("q", "i", 65, -2 ** 31 - 1, False), ("q", "i", 65, -2 ** 31, True),
+    ("q", "q", 2 ** 63 - 1, -2 ** 63, True),                          # 64-bit elements hold every int64
+]
+CODE = {"b": 0, "h": 1, "i": 2, "q": 3, "f": 4, "d": 5}
+
+
+@pytest.mark.parametrize("ic, lc, mask_token, ignore_index, ok", EDGE_RULES)
+def test_mask_token_and_ignore_index_must_fit_their_types(ic, lc, mask_token, ignore_index, ok):
+    """The rule of the element types (bsq_dtype_holds) on the inputs, [0, max(vocab - 1, mask_token)], and on the labels,
+    [min(ignore_index, 0), max(ignore_index, V - 1)]: refused with both buffers untouched, accepted with exact values."""
+    import bioseq_amd
+    from bioseq_amd import kmers
+    capi, L = _lib()
+    lut, A = _lut("DNA4")
+    chars, offs = _pack(SEQS + [b"ACGTTGCATGCATGCAAACCGGTT"])
+    it, lt = CODE[ic], CODE[lc]
+    assert ok == (kmer_twin.holds(it, 0, max(64, mask_token)) and kmer_twin.holds(lt, min(ignore_index, 0), max(ignore_index, 63)))
+    m = _m(capi, 0.4, mask_prob=0.5, random_prob=0.2, mask_token=mask_token, ignore_index=ignore_index, seed=3)
+    st, gi, gl, intact = _host("DNA4", (0, 0, 0), chars, offs, 3, 1, 20, m, it, lt)
+    d, km = capi.make_desc("DNA4"), capi.Kmer(3, 1)
+    name = L.bsq_kmer_mlm_kernel_name(ctypes.byref(d), ctypes.byref(km), ctypes.byref(m), 6, 20, 1, it, lt)
+    tok = bioseq_amd.Tokenizer("DNA4")
+    kw = dict(anchor_prob=0.4, span=3, mask_prob=0.5, random_prob=0.2, mask_token=mask_token, ignore_index=ignore_index, seed=3, label_destchar=lc)
+    if not ok:
+        assert st == capi.ERR_DTYPE and intact and _untouched(gi) and _untouched(gl)
+        assert L.bsq_last_error() != b"" and name == b""
+        # the device call refuses the same arguments before it touches a device (host pointers are never read)
+        out = np.full(6 * 20 * 8, 0xAB, dtype=np.uint8)
+        assert L.bsq_kmer_mlm_tokenize_device(ctypes.byref(d), chars.ctypes.data, offs.ctypes.data, 6, 20, 1, ctypes.byref(km), ctypes.byref(m),
+                                              it, out.ctypes.data, lt, out.ctypes.data, None) == capi.ERR_DTYPE
+        assert (out == 0xAB).all()
+        with pytest.raises(ValueError):
+            kmers.kmer_mlm_tokenize_host(tok, chars, offs, 3, 20, ic, **kw)
+        return
+    assert st == capi.OK and intact and name == b"k_kmer_mlm_bp<s1>"
+    ti, tl = twin.mlm(lut, A, chars, offs, 3, 1, 20, anchor_prob=0.4, span=3, mask_prob=0.5, random_prob=0.2, mask_token=mask_token,
+                      ignore_index=ignore_index, seed=3)
+    assert (ti == mask_token).any() and (tl == ignore_index).any() and (tl != ignore_index).any()
+    assert np.array_equal(kmer_twin.back(gi), ti) and np.array_equal(kmer_twin.back(gl), tl)
+    pi, pl = kmers.kmer_mlm_tokenize_host(tok, chars, offs, 3, 20, ic, **kw)
+    assert np.array_equal(kmer_twin.back(pi), ti) and np.array_equal(kmer_twin.back(pl), tl)
+
+
+def test_float_inputs_at_the_largest_vocabulary():
+    """V = 2^24 (DNA4, k = 12): f32 inputs are accepted only without BOS / EOS / PAD and with a mask_token <= 2^24 -- the default, the
+    vocabulary size 2^24 + 1, is not --; f64 and the integer types take every flag."""
+    import bioseq_amd
+    from bioseq_amd import kmers
+    capi, _ = _lib()
+    lut, A = _lut("DNA4")
+    chars, offs = _pack([b"T" * 14, b"A" * 13, b"ACGTACGTACGTNACGTACGTACGTA", b""])
+    V = 4 ** 12
+    for flags in FLAGS:
+        vocab = kmer_twin.specials(A, 12, *flags)["vocab"]
+        for mt in (V, vocab):
+            m = _m(capi, 0.5, 0.5, 0.3, span=2, mask_token=mt, seed=5)
+            ti, tl = twin.mlm(lut, A, chars, offs, 12, 1, 8, *flags, anchor_prob=0.5, span=2, mask_prob=0.5, random_prob=0.3, mask_token=mt, seed=5)
+            for it, lt in ((capi.F32, capi.F32), (capi.F64, capi.F32), (capi.I32, capi.F64)):
+                st, gi, gl, intact = _host("DNA4", flags, chars, offs, 12, 1, 8, m, it, lt)
+                if not kmer_twin.holds(it, 0, max(vocab - 1, mt)):
+                    assert it == capi.F32 and (any(flags) or mt > V)
+                    assert st == capi.ERR_DTYPE and intact and _untouched(gi) and _untouched(gl), (flags, mt, it)
+                    continue
+                assert st == capi.OK and intact, (flags, mt, it)
+                assert np.array_equal(kmer_twin.back(gi), ti) and np.array_equal(kmer_twin.back(gl), tl), (flags, mt, it)
+        assert (tl == V - 1).any() and (ti == V).any()  # the top plain id is a label; UNK (the N) and / or the mask token read 2^24
+    plain = bioseq_amd.Tokenizer("DNA4")
+    with pytest.raises(ValueError):
+        kmers.kmer_mlm_tokenize_host(plain, chars, offs, 12, 8, "f")  # the default mask_token = vocab = 2^24 + 1
+    assert kmers.kmer_mlm_tokenize_host(plain, chars, offs, 12, 8, "f", mask_token=V)[0].dtype == np.float32
+    with pytest.raises(ValueError):
+        kmers.kmer_mlm_tokenize_host(bioseq_amd.Tokenizer("DNA4", True, True, True), chars, offs, 12, 8, "f", mask_token=V)
 
 
 def test_anchor_prob_helper():

@@ -22,15 +22,21 @@ def _lut(key):
     return np.array(lut, dtype=np.int8), n.value
 
 
-def _batch(rng, B, maxlen, k, pool=DNA_POOL, fixed=False):
-    """Packed batch whose LAST row ends at the last byte of chars; rows of length 0, < k and == k among the first ones."""
+def _batch(rng, B, maxlen, k, pool=DNA_POOL, fixed=False, pins=()):
+    """Packed batch whose LAST row ends at the last byte of chars; rows of length 0, < k and == k among the first ones.
+    pins: (length, byte or None) for rows 4, 5, ...: rows of that length, filled with that byte (None: drawn from the pool)."""
     lens = np.full(B, maxlen, dtype=np.int64) if fixed else rng.integers(0, maxlen + 1, B).astype(np.int64)
     if B > 4 and not fixed:
         lens[:4] = (0, max(k - 1, 0), k, 0)
         lens[-1] = maxlen
+    for r, (n, _) in enumerate(pins):
+        lens[4 + r] = n
     chars = rng.choice(pool, int(lens.sum())).astype(np.uint8)
     offs = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(lens, out=offs[1:])
+    for r, (_, byte) in enumerate(pins):
+        if byte is not None:
+            chars[offs[4 + r]:offs[5 + r]] = byte
     return chars, offs
 
 
@@ -112,6 +118,66 @@ def test_generic_kernel_equals_the_twin(gpu, bsq, k, s, B, P, bf, flags):
         got = kmers.kmer_tokenize_packed(tok, _dev(chars, gpu), _dev(offs, gpu), k, P, dc, bf, stride=s, validate=False)
         torch.cuda.synchronize()
         assert got.cpu().numpy().tobytes() == _expect("DNA4", flags, chars, offs, k, s, P, bf, NP_OF[dc]).tobytes(), dc
+
+
+CODE = {"b": 0, "h": 1, "i": 2, "q": 3, "f": 4, "d": 5}
+S1K, SKK, GENK = "k_kmer_bp<s1>", "k_kmer_bp<sk>", "k_kmer_generic"
+# (kernel, key, k, stride, batch_first): the vocabularies at and next to A^k = 2^24, through every kernel
+TOP_CASES = ([(S1K, key, k, 1, True) for key, k in (("DNA4", 12), ("SEB8", 8), ("BYTES", 3), ("AMINO20", 5), ("PURPYR", 16))] +
+             [(SKK, key, k, k, True) for key, k in (("SEB8", 8), ("BYTES", 3), ("AMINO20", 5))] +
+             [(GENK, key, k, 1, False) for key, k in (("DNA4", 12), ("SEB8", 8), ("BYTES", 3), ("AMINO20", 5), ("PURPYR", 16))] +
+             [(GENK, key, k, k, False) for key, k in (("SEB8", 8), ("BYTES", 3), ("AMINO20", 5))] + [(GENK, "DNA4", 12, 12, True)])
+
+
+@pytest.mark.parametrize("kernel, key, k, s, bf", TOP_CASES)
+def test_top_of_the_id_range_in_every_element_type(gpu, bsq, kernel, key, k, s, bf):
+    """B = 37 rows at P = 40 (row pieces, unstaged stores) and P = 272 (629 pieces: two staged workgroups and a partial one), without
+    flags and with all three.  Every element type the rule of include/bsq.h accepts -- 'f' and 'd' included -- holds the twin's values
+    when cast back to int64 (the expected side never passes through the element type); every other type is a ValueError, and the raw
+    entry point refuses it with BSQ_ERR_DTYPE and writes nothing.  Each batch holds 0, the top id (a whole lane of it), UNK and the
+    enabled specials -- asserted, or the case would prove nothing."""
+    import torch
+    from bioseq_amd import capi, kmers
+    L = capi.load()
+    lut, A = _lut(key)
+    V, B = A ** k, 37
+    first, last, _, top = twin.edge_bytes(lut, A, k)
+    assert top == V - 1 or key == "BYTES"  # (BYTES maps the bytes below 0x80 only: its top id is 127 * (V - 1) / 255)
+    pool = twin.edge_pool(lut)
+    for P, flags in ((40, (0, 0, 0)), (40, (1, 1, 1)), (272, (0, 0, 0)), (272, (1, 1, 1))):
+        rng = np.random.default_rng(P + k + s + flags[0])
+        room = P - flags[0] - flags[1]
+        fill = (room - 1) * s + k
+        # rows 4 ..: k + 15 copies of the last class (a lane's 16 windows at the top id), of the first class, a row that fills the
+        # matrix exactly; the last row is over-long (clamped) and ends at the last byte of chars
+        chars, offs = _batch(rng, B, fill + 2 * s + 3, k, pool, pins=((k + 15 * s, last), (k + 15 * s, first), (fill, None)))
+        assert offs[-1] == chars.size and offs[-1] - offs[-2] > fill
+        dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+        tok = _tok(bsq, key, flags)
+        sp = twin.specials(A, k, *flags)
+        want = twin.rows_fast(lut, A, chars, offs, k, s, P, *flags)
+        stored = [0, top, sp["unk"]] + [sp[n] for n, on in zip(("bos", "eos", "pad"), flags) if on]
+        assert set(stored) <= set(want.reshape(-1).tolist()), (P, flags)
+        assert (want[4, flags[0]:flags[0] + 16] == top).all()
+        accepted = []
+        for dc in "bhiqfd":
+            if not twin.holds(CODE[dc], 0, sp["vocab"] - 1):
+                with pytest.raises(ValueError):
+                    kmers.kmer_tokenize_packed(tok, dch, dof, k, P, dc, bf, stride=s, validate=False)
+                d, km = capi.make_desc(key, eos=flags[1], bos=flags[0], padchar=flags[2]), capi.Kmer(k, s)
+                buf = torch.full((B * P + 512,), -77, dtype=capi.torch_dtype(CODE[dc]), device=gpu)
+                st = L.bsq_kmer_tokenize_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), B, P, int(bf), ctypes.byref(km), CODE[dc],
+                                                buf.data_ptr() + 256 * buf.element_size(), None)
+                torch.cuda.synchronize()
+                assert st == capi.ERR_DTYPE and bool((buf == -77).all()), (P, flags, dc)
+                continue
+            assert kmers.kmer_kernel_name(tok, k, B, P, dc, bf, stride=s) == kernel
+            got = kmers.kmer_tokenize_packed(tok, dch, dof, k, P, dc, bf, stride=s, validate=False)
+            torch.cuda.synchronize()
+            vals = got.cpu().numpy().astype(np.int64)
+            assert np.array_equal(vals if bf else vals.T, want), (kernel, P, flags, dc)
+            accepted.append(dc)
+        assert "".join(accepted) == ("iqfd" if V < 2 ** 24 or not any(flags) else "iqd"), (P, flags, accepted)
 
 
 def test_guard_bytes_offsets_not_at_zero_and_an_empty_batch(gpu, bsq):

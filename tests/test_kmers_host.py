@@ -127,12 +127,13 @@ def test_host_twin_equals_numpy_twin(key, k):
                 for dt in range(6):
                     for bf in (True, False):
                         st, got, intact = _host(key, flags, chars, offs, k, s, P, dt, bf)
-                        if (dt == capi.I8 and vocab > 128) or (dt == capi.I16 and vocab > 32768):
-                            assert st == capi.ERR_DTYPE and intact and (got.view(np.uint8) == 0xAB).all()
+                        if not twin.holds(dt, 0, vocab - 1):
+                            assert st == capi.ERR_DTYPE and intact and (got.view(np.uint8) == 0xAB).all(), (s, flags, P, dt, bf)
                             continue
-                        exp = np.ascontiguousarray(want if bf else want.T).astype(twin.NP_DTYPES[dt])
+                        exp = np.ascontiguousarray(want if bf else want.T)
                         assert st == capi.OK and intact, (s, flags, P, dt, bf)
-                        assert got.tobytes() == exp.tobytes(), (s, flags, P, dt, bf)
+                        assert np.array_equal(twin.back(got), exp), (s, flags, P, dt, bf)  # the values, not the twin through the type
+                        assert got.tobytes() == exp.astype(twin.NP_DTYPES[dt]).tobytes(), (s, flags, P, dt, bf)
                         n += 1
     assert n > 0
     # P = 15 clamps the longer rows (over-long rows are cut, memory-safe) and every row holds at most P - bos - eos ids
@@ -200,10 +201,7 @@ def test_argument_rules_nothing_written():
         assert L.bsq_kmer_tokenize_device(ctypes.byref(d), chars.ctypes.data, offs.ctypes.data, 5, 8, 1, ctypes.byref(km), capi.I8,
                                           out.ctypes.data, None) == capi.ERR_INVALID_ARG
         assert (out == 0xAB).all()
-    # the largest plain vocabularies that are allowed
-    for key, k in (("DNA4", 12), ("AMINO20", 5), ("BYTES", 3), ("PURPYR", 16)):
-        st, _, intact = _host(key, (1, 1, 1), chars, offs, k, 1, 8, capi.F32)
-        assert st == capi.OK and intact, (key, k)
+    # (the largest plain vocabularies that are allowed: test_top_of_range_follows_the_rule_of_the_element_types)
     # element types: int8 holds 128 ids, int16 32768
     for key, flags, k, dt, want in (("PURPYR", (0, 0, 0), 7, capi.I8, capi.ERR_DTYPE),      # vocab 129
                                     ("PURPYR", (1, 1, 1), 6, capi.I8, capi.OK),             # vocab 68
@@ -241,6 +239,122 @@ def test_argument_rules_nothing_written():
     if L.bsq_device_count() == 0:  # the device call alone needs a device
         assert call(True) == capi.ERR_NO_DEVICE
     assert call(False) == capi.OK
+
+
+def test_the_rule_of_the_element_types():
+    """bsq_dtype_holds against the table of include/bsq.h, and the table against what it claims: an integer is held when the conversion
+    to the type and back gives it again (numpy's conversion; the first integer outside each end does not come back)."""
+    capi, L = _lib()
+    edges = sorted({s * 2 ** e + d for e in (0, 7, 15, 24, 31, 53, 62) for s in (-1, 1) for d in (-2, -1, 0, 1, 2)} | {-2 ** 63, 2 ** 63 - 1})
+    edges = [x for x in edges if -2 ** 63 <= x < 2 ** 63]
+    for dt in range(6):
+        lo_t, hi_t = twin.HOLDS[dt]
+        for lo, hi in itertools.combinations_with_replacement(edges, 2):
+            assert bool(L.bsq_dtype_holds(dt, lo, hi)) == (lo_t <= lo and hi <= hi_t) == twin.holds(dt, lo, hi), (dt, lo, hi)
+        if dt == capi.U64:
+            continue
+        np_t = twin.NP_DTYPES[dt]
+        with np.errstate(all="ignore"):
+            survives = lambda x: int(np.array([x], dtype=np.int64).astype(np_t).astype(np.float64 if dt >= 4 else np.int64)[0]) == x
+            assert survives(lo_t) and survives(hi_t) and survives(0) and survives(-1)
+            # past the end: the integer types wrap, the float types round 2^m + 1 to an even neighbour
+            assert not survives(hi_t + 1) and not survives(lo_t - 1), dt
+    assert not any(L.bsq_dtype_holds(bad, 0, 0) for bad in (-1, 6, 99))
+    assert "bsq_dtype_holds" in capi.declared_symbols(capi.HEADER_PATH)
+
+
+TOP_KEYS = [("DNA4", 12), ("SEB8", 8), ("BYTES", 3), ("AMINO20", 5), ("PURPYR", 16)]  # A^k = 2^24 for the first three
+
+
+def _edge_batch(lut, A, k):
+    """Rows that hold the top id three times, 0 twice, 0 then UNK, no window (empty, k - 1 characters), and a mix of both ends."""
+    first, last, unmapped, top = twin.edge_bytes(lut, A, k)
+    f, l, u = bytes([first]), bytes([last]), bytes([unmapped])
+    return _pack([l * (k + 2), f * (k + 1), f * k + u, b"", l * (k - 1), (f + l) * ((k + 3) // 2)]), top
+
+
+@pytest.mark.parametrize("key, k", TOP_KEYS)
+def test_top_of_range_follows_the_rule_of_the_element_types(key, k):
+    """The largest vocabularies, every flag triple, every element type: accepted exactly where the type holds [0, vocab - 1], the values
+    exact where accepted (compared as int64, never through the element type), nothing written where refused -- and, without any twin,
+    the stored forms of 0, the top id, UNK and the enabled specials pairwise distinct and below vocab."""
+    capi, L = _lib()
+    lut, A = _lut(key)
+    V = A ** k
+    (chars, offs), top = _edge_batch(lut, A, k)
+    assert top == V - 1 or key == "BYTES"
+    P, refused, accepted = 8, [], 0
+    for flags in FLAGS:
+        sp = twin.specials(A, k, *flags)
+        want = twin.rows(lut, A, chars, offs, k, 1, P, *flags)
+        stored = [0, top, sp["unk"]] + [sp[n] for n, on in zip(("bos", "eos", "pad"), flags) if on]
+        assert set(stored) <= set(want.reshape(-1).tolist()), (flags, "the batch does not hold every value the check is about")
+        for dt in range(6):
+            st, got, intact = _host(key, flags, chars, offs, k, 1, P, dt)
+            d, km = capi.make_desc(key, eos=flags[1], bos=flags[0], padchar=flags[2]), capi.Kmer(k, 1)
+            name = L.bsq_kmer_kernel_name(ctypes.byref(d), ctypes.byref(km), 6, P, 1, dt)
+            if st == capi.OK:  # whatever the rule says: what the library accepts, it stores without two ids falling together
+                vals = twin.back(got)
+                seen = [int(vals[want == w][0]) for w in stored]  # the library's own conversion of each id, read back
+                assert len(set(seen)) == len(stored) and max(seen) < sp["vocab"] and min(seen) >= 0, (flags, dt, seen)
+            if not twin.holds(dt, 0, sp["vocab"] - 1):
+                assert st == capi.ERR_DTYPE and intact and (got.view(np.uint8) == 0xAB).all(), (flags, dt)
+                assert L.bsq_last_error() != b"" and name == b""
+                refused.append((flags, dt))
+                continue
+            assert st == capi.OK and intact and name == b"k_kmer_bp<s1>", (flags, dt)
+            assert np.array_equal(vals, want), (flags, dt)
+            accepted += 1
+    # the consequences the specification names
+    f32_refused = [f for f, dt in refused if dt == capi.F32]
+    assert f32_refused == ([f for f in FLAGS if any(f)] if V == 2 ** 24 else []), f32_refused
+    assert not [x for x in refused if x[1] in (capi.I32, capi.U64, capi.F64)]
+    assert [dt for f, dt in refused if dt in (capi.I8, capi.I16)] == [capi.I8, capi.I16] * 8  # (vocab > 32768 at every key)
+    assert accepted == 48 - len(refused)
+
+
+def test_python_layer_refuses_what_the_library_refuses():
+    import bioseq_amd
+    from bioseq_amd import kmers
+    chars, offs = _pack(SEQS)
+    for flags in FLAGS:
+        tok = bioseq_amd.Tokenizer("DNA4", bool(flags[1]), bool(flags[0]), bool(flags[2]))  # (eos, bos, padchar)
+        if any(flags):
+            for call in (lambda: kmers.kmer_tokenize_host(tok, chars, offs, 12, 8, "f"), lambda: kmers.kmer_kernel_name(tok, 12, 5, 8, "f")):
+                with pytest.raises(ValueError):
+                    call()
+        else:
+            assert kmers.kmer_tokenize_host(tok, chars, offs, 12, 8, "f").dtype == np.float32
+            assert kmers.kmer_kernel_name(tok, 12, 5, 8, "f") == "k_kmer_bp<s1>"
+        assert kmers.kmer_tokenize_host(tok, chars, offs, 12, 8, "d").dtype == np.float64
+    amino = bioseq_amd.Tokenizer("AMINO20", True, True, True)
+    assert kmers.kmer_tokenize_host(amino, chars, offs, 5, 8, "f").dtype == np.float32
+
+
+@pytest.mark.parametrize("key, k", [("AMINO20", 5), ("SEB8", 8)])
+def test_decoded_ids_spell_the_windows(key, k):
+    """kmer_decode as the inverse of the ids, without the Horner sum: over mapped characters only, the word of window j is the
+    characters j .. j + k - 1, each written as the first byte of its class."""
+    import bioseq_amd
+    from bioseq_amd import kmers
+    lut, A = _lut(key)
+    rng = np.random.default_rng(k)
+    mapped = np.flatnonzero(lut >= 0).astype(np.uint8)
+    canon = {int(c): chr(int(np.flatnonzero(lut == lut[c])[0])) for c in mapped}
+    seqs = [bytes(mapped[rng.integers(0, mapped.size, n)]) for n in (k, k + 1, 40, 33)]
+    first, last, _, _ = twin.edge_bytes(lut, A, k)
+    seqs += [bytes([last]) * (k + 2), bytes([first]) * k]
+    chars, offs = _pack(seqs)
+    tok = bioseq_amd.Tokenizer(key)
+    P = 40 - k + 1
+    ids = kmers.kmer_tokenize_host(tok, chars, offs, k, P, "q")
+    assert len({chr(c) for c in mapped} - set(canon.values())) > 0  # (some classes have several bytes: the spelling is by class)
+    n = 0
+    for q, row in zip(seqs, ids):
+        words = kmers.kmer_decode(tok, k, row[:len(q) - k + 1])
+        assert words == ["".join(canon[c] for c in q[j:j + k]) for j in range(len(q) - k + 1)], q
+        n += len(words)
+    assert n > 60 and int(ids.max()) == A ** k - 1 and int(ids.min()) == 0
 
 
 def test_id_helpers_follow_the_formulas():
