@@ -50,6 +50,12 @@ class KmerMlm(ctypes.Structure):
                 ("mask_token", ctypes.c_int64), ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
 
 
+class KmerSpectrum(ctypes.Structure):
+    """struct bsq_kmer_spectrum"""
+    _fields_ = [("both_strands", ctypes.c_int32), ("normalize", ctypes.c_int32), ("form", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("total_chars", ctypes.c_int64)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -153,6 +159,10 @@ def load():
         "bsq_kmer_mlm_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), ctypes.POINTER(KmerMlm), c_int, vp, c_int, vp, vp]),
         "bsq_kmer_mlm_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, ctypes.POINTER(Kmer), ctypes.POINTER(KmerMlm), c_int, vp, c_int, vp]),
         "bsq_kmer_mlm_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(Kmer), ctypes.POINTER(KmerMlm), i64, i64, i32, c_int, c_int]),
+        "bsq_kmer_spectrum_width": (i64, [dp, ctypes.POINTER(Kmer)]),
+        "bsq_kmer_spectrum_device": (i32, [dp, vp, vp, i64, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), c_int, vp, vp]),
+        "bsq_kmer_spectrum_host": (i32, [dp, vp, vp, i64, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), c_int, vp]),
+        "bsq_kmer_spectrum_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), i64, c_int]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -1,0 +1,325 @@
+// k-mer spectrum of a packed batch on the device (gfx950): include/bsq.h ("k-mer spectrum") documents the rule, bsq_kmer_spectrum_dev.h
+// holds what the kernels and the CPU twin share.  Unlike every other kernel of the library these are per-row REDUCTIONS: a histogram of
+// V = A^k u32 bins in LDS, built with LDS atomics (ds_add_u32, no return value), converted and written out once -- the (B, V) matrix is
+// never cleared and never touched by a global atomic.
+//
+// k_kmer_spectrum_wave<T, S1>         V <= 1024: a wave per row, four rows per workgroup, each wave with its own histogram (16 KiB per
+//            workgroup).  The waves of a workgroup never meet after the table is staged: a wave orders its own clear, atomics and reads
+//            with a wavefront-scope fence (LDS serves one wave's instructions in order).
+// k_kmer_spectrum_block<T, BINS, S1>  a 256-thread workgroup per row, BINS = 1024 / 4096 / 16384 bins (4 / 16 / 64 KiB): long rows and
+//            every V above 1024.
+// Both sweep a row in pieces of (lanes x 16) windows: a lane takes 16 consecutive windows.
+//            <S1> stride 1: the two 16-byte loads, the rolling id and the mapped-run counter of k_kmer_bp<s1> (bsq_kmer.hip);
+//            otherwise one 16-byte load (k <= 16) and a Horner sum per window.
+// Loads are 16 bytes wide where they end at or before offsets[B], byte by byte behind that bound otherwise.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "bsq.h"
+#include "bsq_device.h"
+#include "bsq_internal.h"
+#include "bsq_kmer_dev.h"
+#include "bsq_kmer_spectrum_dev.h"
+
+namespace {
+
+using namespace bsq_dev;  // kThreads, store16, u32x4_unaligned
+using bsq_kmerd::Geometry;
+using bsq_specd::Form;
+
+constexpr int kRun = 16;                // windows of a lane's run
+struct SpecParams {
+    const uint8_t *chars;
+    const int64_t *offsets;
+    void *out;
+    int64_t B;
+    int32_t V, k, stride, A;
+    uint32_t lead;  // A^(k-1)
+    int32_t both, normalize;
+    int8_t lut[256];
+};
+
+__device__ __forceinline__ void stage_lut(int8_t *s_lut, const SpecParams &p) {
+    s_lut[threadIdx.x] = p.lut[threadIdx.x];  // (kThreads == 256)
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int c) { return (w[c >> 2] >> (8 * (c & 3))) & 0xFFu; }
+
+// bsq_specd::rc_id without the loop: complement every digit, reverse the bits, swap the two bits of every digit back (k <= 7)
+__device__ __forceinline__ uint32_t rc_fast(uint32_t v, int32_t k) {
+    const uint32_t x = __brev(~v) >> (32 - 2 * k);
+    return ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u);
+}
+
+__device__ __forceinline__ void count_window(uint32_t *hist, uint32_t id, const SpecParams &p) {
+    atomicAdd(hist + id, 1u);
+    if (p.both) atomicAdd(hist + rc_fast(id, p.k), 1u);
+}
+
+// 16 bytes from chars + a, zero where the byte lies outside [0, total) or at / behind `lim` bytes from a
+__device__ __forceinline__ void load16(const uint8_t *chars, int64_t a, int64_t total, int32_t lim, uint32_t (&w)[4]) {
+    if (a >= 0 && a + 16 <= total) {
+        const u32x4_unaligned x = *reinterpret_cast<const u32x4_unaligned *>(chars + a);
+        w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
+    } else {
+        w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            if (c < lim && a + c >= 0 && a + c < total) w[c >> 2] |= static_cast<uint32_t>(chars[a + c]) << (8 * (c & 3));
+    }
+}
+
+// The windows [0, n) of the row at `start` into `hist`, by NL lanes (lane: 0 .. NL - 1); the lane's number of counted windows.
+template <bool S1, int NL>
+__device__ __forceinline__ uint32_t sweep(const SpecParams &p, const int8_t *s_lut, uint32_t *hist, int64_t start, int64_t total, int32_t n,
+                                          int lane) {
+    const int32_t k = p.k, A = p.A;
+    uint32_t counted = 0;
+    for (int32_t j0 = lane * kRun; j0 < n; j0 += NL * kRun) {
+        if constexpr (S1) {
+            // W: the characters j0 .. j0 + 15 (each starts a window of the run), M: j0 + k - 1 .. j0 + k + 14 (each ends one); a character
+            // behind the row's last window belongs to no counted window, whatever it is
+            const int32_t km1 = k - 1;
+            const int32_t chars_left = n + km1 - j0;  // characters of the row's windows from j0 on (> km1)
+            uint32_t W[4], M[4];
+            load16(p.chars, start + j0, total, chars_left, W);
+            load16(p.chars, start + j0 + km1, total, chars_left - km1, M);
+            uint32_t val = 0;
+            int32_t run = 0;  // mapped characters in a row, up to the current one
+#pragma unroll
+            for (int c = 0; c < bsq_kmerd::kMaxK - 1; ++c) {
+                if (c < km1) {  // (uniform)
+                    const int32_t id = s_lut[byte_of(W, c)];
+                    val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
+                    run = id < 0 ? 0 : run + 1;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kRun; ++q) {
+                if (q > 0) {  // the character that leaves the window
+                    const int32_t gone = s_lut[byte_of(W, q - 1)];
+                    val -= __umul24(static_cast<uint32_t>(gone < 0 ? 0 : gone), p.lead);
+                }
+                const int32_t id = s_lut[byte_of(M, q)];
+                val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
+                run = id < 0 ? 0 : run + 1;
+                if (run >= k && j0 + q < n) {  // (val < V: it is the Horner sum of the last k characters, unmapped ones as 0)
+                    count_window(hist, val, p);
+                    ++counted;
+                }
+            }
+        } else {
+            const int32_t last = n - j0 < kRun ? n - j0 : kRun;
+#pragma unroll 1
+            for (int q = 0; q < last; ++q) {
+                uint32_t w[4];
+                load16(p.chars, start + static_cast<int64_t>(j0 + q) * p.stride, total, k, w);
+                uint32_t val = 0;
+                bool unk = false;
+#pragma unroll
+                for (int c = 0; c < bsq_kmerd::kMaxK; ++c) {
+                    if (c < k) {  // (uniform)
+                        const int32_t id = s_lut[byte_of(w, c)];
+                        unk |= id < 0;
+                        val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
+                    }
+                }
+                if (!unk) {
+                    count_window(hist, val, p);
+                    ++counted;
+                }
+            }
+        }
+    }
+    return counted;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+// hist[0 .. V) -> row[0 .. V) as T, by NL lanes: 16-byte stores where the row starts on a 16-byte boundary, element stores otherwise
+// and for the last V % (16 / sizeof(T)) elements; every element exactly once.
+template <typename T, int NL>
+__device__ __forceinline__ void write_row(T *row, const uint32_t *hist, int32_t V, uint32_t sum, bool normalize, int lane) {
+    constexpr int E = 16 / sizeof(T);
+    const int32_t nvec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0 ? V / E : 0;  // (uniform over the row's lanes)
+    for (int32_t g = lane; g < nvec; g += NL) {
+        union {
+            T v[E];
+            uint4 u;
+        } x;
+#pragma unroll
+        for (int e = 0; e < E; ++e) x.v[e] = bsq_specd::element<T>(hist[g * E + e], sum, normalize);
+        store16<true>(row + g * E, x.u);
+    }
+    for (int32_t e = nvec * E + lane; e < V; e += NL) __builtin_nontemporal_store(bsq_specd::element<T>(hist[e], sum, normalize), row + e);
+}
+
+// what orders one wave's LDS accesses: nothing of another wave is waited for
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ int32_t windows_of(const SpecParams &p, int64_t i, int64_t *start) {
+    *start = p.offsets[i];
+    return static_cast<int32_t>(bsq_specd::row_windows(p.offsets[i + 1] - *start, p.k, p.stride));
+}
+
+template <typename T, bool S1>
+__global__ __launch_bounds__(kThreads) void k_kmer_spectrum_wave(const SpecParams p) {
+    __shared__ int8_t s_lut[256];
+    __shared__ __align__(16) uint32_t s_hist[kThreads / 64][bsq_specd::kWaveMaxV];
+    stage_lut(s_lut, p);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t *hist = s_hist[wave];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave;  // (wave-uniform)
+    if (i >= p.B) return;  // (no workgroup barrier follows)
+    for (int32_t v = lane; v < p.V; v += 64) hist[v] = 0;
+    wave_sync();
+    int64_t start;
+    const int32_t n = windows_of(p, i, &start);
+    const uint32_t sum = wave_sum(sweep<S1, 64>(p, s_lut, hist, start, p.offsets[p.B], n, lane)) << (p.both ? 1 : 0);
+    wave_sync();
+    write_row<T, 64>(static_cast<T *>(p.out) + i * p.V, hist, p.V, sum, p.normalize != 0, lane);
+}
+
+template <typename T, int BINS, bool S1>
+__global__ __launch_bounds__(kThreads) void k_kmer_spectrum_block(const SpecParams p) {
+    __shared__ int8_t s_lut[256];
+    __shared__ __align__(16) uint32_t s_hist[BINS];
+    __shared__ uint32_t s_sum;
+    const int tid = threadIdx.x;
+    const int64_t i = blockIdx.x;  // (< B)
+    for (int32_t v = tid; v < p.V; v += kThreads) s_hist[v] = 0;
+    if (tid == 0) s_sum = 0;
+    stage_lut(s_lut, p);  // (its barrier also orders the clear before the atomics)
+    int64_t start;
+    const int32_t n = windows_of(p, i, &start);
+    const uint32_t mine = wave_sum(sweep<S1, kThreads>(p, s_lut, s_hist, start, p.offsets[p.B], n, tid));
+    if ((tid & 63) == 0 && mine) atomicAdd(&s_sum, mine);
+    __syncthreads();
+    const uint32_t sum = s_sum << (p.both ? 1 : 0);
+    write_row<T, kThreads>(static_cast<T *>(p.out) + i * p.V, s_hist, p.V, sum, p.normalize != 0, tid);
+}
+
+bsq_status check_all(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
+                     const bsq_kmer_spectrum *o, bsq_dtype t, const void *out, Geometry *g) {
+    const char *why = "";
+    const bsq_status st = bsq_specd::check(d, km, o, B, t, g, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (B > 0 && (!chars || !offsets || !out)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "chars, offsets or out is null");
+    return BSQ_OK;
+}
+
+// f(T{}) with the element type of a spectrum (check() has refused every other one)
+template <typename F>
+bsq_status with_spectrum_type(bsq_dtype t, F &&f) {
+    switch (t) {
+    case BSQ_I32: return f(int32_t{});
+    case BSQ_U64: return f(uint64_t{});
+    case BSQ_F32: return f(float{});
+    case BSQ_F64: return f(double{});
+    default: return bsq_internal::set_error(BSQ_ERR_DTYPE, "bad bsq_dtype");
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t bsq_kmer_spectrum_width(const bsq_desc *d, const bsq_kmer *km) {
+    Geometry g;
+    const char *why = "";
+    if (bsq_kmerd::make_geometry(d, km, &g, &why) != BSQ_OK) return -static_cast<int64_t>(bsq_internal::set_error(BSQ_ERR_INVALID_ARG, why));
+    if (g.V > bsq_specd::kMaxV)
+        return -static_cast<int64_t>(bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "nchars^k exceeds 2^14: a dense (B, nchars^k) spectrum is not built beyond that"));
+    return g.V;
+}
+
+const char *bsq_kmer_spectrum_kernel_name(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_spectrum *o, int64_t B, bsq_dtype t) {
+    Geometry g;
+    const char *why = "";
+    if (bsq_specd::check(d, km, o, B, t, &g, &why) != BSQ_OK) return "";
+    return bsq_specd::form_name(bsq_specd::form_of(g.V, B, o->total_chars, o->form));
+}
+
+bsq_status bsq_kmer_spectrum_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
+                                    const bsq_kmer_spectrum *o, bsq_dtype t, void *out, void *hip_stream) {
+    Geometry g;
+    bsq_status st = check_all(d, chars, offsets, B, km, o, t, out, &g);
+    if (st != BSQ_OK || B == 0) return st;
+    SpecParams p;
+    std::memcpy(p.lut, d->lut, 256);
+    p.chars = chars;
+    p.offsets = offsets;
+    p.out = out;
+    p.B = B;
+    p.V = static_cast<int32_t>(g.V);
+    p.k = g.k;
+    p.stride = g.stride;
+    p.A = g.A;
+    p.lead = static_cast<uint32_t>(g.lead);
+    p.both = o->both_strands;
+    p.normalize = o->normalize;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const Form form = bsq_specd::form_of(g.V, B, o->total_chars, o->form);
+    // one wave (wave form) or one workgroup (block form) per row: B <= 2^31 - 1 (bsq_specd::check) fits the grid
+    const dim3 grid(static_cast<unsigned>(form == Form::wave ? (B + kThreads / 64 - 1) / (kThreads / 64) : B)), block(kThreads);
+    st = with_spectrum_type(t, [&](auto tag) {
+        using T = decltype(tag);
+        return bsq_internal::with_flags(
+            [&](auto s1) {
+                constexpr bool S1 = decltype(s1)::value;
+                switch (form) {
+                case Form::wave: hipLaunchKernelGGL((k_kmer_spectrum_wave<T, S1>), grid, block, 0, s, p); break;
+                case Form::block1024: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 1024, S1>), grid, block, 0, s, p); break;
+                case Form::block4096: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 4096, S1>), grid, block, 0, s, p); break;
+                default: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 16384, S1>), grid, block, 0, s, p); break;
+                }
+                return BSQ_OK;
+            },
+            g.stride == 1);
+    });
+    return st != BSQ_OK ? st : bsq_internal::check_launch(bsq_specd::form_name(form));
+}
+
+bsq_status bsq_kmer_spectrum_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
+                                  const bsq_kmer_spectrum *o, bsq_dtype t, void *out) {
+    Geometry g;
+    const bsq_status st = check_all(d, chars, offsets, B, km, o, t, out, &g);
+    if (st != BSQ_OK || B == 0) return st;
+    return with_spectrum_type(t, [&](auto tag) {
+        using T = decltype(tag);
+        T *dst = static_cast<T *>(out);
+        std::vector<uint32_t> hist(static_cast<size_t>(g.V));
+        for (int64_t b = 0; b < B; ++b) {
+            std::fill(hist.begin(), hist.end(), 0u);
+            const int64_t n = bsq_specd::row_windows(offsets[b + 1] - offsets[b], g.k, g.stride);
+            uint32_t sum = 0;
+            for (int64_t j = 0; j < n; ++j) {
+                const int64_t id = bsq_kmerd::window_id(g, d->lut, chars + offsets[b] + j * g.stride);
+                if (id == g.V) continue;
+                hist[id] += 1;
+                sum += 1;
+                if (o->both_strands) {
+                    hist[bsq_specd::rc_id(static_cast<uint32_t>(id), g.k)] += 1;
+                    sum += 1;
+                }
+            }
+            for (int64_t v = 0; v < g.V; ++v) dst[b * g.V + v] = bsq_specd::element<T>(hist[v], sum, o->normalize != 0);
+        }
+        return BSQ_OK;
+    });
+}
+
+}  // extern "C"

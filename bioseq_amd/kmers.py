@@ -15,7 +15,12 @@ its specials.  A tail shorter than k is dropped.  include/bsq.h (`bsq_kmer`) has
 * `kmer_tokenize_host`    the library's CPU twin of the ids (numpy in, numpy out; no device);
 * `kmer_mlm_tokenize_packed`  span-masked masked-LM pairs (inputs, labels) over the k-mer ids, drawn in the encode launch (DNABERT's
                           objective: contiguous runs of `span` windows are selected, then BERT's 80/10/10 replacement);
-* `kmer_mlm_tokenize_host`, `span_anchor_prob`, `kmer_mlm_kernel_name`  its CPU twin, the share -> anchor rate helper, the kernel taken.
+* `kmer_mlm_tokenize_host`, `span_anchor_prob`, `kmer_mlm_kernel_name`  its CPU twin, the share -> anchor rate helper, the kernel taken;
+* `kmer_spectrum_packed`  the k-mer SPECTRUM of a packed batch: one (B, nchars ** k) matrix of per-sequence counts or frequencies
+                          (tetranucleotide frequencies, di- / tripeptide composition, 6-mer profiles), one strand or both, in one launch
+                          -- a histogram per row in LDS, no id matrix, no scatter_add_ (`bsq_kmer_spectrum_device`);
+* `kmer_spectrum_host`, `kmer_spectrum_width`, `kmer_spectrum_kernel_name`, `kmer_canonical_columns`  its CPU twin, its width, the
+                          kernel taken, and the columns v <= rc(v) that turn a both-strand spectrum into the canonical-k-mer profile.
 
 The crops and reverse-complement views of `views` hand this module packed batches as they are:
 `kmer_tokenize_packed(tok, *views.crop_packed(chars, offsets, 1000, revcomp_frac=0.5), k=6, padlen=...)`.
@@ -283,6 +288,108 @@ def kmer_mlm_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch
     return inputs, labels
 
 
+_SPECTRUM_MAX_WINDOWS = 1 << 23  # (include/bsq.h, "k-mer spectrum": a row counts its first 2 ** 23 windows)
+
+
+def _strands(desc):
+    """Whether the alphabet has strands as the spectrum reads them: four classes, A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)."""
+    return desc.nchars == 4 and [desc.lut[ord(c)] for c in "ACGT"] == [0, 1, 2, 3]
+
+
+def _spectrum(tok, k, stride, destchar, both_strands, normalize, form, total_chars=0):
+    """(desc, km, bsq_kmer_spectrum, dtype code, torch dtype, V) with the library's argument rules applied as ValueError."""
+    desc, km = _kmer(tok, k, stride)
+    V = int(_lib.bsq_kmer_spectrum_width(ctypes.byref(desc), ctypes.byref(km)))
+    if V < 0:
+        raise ValueError("k = %r with %d classes: %s" % (k, desc.nchars, _lib.bsq_last_error().decode()))
+    try:
+        dt, tdt = capi.dtype_of(destchar)
+    except RuntimeError as e:
+        raise ValueError("bad destchar %r: %s" % (destchar, e)) from None
+    allowed = (capi.F32, capi.F64) if normalize else (capi.I32, capi.U64, capi.F32, capi.F64)
+    if dt not in allowed:
+        raise ValueError("destchar %r: a spectrum of %s takes %s" % (destchar, "frequencies" if normalize else "counts",
+                                                                     "'f' or 'd'" if normalize else "'i', 'q', 'f' or 'd'"))
+    if both_strands and not _strands(desc):
+        raise ValueError("both_strands needs an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
+    form = 0 if form is None else int(form)
+    if form not in (0, 1, 2) or (form == 1 and V > 1024):
+        raise ValueError("form must be None, 1 (a wave per row: nchars ** k <= 1024) or 2 (a workgroup per row), got %r at width %d" % (form, V))
+    return desc, km, capi.KmerSpectrum(int(bool(both_strands)), int(bool(normalize)), form, 0, int(total_chars)), dt, tdt, V
+
+
+def kmer_spectrum_width(tok, k):
+    """Columns of the spectrum: nchars ** k (ValueError beyond 2 ** 14: DNA4 up to k = 7, DNA5 6, AMINO20 3, SEB8 4)."""
+    desc, km = _kmer(tok, k)
+    V = int(_lib.bsq_kmer_spectrum_width(ctypes.byref(desc), ctypes.byref(km)))
+    if V < 0:
+        raise ValueError("k = %r with %d classes: %s" % (k, desc.nchars, _lib.bsq_last_error().decode()))
+    return V
+
+
+def kmer_canonical_columns(tok, k):
+    """The sorted int64 columns v with v <= rc(v) (host numpy): `spectrum[:, cols]` of a `both_strands` spectrum is the canonical-k-mer
+    profile -- (4 ** k + 4 ** (k / 2)) / 2 columns for even k, 4 ** k / 2 for odd k.  ValueError for an alphabet without strands."""
+    desc, km = _kmer(tok, k)
+    if not _strands(desc):
+        raise ValueError("canonical k-mers need an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
+    V = kmer_spectrum_width(tok, k)
+    v = np.arange(V, dtype=np.int64)
+    rc, rest = np.zeros(V, dtype=np.int64), v.copy()
+    for _ in range(km.k):
+        rc = rc * 4 + (3 - rest % 4)
+        rest //= 4
+    return v[v <= rc]
+
+
+def kmer_spectrum_kernel_name(tok, k, B, destchar="f", *, stride=1, both_strands=False, normalize=False, form=None, total_chars=0):
+    """The kernel `kmer_spectrum_packed` takes (host only: profiling labels, tests); total_chars: `chars.numel()` of the call, 0 = unknown."""
+    desc, km, o, dt, _, _ = _spectrum(tok, k, stride, destchar, both_strands, normalize, form, total_chars)
+    return _lib.bsq_kmer_spectrum_kernel_name(ctypes.byref(desc), ctypes.byref(km), ctypes.byref(o), int(B), dt).decode()
+
+
+def kmer_spectrum_host(tok, chars, offsets, k, destchar="f", *, stride=1, both_strands=False, normalize=False):
+    """The library's CPU twin (`bsq_kmer_spectrum_host`, the window and element code of the kernels) on numpy arrays: a (B, V) matrix."""
+    desc, km, o, dt, _, V = _spectrum(tok, k, stride, destchar, both_strands, normalize, None)
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    B = offsets.size - 1
+    out = np.empty((B, V), dtype=_NUMPY[dt])
+    keep = chars if chars.size else np.zeros(16, np.uint8)
+    if B > 0:
+        capi.check(_lib.bsq_kmer_spectrum_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, ctypes.byref(km), ctypes.byref(o), dt,
+                                               out.ctypes.data))
+    return out
+
+
+def kmer_spectrum_packed(tok, chars, offsets, k, destchar="f", *, stride=1, both_strands=False, normalize=False, form=None, validate=True):
+    """The k-mer spectrum of a packed batch on the device (chars uint8[total], offsets int64[B + 1]): a (B, nchars ** k) device tensor
+    on torch's current stream, one launch, nothing read back.
+
+    out[i, v] = the windows of row i (those of `kmer_tokenize_packed` at the same k and stride; BOS / EOS / PAD play no part) whose id is
+    v; a window with an unmapped character counts nowhere.  both_strands (DNA, DNA4): every window also counts at the id of its reverse
+    complement, so columns v and rc(v) are equal and `[:, kmer_canonical_columns(tok, k)]` is the canonical profile.  normalize: each row
+    divided by its sum (destchar 'f' or 'd'; an empty row stays zero); counts take 'i', 'q', 'f' or 'd'.  form: None = the library
+    chooses from `chars.numel()` / B, 1 = a wave per row, 2 = a workgroup per row.  validate: malformed offsets and a row of more than
+    2 ** 23 windows raise the library's errors instead of being clamped."""
+    import torch
+    B = capi.packed_on_device(chars, offsets, "kmer_spectrum_packed works on packed batches resident on the device (chars, offsets tensors)")
+    desc, km, o, dt, tdt, V = _spectrum(tok, k, stride, destchar, both_strands, normalize, form, chars.numel())
+    if validate and B > 0:
+        bad = ctypes.c_int64(-1)
+        with capi.launching(chars.device) as stream:
+            capi.check(_lib.bsq_validate_packed_device(offsets.data_ptr(), B, (_SPECTRUM_MAX_WINDOWS - 1) * km.stride + km.k, 0, 0, chars.numel(),
+                                                       ctypes.byref(bad), stream))
+    out = torch.empty((B, V), dtype=tdt, device=chars.device)
+    if B > 0:
+        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_kmer_spectrum_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, ctypes.byref(km), ctypes.byref(o), dt,
+                                                     out.data_ptr(), stream))
+    return out
+
+
 __all__ = ["kmer_tokenize_packed", "kmer_tokenize_host", "kmer_vocab_size", "kmer_special_ids", "kmer_count", "kmer_padlen",
            "kmer_max_length", "kmer_decode", "kmer_kernel_name", "kmer_mlm_tokenize_packed", "kmer_mlm_tokenize_host", "span_anchor_prob",
-           "kmer_mlm_kernel_name"]
+           "kmer_mlm_kernel_name", "kmer_spectrum_packed", "kmer_spectrum_host", "kmer_spectrum_width", "kmer_spectrum_kernel_name",
+           "kmer_canonical_columns"]

@@ -74,6 +74,12 @@ class FlatFileDataset(torch.utils.data.Dataset):
     masked=True or pack= it raises ValueError, and so it does without kmer=.  `token_dtype` must hold every id and the mask token
     (the rule of include/bsq.h): 'f' at nchars ** kmer = 2 ** 24 (DNA4 kmer=12) cannot, and the first batch raises ValueError.
 
+    spectrum=k (keyword; off by default): a batch is the (B, nchars ** k) float32 k-mer spectrum of its sequences
+    (kmers.kmer_spectrum_packed, one launch): frequencies (`spectrum_normalize`, the default) or counts of the windows `spectrum_stride`
+    characters apart, of one strand or, with `spectrum_both_strands` (DNA, DNA4), of both.  `get_batch`, `__getitems__` and `batches()`
+    hand the matrix out; it composes with crop, revcomp_frac, shuffle and prefetch.  With cnn=True, augment > 0, masked=True, kmer=,
+    pack= or group > 1 it raises ValueError.
+
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
     (tokens, segment_ids, position_ids), each (rows, max_seq_len), rows being what the batch needs (one 8-byte read-back per batch:
@@ -95,7 +101,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
                  crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False,
-                 kmer_mlm=False, kmer_span=None):
+                 kmer_mlm=False, kmer_span=None, spectrum=None, spectrum_stride=1, spectrum_both_strands=False, spectrum_normalize=True):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -157,6 +163,16 @@ class FlatFileDataset(torch.utils.data.Dataset):
         self.pack_mlm = bool(pack_mlm)
         if self.pack_mlm and pack is None:
             raise ValueError("pack_mlm=True masks the packed batches of pack=: give pack='nextfit' or pack='stream' with it")
+        self.spectrum = None if spectrum is None else int(spectrum)
+        self.spectrum_stride, self.spectrum_both_strands = int(spectrum_stride), bool(spectrum_both_strands)
+        self.spectrum_normalize = bool(spectrum_normalize)
+        if self.spectrum is not None:
+            if cnn or augment or masked or kmer is not None or pack is not None:
+                raise ValueError("spectrum= gives one k-mer spectrum per sequence of the plain batch: it cannot be combined with cnn=True, "
+                                 "augment > 0, masked=True, kmer= or pack=")
+            # (k, stride, nchars ** k and the strands are checked here)
+            kmers.kmer_spectrum_kernel_name(tokenizer, self.spectrum, 1, "f", stride=self.spectrum_stride,
+                                            both_strands=self.spectrum_both_strands, normalize=self.spectrum_normalize)
 
     def __len__(self):
         return self.ff.nseqs()
@@ -243,6 +259,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
         if self.kmer is not None:
             return kmers.kmer_tokenize_packed(self.tokenizer, chars, offs, self.kmer, self.max_seq_len, self.token_dtype, True,
                                               stride=self.kmer_stride, validate=not trusted)
+        if self.spectrum is not None:
+            return kmers.kmer_spectrum_packed(self.tokenizer, chars, offs, self.spectrum, "f", stride=self.spectrum_stride,
+                                              both_strands=self.spectrum_both_strands, normalize=self.spectrum_normalize, validate=not trusted)
         if self.augment:
             self._calls += 1
             seed = self._seed + self._calls
@@ -329,6 +348,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             raise ValueError("batch_size must be positive")
         if self.pack is not None and int(group) > 1:
             raise ValueError("group > 1 cannot be combined with pack=: a super-batch's row blocks are not the batches' own packings")
+        if self.spectrum is not None and int(group) > 1:
+            raise ValueError("group > 1 cannot be combined with spectrum=")
         pairs = self.masked or self.pack is not None or self.kmer_mlm  # a batch is a tuple of tensors
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n

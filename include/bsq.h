@@ -38,7 +38,8 @@ extern "C" {
                            * bsq_kmer_tokenize_host, bsq_kmer_kernel_name, bsq_pack_plan_device, bsq_pack_plan_host, bsq_pack_plan_parallel_host,
                            * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name, bsq_pack_mlm_tokenize_device,
                            * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name, bsq_kmer_mlm, bsq_kmer_mlm_anchor_prob,
-                           * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds; nothing removed */
+                           * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds, bsq_kmer_spectrum,
+                           * bsq_kmer_spectrum_width, bsq_kmer_spectrum_device, bsq_kmer_spectrum_host, bsq_kmer_spectrum_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -459,6 +460,63 @@ bsq_status bsq_kmer_tokenize_host(const bsq_desc *d, const uint8_t *chars, const
 /* Host only: the kernel bsq_kmer_tokenize_device takes for this shape ("k_kmer_bp<s1>", "k_kmer_bp<sk>", "k_kmer_generic"), from the
  * predicate the launch uses; "" for arguments the device call refuses. */
 const char *bsq_kmer_kernel_name(const bsq_desc *d, const bsq_kmer *km, int64_t B, int64_t P, int32_t batch_first, bsq_dtype t);
+
+/* ---- k-mer spectrum: one fixed-width vector per sequence holding the count or the frequency of each of the A^k words -- tetranucleotide
+ * frequencies for binners and contig classifiers, di- and tripeptide composition for protein classifiers, the 6-mer profile a DNA
+ * language model is compared against -- in ONE launch from the packed batch, instead of the k-mer id matrix + a mask + scatter_add_ into
+ * a zeroed matrix in the framework.
+ *
+ * THE RULE.  For a tokenizer description d (A = d->nchars classes), a bsq_kmer (k, stride s) and a row of L characters:
+ *     windows  exactly bsq_kmer's: window j covers characters [j*s, j*s + k), id(w) is the lexicographic Horner sum; a window with ANY
+ *              unmapped character (bsq_kmer's UNK) contributes nothing.  d->bos, d->eos and d->padchar are ignored: BOS, EOS and PAD
+ *              play no part.
+ *     n        = min(n_tok(L), 2^23); a negative L (malformed offsets) counts as 0; a longer row is clamped to its first 2^23 windows,
+ *              memory-safe.
+ *     out      (B, V), C-contiguous, V = A^k: out[i, v] = the number of windows j < n of row i with id = v.  Every element is written
+ *              exactly once, zeros included: no memset pass runs before the kernel and the caller's buffer need not be cleared.
+ *     both_strands   accepted only when A = 4 and the table maps A, C, G, T to 0, 1, 2, 3 (DNA, DNA4); every other alphabet:
+ *              BSQ_ERR_INVALID_ARG.  Every counted window adds 1 at id(w) and 1 at id(rc(w)), rc(w)[i] = 3 - w[k-1-i], so
+ *              id(rc(w)) = sum_j (3 - c_j) * 4^j.  A window that is its own reverse complement adds 2 to its column; columns v and
+ *              rc(v) are always equal.
+ *     normalize      0: counts.  1: frequencies out[i, v] = count / S_i with S_i the row's sum of counts (all zeros when S_i = 0):
+ *              (float)count / (float)S with IEEE correctly rounded division for BSQ_F32, the same in double for BSQ_F64.  Both
+ *              operands are exact (counts are at most 2^24), so a numpy twin reproduces the bits.
+ *     types    counts: BSQ_I32, BSQ_U64 (int64 bits, as everywhere), BSQ_F32, BSQ_F64; frequencies: BSQ_F32, BSQ_F64; anything else is
+ *              BSQ_ERR_DTYPE (BSQ_I8 / BSQ_I16 cannot hold the count of a row whose length the host does not know).
+ *
+ * Limits, checked before anything is launched: bsq_kmer's own; V <= 2^14 (DNA4 up to k = 7, DNA5 up to k = 6, AMINO20 up to k = 3, SEB8
+ * up to k = 4) -- beyond that BSQ_ERR_INVALID_ARG: a dense (B, V) matrix above that is no longer a feature vector, and the histogram no
+ * longer fits the LDS design; any stride >= 1; B <= 2^31 - 1.  B == 0 is BSQ_OK with nothing launched; stream-ordered, never synchronises; null or
+ * negative arguments, flags other than 0 / 1, form outside 0 .. 2, reserved != 0: BSQ_ERR_INVALID_ARG.  Every refusal leaves `out` untouched
+ * and sets bsq_last_error().
+ *
+ * Known answers (DNA4, k = 2, s = 1, counts; the batch ACGTAC, ACGNACGT, AC, "", TTTTTTT; columns not listed are 0):
+ *     one strand    {1:2, 6:1, 11:1, 12:1}   {1:2, 6:2, 11:1}   {1:1}         {}   {15:6}
+ *     both strands  {1:3, 6:2, 11:3, 12:2}   {1:3, 6:4, 11:3}   {1:1, 11:1}   {}   {0:6, 15:6}
+ *     k = 3, s = 2, one strand:  {6:1, 44:1}   {6:2}   {}   {}   {63:3}
+ * The columns of the k = 2 vocabulary with v <= rc(v) -- the canonical 2-mers -- are 0 1 2 3 4 5 6 8 9 12.
+ *
+ * Kernels: a histogram of V u32 bins in LDS per row, LDS atomics, one conversion and write-out.  k_kmer_spectrum_wave (V <= 1024): a
+ * wave per row, four rows per workgroup -- reads, proteins.  k_kmer_spectrum_block<1024 | 4096 | 16384>: a workgroup per row -- long rows
+ * (contigs) and every V above 1024.  form = 0 takes the wave form when V <= 1024 and (total_chars == 0 or total_chars / B < 2048, or
+ * < 16384 in a batch of at least 4096 rows: a measured choice, bsq_kmer_spectrum_dev.h), else the block form.  One row is never split across workgroups: a handful of chromosome-length rows run on a handful of CUs. */
+typedef struct bsq_kmer_spectrum {
+    int32_t both_strands; /* 0 / 1 */
+    int32_t normalize;    /* 0 counts, 1 frequencies */
+    int32_t form;         /* 0: the library chooses; 1: wave per row; 2: workgroup per row (a form that cannot take V: BSQ_ERR_INVALID_ARG) */
+    int32_t reserved;     /* 0 */
+    int64_t total_chars;  /* hint for the choice of kernel only (0: unknown); never bounds a load */
+} bsq_kmer_spectrum;
+/* V = A^k, or a negative bsq_status (-BSQ_ERR_INVALID_ARG) for what bsq_kmer refuses and for V > 2^14. */
+int64_t bsq_kmer_spectrum_width(const bsq_desc *d, const bsq_kmer *km);
+bsq_status bsq_kmer_spectrum_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
+                                    const bsq_kmer_spectrum *o, bsq_dtype t, void *out, void *hip_stream);
+/* CPU twin on host buffers (the same window and element code; no device is needed). */
+bsq_status bsq_kmer_spectrum_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
+                                  const bsq_kmer_spectrum *o, bsq_dtype t, void *out);
+/* Host only: the kernel bsq_kmer_spectrum_device takes ("k_kmer_spectrum_wave", "k_kmer_spectrum_block<1024>", "...<4096>",
+ * "...<16384>"), from the predicate the launch uses; "" for arguments the device call refuses. */
+const char *bsq_kmer_spectrum_kernel_name(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_spectrum *o, int64_t B, bsq_dtype t);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the

@@ -1,0 +1,342 @@
+"""GPU: the k-mer spectrum of packed batches (bioseq_amd.kmers.kmer_spectrum_packed, bsq_kmer_spectrum_device) against the numpy twin
+(tests/kmer_spectrum_twin.py) and the library's host twin, byte for byte, on shapes that reach both kernels and their boundaries; the two
+forms against each other; two independent device paths; the layout guards; the Python surface and the spectrum FlatFileDataset."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import kmer_spectrum_twin as twin
+import views_twin
+
+pytestmark = pytest.mark.gpu
+
+I32, U64, F32, F64 = 2, 3, 4, 5
+CODE = {"i": I32, "q": U64, "f": F32, "d": F64}
+COMBOS = [("i", False), ("q", False), ("f", False), ("d", False), ("f", True), ("d", True)]
+WAVE, BLOCK = "k_kmer_spectrum_wave", "k_kmer_spectrum_block<%d>"
+POOLS = {
+    "DNA4": b"ACGTACGTACGTACGTACGTACGTACGTNacgtn*\xff",
+    "DNA5": b"ACGTNACGTNACGTNACGTNacgtn*\xff",
+    "AMINO20": b"ACDEFGHIKLMNPQRSTVWYACDEFGHIKLMNPQRSTVWYXBZ*acd",
+    "PURPYR": b"ACGTRYACGTRYACGTRYacgt*N\xc1",
+}
+
+
+def _lut(key):
+    from bioseq_amd import capi
+    lut = (ctypes.c_int8 * 256)()
+    n = ctypes.c_int32(0)
+    assert capi.load().bsq_lut_get(key.encode(), lut, ctypes.byref(n)) == capi.OK
+    return np.array(lut, dtype=np.int8), n.value
+
+
+def _batch(rng, key, lens):
+    """Packed batch of rows of the given lengths; the LAST row ends at the last byte of chars (the guarded tail loads)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    chars = rng.choice(np.frombuffer(POOLS[key], np.uint8), int(lens.sum())).astype(np.uint8)
+    offs = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    assert offs[-1] == chars.size
+    return chars, offs
+
+
+def _dev(a, gpu):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+
+
+def _tok(bsq, key):
+    return bsq.Tokenizer(key, False, False, False)
+
+
+def _check(bsq, gpu, key, chars, offs, k, s=1, combos=(("i", False), ("f", True)), both=False, forms=(None,), kernel=None, dev=None):
+    """kmer_spectrum_packed == the numpy twin == the library's host twin, byte for byte, for every (destchar, normalize) and form."""
+    import torch
+    from bioseq_amd import kmers
+    tok = _tok(bsq, key)
+    lut, A = _lut(key)
+    dch, dof = dev if dev is not None else (_dev(chars, gpu), _dev(offs, gpu))
+    B = len(offs) - 1
+    for dc, norm in combos:
+        exp = twin.spectrum(lut, A, chars, offs, k, s, CODE[dc], both, norm)
+        host = kmers.kmer_spectrum_host(tok, chars, offs, k, dc, stride=s, both_strands=both, normalize=norm)
+        assert host.tobytes() == exp.tobytes(), (key, k, s, dc, norm, both)
+        for form in forms:
+            if kernel is not None:
+                assert kmers.kmer_spectrum_kernel_name(tok, k, B, dc, stride=s, both_strands=both, normalize=norm, form=form,
+                                                       total_chars=chars.size) == kernel
+            got = kmers.kmer_spectrum_packed(tok, dch, dof, k, dc, stride=s, both_strands=both, normalize=norm, form=form, validate=False)
+            torch.cuda.synchronize()
+            assert got.shape == (B, A ** k) and got.is_contiguous() and got.dtype == torch.from_numpy(exp).dtype
+            assert got.cpu().numpy().tobytes() == exp.tobytes(), (key, k, s, dc, norm, both, form)
+
+
+WAVE_CASES = [("PURPYR", 1, 2), ("DNA4", 2, 16), ("DNA5", 3, 125), ("DNA4", 4, 256), ("AMINO20", 2, 400), ("DNA4", 5, 1024)]
+
+
+@pytest.mark.parametrize("key, k, V", WAVE_CASES)
+@pytest.mark.parametrize("B", [1, 3, 5, 257])
+def test_wave_form_equals_the_twins(gpu, bsq, key, k, V, B):
+    """Random lengths 0 .. 700 with rows pinned on the lane-run (16 windows), 64-window and wave-sweep (64 x 16 windows) boundaries; B = 1,
+    3, 5: rows that do not fill four waves, B = 257: a partial last workgroup."""
+    assert _lut(key)[1] ** k == V
+    rng = np.random.default_rng(V * 1000 + B)
+    lens = rng.integers(0, 701, B)
+    pins = {1: [16 * 64 + k - 1], 3: [0, 63 + k, 64 + k], 5: [0, k - 1, k, 63 + k, 16 * 64 + k - 1],
+            257: [0, k - 1, k, 63 + k, 64 + k, 16 * 64 + k - 1, 15 + k, 16 + k, 16 * 64 + k]}[B]
+    lens[:len(pins)] = pins
+    if B == 257:
+        lens[-1] = 700
+    chars, offs = _batch(rng, key, lens)
+    _check(bsq, gpu, key, chars, offs, k, kernel=WAVE)
+
+
+BLOCK_CASES = [("DNA4", 6, 4096, None, 4096), ("AMINO20", 3, 8000, None, 16384), ("DNA4", 7, 16384, None, 16384), ("DNA4", 4, 256, 2, 1024)]
+
+
+@pytest.mark.parametrize("key, k, V, form, bins", BLOCK_CASES)
+@pytest.mark.parametrize("B", [1, 7])
+def test_block_form_equals_the_twins(gpu, bsq, key, k, V, form, bins, B):
+    """Rows of one piece (256 x 16 windows), on the piece boundary and of several pieces."""
+    assert _lut(key)[1] ** k == V
+    rng = np.random.default_rng(V + B)
+    lens = [4097] if B == 1 else [0, k, 4095, 4096, 4097, 20000, 4096 + k - 1]
+    chars, offs = _batch(rng, key, lens)
+    _check(bsq, gpu, key, chars, offs, k, forms=(form,), kernel=BLOCK % bins)
+
+
+def test_both_forms_agree_and_the_name_follows_the_hint(gpu, bsq):
+    import torch
+    from bioseq_amd import kmers
+    rng = np.random.default_rng(11)
+    for key, k in (("DNA4", 3), ("DNA4", 5), ("AMINO20", 2)):
+        tok = _tok(bsq, key)
+        lens = rng.integers(0, 3000, 41)
+        lens[:3] = (0, k, 5000)
+        chars, offs = _batch(rng, key, lens)
+        dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+        for dc, norm in (("q", False), ("d", True)):
+            a = kmers.kmer_spectrum_packed(tok, dch, dof, k, dc, normalize=norm, form=1)
+            b = kmers.kmer_spectrum_packed(tok, dch, dof, k, dc, normalize=norm, form=2)
+            c = kmers.kmer_spectrum_packed(tok, dch, dof, k, dc, normalize=norm)
+            torch.cuda.synchronize()
+            assert torch.equal(a, b) and torch.equal(a, c), (key, k, dc)
+        name = kmers.kmer_spectrum_kernel_name
+        assert name(tok, k, 41, form=1) == WAVE and name(tok, k, 41, form=2) == BLOCK % 1024
+        assert name(tok, k, 41) == WAVE                                 # no hint: the wave form
+        assert name(tok, k, 41, total_chars=41 * 2047) == WAVE          # the mean row is short
+        assert name(tok, k, 41, total_chars=41 * 2048) == BLOCK % 1024  # the mean row is long
+        assert name(tok, k, 41, total_chars=41 * 2048, form=1) == WAVE
+    tok = _tok(bsq, "DNA4")
+    assert name(tok, 6, 41) == BLOCK % 4096 and name(tok, 6, 41, total_chars=41) == BLOCK % 4096 and name(tok, 7, 41) == BLOCK % 16384
+
+
+def test_contention_every_lane_on_one_bin(gpu, bsq):
+    """5 000 A: every window of every lane hits one bin (two with both strands: 0 and V - 1); ACAC...: two bins (four)."""
+    import torch
+    from bioseq_amd import kmers
+    chars = np.frombuffer(b"A" * 5000 + b"AC" * 2500, dtype=np.uint8).copy()
+    offs = np.array([0, 5000, 10000], dtype=np.int64)
+    tok = _tok(bsq, "DNA4")
+    dev = _dev(chars, gpu), _dev(offs, gpu)
+    for k, forms in ((4, (1, 2)), (6, (2,))):
+        V, n = 4 ** k, 5000 - k + 1
+        for both in (False, True):
+            _check(bsq, gpu, "DNA4", chars, offs, k, combos=(("i", False), ("f", True)), both=both, forms=forms, dev=dev)
+            for form in forms:
+                got = kmers.kmer_spectrum_packed(tok, *dev, k, "q", both_strands=both, form=form).cpu().numpy()
+                assert got[0, 0] == n and got[0, V - 1] == (n if both else 0) and got[0].sum() == (2 * n if both else n)
+                assert got[1].sum() == (2 * n if both else n) and np.count_nonzero(got[1]) == (4 if both else 2)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("key, k, form", [("DNA4", 4, 1), ("DNA4", 4, 2), ("DNA4", 6, 2), ("AMINO20", 2, 1), ("DNA5", 3, 2)])
+def test_strides_strands_and_every_element_type(gpu, bsq, key, k, form):
+    rng = np.random.default_rng(k + form)
+    lens = rng.integers(0, 1500, 37)
+    lens[:4] = (0, k - 1, k, 4100)
+    chars, offs = _batch(rng, key, lens)
+    dev = _dev(chars, gpu), _dev(offs, gpu)
+    for s in (1, 2, k):
+        for both in ((False, True) if key == "DNA4" else (False,)):
+            _check(bsq, gpu, key, chars, offs, k, s=s, combos=COMBOS, both=both, forms=(form,), dev=dev)
+    _check(bsq, gpu, key, chars, offs, k, s=1000, forms=(form,), dev=dev)  # a stride longer than most rows
+
+
+def test_guard_bytes_offsets_not_at_zero_and_an_empty_batch(gpu, bsq):
+    """The raw entry point on a batch inside a larger buffer (offsets[0] > 0), into the middle of a 0xAB-filled output, on a side stream:
+    every byte of the (B, V) block is written -- zeros included --, the guards stay; B == 0 launches nothing; a refusal writes nothing."""
+    import torch
+    from bioseq_amd import capi
+    L = capi.load()
+    rng = np.random.default_rng(5)
+    lens = rng.integers(0, 90, 133)
+    lens[:3] = (0, 3, 4200)
+    chars, offs = _batch(rng, "DNA4", lens)
+    lead = 7
+    big = np.concatenate([np.full(lead, ord("N"), np.uint8), chars])
+    offs = offs + lead
+    dch, dof = _dev(big, gpu), _dev(offs, gpu)
+    d = capi.make_desc("DNA4", eos=True, bos=True, padchar=True)
+    lut, A = _lut("DNA4")
+    side = torch.cuda.Stream(device=gpu)
+    B, guard = 133, 256
+    for k, s, form, dt, both, norm in ((4, 1, 1, I32, 0, 0), (4, 1, 2, F32, 1, 1), (3, 3, 0, U64, 0, 0), (6, 2, 0, F64, 1, 0), (1, 1, 0, I32, 1, 0)):
+        km, o = capi.Kmer(k, s), capi.KmerSpectrum(both, norm, form, 0, big.size)
+        V = 4 ** k
+        size = np.dtype(twin.NP_DTYPES[dt]).itemsize
+        n = B * V * size
+        # (the block does not start on a 16-byte boundary for k = 1: rows of 16 bytes at an offset of 4)
+        skew = 4 if k == 1 else 0
+        buf = torch.full((n + 2 * guard + skew,), 0xAB, dtype=torch.uint8, device=gpu)
+        side.wait_stream(torch.cuda.current_stream())
+        capi.check(L.bsq_kmer_spectrum_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), B, ctypes.byref(km), ctypes.byref(o), dt,
+                                              buf.data_ptr() + guard + skew, ctypes.c_void_p(side.cuda_stream)))
+        side.synchronize()
+        raw = buf.cpu().numpy()
+        assert (raw[:guard + skew] == 0xAB).all() and (raw[guard + skew + n:] == 0xAB).all(), "a guard byte of out was overwritten"
+        exp = twin.spectrum(lut, A, big, offs, k, s, dt, bool(both), bool(norm))
+        assert raw[guard + skew:guard + skew + n].tobytes() == exp.tobytes(), (k, s, form, dt)
+        capi.check(L.bsq_kmer_spectrum_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), 0, ctypes.byref(km), ctypes.byref(o), dt,
+                                              buf.data_ptr(), ctypes.c_void_p(side.cuda_stream)))
+        capi.check(L.bsq_kmer_spectrum_device(ctypes.byref(d), None, None, 0, ctypes.byref(km), ctypes.byref(o), dt, None, None))
+        side.synchronize()
+        assert (buf[:guard].cpu().numpy() == 0xAB).all()
+    # refusals leave the device buffer untouched
+    buf = torch.full((B * 4096 * 4,), 0xAB, dtype=torch.uint8, device=gpu)
+    for k, dt, o in ((6, I32, capi.KmerSpectrum(0, 0, 1, 0, 0)), (8, I32, capi.KmerSpectrum(0, 0, 0, 0, 0)), (4, 0, capi.KmerSpectrum(0, 0, 0, 0, 0)),
+                     (4, I32, capi.KmerSpectrum(0, 1, 0, 0, 0))):
+        km = capi.Kmer(k, 1)
+        st = L.bsq_kmer_spectrum_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), B, ctypes.byref(km), ctypes.byref(o), dt, buf.data_ptr(), None)
+        torch.cuda.synchronize()
+        assert st in (capi.ERR_INVALID_ARG, capi.ERR_DTYPE) and bool((buf == 0xAB).all()), (k, dt)
+
+
+def test_bincount_of_the_kmer_ids_is_the_count_spectrum(gpu, bsq):
+    """An independent device path: per row, torch.bincount of the ids < V of kmer_tokenize_packed at the same k and stride."""
+    import torch
+    from bioseq_amd import kmers
+    rng = np.random.default_rng(8)
+    B, k, V = 300, 4, 256
+    lens = rng.integers(0, 201, B)
+    lens[-1] = 200
+    chars, offs = _batch(rng, "DNA4", lens)
+    dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+    padded = bsq.Tokenizer("DNA4", False, False, True)  # PAD = V + 1: no pad position reads as the id 0
+    for s in (1, 3):
+        P = kmers.kmer_padlen(padded, k, 200, stride=s)
+        ids = kmers.kmer_tokenize_packed(padded, dch, dof, k, P, "q", True, stride=s)
+        keyed = ids + torch.arange(B, device=gpu)[:, None] * V
+        want = torch.bincount(keyed[ids < V], minlength=B * V).reshape(B, V)
+        for form in (1, 2):
+            got = kmers.kmer_spectrum_packed(_tok(bsq, "DNA4"), dch, dof, k, "q", stride=s, form=form)
+            assert torch.equal(got, want), (s, form)
+
+
+def test_both_strands_is_the_batch_plus_its_reverse_complement_view(gpu, bsq):
+    import torch
+    from bioseq_amd import kmers, views
+    rng = np.random.default_rng(9)
+    lens = rng.integers(0, 400, 200)
+    lens[:2] = (0, 2500)
+    chars, offs = _batch(rng, "DNA4", lens)
+    dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+    tok = _tok(bsq, "DNA4")
+    vch, vof = views.crop_packed(dch, dof, 2500, mode="head", revcomp_frac=1.0)
+    assert torch.equal(vof, dof)  # window >= the longest row: every view is its whole row, reverse-complemented
+    for k, s in ((4, 1), (6, 1), (5, 2), (3, 3)):
+        if s == 1:
+            both = kmers.kmer_spectrum_packed(tok, dch, dof, k, "q", stride=s, both_strands=True)
+            fwd = kmers.kmer_spectrum_packed(tok, dch, dof, k, "q", stride=s)
+            rev = kmers.kmer_spectrum_packed(tok, vch, vof, k, "q", stride=s)
+            assert torch.equal(both, fwd + rev), (k, s)
+        cols = torch.from_numpy(kmers.kmer_canonical_columns(tok, k)).to(gpu)
+        both = kmers.kmer_spectrum_packed(tok, dch, dof, k, "f", stride=s, both_strands=True, normalize=True)
+        rc = torch.from_numpy(twin.rc_ids(4 ** k, k)).to(gpu)
+        assert torch.equal(both, both[:, rc]) and both[:, cols].shape == (200, cols.numel())
+
+
+def test_python_surface(gpu, bsq):
+    import torch
+    from bioseq_amd import kmers
+    tok = _tok(bsq, "DNA4")
+    chars, offs = _batch(np.random.default_rng(1), "DNA4", [40] * 50)
+    dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+    got = kmers.kmer_spectrum_packed(tok, dch, dof, 3)  # validate=True: well-formed offsets
+    assert got.dtype == torch.float32 and got.shape == (50, 64) and bool((got.sum(dim=1) <= 38).all())
+    bad = dof.clone()
+    bad[3] = bad[2] - 1
+    with pytest.raises(RuntimeError):
+        kmers.kmer_spectrum_packed(tok, dch, bad, 3)  # malformed offsets
+    beyond = dof.clone()
+    beyond[-1] += 5
+    with pytest.raises(RuntimeError):
+        kmers.kmer_spectrum_packed(tok, dch, beyond, 3)  # offsets beyond the characters
+    empty = kmers.kmer_spectrum_packed(tok, dch[:0], dof[:1], 3, "q")
+    assert empty.shape == (0, 64) and empty.dtype == torch.int64
+    zeros = torch.zeros(4, dtype=torch.int64, device=gpu)
+    assert not kmers.kmer_spectrum_packed(tok, dch[:0], zeros, 3, normalize=True).any()  # three empty rows: all zeros, not NaN
+    amino = _tok(bsq, "AMINO20")
+    for call in (lambda: kmers.kmer_spectrum_packed(tok, chars, offs, 3),                       # host arrays
+                 lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 3, "b"), lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 3, "h"),
+                 lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 3, "i", normalize=True),
+                 lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 3, "?"),
+                 lambda: kmers.kmer_spectrum_packed(amino, dch, dof, 2, both_strands=True),       # an alphabet without strands
+                 lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 8), lambda: kmers.kmer_spectrum_packed(amino, dch, dof, 4),  # V > 2^14
+                 lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 6, form=1), lambda: kmers.kmer_spectrum_packed(tok, dch, dof, 3, stride=0)):
+        with pytest.raises(ValueError):
+            call()
+
+
+def test_spectrum_dataset_epochs(gpu, bsq, tmp_path):
+    import torch
+    from bioseq_amd.flatfile import FlatFile, write_flatfile
+    from bioseq_amd.loaders import FlatFileDataset
+    rng = np.random.default_rng(2)
+    lens = rng.integers(0, 900, 1000)
+    lens[:3] = (0, 3, 5000)
+    seqs = [bytes(rng.choice(np.frombuffer(b"ACGTACGTACGTNacgtRY", np.uint8), int(n))) for n in lens]
+    ff = FlatFile(write_flatfile(seqs, str(tmp_path / "spectrum.ff")))
+    tok = bsq.Tokenizer("DNA4", True, True, True)
+    for kw in ({"cnn": True}, {"augment": 1}, {"masked": True}, {"kmer": 4}, {"pack": "nextfit"}, {"spectrum_both_strands": True, "revcomp_frac": 0.0, "spectrum": 9}):
+        with pytest.raises(ValueError):
+            FlatFileDataset(ff, tok, device=gpu, **{"spectrum": 4, **kw})
+    with pytest.raises(ValueError):
+        FlatFileDataset(ff, bsq.Tokenizer("AMINO20", False, False, False), device=gpu, spectrum=2, spectrum_both_strands=True)
+    with pytest.raises(ValueError):
+        next(iter(FlatFileDataset(ff, tok, device=gpu, spectrum=4).batches(128, group=2)))
+    lut, A = _lut("DNA4")
+    for crop, frac, shuffle, both, norm in ((None, 0.0, False, False, True), (None, 0.0, True, True, True), (256, 0.5, True, False, False)):
+        def epoch(**opts):
+            ds = FlatFileDataset(ff, tok, device=gpu, spectrum=4, crop=crop, revcomp_frac=frac, spectrum_both_strands=both, spectrum_normalize=norm)
+            g = torch.Generator(device=gpu).manual_seed(5)
+            out = [b.clone() for b in ds.batches(128, shuffle=shuffle, generator=g, **opts)]
+            torch.cuda.synchronize()
+            return ds, out
+
+        ds, base = epoch()
+        assert all(b.dtype == torch.float32 and b.shape[1] == 256 for b in base) and sum(b.shape[0] for b in base) == 1000
+        g = torch.Generator(device=gpu).manual_seed(5)
+        order = torch.randperm(len(ff), device=gpu, generator=g).cpu().numpy() if shuffle else np.arange(1000)
+        if crop or frac:
+            key = (13 * 0xC2B2AE3D27D4EB4F + 1) & (2 ** 64 - 1)  # the dataset's first view key (seed 13)
+            starts, lengths, strand = views_twin.plan(ff._offsets, crop or 0, order, mode="random", revcomp_frac=frac, seed=key, first_row=0)
+            e_chars, e_offs = views_twin.apply(np.asarray(ff._chars), ff._offsets, order, starts, lengths, strand)
+        else:
+            e_chars = np.frombuffer(b"".join(seqs[i] for i in order), np.uint8)
+            e_offs = np.concatenate([[0], np.cumsum([len(seqs[i]) for i in order])]).astype(np.int64)
+        exp = twin.spectrum(lut, A, e_chars, e_offs, 4, 1, F32, both, norm)
+        assert torch.cat(base).cpu().numpy().tobytes() == exp.tobytes(), (crop, frac, shuffle)
+        _, got = epoch(prefetch=2)
+        assert len(got) == len(base) and all(torch.equal(a, b) for a, b in zip(base, got))
+        # the other access paths hand out rows of the same width
+        assert ds[1].shape == (256,) and ds.get_batch(0, 10).shape == (10, 256) and ds.__getitems__([5, 1, 7]).shape == (3, 256)
+        if not (crop or frac):
+            assert ds.get_batch(0, 10).cpu().numpy().tobytes() == twin.spectrum(lut, A, *_packed(seqs[:10]), 4, 1, F32, both, norm).tobytes()
+
+
+def _packed(seqs):
+    chars = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    return chars, offs
