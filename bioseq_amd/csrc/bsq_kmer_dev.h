@@ -94,6 +94,19 @@ BSQ_KMER_HD int64_t window_id(const Geometry &g, const Lut &lut, const uint8_t *
     return unk ? g.V : v;
 }
 
+// The kernel a (B, P) shape takes in both k-mer families (k_kmer_* and k_kmer_mlm_*): their launches and their kernel-name calls ask here.
+constexpr int64_t kMaxFastP = int64_t(1) << 24;  // the fast kernel's position and character arithmetic is 32-bit
+constexpr int32_t kMaxSkK = 8;                    // <sk>: a window is one 8-byte load (k > 8 would need a second register per window)
+constexpr int64_t kFastThreads = 256;             // lanes of a fast kernel's workgroup (bsq_dev::kThreads: bsq_kmer_lane.h asserts it)
+enum class Form { generic, s1, sk };
+inline Form form_of(const Geometry &g, int64_t B, int64_t P, int32_t batch_first) {
+    if (!batch_first || P > kMaxFastP) return Form::generic;
+    if ((B * ((P + 15) / 16) + kFastThreads - 1) / kFastThreads >= (int64_t(1) << 31)) return Form::generic;
+    if (g.stride == 1) return Form::s1;
+    if (g.stride == g.k && g.k <= kMaxSkK) return Form::sk;
+    return Form::generic;
+}
+
 // position t of a row whose sequence is seq[0 .. L), n = row_tokens(g, L, P)
 template <typename Lut>
 BSQ_KMER_HD int64_t element(const Geometry &g, const Lut &lut, const uint8_t *seq, int64_t n, int64_t t) {

@@ -2,8 +2,7 @@
 // include/bsq.h documents the draw ("k-mer masked-LM"), bsq_kmer_mlm_dev.h holds the value of one element as host + device code.
 //
 // k_kmer_mlm_bp<TI, TL, SK>  (B, P): k_kmer_bp (bsq_kmer.hip) with the draw inside: a lane owns 16 consecutive positions of one row and
-//            computes their 16 plain ids as k_kmer_bp does -- the id code below is a COPY of k_kmer_bp's (its twin: change both), kept
-//            apart so that bsq_kmer.hip's kernels stay instruction for instruction what they were.  Then
+//            computes their 16 plain ids with the text k_kmer_bp uses: lane_ids<SK> (bsq_kmer_lane.h).  What is here is the draw:
 //            - the anchor bits of window indices j0 - span + 1 .. j0 + 15 as one 32-bit mask (bit b: index j0 - span + 1 + b): one
 //              selection hash per quad of indices the span reaches (six at span 6, nine at most), none for quads at or behind the row's
 //              last window;
@@ -16,147 +15,46 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 
 #include "bsq.h"
 #include "bsq_device.h"
 #include "bsq_internal.h"
 #include "bsq_kmer_dev.h"
+#include "bsq_kmer_lane.h"
 #include "bsq_kmer_mlm_dev.h"
 #include "bsq_piece_store.h"
 
 namespace {
 
-using namespace bsq_dev;  // kThreads, Div64, write_out
-using bsq_kmerd::Geometry;
+using namespace bsq_dev;    // kThreads, write_out
+using namespace bsq_kmerd;  // Geometry, Form, form_of, lane_ids, stage_lut
 using bsq_kmlmd::Draw;
 
-constexpr int64_t kMaxFastP = int64_t(1) << 24;  // the fast kernel's position and character arithmetic is 32-bit
-constexpr int32_t kMaxSkK = 8;                    // <sk>: a window is one 8-byte load
-
-struct KmerMlmParams {
+struct KmerMlmParams {  // (bsq_kmer_lane.h: Params)
     const uint8_t *chars;
     const int64_t *offsets;
     void *in;   // nullable
     void *lab;  // nullable
     int64_t B, P, nthreads;
-    Div64 div_g;  // floor(x / pieces per row)
+    Div64 div_g;
     uint32_t pieces;
-    uint32_t k_magic, k_shift, k_pow2;  // fast_div by k (<sk>)
+    uint32_t k_magic, k_shift, k_pow2;
     Geometry g;
     Draw dr;
     int8_t lut[256];
 };
-
-__device__ __forceinline__ void stage_lut(int8_t *s_lut, const KmerMlmParams &p) {
-    s_lut[threadIdx.x] = p.lut[threadIdx.x];  // (kThreads == 256)
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int c) { return (w[c >> 2] >> (8 * (c & 3))) & 0xFFu; }
 
 template <typename TI, typename TL, bool SK>
 __global__ __launch_bounds__(kThreads) void k_kmer_mlm_bp(const KmerMlmParams p) {
     __shared__ int8_t s_lut[256];
     constexpr int kWide = sizeof(TI) > sizeof(TL) ? sizeof(TI) : sizeof(TL);
     __shared__ __align__(16) uint4 s_out[kWide > 1 ? kThreads * kWide : 1];
-    stage_lut(s_lut, p);
-    const int64_t first = static_cast<int64_t>(blockIdx.x) * kThreads;
-    const bool staged = p.P % 16 == 0 && first + kThreads <= p.nthreads;  // (block-uniform)
-    int64_t gid = first + threadIdx.x;
-    const bool valid = gid < p.nthreads;
-    if (!valid) gid = p.nthreads - 1;  // (a thread past the end computes the last piece again and stores nothing)
-    const int64_t i = static_cast<int64_t>(div64(static_cast<uint64_t>(gid), p.div_g));
-    const int32_t t0 = static_cast<int32_t>(gid - i * p.pieces) * 16;
-    const int32_t P = static_cast<int32_t>(p.P);
-    const uint32_t n_el = static_cast<uint32_t>(P - t0 < 16 ? P - t0 : 16);
-    const int64_t start = p.offsets[i], total = p.offsets[p.B];
-    const int64_t L64 = p.offsets[i + 1] - start;
-    const int32_t k = p.g.k, bos = p.g.bos, A = p.g.A;
-    const uint32_t V = static_cast<uint32_t>(p.g.V), lead = static_cast<uint32_t>(p.g.lead);
-    const int32_t room = P - bos - p.g.eos < 0 ? 0 : P - bos - p.g.eos;
-    // characters of the row that can matter, as 32 bits: (room + 1) * k of them hold more than `room` windows at either stride
-    const int32_t cap = (room + 1) * k;
-    const int32_t L = L64 < 0 ? 0 : (L64 > cap ? cap : static_cast<int32_t>(L64));
-    int32_t n;  // tokens of the row
-    if (SK) n = static_cast<int32_t>(fast_div(static_cast<uint32_t>(L), p.k_magic, p.k_shift, p.k_pow2));
-    else n = L < k ? 0 : L - k + 1;
-    n = n < room ? n : room;
-    const int32_t j0 = t0 - bos;  // window index of the piece's first position (-1: the BOS of the row)
-
-    // ---- the 16 plain ids: k_kmer_bp's code (bsq_kmer.hip), copied
+    stage_lut(s_lut, p.lut);
     uint32_t ids[16];
-    if (!SK) {
-        // W: the characters j0 .. j0 + 15 (each starts a window of the piece), M: j0 + k - 1 .. j0 + k + 14 (each ends one)
-        uint32_t W[4] = {0, 0, 0, 0}, M[4] = {0, 0, 0, 0};
-        const int32_t km1 = k - 1;
-        if (j0 < n) {
-            const int64_t a = start + j0;
-            if (a >= 0 && a + km1 + 16 <= total) {
-                const u32x4_unaligned x = *reinterpret_cast<const u32x4_unaligned *>(p.chars + a);
-                const u32x4_unaligned y = *reinterpret_cast<const u32x4_unaligned *>(p.chars + a + km1);
-                W[0] = x.x, W[1] = x.y, W[2] = x.z, W[3] = x.w;
-                M[0] = y.x, M[1] = y.y, M[2] = y.z, M[3] = y.w;
-            } else {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const int32_t jw = j0 + c, jm = jw + km1;
-                    if (jw >= 0 && jw < L && start + jw < total) W[c >> 2] |= static_cast<uint32_t>(p.chars[start + jw]) << (8 * (c & 3));
-                    if (jm >= 0 && jm < L && start + jm < total) M[c >> 2] |= static_cast<uint32_t>(p.chars[start + jm]) << (8 * (c & 3));
-                }
-            }
-        }
-        uint32_t val = 0;
-        int32_t run = 0;  // mapped characters in a row, up to the current one
-#pragma unroll
-        for (int c = 0; c < bsq_kmerd::kMaxK - 1; ++c) {
-            if (c < km1) {  // (uniform)
-                const int32_t id = s_lut[byte_of(W, c)];
-                val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
-                run = id < 0 ? 0 : run + 1;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            if (q > 0) {  // the character that leaves the window
-                const int32_t gone = s_lut[byte_of(W, q - 1)];
-                val -= __umul24(static_cast<uint32_t>(gone < 0 ? 0 : gone), lead);
-            }
-            const int32_t id = s_lut[byte_of(M, q)];
-            val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
-            run = id < 0 ? 0 : run + 1;
-            ids[q] = run >= k ? val : V;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int32_t j = j0 + q;
-            uint32_t id_q = V;
-            if (j >= 0 && j < n) {
-                const int64_t a = start + static_cast<int64_t>(j) * k;
-                uint64_t w = 0;
-                if (a >= 0 && a + 8 <= total) {
-                    w = *reinterpret_cast<const u64_unaligned *>(p.chars + a);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < kMaxSkK; ++c)
-                        if (c < k && a + c >= 0 && a + c < total) w |= static_cast<uint64_t>(p.chars[a + c]) << (8 * c);
-                }
-                uint32_t val = 0;
-                bool unk = false;
-#pragma unroll
-                for (int c = 0; c < kMaxSkK; ++c) {
-                    if (c < k) {  // (uniform)
-                        const int32_t id = s_lut[static_cast<uint32_t>(w >> (8 * c)) & 0xFFu];
-                        unk |= id < 0;
-                        val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
-                    }
-                }
-                id_q = unk ? V : val;
-            }
-            ids[q] = id_q;
-        }
-    }
+    const Piece pc = lane_ids<SK>(p, s_lut, ids);
+    const int64_t i = pc.i;
+    const int32_t j0 = pc.j0, n = pc.n;
+    const uint32_t V = static_cast<uint32_t>(p.g.V);
 
     // ---- the selection.  lo = the first window index whose anchor reaches the piece; bit 4 q + l of `quads` is index 4 (qb + q) + l,
     // so index lo + b is bit b + (lo - 4 qb) of it.  lo >= -16 (j0 >= -1, span <= 16).
@@ -191,7 +89,7 @@ __global__ __launch_bounds__(kThreads) void k_kmer_mlm_bp(const KmerMlmParams p)
     }
     sel &= cov;
 
-    const int64_t e0 = i * p.P + t0;
+    const int64_t e0 = i * p.P + pc.t0;
     if (p.in) {
         TI v[16];
 #pragma unroll
@@ -206,21 +104,21 @@ __global__ __launch_bounds__(kThreads) void k_kmer_mlm_bp(const KmerMlmParams p)
             if ((sel >> q) & 1u) input = bsq_kmlmd::replace(bsq_kmlmd::replace_word(h, static_cast<uint64_t>(j)), p.dr.th, p.dr.mask_token, V, x);
             v[q] = static_cast<TI>(input);
         }
-        write_out(static_cast<TI *>(p.in), gid, e0, v, n_el, valid, staged, s_out);
+        write_out(static_cast<TI *>(p.in), pc.gid, e0, v, pc.n_el, pc.valid, pc.staged, s_out);
     }
     if (p.lab) {
         const TL ign = static_cast<TL>(p.dr.ignore);
         TL v[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = ((sel >> q) & 1u) ? static_cast<TL>(static_cast<int64_t>(ids[q])) : ign;
-        write_out(static_cast<TL *>(p.lab), gid, e0, v, n_el, valid, staged, s_out);
+        write_out(static_cast<TL *>(p.lab), pc.gid, e0, v, pc.n_el, pc.valid, pc.staged, s_out);
     }
 }
 
 template <typename TI, typename TL>
 __global__ __launch_bounds__(kThreads) void k_kmer_mlm_generic(const KmerMlmParams p, int32_t batch_first) {
     __shared__ int8_t s_lut[256];
-    stage_lut(s_lut, p);
+    stage_lut(s_lut, p.lut);
     const int64_t nel = p.B * p.P;
     const int64_t step = static_cast<int64_t>(gridDim.x) * kThreads;
     TI *in = static_cast<TI *>(p.in);
@@ -238,15 +136,7 @@ __global__ __launch_bounds__(kThreads) void k_kmer_mlm_generic(const KmerMlmPara
     }
 }
 
-// The kernel a shape takes: the launch and bsq_kmer_mlm_kernel_name both ask here (the predicate of bsq_kmer.hip's form_of).
-enum class Form { generic, s1, sk };
-Form form_of(const Geometry &g, int64_t B, int64_t P, int32_t batch_first) {
-    if (!batch_first || P > kMaxFastP) return Form::generic;
-    if ((B * ((P + 15) / 16) + kThreads - 1) / kThreads >= (int64_t(1) << 31)) return Form::generic;
-    if (g.stride == 1) return Form::s1;
-    if (g.stride == g.k && g.k <= kMaxSkK) return Form::sk;
-    return Form::generic;
-}
+// The names of the kernels form_of (bsq_kmer_dev.h) picks: the launch and bsq_kmer_mlm_kernel_name both ask it.
 const char *form_name(Form f) {
     return f == Form::s1 ? "k_kmer_mlm_bp<s1>" : (f == Form::sk ? "k_kmer_mlm_bp<sk>" : "k_kmer_mlm_generic");
 }
@@ -271,20 +161,11 @@ bsq_status bsq_kmer_mlm_tokenize_device(const bsq_desc *d, const uint8_t *chars,
     KmerMlmParams p;
     const bsq_status st = bsq_kmlmd::check_args(d, chars, offsets, B, P, km, m, in_dtype, inputs_or_null, label_dtype, labels_or_null, true, &p.g, &p.dr);
     if (st != BSQ_OK || B == 0) return st;
-    std::memcpy(p.lut, d->lut, 256);
-    p.chars = chars;
-    p.offsets = offsets;
+    fill_lane(&p, d, chars, offsets, B, P);
     p.in = inputs_or_null;
     p.lab = labels_or_null;
-    p.B = B;
-    p.P = P;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const Form form = form_of(p.g, B, P, batch_first);
-    const int64_t pieces = (P + 15) / 16;
-    p.pieces = static_cast<uint32_t>(pieces);
-    p.div_g = div64_constants(static_cast<uint64_t>(pieces));
-    p.nthreads = B * pieces;
-    div_constants(static_cast<uint32_t>(p.g.k), &p.k_magic, &p.k_shift, &p.k_pow2);
     const bsq_status launched = bsq_internal::with_value_type(in_dtype, [&](auto ti) {
         using TI = decltype(ti);
         return bsq_internal::with_value_type(label_dtype, [&](auto tl) {

@@ -9,7 +9,7 @@
 // k_kmer_spectrum_block<T, BINS, S1>  a 256-thread workgroup per row, BINS = 1024 / 4096 / 16384 bins (4 / 16 / 64 KiB): long rows and
 //            every V above 1024.
 // Both sweep a row in pieces of (lanes x 16) windows: a lane takes 16 consecutive windows.
-//            <S1> stride 1: the two 16-byte loads, the rolling id and the mapped-run counter of k_kmer_bp<s1> (bsq_kmer.hip);
+//            <S1> stride 1: two 16-byte loads, then the rolling id and mapped-run counter k_kmer_bp<s1> uses: roll16 (bsq_kmer_lane.h);
 //            otherwise one 16-byte load (k <= 16) and a Horner sum per window.
 // Loads are 16 bytes wide where they end at or before offsets[B], byte by byte behind that bound otherwise.
 #include <hip/hip_runtime.h>
@@ -24,12 +24,14 @@
 #include "bsq_device.h"
 #include "bsq_internal.h"
 #include "bsq_kmer_dev.h"
+#include "bsq_kmer_lane.h"
 #include "bsq_kmer_spectrum_dev.h"
 
 namespace {
 
 using namespace bsq_dev;  // kThreads, store16, u32x4_unaligned
 using bsq_kmerd::Geometry;
+using bsq_kmerd::stage_lut;
 using bsq_specd::Form;
 
 constexpr int kRun = 16;                // windows of a lane's run
@@ -43,13 +45,6 @@ struct SpecParams {
     int32_t both, normalize;
     int8_t lut[256];
 };
-
-__device__ __forceinline__ void stage_lut(int8_t *s_lut, const SpecParams &p) {
-    s_lut[threadIdx.x] = p.lut[threadIdx.x];  // (kThreads == 256)
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int c) { return (w[c >> 2] >> (8 * (c & 3))) & 0xFFu; }
 
 // bsq_specd::rc_id without the loop: complement every digit, reverse the bits, swap the two bits of every digit back (k <= 7)
 __device__ __forceinline__ uint32_t rc_fast(uint32_t v, int32_t k) {
@@ -90,30 +85,12 @@ __device__ __forceinline__ uint32_t sweep(const SpecParams &p, const int8_t *s_l
             uint32_t W[4], M[4];
             load16(p.chars, start + j0, total, chars_left, W);
             load16(p.chars, start + j0 + km1, total, chars_left - km1, M);
-            uint32_t val = 0;
-            int32_t run = 0;  // mapped characters in a row, up to the current one
-#pragma unroll
-            for (int c = 0; c < bsq_kmerd::kMaxK - 1; ++c) {
-                if (c < km1) {  // (uniform)
-                    const int32_t id = s_lut[byte_of(W, c)];
-                    val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
-                    run = id < 0 ? 0 : run + 1;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < kRun; ++q) {
-                if (q > 0) {  // the character that leaves the window
-                    const int32_t gone = s_lut[byte_of(W, q - 1)];
-                    val -= __umul24(static_cast<uint32_t>(gone < 0 ? 0 : gone), p.lead);
-                }
-                const int32_t id = s_lut[byte_of(M, q)];
-                val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
-                run = id < 0 ? 0 : run + 1;
-                if (run >= k && j0 + q < n) {  // (val < V: it is the Horner sum of the last k characters, unmapped ones as 0)
+            bsq_kmerd::roll16(W, M, s_lut, k, A, p.lead, [&](int q, uint32_t val, bool whole) {
+                if (whole && j0 + q < n) {  // (val < V: it is the Horner sum of the last k characters)
                     count_window(hist, val, p);
                     ++counted;
                 }
-            }
+            });
         } else {
             const int32_t last = n - j0 < kRun ? n - j0 : kRun;
 #pragma unroll 1
@@ -125,7 +102,7 @@ __device__ __forceinline__ uint32_t sweep(const SpecParams &p, const int8_t *s_l
 #pragma unroll
                 for (int c = 0; c < bsq_kmerd::kMaxK; ++c) {
                     if (c < k) {  // (uniform)
-                        const int32_t id = s_lut[byte_of(w, c)];
+                        const int32_t id = s_lut[bsq_kmerd::byte_of(w, c)];
                         unk |= id < 0;
                         val = __umul24(val, static_cast<uint32_t>(A)) + static_cast<uint32_t>(id < 0 ? 0 : id);
                     }
@@ -179,7 +156,7 @@ template <typename T, bool S1>
 __global__ __launch_bounds__(kThreads) void k_kmer_spectrum_wave(const SpecParams p) {
     __shared__ int8_t s_lut[256];
     __shared__ __align__(16) uint32_t s_hist[kThreads / 64][bsq_specd::kWaveMaxV];
-    stage_lut(s_lut, p);
+    stage_lut(s_lut, p.lut);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint32_t *hist = s_hist[wave];
     const int64_t i = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave;  // (wave-uniform)
@@ -202,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void k_kmer_spectrum_block(const SpecPara
     const int64_t i = blockIdx.x;  // (< B)
     for (int32_t v = tid; v < p.V; v += kThreads) s_hist[v] = 0;
     if (tid == 0) s_sum = 0;
-    stage_lut(s_lut, p);  // (its barrier also orders the clear before the atomics)
+    stage_lut(s_lut, p.lut);  // (its barrier also orders the clear before the atomics)
     int64_t start;
     const int32_t n = windows_of(p, i, &start);
     const uint32_t mine = wave_sum(sweep<S1, kThreads>(p, s_lut, s_hist, start, p.offsets[p.B], n, tid));
