@@ -18,6 +18,7 @@ I8, I16, I32, U64, F32, F64 = range(6)
 SPACE_HOST, SPACE_DEVICE = 0, 1
 CROP_RANDOM, CROP_HEAD, CROP_CENTER = range(3)
 PACK_STREAM, PACK_NEXTFIT = range(2)
+FRAME_SIX = 6  # bsq_translate.frame: all six frames of every source row (0 .. 5: one frame)
 OK, ERR_INVALID_KEY, ERR_INVALID_ARG, ERR_DTYPE, ERR_SEQ_TOO_LONG, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = range(8)
 
 
@@ -37,6 +38,11 @@ class Crop(ctypes.Structure):
     """struct bsq_crop"""
     _fields_ = [("window", ctypes.c_int64), ("mode", ctypes.c_int32), ("revcomp_frac", ctypes.c_double), ("seed", ctypes.c_uint64),
                 ("first_row", ctypes.c_int64)]
+
+
+class Translate(ctypes.Structure):
+    """struct bsq_translate"""
+    _fields_ = [("code", ctypes.c_uint8 * 64), ("unknown", ctypes.c_uint8), ("frame", ctypes.c_int32)]
 
 
 class Kmer(ctypes.Structure):
@@ -145,6 +151,11 @@ def load():
         "bsq_crop_plan_host": (i32, [vp, i64, vp, i64, ctypes.POINTER(Crop), vp, vp, vp]),
         "bsq_views_packed_device": (i32, [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp]),
         "bsq_complement_table": (i32, [vp]),
+        "bsq_codon_table": (i32, [i32, vp]),
+        "bsq_translate_length": (i64, [i64, i32]),
+        "bsq_translate_packed_device": (i32, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(Translate), vp, i64, vp, vp, vp]),
+        "bsq_translate_packed_host": (i32, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(Translate), vp, i64, vp, vp]),
+        "bsq_translate_kernel_name": (ctypes.c_char_p, [i64, ctypes.POINTER(Translate)]),
         "bsq_kmer_vocab_size": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_unk_id": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_bos_id": (i64, [dp, ctypes.POINTER(Kmer)]),

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import blosum, kmers, masking, packing, views
+from . import translate as translation
 from .flatfile import FlatFile
 
 
@@ -80,6 +81,14 @@ class FlatFileDataset(torch.utils.data.Dataset):
     hand the matrix out; it composes with crop, revcomp_frac, shuffle and prefetch.  With cnn=True, augment > 0, masked=True, kmer=,
     pack= or group > 1 it raises ValueError.
 
+    translate=0 | 1 | 2 (keyword; off by default): the store holds NUCLEOTIDES, the tokenizer is a protein one, and every batch is
+    translated on the device in that forward frame (translate.translate_packed, NCBI table `codon_table` or 64 bytes of the caller's
+    own) after the gather or the crop / strand views and before everything else: masked, pack, pack_mlm, cnn, augment, kmer,
+    spectrum, group and prefetch see a protein batch and work unchanged.  max_seq_len = (crop or the longest sequence) // 3 + bos + eos.
+    A codon with a byte that is no base becomes X and a stop stays '*': unmapped characters to the protein tokenizers, encoded as
+    they encode any unmapped character.  revcomp_frac > 0 is allowed with it whatever the tokenizer: the strand draw in front of the
+    frame makes the batch a sample of the six frames.  Translation draws nothing: no key or counter is added, no existing draw shifts.
+
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
     (tokens, segment_ids, position_ids), each (rows, max_seq_len), rows being what the batch needs (one 8-byte read-back per batch:
@@ -101,7 +110,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
 
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
                  crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False,
-                 kmer_mlm=False, kmer_span=None, spectrum=None, spectrum_stride=1, spectrum_both_strands=False, spectrum_normalize=True):
+                 kmer_mlm=False, kmer_span=None, spectrum=None, spectrum_stride=1, spectrum_both_strands=False, spectrum_normalize=True,
+                 translate=None, codon_table=1):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -128,7 +138,12 @@ class FlatFileDataset(torch.utils.data.Dataset):
         if crop is not None and int(crop) <= 0:
             raise ValueError("crop must be a positive number of characters, got %r" % (crop,))
         views._crop(int(crop or 0), crop_mode, revcomp_frac, 0, 0)  # (mode and revcomp_frac checked here)
-        if float(revcomp_frac) > 0 and tokenizer.key not in self.NUCLEOTIDE_KEYS:
+        if translate is not None and (isinstance(translate, (bool, str)) or int(translate) not in (0, 1, 2)):
+            raise ValueError("translate must be a forward frame 0, 1 or 2, got %r" % (translate,))
+        self.translate = None if translate is None else int(translate)
+        # (the table is checked here; the struct is what every batch's launch takes)
+        self._translate_rule = None if translate is None else translation._rule(self.translate, codon_table, "X", "*")[0]
+        if float(revcomp_frac) > 0 and translate is None and tokenizer.key not in self.NUCLEOTIDE_KEYS:
             raise ValueError("revcomp_frac > 0 needs a nucleotide alphabet (%s), not %r" % (", ".join(self.NUCLEOTIDE_KEYS), tokenizer.key))
         self.crop = None if crop is None else int(crop)
         self.crop_mode, self.revcomp_frac = crop_mode, float(revcomp_frac)
@@ -137,6 +152,9 @@ class FlatFileDataset(torch.utils.data.Dataset):
         if self.crop is not None:  # every view fits: nothing to validate
             self.max_seq_len = self.maxseqlen = self.crop + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
             self._trusted_lengths = True
+        if self.translate is not None:  # a row holds at most a third of its source's characters, whatever the frame
+            longest = self.crop if self.crop is not None else ff.maxseqlen
+            self.max_seq_len = self.maxseqlen = longest // 3 + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
         self.kmer = None if kmer is None else int(kmer)
         self.kmer_stride = int(kmer_stride)
         if self.kmer is not None:
@@ -144,6 +162,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
                 raise ValueError("kmer= gives token rows of the plain batch: it cannot be combined with cnn=True, augment > 0 or masked=True")
             # (k, stride and nchars ** k are checked here); at least one position, so that a store of sequences shorter than k still encodes
             longest = self.crop if self.crop is not None else ff.maxseqlen
+            if self.translate is not None:
+                longest //= 3
             self.max_seq_len = self.maxseqlen = max(1, kmers.kmer_padlen(tokenizer, self.kmer, longest, self.kmer_stride))
         self.pack = pack
         if pack is not None:
@@ -178,6 +198,18 @@ class FlatFileDataset(torch.utils.data.Dataset):
         return self.ff.nseqs()
 
     def _packed_device(self, start, stop, indices=None, trusted=False, view=None):
+        """The batch every encode takes: the rows of `_source_device`, translated when translate= is set (one more launch, a fresh
+        buffer; it draws nothing)."""
+        chars, offs = self._source_device(start, stop, indices, trusted, view)
+        if self.translate is None:
+            return chars, offs
+        n = int(offs.numel()) - 1
+        cap = int(chars.numel()) // 3  # (never synchronises: the buffer bounds the batch)
+        if self.crop is not None:
+            cap = min(cap, n * (self.crop // 3))
+        return translation._launch(chars, offs, n, None, None, n, n, self._translate_rule, cap)[:2]
+
+    def _source_device(self, start, stop, indices=None, trusted=False, view=None):
         """The batch's own packed copy on the device (never the resident store when it is going to be mutated).
         trusted: `indices` is this dataset's own permutation (in range, no repeats) -- nothing to check, nothing read back.
         view: (key, first_row) of the crop / strand draw (None: the next key of the dataset's counter, rows from 0)."""

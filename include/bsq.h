@@ -39,7 +39,9 @@ extern "C" {
                            * bsq_pack_tokenize_device, bsq_pack_tokenize_host, bsq_pack_kernel_name, bsq_pack_mlm_tokenize_device,
                            * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name, bsq_kmer_mlm, bsq_kmer_mlm_anchor_prob,
                            * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds, bsq_kmer_spectrum,
-                           * bsq_kmer_spectrum_width, bsq_kmer_spectrum_device, bsq_kmer_spectrum_host, bsq_kmer_spectrum_kernel_name; nothing removed */
+                           * bsq_kmer_spectrum_width, bsq_kmer_spectrum_device, bsq_kmer_spectrum_host, bsq_kmer_spectrum_kernel_name, bsq_translate,
+                           * bsq_codon_table, bsq_translate_length, bsq_translate_packed_device, bsq_translate_packed_host, bsq_translate_kernel_name;
+                           * nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -396,6 +398,60 @@ bsq_status bsq_views_packed_device(const uint8_t *chars, const int64_t *offsets,
                                    int64_t *out_offsets, int64_t *status_dev, void *hip_stream);
 /* out[c] <- comp(c) for every byte c: the library's own complement table. */
 bsq_status bsq_complement_table(uint8_t out[256]);
+
+/* ---- codon translation: protein views of a nucleotide store -- the residues of one reading frame, or of all six, of index-list
+ * rows, rebuilt on the device as a packed batch (chars, offsets) in the amino-acid alphabet that every encode path takes as it is.
+ *
+ * GENETIC CODE.  A table is 64 bytes: entry 16 * b0 + 4 * b1 + b2 is the letter of codon b0 b1 b2, bases numbered in NCBI's order
+ * T = 0, C = 1, A = 2, G = 3.  The standard code (NCBI table 1) is
+ *     FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG
+ * bsq_codon_table(id, out) copies out table 1, table 11 (the same letters), table 4 (table 1 with TGA -> W) or table 2 (table 1 with
+ * TGA -> W, ATA -> M, AGA -> *, AGG -> *); any other id is BSQ_ERR_INVALID_ARG.  bsq_translate.code may hold any 64 bytes of the
+ * caller's own instead.  Stops are the table's bytes ('*' in the tables above): a row is never cut at a stop.
+ *
+ * BASES.  A C G T U in either case are bases, U reads as T.  A codon that holds ANY other byte (N, the IUPAC codes, gaps, NUL, bytes
+ * >= 0x80) becomes bsq_translate.unknown; nothing is resolved partially (GCN is unknown, not A).  Output letters are the table's
+ * bytes as given, however the input was cased.
+ *
+ * FRAMES.  Frame codes 0, 1, 2 are forward, 3, 4, 5 reverse; code c has phase f = c % 3.  A source row of length L gives
+ *     m = max(0, L - f) / 3                                   residues (a trailing partial codon is dropped, as the k-mer tail is)
+ *     forward  residue k = code[s[f + 3k] s[f + 3k + 1] s[f + 3k + 2]]
+ *     reverse  residue k = code[comp(s[q]) comp(s[q - 1]) comp(s[q - 2])],  q = L - 1 - f - 3k,  comp: A <-> T / U, C <-> G
+ * On input without U / u the frames 3 .. 5 are the frames 0 .. 2 of the row bsq_views_packed_device gives with strand = 1.  With U
+ * they differ: the complement table of the views leaves U as it is (it is no letter of that table's pairs), translation reads it as
+ * T and complements it to A.
+ *
+ * ROWS.  Source row i is store sequence index[i] (index_or_null == NULL: sequence i, n <= n_store).  Its frame code is
+ *     frames_or_null[i]             when frames_or_null != NULL (bsq_translate.frame must then not be BSQ_FRAME_SIX);
+ *     bsq_translate.frame           0 .. 5: one output row per source row, n rows and n + 1 offsets;
+ *     BSQ_FRAME_SIX                 source row i yields the output rows 6 * i + c, c = 0 .. 5: n_out = 6 * n rows, 6 * n + 1 offsets.
+ *
+ * STATUS, the convention of the views: stream-ordered, never synchronises; *status_dev (device int64, may be NULL) = -1 when every
+ * row was valid and everything fitted, else the smallest of { i: source row i had a bad index or a frame code > 5 (its output rows are
+ * empty), n_out + r: output row r did not fit into out_capacity bytes (it is cut there, nothing is written past the buffer) }.
+ * Argument errors (BSQ_ERR_INVALID_ARG, nothing launched): null pointers, negative sizes, a frame outside 0 .. BSQ_FRAME_SIX,
+ * frames_or_null together with BSQ_FRAME_SIX, index_or_null == NULL with n > n_store.  Up to 4096 output rows take ONE launch
+ * (k_translate_small), more take k_translate_lengths + k_translate_place, beyond 2^20 rows with k_translate_scan between them. */
+enum { BSQ_FRAME_F0 = 0, BSQ_FRAME_F1 = 1, BSQ_FRAME_F2 = 2, BSQ_FRAME_R0 = 3, BSQ_FRAME_R1 = 4, BSQ_FRAME_R2 = 5, BSQ_FRAME_SIX = 6 };
+typedef struct bsq_translate {
+    uint8_t code[64]; /* the genetic code, NCBI order (above) */
+    uint8_t unknown;  /* the letter of a codon with a byte that is no base ('X') */
+    int32_t frame;    /* 0 .. 5, or BSQ_FRAME_SIX */
+} bsq_translate;
+/* out[0 .. 64) <- NCBI table `id` (1, 2, 4 or 11). */
+bsq_status bsq_codon_table(int32_t id, uint8_t out[64]);
+/* m of a source row of L characters under frame code 0 .. 5; -1 for L < 0 or any other code. */
+int64_t bsq_translate_length(int64_t L, int32_t frame_code);
+bsq_status bsq_translate_packed_device(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index_or_null,
+                                       const uint8_t *frames_or_null, int64_t n, const bsq_translate *t, uint8_t *out_chars,
+                                       int64_t out_capacity, int64_t *out_offsets, int64_t *status_dev, void *hip_stream);
+/* CPU twin on host arrays (the same rule text, csrc/bsq_translate_dev.h): the same rows, cuts and *status (host int64, may be NULL). */
+bsq_status bsq_translate_packed_host(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index_or_null,
+                                     const uint8_t *frames_or_null, int64_t n, const bsq_translate *t, uint8_t *out_chars,
+                                     int64_t out_capacity, int64_t *out_offsets, int64_t *status);
+/* Host only: the launches bsq_translate_packed_device takes for n source rows ("k_translate_small", "k_translate_lengths+k_translate_place",
+ * "k_translate_lengths+k_translate_scan+k_translate_place"); "" for arguments the call refuses. */
+const char *bsq_translate_kernel_name(int64_t n, const bsq_translate *t);
 
 /* ---- k-mer ids of a packed batch: the vocabulary DNA language models are trained on -- overlapping 3- to 6-mers (stride 1),
  * non-overlapping 6-mers (stride k), and the same over reduced protein alphabets -- in ONE launch instead of tokens + unfold +
