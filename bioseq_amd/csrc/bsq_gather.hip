@@ -10,19 +10,18 @@
 //   k_gather_scan     in-place inclusive prefix sum -> out_offsets[i + 1] = end of output sequence i  (one workgroup;
 //                     a batch is 10^3 .. 10^6 sequences: 8 MB at most, microseconds)
 //   k_gather_chars    16 lanes per output sequence copy its characters with unaligned 16-byte loads / stores
-// gfx950 only.
+// The offsets scaffold of the launch classes (front sums, scans, the cut at the capacity, the scratch of the sums) is bsq_ragged_out.h,
+// shared with the views and the translation and described there; this file keeps the index look-up, the copy loops, the knob and the
+// order of its launches.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 #include "bsq.h"
 #include "bsq_internal.h"
+#include "bsq_ragged_out.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-typedef uint32_t g_u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 
 __global__ __launch_bounds__(kThreads) void k_gather_lengths(const int64_t *offsets, int64_t n_store, const int64_t *index,
                                                              int64_t n, int64_t *out_offsets, unsigned long long *first_bad) {
@@ -40,31 +39,7 @@ __global__ __launch_bounds__(kThreads) void k_gather_lengths(const int64_t *offs
     out_offsets[i + 1] = len;
 }
 
-// in-place inclusive prefix sum of v[0 .. n) by ONE workgroup of 1024 threads (pieces of 1024 with a running carry)
-__global__ __launch_bounds__(1024) void k_gather_scan(int64_t *v, int64_t n) {
-    __shared__ int64_t s_wave[16];
-    __shared__ int64_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + threadIdx.x;
-        int64_t x = i < n ? v[i] : 0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (lane >= d) x += o;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        int64_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) v[i] = x + before;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = x + before;
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(1024) void k_gather_scan(int64_t *v, int64_t n) { scan_inclusive_block(v, n); }
 
 // 16 lanes per output sequence.  capacity: bytes of out_chars; a batch that does not fit is cut there (never a write
 // past the buffer) and recorded in first_bad as position n + i.
@@ -77,25 +52,17 @@ __global__ __launch_bounds__(kThreads) void k_gather_chars(const uint8_t *chars,
     const int64_t j = index[i];
     if (j < 0 || j >= n_store) return;
     const int64_t src0 = offsets[j], d0 = out_offsets[i];
-    int64_t len = out_offsets[i + 1] - d0;
-    if (d0 + len > capacity) {
-        if (sub == 0 && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(n + i));
-        len = capacity > d0 ? capacity - d0 : 0;
-    }
+    const int64_t len = cut_at_capacity(d0, out_offsets[i + 1] - d0, capacity, n, i, sub, first_bad);
     const uint8_t *src = chars + src0;
     uint8_t *dst = out_chars + d0;
     const int64_t body = len & ~int64_t(15);
     for (int64_t p = sub * 16; p < body; p += 256)
-        *reinterpret_cast<g_u32x4u *>(dst + p) = *reinterpret_cast<const g_u32x4u *>(src + p);
+        *reinterpret_cast<v_u32x4u *>(dst + p) = *reinterpret_cast<const v_u32x4u *>(src + p);
     if (sub < (len & 15)) dst[body + sub] = src[body + sub];
 }
 
-// Loader-sized batches (n <= kSmallN: what a training step asks for) in ONE launch instead of memset + three: a workgroup owns 16
-// output sequences (16 lanes each, as k_gather_chars), sums the lengths of every sequence in front of its own -- all 256 threads,
-// every load of the sum independent of the others -- and then does lengths, offsets and characters of its 16.  n^2 / 16 length
-// look-ups in total (1 M at n = 4096, L2 hits) buy three launches' worth of latency per batch: the step of a shuffled epoch is
-// host- and launch-bound (profiles/r04/loader_step_lab.txt).  first_bad may be null (a caller that vouches for its indices).
-constexpr int64_t kSmallN = 4096;
+// Loader-sized batches (n <= kSmallN: what a training step asks for) in ONE launch instead of memset + three (the `small` class of
+// bsq_ragged_out.h; profiles/r04/loader_step_lab.txt).  first_bad may be null (a caller that vouches for its indices).
 __global__ __launch_bounds__(kThreads) void k_gather_small(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index,
                                                            int64_t n, int64_t *out_offsets, uint8_t *out_chars, int64_t capacity,
                                                            unsigned long long *first_bad) {
@@ -103,21 +70,12 @@ __global__ __launch_bounds__(kThreads) void k_gather_small(const uint8_t *chars,
     __shared__ int64_t s_len[16];
     const int tid = threadIdx.x, sub = tid & 15, g = tid >> 4;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * 16;
-    int64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < int(kSmallN / kThreads); ++k) {
-        const int64_t j = tid + kThreads * k;
-        if (j < first) {
-            const int64_t src = index[j];
-            if (src >= 0 && src < n_store) {
-                const int64_t l = offsets[src + 1] - offsets[src];
-                acc += l > 0 ? l : 0;
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+    small_front_sum<int(kSmallN / kThreads)>(first, s_part, [=](int64_t j) {
+        const int64_t src = index[j];
+        int64_t l = 0;
+        if (src >= 0 && src < n_store) l = offsets[src + 1] - offsets[src];
+        return l > 0 ? l : 0;
+    });
     const int64_t i = first + g;
     const bool live = i < n;
     const int64_t src = live ? index[i] : -1;
@@ -139,44 +97,34 @@ __global__ __launch_bounds__(kThreads) void k_gather_small(const uint8_t *chars,
     if (!live) return;
     if (sub == 0) out_offsets[i + 1] = d0 + len;
     if (!ok || !chars || !out_chars) return;
-    if (d0 + len > capacity) {
-        if (sub == 0 && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(n + i));
-        len = capacity > d0 ? capacity - d0 : 0;
-    }
+    len = cut_at_capacity(d0, len, capacity, n, i, sub, first_bad);
     const uint8_t *sp = chars + src0;
     uint8_t *dst = out_chars + d0;
     const int64_t body = len & ~int64_t(15);
     for (int64_t p = sub * 16; p < body; p += 256)
-        *reinterpret_cast<g_u32x4u *>(dst + p) = *reinterpret_cast<const g_u32x4u *>(sp + p);
+        *reinterpret_cast<v_u32x4u *>(dst + p) = *reinterpret_cast<const v_u32x4u *>(sp + p);
     if (sub < (len & 15)) dst[body + sub] = sp[body + sub];
 }
 
 // Lists beyond kSmallN in TWO launches (round 6; rounds 2-5: three, the middle one a prefix sum by ONE workgroup walking the list in
-// pieces of 1024 -- 16 384 indices of BASELINE config 5's store took 31 us, twice the encode that follows them):
-//   k_gather_lengths2  out_offsets[i + 1] <- length of sequence index[i], and the SUM of every 64 of them (one wave) -> wave_sums[i / 64]
-//   k_gather_place     a workgroup owns 64 output sequences: the sums of the groups in front of it (coalesced loads, all threads: n / 64
-//                      of them at most -- lists of up to 2^20 indices) + a wave scan of its own 64 lengths give their offsets; 16 lanes
-//                      per sequence copy the characters, four rounds.  A workgroup rewrites only its OWN entries of out_offsets.
-constexpr int kPlaceS = 64;
+// pieces of 1024 -- 16 384 indices of BASELINE config 5's store took 31 us, twice the encode that follows them): the `place` class of
+// bsq_ragged_out.h, lists of up to 2^20 indices.  The place kernel stages the source position of its 64 sequences (and their lengths)
+// in LDS next to the scan, so that index is read once.
 __global__ __launch_bounds__(kThreads) void k_gather_lengths2(const int64_t *offsets, int64_t n_store, const int64_t *index, int64_t n,
                                                               int64_t *out_offsets, int64_t *wave_sums, unsigned long long *first_bad) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (i == 0) out_offsets[0] = 0;
-    int64_t len = 0;
-    if (i < n) {
+    lengths_step(i, n, out_offsets, wave_sums, [=](int64_t i) {
         const int64_t j = index[i];
+        int64_t len = 0;
         if (j >= 0 && j < n_store) {
             len = offsets[j + 1] - offsets[j];
             if (len < 0) len = 0;
         } else if (first_bad) {
             atomicMin(first_bad, static_cast<unsigned long long>(i));
         }
-        out_offsets[i + 1] = len;
-    }
-    int64_t acc = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0 && i < n) wave_sums[i >> 6] = acc;
+        return len;
+    });
 }
 
 __global__ __launch_bounds__(kThreads) void k_gather_place(const uint8_t *chars, const int64_t *offsets, int64_t n_store, const int64_t *index,
@@ -186,32 +134,11 @@ __global__ __launch_bounds__(kThreads) void k_gather_place(const uint8_t *chars,
     __shared__ int64_t s_src0[kPlaceS], s_d0[kPlaceS], s_len[kPlaceS];
     const int tid = threadIdx.x;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * kPlaceS;
-    int64_t acc = 0;  // the sums of the 64-sequence groups in front of this one: coalesced, every thread
-    for (int64_t k = tid; k < static_cast<int64_t>(blockIdx.x); k += kThreads) acc += wave_sums[k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    int64_t len = 0, x = 0;
-    if (tid < kPlaceS) {  // (one wave)
-        const int64_t i = first + tid;
-        if (i < n) len = out_offsets[i + 1];
+    place_offsets<false>(n, out_offsets, wave_sums, s_part, s_d0, [=](int t, int64_t i, int64_t len) {
         const int64_t src = i < n ? index[i] : -1;
-        s_src0[tid] = (src >= 0 && src < n_store) ? offsets[src] : -1;  // -1: nothing to copy
-        s_len[tid] = len;
-        x = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (tid >= d) x += o;
-        }
-    }
-    __syncthreads();  // (every read of the lengths in out_offsets is done: this workgroup's own entries are overwritten below, nobody else's)
-    if (tid < kPlaceS) {
-        const int64_t end = s_part[0] + s_part[1] + s_part[2] + s_part[3] + x;
-        s_d0[tid] = end - len;
-        if (first + tid < n) out_offsets[first + tid + 1] = end;
-    }
-    __syncthreads();
+        s_src0[t] = (src >= 0 && src < n_store) ? offsets[src] : -1;  // -1: nothing to copy
+        s_len[t] = len;
+    });
     if (!chars || !out_chars) return;
     const int sub = tid & 15;
 #pragma unroll
@@ -221,16 +148,12 @@ __global__ __launch_bounds__(kThreads) void k_gather_place(const uint8_t *chars,
         const int64_t src0 = s_src0[g];
         if (i >= n || src0 < 0) continue;
         const int64_t d0 = s_d0[g];
-        int64_t l = s_len[g];
-        if (d0 + l > capacity) {
-            if (sub == 0 && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(n + i));
-            l = capacity > d0 ? capacity - d0 : 0;
-        }
+        const int64_t l = cut_at_capacity(d0, s_len[g], capacity, n, i, sub, first_bad);
         const uint8_t *sp = chars + src0;
         uint8_t *dst = out_chars + d0;
         const int64_t body = l & ~int64_t(15);
         for (int64_t p = sub * 16; p < body; p += 256)
-            *reinterpret_cast<g_u32x4u *>(dst + p) = *reinterpret_cast<const g_u32x4u *>(sp + p);
+            *reinterpret_cast<v_u32x4u *>(dst + p) = *reinterpret_cast<const v_u32x4u *>(sp + p);
         if (sub < (l & 15)) dst[body + sub] = sp[body + sub];
     }
 }
@@ -247,47 +170,27 @@ bsq_status bsq_gather_packed_device(const uint8_t *chars, const int64_t *offsets
     if ((n + kThreads - 1) / kThreads >= (int64_t(1) << 31) || (n + 15) / 16 >= (int64_t(1) << 31) || (n + kPlaceS - 1) / kPlaceS >= (int64_t(1) << 31))
         return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "index list too long");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    hipError_t e = hipSuccess;
-    // status_dev == NULL: the caller vouches for its indices and its capacity (bad indices still read nothing, an overflow is still cut)
-    if (status_dev) e = hipMemsetAsync(status_dev, 0xFF, sizeof(int64_t), s);  // -1 = every index valid, everything fitted
-    if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(gather status)", e);
+    const bsq_status st = ragged_reset("gather", n, out_offsets, status_dev, s);
+    if (st != BSQ_OK || n == 0) return st;
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(status_dev);
-    if (n == 0) {
-        e = hipMemsetAsync(out_offsets, 0, sizeof(int64_t), s);
-        if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(gather offsets)", e);
-        return BSQ_OK;
+    const bool classic = bsq_internal::tuning().gather_small == 1;  // the three launches of rounds 2-5, whatever the size
+    if (!classic && form_of(n) == Form::Small) {
+        hipLaunchKernelGGL(k_gather_small, small_grid(n), dim3(kThreads), 0, s, chars, offsets, n_store, index, n, out_offsets, out_chars,
+                           out_chars ? out_capacity : 0, bad);
+        return bsq_internal::check_launch("k_gather_small");
     }
-    if (n <= kSmallN && bsq_internal::tuning().gather_small != 1) {
-        hipLaunchKernelGGL(k_gather_small, dim3(unsigned((n + 15) / 16)), dim3(kThreads), 0, s, chars, offsets, n_store, index, n, out_offsets,
-                           out_chars, out_chars ? out_capacity : 0, bad);
-        e = hipGetLastError();
-        if (e != hipSuccess) return bsq_internal::set_hip_error("k_gather_small", e);
-        return BSQ_OK;
-    }
-    if (bsq_internal::tuning().gather_small != 1 && n <= (int64_t(1) << 20)) {  // two launches; the sums of 64 lengths travel through the stream's scratch
-        const int64_t nblk = (n + kThreads - 1) / kThreads;
-        std::lock_guard<std::mutex> scratch_turn(bsq_internal::workspace_mutex());
-        void *ws = nullptr;
-        const bsq_status st = bsq_internal::workspace_acquire(size_t((n + 63) / 64) * sizeof(int64_t), s, &ws);
-        if (st != BSQ_OK) return st;
-        hipLaunchKernelGGL(k_gather_lengths2, dim3(unsigned(nblk)), dim3(kThreads), 0, s, offsets, n_store, index, n, out_offsets,
-                           static_cast<int64_t *>(ws), bad);
-        hipLaunchKernelGGL(k_gather_place, dim3(unsigned((n + kPlaceS - 1) / kPlaceS)), dim3(kThreads), 0, s, chars, offsets, n_store, index, n,
-                           out_offsets, static_cast<const int64_t *>(ws), out_capacity > 0 ? out_chars : nullptr, out_capacity, bad);
-        e = hipGetLastError();
-        bsq_internal::workspace_release(ws, s);
-        if (e != hipSuccess) return bsq_internal::set_hip_error("k_gather_lengths2 / k_gather_place", e);
-        return BSQ_OK;
-    }
-    hipLaunchKernelGGL(k_gather_lengths, dim3(unsigned((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, offsets, n_store,
-                       index, n, out_offsets, bad);
+    if (!classic && form_of(n) == Form::Place)  // beyond kPlaceSumMax the gather has no scanned place: the three launches again
+        return with_wave_sums(n, s, "k_gather_lengths2 / k_gather_place", [&](int64_t *sums) {
+            hipLaunchKernelGGL(k_gather_lengths2, lengths_grid(n), dim3(kThreads), 0, s, offsets, n_store, index, n, out_offsets, sums, bad);
+            hipLaunchKernelGGL(k_gather_place, place_grid(n), dim3(kThreads), 0, s, chars, offsets, n_store, index, n, out_offsets,
+                               static_cast<const int64_t *>(sums), out_capacity > 0 ? out_chars : nullptr, out_capacity, bad);
+        });
+    hipLaunchKernelGGL(k_gather_lengths, lengths_grid(n), dim3(kThreads), 0, s, offsets, n_store, index, n, out_offsets, bad);
     hipLaunchKernelGGL(k_gather_scan, dim3(1), dim3(1024), 0, s, out_offsets + 1, n);
     if (chars && out_chars && out_capacity > 0)
-        hipLaunchKernelGGL(k_gather_chars, dim3(unsigned((n + 15) / 16)), dim3(kThreads), 0, s, chars, offsets, n_store, index, n,
-                           out_offsets, out_chars, out_capacity, bad);
-    e = hipGetLastError();
-    if (e != hipSuccess) return bsq_internal::set_hip_error("k_gather_*", e);
-    return BSQ_OK;
+        hipLaunchKernelGGL(k_gather_chars, small_grid(n), dim3(kThreads), 0, s, chars, offsets, n_store, index, n, out_offsets, out_chars,
+                           out_capacity, bad);
+    return bsq_internal::check_launch("k_gather_*");
 }
 
 }  // extern "C"

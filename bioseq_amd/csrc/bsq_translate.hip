@@ -2,13 +2,9 @@
 // index-list rows, rebuilt on the device as a packed batch (chars, offsets) in the amino-acid alphabet.  The rule is
 // bsq_translate_dev.h (include/bsq.h, "codon translation", documents it); the host twin compiles the same text.
 //
-// The launch classes are those of the views (bsq_views.hip), by OUTPUT rows; that file and the gather's are not touched, this family
-// carries its own copy of the small offsets scaffolding:
-//   k_translate_small    <= 4096 output rows (a loader batch, or 682 source rows in six frames) in ONE launch: a workgroup owns 16 rows,
-//                        sums the lengths of every row in front of its own (all 256 threads) and then writes offsets and residues of its 16.
-//   k_translate_lengths  more rows: out_offsets[r + 1] <- residues of row r, and the sum of every 64 -> wave_sums[r / 64];
-//   k_translate_place    a workgroup owns 64 rows: the sums in front of it + a wave scan give their offsets, 16 lanes per row translate.
-//                        Beyond 2^20 rows the sums in front are scanned once by k_translate_scan (one workgroup).
+// The launch classes and their offsets scaffold are bsq_ragged_out.h, shared with the gather and the views, here by OUTPUT rows:
+// k_translate_small (<= 4096 output rows: a loader batch, or 682 source rows in six frames, in ONE launch), k_translate_lengths +
+// k_translate_place beyond, with k_translate_scan between the two beyond 2^20 rows.
 // A row's length is (L - phase) / 3 of its offsets: no character is read before the place step.  In six-frame mode the rows 6i .. 6i + 5
 // of source row i are neighbours, so a workgroup (16 or 64 consecutive rows) fetches a source row once and finds it in cache five times.
 //
@@ -30,10 +26,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 #include "bsq.h"
 #include "bsq_internal.h"
+#include "bsq_ragged_out.h"
 #include "bsq_translate_dev.h"
 
 namespace {
@@ -42,24 +38,15 @@ using bsq_translated::Plan;
 using bsq_translated::Row;
 using bsq_translated::RowSrc;
 
-constexpr int kThreads = 256;
-constexpr int kLanes = 16;   // lanes per row
 constexpr int kUnroll = 4;   // 16-residue groups a lane has in flight
 constexpr int kGroup = 16;   // residues of a group (one 16-byte store, 48 source bytes)
-constexpr int64_t kSmallN = 4096;
-constexpr int kPlaceS = 64;
-constexpr int64_t kPlaceSumMax = int64_t(1) << 20;  // beyond this many rows the sums in front of a workgroup are scanned once
 constexpr int64_t kMaxRows = (int64_t(1) << 31) * kPlaceS - 1;
-typedef uint32_t v_u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 
 // The plan as the kernels take it: the table by value
 struct Table {
     uint32_t w[16];
     uint32_t unknown4;
 };
-
-// the byte order of a word reversed
-__device__ __forceinline__ uint32_t rev4(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x00010203u); }
 
 // byte i of the result = table byte (idx byte i), idx bytes in 0 .. 63: lookup4 of bsq_views.hip, one level deeper
 __device__ __forceinline__ uint32_t lookup64(const Table &t, uint32_t idx) {
@@ -158,12 +145,7 @@ __device__ __forceinline__ void translate_row(const uint8_t *chars, const Table 
 // The tail of a row (after its offsets are known): cut at the capacity, report, translate
 __device__ __forceinline__ void place_row(const uint8_t *chars, const Table &t, const Row &v, int64_t r, int64_t n_out, int64_t d0,
                                           uint8_t *out_chars, int64_t capacity, int sub, unsigned long long *first_bad) {
-    int64_t len = v.m;
-    if (d0 + len > capacity) {
-        if (sub == 0 && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(n_out + r));
-        len = capacity > d0 ? capacity - d0 : 0;
-    }
-    translate_row(chars, t, v, len, out_chars + d0, sub);
+    translate_row(chars, t, v, cut_at_capacity(d0, v.m, capacity, n_out, r, sub, first_bad), out_chars + d0, sub);
 }
 
 __global__ __launch_bounds__(kThreads) void k_translate_small(RowSrc src, Table t, const uint8_t *chars, int64_t n_out, int64_t *out_offsets,
@@ -172,15 +154,7 @@ __global__ __launch_bounds__(kThreads) void k_translate_small(RowSrc src, Table 
     __shared__ int64_t s_len[kThreads / kLanes];
     const int tid = threadIdx.x, sub = tid & (kLanes - 1), g = tid / kLanes;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * (kThreads / kLanes);
-    int64_t acc = 0;
-#pragma unroll 4
-    for (int k = 0; k < int(kSmallN / kThreads); ++k) {
-        const int64_t j = tid + kThreads * k;
-        if (j < first) acc += bsq_translated::row_of(src, j).m;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+    small_front_sum<4>(first, s_part, [=](int64_t j) { return bsq_translated::row_of(src, j).m; });  // (4 look-ups unrolled together)
     const int64_t r = first + g;
     const bool live = r < n_out;
     Row v{0, 0, 0, 0, 0, false, false};
@@ -203,46 +177,16 @@ __global__ __launch_bounds__(kThreads) void k_translate_lengths(RowSrc src, int6
                                                                 unsigned long long *first_bad) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (r == 0) out_offsets[0] = 0;
-    int64_t len = 0;
-    if (r < n_out) {
+    lengths_step(r, n_out, out_offsets, wave_sums, [=](int64_t r) {
         const Row v = bsq_translated::row_of(src, r);
-        len = v.m;
         if (!v.ok && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(v.src));
-        out_offsets[r + 1] = len;
-    }
-    int64_t acc = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0 && r < n_out) wave_sums[r >> 6] = acc;
+        return v.m;
+    });
 }
 
-// in-place inclusive prefix sum of v[0 .. n) by ONE workgroup of 1024 threads (pieces of 1024 with a running carry)
-__global__ __launch_bounds__(1024) void k_translate_scan(int64_t *v, int64_t n) {
-    __shared__ int64_t s_wave[16];
-    __shared__ int64_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + threadIdx.x;
-        int64_t x = i < n ? v[i] : 0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (lane >= d) x += o;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        int64_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) v[i] = x + before;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = x + before;
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(1024) void k_translate_scan(int64_t *v, int64_t n) { scan_inclusive_block(v, n); }
 
-// SCANNED: wave_sums holds inclusive prefix sums (k_translate_scan ran), else the plain sums of 64 rows
+// SCANNED: k_translate_scan ran (place_offsets)
 template <bool SCANNED>
 __global__ __launch_bounds__(kThreads) void k_translate_place(RowSrc src, Table t, const uint8_t *chars, int64_t n_out, int64_t *out_offsets,
                                                               const int64_t *wave_sums, uint8_t *out_chars, int64_t capacity,
@@ -251,33 +195,7 @@ __global__ __launch_bounds__(kThreads) void k_translate_place(RowSrc src, Table 
     __shared__ int64_t s_d0[kPlaceS];
     const int tid = threadIdx.x;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * kPlaceS;
-    int64_t acc = 0;
-    if constexpr (SCANNED) {
-        if (tid == 0 && blockIdx.x > 0) acc = wave_sums[blockIdx.x - 1];
-    } else {
-        for (int64_t k = tid; k < static_cast<int64_t>(blockIdx.x); k += kThreads) acc += wave_sums[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    }
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    int64_t len = 0, x = 0;
-    if (tid < kPlaceS) {  // (one wave)
-        const int64_t r = first + tid;
-        if (r < n_out) len = out_offsets[r + 1];
-        x = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (tid >= d) x += o;
-        }
-    }
-    __syncthreads();  // (every read of the lengths in out_offsets is done: this workgroup's own entries are overwritten below, nobody else's)
-    if (tid < kPlaceS) {
-        const int64_t end = (SCANNED ? s_part[0] : s_part[0] + s_part[1] + s_part[2] + s_part[3]) + x;
-        s_d0[tid] = end - len;
-        if (first + tid < n_out) out_offsets[first + tid + 1] = end;
-    }
-    __syncthreads();
+    place_offsets<SCANNED>(n_out, out_offsets, wave_sums, s_part, s_d0);
     if (!out_chars) return;
     const int sub = tid & (kLanes - 1);
 #pragma unroll 1
@@ -291,46 +209,22 @@ __global__ __launch_bounds__(kThreads) void k_translate_place(RowSrc src, Table 
     }
 }
 
-enum class Form { Small, Place, ScanPlace };
-Form form_of(int64_t n_out) { return n_out <= kSmallN ? Form::Small : (n_out <= kPlaceSumMax ? Form::Place : Form::ScanPlace); }
-
 bsq_status launch(const RowSrc &src, const Table &t, const uint8_t *chars, int64_t n_out, uint8_t *out_chars, int64_t out_capacity,
                   int64_t *out_offsets, int64_t *status_dev, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (status_dev) e = hipMemsetAsync(status_dev, 0xFF, sizeof(int64_t), s);  // -1 = every row valid, everything fitted
-    if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(translate status)", e);
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(status_dev);
-    if (n_out == 0) {
-        e = hipMemsetAsync(out_offsets, 0, sizeof(int64_t), s);
-        if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(translate offsets)", e);
-        return BSQ_OK;
-    }
     uint8_t *out = out_capacity > 0 ? out_chars : nullptr;
-    const Form form = form_of(n_out);
-    if (form == Form::Small) {
-        hipLaunchKernelGGL(k_translate_small, dim3(unsigned((n_out + kThreads / kLanes - 1) / (kThreads / kLanes))), dim3(kThreads), 0, s, src, t,
-                           chars, n_out, out_offsets, out, out_capacity, bad);
-        return bsq_internal::check_launch("k_translate_small");
-    }
-    const int64_t nsum = (n_out + 63) / 64;
-    std::lock_guard<std::mutex> scratch_turn(bsq_internal::workspace_mutex());
-    void *ws = nullptr;
-    const bsq_status st = bsq_internal::workspace_acquire(size_t(nsum) * sizeof(int64_t), s, &ws);
-    if (st != BSQ_OK) return st;
-    int64_t *sums = static_cast<int64_t *>(ws);
-    hipLaunchKernelGGL(k_translate_lengths, dim3(unsigned((n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, src, n_out, out_offsets, sums,
-                       bad);
-    const dim3 grid(unsigned((n_out + kPlaceS - 1) / kPlaceS));
-    if (form == Form::Place) {
-        hipLaunchKernelGGL(k_translate_place<false>, grid, dim3(kThreads), 0, s, src, t, chars, n_out, out_offsets, sums, out, out_capacity, bad);
-    } else {
-        hipLaunchKernelGGL(k_translate_scan, dim3(1), dim3(1024), 0, s, sums, nsum);
-        hipLaunchKernelGGL(k_translate_place<true>, grid, dim3(kThreads), 0, s, src, t, chars, n_out, out_offsets, sums, out, out_capacity, bad);
-    }
-    const hipError_t le = hipGetLastError();
-    bsq_internal::workspace_release(ws, s);
-    if (le != hipSuccess) return bsq_internal::set_hip_error("k_translate_lengths / k_translate_place", le);
-    return BSQ_OK;
+    const dim3 block(kThreads);
+    return ragged_launch(
+        "translate", "k_translate_small", "k_translate_lengths / k_translate_place", n_out, out_offsets, status_dev, s,
+        [&](dim3 grid) { hipLaunchKernelGGL(k_translate_small, grid, block, 0, s, src, t, chars, n_out, out_offsets, out, out_capacity, bad); },
+        [&](dim3 grid, int64_t *sums) { hipLaunchKernelGGL(k_translate_lengths, grid, block, 0, s, src, n_out, out_offsets, sums, bad); },
+        [&](int64_t *sums, int64_t nsum) { hipLaunchKernelGGL(k_translate_scan, dim3(1), dim3(1024), 0, s, sums, nsum); },
+        [&](dim3 grid, const int64_t *sums) {
+            hipLaunchKernelGGL(k_translate_place<false>, grid, block, 0, s, src, t, chars, n_out, out_offsets, sums, out, out_capacity, bad);
+        },
+        [&](dim3 grid, const int64_t *sums) {
+            hipLaunchKernelGGL(k_translate_place<true>, grid, block, 0, s, src, t, chars, n_out, out_offsets, sums, out, out_capacity, bad);
+        });
 }
 
 // the output rows of n source rows, or -1 when the call refuses them

@@ -2,12 +2,9 @@
 // the device as a packed batch (chars, offsets) that every encode path consumes as it is.  The draw is bsq_views_dev.h (include/bsq.h,
 // bsq_crop, documents it); explicit views (bsq_views_packed_device) carry their own (sequence, start, length, strand) per row.
 //
-// The launch classes are those of the gather (bsq_gather.hip), whose source is not touched:
-//   k_views_small     lists of <= 4096 rows (a loader batch) in ONE launch: a workgroup owns 16 rows, sums the clipped lengths of every
-//                     row in front of its own (all 256 threads) and then writes offsets, starts, strands and characters of its 16.
-//   k_views_lengths2  longer lists: out_offsets[i + 1] <- clipped length of row i, and the sum of every 64 -> wave_sums[i / 64];
-//   k_views_place     a workgroup owns 64 rows: the sums in front of it + a wave scan give their offsets, 16 lanes per row copy.
-//                     Beyond 2^20 rows the sums in front are scanned once by k_views_scan (one workgroup) instead of per workgroup.
+// The launch classes and their offsets scaffold are bsq_ragged_out.h, shared with the gather and the translation: k_views_small (lists
+// of <= 4096 rows in ONE launch), k_views_lengths2 + k_views_place beyond, with k_views_scan between the two beyond 2^20 rows.  This
+// file holds the row sources, the copy, and what a views kernel does around the shared steps: starts and strands of its rows.
 // The copy: 16 lanes per row, a lane moves 16-byte unaligned vectors and has kUnroll of them in flight (every load of a round is
 // issued before its first store): 1 KiB of a row per round, so a 1024-character window is ONE round of four rows per wave.  The
 // gather's loop (one vector per lane per round, a store between loads) was sized for loader rows of a few hundred characters.  A
@@ -17,22 +14,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 #include "bsq.h"
 #include "bsq_internal.h"
+#include "bsq_ragged_out.h"
 #include "bsq_views_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kLanes = 16;                  // lanes per row
 constexpr int kUnroll = 4;                  // 16-byte vectors a lane has in flight
 constexpr int kRound = kLanes * 16 * kUnroll;  // bytes of a row per round (1 KiB)
-constexpr int64_t kSmallN = 4096;
-constexpr int kPlaceS = 64;
-constexpr int64_t kPlaceSumMax = int64_t(1) << 20;  // beyond this many rows the sums in front of a workgroup are scanned once
-typedef uint32_t v_u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 
 // the complement of the low five bits of a letter, four entries per word (lookup4 below reads it)
 constexpr uint32_t comp_word(uint32_t k) {
@@ -62,9 +53,6 @@ __device__ __forceinline__ uint32_t comp4(uint32_t cw) {
     const uint32_t keep = (f << 8) - f;  // 0xFF in those bytes
     return (cw & keep) | (r & ~keep);
 }
-
-// the byte order of a word reversed
-__device__ __forceinline__ uint32_t rev4(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x00010203u); }
 
 struct View {
     int64_t base;  // position in chars of the view's first source character (src0 + start)
@@ -170,12 +158,7 @@ __device__ __forceinline__ void copy_row(const uint8_t *chars, const View &v, in
 // The tail of a row (after its offsets are known): cut at the capacity, report, copy
 __device__ __forceinline__ void place_row(const uint8_t *chars, const View &v, int64_t i, int64_t n, int64_t d0, uint8_t *out_chars,
                                           int64_t capacity, int sub, unsigned long long *first_bad) {
-    int64_t len = v.len;
-    if (d0 + len > capacity) {
-        if (sub == 0 && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(n + i));
-        len = capacity > d0 ? capacity - d0 : 0;
-    }
-    copy_row(chars, v, len, out_chars + d0, sub);
+    copy_row(chars, v, cut_at_capacity(d0, v.len, capacity, n, i, sub, first_bad), out_chars + d0, sub);
 }
 
 template <class Src>
@@ -185,18 +168,10 @@ __global__ __launch_bounds__(kThreads) void k_views_small(Src src, const uint8_t
     __shared__ int64_t s_len[kThreads / kLanes];
     const int tid = threadIdx.x, sub = tid & (kLanes - 1), g = tid / kLanes;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * (kThreads / kLanes);
-    int64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < int(kSmallN / kThreads); ++k) {
-        const int64_t j = tid + kThreads * k;
-        if (j < first) {
-            bool ok;
-            acc += src.clipped(j, &ok);
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+    small_front_sum<int(kSmallN / kThreads)>(first, s_part, [=](int64_t j) {
+        bool ok;
+        return src.clipped(j, &ok);
+    });
     const int64_t i = first + g;
     const bool live = i < n;
     View v{0, 0, 0, 0u, false};
@@ -224,46 +199,17 @@ __global__ __launch_bounds__(kThreads) void k_views_lengths2(Src src, int64_t n,
                                                              unsigned long long *first_bad) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (i == 0) out_offsets[0] = 0;
-    int64_t len = 0;
-    if (i < n) {
+    lengths_step(i, n, out_offsets, wave_sums, [=](int64_t i) {
         bool ok;
-        len = src.clipped(i, &ok);
+        const int64_t len = src.clipped(i, &ok);
         if (!ok && first_bad) atomicMin(first_bad, static_cast<unsigned long long>(i));
-        out_offsets[i + 1] = len;
-    }
-    int64_t acc = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0 && i < n) wave_sums[i >> 6] = acc;
+        return len;
+    });
 }
 
-// in-place inclusive prefix sum of v[0 .. n) by ONE workgroup of 1024 threads (pieces of 1024 with a running carry)
-__global__ __launch_bounds__(1024) void k_views_scan(int64_t *v, int64_t n) {
-    __shared__ int64_t s_wave[16];
-    __shared__ int64_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + threadIdx.x;
-        int64_t x = i < n ? v[i] : 0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (lane >= d) x += o;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        int64_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) v[i] = x + before;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = x + before;
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(1024) void k_views_scan(int64_t *v, int64_t n) { scan_inclusive_block(v, n); }
 
-// SCANNED: wave_sums holds inclusive prefix sums (k_views_scan ran), else the plain sums of 64 rows
+// SCANNED: k_views_scan ran (place_offsets).  Starts and strands are written for every row, with or without out_chars
 template <class Src, bool SCANNED>
 __global__ __launch_bounds__(kThreads) void k_views_place(Src src, const uint8_t *chars, int64_t n, int64_t *out_offsets,
                                                           const int64_t *wave_sums, uint8_t *out_chars, int64_t capacity, int64_t *starts,
@@ -272,33 +218,7 @@ __global__ __launch_bounds__(kThreads) void k_views_place(Src src, const uint8_t
     __shared__ int64_t s_d0[kPlaceS];
     const int tid = threadIdx.x;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * kPlaceS;
-    int64_t acc = 0;
-    if constexpr (SCANNED) {
-        if (tid == 0 && blockIdx.x > 0) acc = wave_sums[blockIdx.x - 1];
-    } else {
-        for (int64_t k = tid; k < static_cast<int64_t>(blockIdx.x); k += kThreads) acc += wave_sums[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    }
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    int64_t len = 0, x = 0;
-    if (tid < kPlaceS) {  // (one wave)
-        const int64_t i = first + tid;
-        if (i < n) len = out_offsets[i + 1];
-        x = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(x, d, 64);
-            if (tid >= d) x += o;
-        }
-    }
-    __syncthreads();  // (every read of the lengths in out_offsets is done: this workgroup's own entries are overwritten below, nobody else's)
-    if (tid < kPlaceS) {
-        const int64_t end = (SCANNED ? s_part[0] : s_part[0] + s_part[1] + s_part[2] + s_part[3]) + x;
-        s_d0[tid] = end - len;
-        if (first + tid < n) out_offsets[first + tid + 1] = end;
-    }
-    __syncthreads();
+    place_offsets<SCANNED>(n, out_offsets, wave_sums, s_part, s_d0);
     const int sub = tid & (kLanes - 1);
 #pragma unroll
     for (int r = 0; r < kPlaceS / (kThreads / kLanes); ++r) {
@@ -318,43 +238,20 @@ __global__ __launch_bounds__(kThreads) void k_views_place(Src src, const uint8_t
 template <class Src>
 bsq_status launch(const Src &src, const uint8_t *chars, int64_t n, uint8_t *out_chars, int64_t out_capacity, int64_t *out_offsets,
                   int64_t *starts, uint8_t *strand, int64_t *status_dev, hipStream_t s, const char *what) {
-    hipError_t e = hipSuccess;
-    if (status_dev) e = hipMemsetAsync(status_dev, 0xFF, sizeof(int64_t), s);  // -1 = every row valid, everything fitted
-    if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(views status)", e);
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(status_dev);
-    if (n == 0) {
-        e = hipMemsetAsync(out_offsets, 0, sizeof(int64_t), s);
-        if (e != hipSuccess) return bsq_internal::set_hip_error("hipMemsetAsync(views offsets)", e);
-        return BSQ_OK;
-    }
     uint8_t *out = out_capacity > 0 ? out_chars : nullptr;
-    if (n <= kSmallN) {
-        hipLaunchKernelGGL(k_views_small<Src>, dim3(unsigned((n + kThreads / kLanes - 1) / (kThreads / kLanes))), dim3(kThreads), 0, s, src,
-                           chars, n, out_offsets, out, out_capacity, starts, strand, bad);
-        e = hipGetLastError();
-        if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-        return BSQ_OK;
-    }
-    const int64_t nsum = (n + 63) / 64;
-    std::lock_guard<std::mutex> scratch_turn(bsq_internal::workspace_mutex());
-    void *ws = nullptr;
-    const bsq_status st = bsq_internal::workspace_acquire(size_t(nsum) * sizeof(int64_t), s, &ws);
-    if (st != BSQ_OK) return st;
-    int64_t *sums = static_cast<int64_t *>(ws);
-    hipLaunchKernelGGL(k_views_lengths2<Src>, dim3(unsigned((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, src, n, out_offsets, sums, bad);
-    const dim3 grid(unsigned((n + kPlaceS - 1) / kPlaceS));
-    if (n <= kPlaceSumMax) {
-        hipLaunchKernelGGL((k_views_place<Src, false>), grid, dim3(kThreads), 0, s, src, chars, n, out_offsets, sums, out, out_capacity, starts,
-                           strand, bad);
-    } else {
-        hipLaunchKernelGGL(k_views_scan, dim3(1), dim3(1024), 0, s, sums, nsum);
-        hipLaunchKernelGGL((k_views_place<Src, true>), grid, dim3(kThreads), 0, s, src, chars, n, out_offsets, sums, out, out_capacity, starts,
-                           strand, bad);
-    }
-    e = hipGetLastError();
-    bsq_internal::workspace_release(ws, s);
-    if (e != hipSuccess) return bsq_internal::set_hip_error(what, e);
-    return BSQ_OK;
+    const dim3 block(kThreads);
+    return ragged_launch(
+        "views", what, what, n, out_offsets, status_dev, s,
+        [&](dim3 grid) { hipLaunchKernelGGL(k_views_small<Src>, grid, block, 0, s, src, chars, n, out_offsets, out, out_capacity, starts, strand, bad); },
+        [&](dim3 grid, int64_t *sums) { hipLaunchKernelGGL(k_views_lengths2<Src>, grid, block, 0, s, src, n, out_offsets, sums, bad); },
+        [&](int64_t *sums, int64_t nsum) { hipLaunchKernelGGL(k_views_scan, dim3(1), dim3(1024), 0, s, sums, nsum); },
+        [&](dim3 grid, const int64_t *sums) {
+            hipLaunchKernelGGL((k_views_place<Src, false>), grid, block, 0, s, src, chars, n, out_offsets, sums, out, out_capacity, starts, strand, bad);
+        },
+        [&](dim3 grid, const int64_t *sums) {
+            hipLaunchKernelGGL((k_views_place<Src, true>), grid, block, 0, s, src, chars, n, out_offsets, sums, out, out_capacity, starts, strand, bad);
+        });
 }
 
 bsq_status check_common(const uint8_t *chars, const int64_t *offsets, int64_t n_store, int64_t n, const uint8_t *out_chars,

@@ -110,6 +110,29 @@ def test_launch_classes_six_frames(gpu, big, n):
     assert translate.kernel_name(n, "six") == ("k_translate_small" if n == 682 else "k_translate_lengths+k_translate_place")
 
 
+def test_scanned_place_beyond_2_pow_20_rows(gpu):
+    """The class beyond 2^20 output rows (k_translate_lengths + k_translate_scan + k_translate_place<true>): 2^20 + 65 rows of 0 .. 3
+    characters, so the last workgroup is partial and the last entry of the scanned sums is the sum of one row.  Frame 1 (no row of
+    these holds a whole codon behind its first character: every offset is 0) and frame 0 (a row in four gives one residue), bit for
+    bit against the library's host twin."""
+    from bioseq_amd import translate
+    n = 2 ** 20 + 65
+    rng = np.random.default_rng(20)
+    lens = np.arange(n, dtype=np.int64) % 4
+    offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    chars = rng.choice(np.frombuffer(b"ACGT", np.uint8), int(offs[-1]))
+    chars[rng.random(chars.size) < 0.01] = ord("N")
+    dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+    for code, total in ((1, 0), (0, n // 4)):
+        assert translate.kernel_name(n, code) == "k_translate_lengths+k_translate_scan+k_translate_place"
+        e_chars, e_offs = translate.translate_host(chars, offs, frame=code)
+        assert e_offs.size == n + 1 and int(e_offs[-1]) == total == e_chars.size
+        got_c, got_o = translate.translate_packed(dch, dof, frame=code)
+        assert np.array_equal(got_o.cpu().numpy(), e_offs)
+        assert got_c[:total].cpu().numpy().tobytes() == e_chars.tobytes()
+
+
 def test_vector_edges_every_length_every_frame(gpu):
     """Every source length 0 .. 150 (15 / 16 / 17 residues, the 47-, 48- and 49-byte bodies at every phase, sources at every alignment
     modulo 16) and the round boundary of 16 lanes x 16 residues x 4: rows of 3 * 1024 - 2 .. 3 * 1024 + 4 characters."""

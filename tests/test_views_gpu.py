@@ -69,6 +69,38 @@ def test_crop_device_equals_twin(gpu, n, window, mode, frac):
     assert np.array_equal(got_starts, e_starts) and np.array_equal(got_strand, e_strand)
 
 
+def test_scanned_place_beyond_2_pow_20_rows(gpu):
+    """The class beyond 2^20 rows (k_views_lengths2 + k_views_scan + k_views_place<SCANNED>): 2^20 + 65 rows of 0 .. 3 characters, so the
+    last workgroup is partial and the last entry of the scanned sums is the sum of one row.  Crops and explicit views of the same rows,
+    bit for bit against the library's host plan applied in numpy."""
+    from bioseq_amd import views
+    n = 2 ** 20 + 65
+    rng = np.random.default_rng(20)
+    lens = np.arange(n, dtype=np.int64) % 4
+    offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    chars = rng.choice(np.frombuffer(b"ACGT", np.uint8), int(offs[-1]))
+    chars[rng.random(chars.size) < 0.01] = ord("N")
+    dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+    opts = dict(mode="head", revcomp_frac=0.5, seed=17)
+    starts, vlen, strand = views.crop_plan(offs, 2, **opts)
+    assert np.array_equal(vlen, np.minimum(lens, 2)) and not starts.any() and 0.4 < strand.mean() < 0.6
+    e_offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(vlen, out=e_offs[1:])
+    row = np.repeat(np.arange(n), vlen)
+    k = np.arange(int(e_offs[-1])) - e_offs[row]  # position in the row
+    rc = strand[row] != 0
+    e_chars = chars[offs[row] + starts[row] + np.where(rc, vlen[row] - 1 - k, k)]
+    e_chars[rc] = twin.COMP[e_chars[rc]]
+    got_c, got_o, got_st, got_sd = views.crop_packed(dch, dof, 2, return_origin=True, **opts)
+    assert np.array_equal(got_o.cpu().numpy(), e_offs)
+    assert got_c[:int(e_offs[-1])].cpu().numpy().tobytes() == e_chars.tobytes()
+    assert np.array_equal(got_st.cpu().numpy(), starts) and np.array_equal(got_sd.cpu().numpy(), strand)
+    got_c, got_o = views.gather_views(dch, dof, np.arange(n), starts, vlen, strand)
+    assert np.array_equal(got_o.cpu().numpy(), e_offs)
+    assert got_c[:int(e_offs[-1])].cpu().numpy().tobytes() == e_chars.tobytes()
+
+
 @pytest.mark.parametrize("n", [5, 3000])
 def test_crop_without_index_bad_indices_and_overflow(gpu, n):
     from bioseq_amd import capi
