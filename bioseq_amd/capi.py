@@ -45,6 +45,11 @@ class Translate(ctypes.Structure):
     _fields_ = [("code", ctypes.c_uint8 * 64), ("unknown", ctypes.c_uint8), ("frame", ctypes.c_int32)]
 
 
+class Orf(ctypes.Structure):
+    """struct bsq_orf"""
+    _fields_ = [("stop", ctypes.c_uint8), ("start", ctypes.c_int32), ("min_len", ctypes.c_int64)]
+
+
 class Kmer(ctypes.Structure):
     """struct bsq_kmer"""
     _fields_ = [("k", ctypes.c_int32), ("stride", ctypes.c_int32)]
@@ -156,6 +161,11 @@ def load():
         "bsq_translate_packed_device": (i32, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(Translate), vp, i64, vp, vp, vp]),
         "bsq_translate_packed_host": (i32, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(Translate), vp, i64, vp, vp]),
         "bsq_translate_kernel_name": (ctypes.c_char_p, [i64, ctypes.POINTER(Translate)]),
+        "bsq_orf_count_device": (i32, [vp, vp, i64, ctypes.POINTER(Orf), vp, vp, vp]),
+        "bsq_orf_emit_device": (i32, [vp, vp, i64, ctypes.POINTER(Orf), vp, i64, vp, vp, vp, vp]),
+        "bsq_orf_count_host": (i32, [vp, vp, i64, ctypes.POINTER(Orf), vp, vp]),
+        "bsq_orf_emit_host": (i32, [vp, vp, i64, ctypes.POINTER(Orf), vp, i64, vp, vp, vp]),
+        "bsq_orf_kernel_name": (ctypes.c_char_p, [i64]),
         "bsq_kmer_vocab_size": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_unk_id": (i64, [dp, ctypes.POINTER(Kmer)]),
         "bsq_kmer_bos_id": (i64, [dp, ctypes.POINTER(Kmer)]),

@@ -40,7 +40,8 @@ extern "C" {
                            * bsq_pack_mlm_tokenize_host, bsq_pack_mlm_kernel_name, bsq_kmer_mlm, bsq_kmer_mlm_anchor_prob,
                            * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds, bsq_kmer_spectrum,
                            * bsq_kmer_spectrum_width, bsq_kmer_spectrum_device, bsq_kmer_spectrum_host, bsq_kmer_spectrum_kernel_name, bsq_translate,
-                           * bsq_codon_table, bsq_translate_length, bsq_translate_packed_device, bsq_translate_packed_host, bsq_translate_kernel_name;
+                           * bsq_codon_table, bsq_translate_length, bsq_translate_packed_device, bsq_translate_packed_host, bsq_translate_kernel_name,
+                           * bsq_orf, bsq_orf_count_device, bsq_orf_emit_device, bsq_orf_count_host, bsq_orf_emit_host, bsq_orf_kernel_name;
                            * nothing removed */
 
 typedef int32_t bsq_status;
@@ -452,6 +453,51 @@ bsq_status bsq_translate_packed_host(const uint8_t *chars, const int64_t *offset
 /* Host only: the launches bsq_translate_packed_device takes for n source rows ("k_translate_small", "k_translate_lengths+k_translate_place",
  * "k_translate_lengths+k_translate_scan+k_translate_place"); "" for arguments the call refuses. */
 const char *bsq_translate_kernel_name(int64_t n, const bsq_translate *t);
+
+/* ---- open reading frames: the stop-free stretches of the rows of a packed residue batch (chars, offsets) -- any batch of n_rows
+ * rows whose bytes are residues, in practice the six-frame output of bsq_translate_packed_device -- found, numbered and handed out
+ * on the device as (row, start, length) view rows that bsq_views_packed_device copies into a packed batch.
+ *
+ * THE RULE is a bsq_orf: a stop byte, a start byte or -1 for none, and min_len >= 1.  In a row of m residues
+ *     the terminators   are the positions e with row[e] == stop, and e = m (the row's end);
+ *     the segment       of a terminator e runs from p + 1, p the stop in front of e, or from 0 when there is none, up to e;
+ *     s                 is the segment's first position when start == -1, else the position of the first residue equal to start in
+ *                       the segment -- a segment without one yields nothing;
+ *     the ORF           [s, e) is yielded when e - s >= min_len.
+ * So a segment yields at most one ORF, its longest; the stop is not part of it; the translation's `unknown` letter is a residue like
+ * any other; an empty row yields nothing.  ORFs are numbered by (row, start) ascending: that order is part of the contract.
+ *
+ * bsq_orf_count_device: orf_offsets (device, n_rows + 1) <- orf_offsets[r] = the number of ORFs in the rows < r, a CSR over rows (the
+ * ORFs of row r are the ranks orf_offsets[r] .. orf_offsets[r + 1]); *residues_or_null (device int64) <- the summed length of all
+ * ORFs.  n_rows == 0 writes orf_offsets[0] = 0.
+ * bsq_orf_emit_device: out_row / out_start / out_length [k] <- row, s and e - s of the ORF of rank k, for every rank < max_orfs;
+ * nothing is written at or past index max_orfs.  orf_offsets is what bsq_orf_count_device wrote for the same batch and rule.  A caller
+ * that sized its arrays from orf_offsets[n_rows] passes that as max_orfs; one that must not read back passes a bound and learns from
+ * orf_offsets[n_rows] later whether it was cut.
+ * Both are stream-ordered and never synchronise.  Argument errors (BSQ_ERR_INVALID_ARG, nothing launched): min_len < 1, start outside
+ * -1 .. 255, start == stop, null pointers (the output arrays may be null when max_orfs == 0), negative sizes.
+ * The launches: k_orf_count + k_orf_offsets for the count (k_orf_scan between them beyond 2^20 rows), k_orf_emit.  Four lanes of a wave
+ * own a row and walk it in pieces of 64 residues; a row is never split across waves, so a batch of a few chromosome-length rows is
+ * out of scope, as for the k-mer spectrum.  Measured cold on six frames, min_len 30 (profiles/r18/orf_lab.txt): count 191 us + emit
+ * 189 us on 262 144 x 512 characters (0.71x the six-frame translate launch in front of them), 451 + 219 us on 1 M reads x 150 (0.34x),
+ * 1 287 + 1 364 us on 4 096 contigs of 2 000 - 200 000 (1.81x: the walk is bound by vector issue and, there, by 1.5 waves per SIMD). */
+typedef struct bsq_orf {
+    uint8_t stop;    /* the stop byte ('*') */
+    int32_t start;   /* -1: an ORF begins behind the previous stop; 0 .. 255: at the first residue equal to this byte ('M') */
+    int64_t min_len; /* >= 1: the fewest residues of an ORF */
+} bsq_orf;
+bsq_status bsq_orf_count_device(const uint8_t *chars, const int64_t *offsets, int64_t n_rows, const bsq_orf *o, int64_t *orf_offsets,
+                                int64_t *residues_or_null, void *hip_stream);
+bsq_status bsq_orf_emit_device(const uint8_t *chars, const int64_t *offsets, int64_t n_rows, const bsq_orf *o, const int64_t *orf_offsets,
+                               int64_t max_orfs, int64_t *out_row, int64_t *out_start, int64_t *out_length, void *hip_stream);
+/* CPU twins on host arrays (the same rule text, csrc/bsq_orf_dev.h): the same offsets, total and arrays. */
+bsq_status bsq_orf_count_host(const uint8_t *chars, const int64_t *offsets, int64_t n_rows, const bsq_orf *o, int64_t *orf_offsets,
+                              int64_t *residues_or_null);
+bsq_status bsq_orf_emit_host(const uint8_t *chars, const int64_t *offsets, int64_t n_rows, const bsq_orf *o, const int64_t *orf_offsets,
+                             int64_t max_orfs, int64_t *out_row, int64_t *out_start, int64_t *out_length);
+/* Host only: the launches of the two device calls for n_rows rows, the count's before the ';' ("k_orf_count+k_orf_offsets;k_orf_emit",
+ * "k_orf_count+k_orf_scan+k_orf_offsets;k_orf_emit" beyond 2^20 rows, "hipMemsetAsync" for no rows); "" for a size the calls refuse. */
+const char *bsq_orf_kernel_name(int64_t n_rows);
 
 /* ---- k-mer ids of a packed batch: the vocabulary DNA language models are trained on -- overlapping 3- to 6-mers (stride 1),
  * non-overlapping 6-mers (stride k), and the same over reduced protein alphabets -- in ONE launch instead of tokens + unfold +
