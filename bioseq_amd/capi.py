@@ -67,6 +67,12 @@ class KmerSpectrum(ctypes.Structure):
                 ("total_chars", ctypes.c_int64)]
 
 
+class MinHash(ctypes.Structure):
+    """struct bsq_minhash"""
+    _fields_ = [("k", ctypes.c_int32), ("buckets", ctypes.c_int32), ("canonical", ctypes.c_int32), ("form", ctypes.c_int32),
+                ("seed", ctypes.c_uint64), ("total_chars", ctypes.c_int64), ("reserved", ctypes.c_int32)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -184,6 +190,11 @@ def load():
         "bsq_kmer_spectrum_device": (i32, [dp, vp, vp, i64, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), c_int, vp, vp]),
         "bsq_kmer_spectrum_host": (i32, [dp, vp, vp, i64, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), c_int, vp]),
         "bsq_kmer_spectrum_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(Kmer), ctypes.POINTER(KmerSpectrum), i64, c_int]),
+        "bsq_minhash_device": (i32, [dp, vp, vp, i64, ctypes.POINTER(MinHash), c_int, vp, vp]),
+        "bsq_minhash_host": (i32, [dp, vp, vp, i64, ctypes.POINTER(MinHash), c_int, vp]),
+        "bsq_minhash_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(MinHash), i64, c_int]),
+        "bsq_sketch_compare_device": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp, vp]),
+        "bsq_sketch_compare_host": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

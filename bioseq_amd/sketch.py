@@ -1,0 +1,169 @@
+"""MinHash sketches of packed batches and the all-pairs similarity of sketches, on the device (`bsq_minhash_device`,
+`bsq_sketch_compare_device`): what a training set is checked with for near-duplicates and train / test leakage without going back to
+the host.
+
+A sketch is one fixed-width row of `buckets` values per sequence: every window of `k` characters (k = 21 for nucleotides, about 7 to 14
+for proteins; any alphabet of the package with `nchars ** k <= 2 ** 64`) is hashed, the hash picks a bucket, and the bucket keeps the
+smallest value that fell into it (one-permutation MinHash; `EMPTY` = -1 marks a bucket nothing fell into).  Two sequences that share a
+fraction J of their k-mers agree in about that fraction of their non-empty buckets.  include/bsq.h ("MinHash sketch") has the rule.
+
+* `minhash_packed`    the (B, buckets) sketches of a packed batch resident on the device, one launch;
+* `minhash_host`, `minhash_kernel_name`    the library's CPU twin (numpy), the kernel taken;
+* `sketch_compare`    `match` and `either` counts of every pair of rows of two sketch matrices, (Ba, Bb) int32, one launch -- no
+                      `Ba * Bb * buckets` boolean tensor;
+* `sketch_compare_host`    its CPU twin;
+* `sketch_jaccard`    match / either as float32, 0 where either == 0.
+
+The sketch of a sequence equals the bucket-wise UNSIGNED minimum of the sketches of pieces that together cover all its windows (EMPTY
+is the largest value), so sketches of longer sequences, or of sets of sequences, are merged without the characters.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import capi
+
+_lib = capi.load()
+
+EMPTY = -1
+_MAX_WINDOWS = 1 << 30  # (include/bsq.h, "MinHash sketch": a row sketches its first 2 ** 30 windows)
+_NUMPY = {capi.I32: np.int32, capi.U64: np.uint64}
+
+
+def _strands(desc):
+    """Whether the alphabet has strands as the sketch reads them: four classes, A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)."""
+    return desc.nchars == 4 and [desc.lut[ord(c)] for c in "ACGT"] == [0, 1, 2, 3]
+
+
+def _minhash(tok, k, buckets, destchar, canonical, seed, form, total_chars=0):
+    """(desc, bsq_minhash, dtype code, torch dtype) with the library's argument rules applied as ValueError (no device is touched)."""
+    desc = capi.desc_of(tok)
+    k, buckets = int(k), int(buckets)
+    if not 1 <= k <= 32 or desc.nchars ** k > 2 ** 64:
+        raise ValueError("k = %r with %d classes: k must lie in 1 .. 32 and nchars ** k within 2 ** 64" % (k, desc.nchars))
+    if not 1 <= buckets <= 1 << 14:
+        raise ValueError("buckets must lie in 1 .. 2 ** 14, got %r" % (buckets,))
+    try:
+        dt, tdt = capi.dtype_of(destchar)
+    except RuntimeError as e:
+        raise ValueError("bad destchar %r: %s" % (destchar, e)) from None
+    if dt not in (capi.I32, capi.U64):
+        raise ValueError("destchar %r: a sketch takes 'i' (int32) or 'q' (int64)" % (destchar,))
+    if canonical and not _strands(desc):
+        raise ValueError("canonical needs an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
+    form = 0 if form is None else int(form)
+    if form not in (0, 1, 2) or (form == 1 and buckets > 1024):
+        raise ValueError("form must be None, 1 (a wave per row: buckets <= 1024) or 2 (a workgroup per row), got %r at %d buckets" % (form, buckets))
+    m = capi.MinHash(k, buckets, int(bool(canonical)), form, int(seed) & (2 ** 64 - 1), int(total_chars), 0)
+    if not _lib.bsq_minhash_kernel_name(ctypes.byref(desc), ctypes.byref(m), 0, dt):  # (whatever the rules above do not restate)
+        raise ValueError("the library refuses these sketch arguments (include/bsq.h, \"MinHash sketch\")")
+    return desc, m, dt, tdt
+
+
+def minhash_kernel_name(tok, k, B, buckets=1024, destchar="i", *, canonical=False, form=None, total_chars=0):
+    """The kernel `minhash_packed` takes (host only: profiling labels, tests); total_chars: `chars.numel()` of the call, 0 = unknown."""
+    desc, m, dt, _ = _minhash(tok, k, buckets, destchar, canonical, 0, form, total_chars)
+    return _lib.bsq_minhash_kernel_name(ctypes.byref(desc), ctypes.byref(m), int(B), dt).decode()
+
+
+def minhash_host(tok, chars, offsets, k, buckets=1024, destchar="i", *, canonical=False, seed=0):
+    """The library's CPU twin (`bsq_minhash_host`, the word, hash and element code of the kernels) on numpy arrays: a (B, buckets) matrix,
+    int32 for 'i' and uint64 for 'q' (EMPTY = all bits set: -1 as a signed value)."""
+    desc, m, dt, _ = _minhash(tok, k, buckets, destchar, canonical, seed, None)
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    B = offsets.size - 1
+    out = np.empty((B, m.buckets), dtype=_NUMPY[dt])
+    keep = chars if chars.size else np.zeros(16, np.uint8)
+    if B > 0:
+        capi.check(_lib.bsq_minhash_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, ctypes.byref(m), dt, out.ctypes.data))
+    return out
+
+
+def minhash_packed(tok, chars, offsets, k, buckets=1024, destchar="i", *, canonical=False, seed=0, form=None, validate=True):
+    """The MinHash sketches of a packed batch on the device (chars uint8[total], offsets int64[B + 1]): a (B, buckets) device tensor on
+    torch's current stream, one launch, nothing read back.
+
+    out[i, s] = the smallest hash value of the windows of k characters of row i that fall into bucket s, `EMPTY` (-1) where none does; a
+    window with an unmapped character counts nowhere.  destchar 'i': int32 holding the 32 bits (compare as unsigned), 'q': int64 holding
+    0 .. 2 ** 32 - 2.  canonical (DNA, DNA4): a window and its reverse complement hash alike, so a row and its reverse complement have
+    equal sketches.  seed: another hash family.  form: None = the library chooses from `chars.numel()` / B, 1 = a wave per row
+    (buckets <= 1024), 2 = a workgroup per row.  validate: malformed offsets and a row of more than 2 ** 30 windows raise the library's
+    errors instead of being clamped."""
+    import torch
+    B = capi.packed_on_device(chars, offsets, "minhash_packed works on packed batches resident on the device (chars, offsets tensors)")
+    desc, m, dt, tdt = _minhash(tok, k, buckets, destchar, canonical, seed, form, chars.numel())
+    if validate and B > 0:
+        bad = ctypes.c_int64(-1)
+        with capi.launching(chars.device) as stream:
+            capi.check(_lib.bsq_validate_packed_device(offsets.data_ptr(), B, _MAX_WINDOWS - 1 + m.k, 0, 0, chars.numel(), ctypes.byref(bad), stream))
+    out = torch.empty((B, m.buckets), dtype=tdt, device=chars.device)
+    if B > 0:
+        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_minhash_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, ctypes.byref(m), dt, out.data_ptr(), stream))
+    return out
+
+
+def _pair_shape(a, b):
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or a.dtype != b.dtype:
+        raise ValueError("sketch matrices are 2-D, of one element type and one width; got %r %s and %r %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    if not 1 <= a.shape[1] <= 1 << 14:
+        raise ValueError("sketches are 1 .. 2 ** 14 buckets wide, got %d" % a.shape[1])
+    return int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+
+
+def sketch_compare_host(a, b=None, *, either=True):
+    """The library's CPU twin of `sketch_compare` (`bsq_sketch_compare_host`) on numpy matrices of int32, int64 or uint64: (match,
+    either or None), int32 (Ba, Bb)."""
+    a = np.ascontiguousarray(a)
+    b = a if b is None else np.ascontiguousarray(b)
+    codes = {np.dtype(np.int32): capi.I32, np.dtype(np.int64): capi.U64, np.dtype(np.uint64): capi.U64}
+    if a.dtype not in codes:
+        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
+    Ba, Bb, S = _pair_shape(a, b)
+    match = np.empty((Ba, Bb), np.int32)
+    eith = np.empty((Ba, Bb), np.int32) if either else None
+    if Ba and Bb:
+        capi.check(_lib.bsq_sketch_compare_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, codes[a.dtype], match.ctypes.data,
+                                                eith.ctypes.data if either else None))
+    return match, eith
+
+
+def sketch_compare(a, b=None, *, either=True):
+    """All pairs of rows of two sketch matrices on the device: (match, either or None), int32 (Ba, Bb) device tensors on torch's current
+    stream, one launch.  a (Ba, S), b (Bb, S): contiguous int32 or int64 device tensors as `minhash_packed` returns them; b = None
+    compares a with itself.
+
+    match[i, j] = the buckets in which a[i] and b[j] hold the same non-EMPTY value; either[i, j] = the buckets that are non-EMPTY in a[i]
+    or in b[j].  match / either estimates the Jaccard similarity of the two rows' k-mer sets (`sketch_jaccard`)."""
+    import torch
+    b = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda and a.device == b.device):
+        raise ValueError("sketch_compare works on sketch matrices resident on one device")
+    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("sketches are contiguous int32 or int64 tensors")
+    Ba, Bb, S = _pair_shape(a, b)
+    match = torch.empty((Ba, Bb), dtype=torch.int32, device=a.device)
+    eith = torch.empty((Ba, Bb), dtype=torch.int32, device=a.device) if either else None
+    if Ba and Bb:
+        with capi.launching(a.device) as stream:
+            capi.check(_lib.bsq_sketch_compare_device(a.data_ptr(), Ba, b.data_ptr(), Bb, S, capi.I32 if a.dtype == torch.int32 else capi.U64,
+                                                      match.data_ptr(), eith.data_ptr() if either else None, stream))
+    return match, eith
+
+
+def sketch_jaccard(a, b=None):
+    """The Jaccard estimate of every pair of rows: float32 (Ba, Bb), match / either of `sketch_compare` and 0 where either == 0 -- the
+    division of the exact integers.  Device tensors give a device tensor; numpy matrices go through the CPU twin and give numpy."""
+    if isinstance(a, np.ndarray):
+        m, e = sketch_compare_host(a, b)
+        return np.where(e > 0, m.astype(np.float32) / np.maximum(e, 1).astype(np.float32), np.float32(0)).astype(np.float32)
+    import torch
+    m, e = sketch_compare(a, b)
+    return torch.where(e > 0, m.to(torch.float32) / e.clamp(min=1).to(torch.float32), torch.zeros((), dtype=torch.float32, device=m.device))
+
+
+__all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard"]

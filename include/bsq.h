@@ -41,8 +41,9 @@ extern "C" {
                            * bsq_kmer_mlm_tokenize_device, bsq_kmer_mlm_tokenize_host, bsq_kmer_mlm_kernel_name, bsq_dtype_holds, bsq_kmer_spectrum,
                            * bsq_kmer_spectrum_width, bsq_kmer_spectrum_device, bsq_kmer_spectrum_host, bsq_kmer_spectrum_kernel_name, bsq_translate,
                            * bsq_codon_table, bsq_translate_length, bsq_translate_packed_device, bsq_translate_packed_host, bsq_translate_kernel_name,
-                           * bsq_orf, bsq_orf_count_device, bsq_orf_emit_device, bsq_orf_count_host, bsq_orf_emit_host, bsq_orf_kernel_name;
-                           * nothing removed */
+                           * bsq_orf, bsq_orf_count_device, bsq_orf_emit_device, bsq_orf_count_host, bsq_orf_emit_host, bsq_orf_kernel_name,
+                           * bsq_minhash, bsq_minhash_device, bsq_minhash_host, bsq_minhash_kernel_name, bsq_sketch_compare_device,
+                           * bsq_sketch_compare_host; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -619,6 +620,91 @@ bsq_status bsq_kmer_spectrum_host(const bsq_desc *d, const uint8_t *chars, const
 /* Host only: the kernel bsq_kmer_spectrum_device takes ("k_kmer_spectrum_wave", "k_kmer_spectrum_block<1024>", "...<4096>",
  * "...<16384>"), from the predicate the launch uses; "" for arguments the device call refuses. */
 const char *bsq_kmer_spectrum_kernel_name(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_spectrum *o, int64_t B, bsq_dtype t);
+
+/* ---- MinHash sketch: one fixed-width (B, S) vector per sequence whose buckets hold the smallest hash of the row's (canonical) k-mers
+ * that fall into them, and the all-pairs comparison of two sketch matrices -- what a training set is checked with for near-duplicates
+ * and train / test leakage (k = 21 for nucleotides, about 7 to 14 for proteins) without leaving the device.  The dense k-mer calls stop
+ * far below such k (bsq_kmer at A^k <= 2^24, the spectrum at A^k <= 2^14); a sketch needs no dense id, only a 64-bit word.
+ *
+ * THE RULE.  For a tokenizer description d (A = d->nchars classes), a bsq_minhash (k, S = buckets, canonical, seed) and a row of L
+ * characters:
+ *     windows  every window of k consecutive characters, at stride 1: window j covers characters [j, j + k).  A window with ANY unmapped
+ *              character contributes nothing.  d->bos, d->eos and d->padchar are ignored.
+ *     n        = min(max(L - k + 1, 0), 2^30); a negative L (malformed offsets) counts as 0; a longer row is clamped to its first 2^30
+ *              windows, memory-safe.
+ *     word     id(w) = the lexicographic Horner sum of the window's class ids, first character most significant, as bsq_kmer's -- but
+ *              as an UNSIGNED 64-BIT value.
+ *     canonical   0 / 1; accepted only when A = 4 and the table maps A, C, G, T to 0, 1, 2, 3 (DNA, DNA4: the spectrum's both_strands
+ *              predicate), every other alphabet: BSQ_ERR_INVALID_ARG.  The word becomes min(id(w), id(rc(w))), rc(w)[i] = 3 - w[k-1-i].
+ *     hash     h = mix64(word ^ s'),  s' = mix64(seed ^ 0x534B455443485F5F), mix64 = splitmix64's finalizer:
+ *              z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)   (mod 2^64).
+ *              For seed 0, s' = 0x680def4ba05b88ed.
+ *     bucket   = ((h >> 32) * S) >> 32,   value = min((uint32)h, 0xFFFFFFFE).  Every bucket holds the unsigned minimum of the values that
+ *              fall into it; a bucket no window falls into holds EMPTY = 0xFFFFFFFF.  (One-permutation MinHash.)
+ *     out      (B, S), C-contiguous.  Every element is written exactly once, EMPTY included: no memset pass runs and the caller's
+ *              buffer need not be cleared.  BSQ_I32: the 32 bits as they are, so EMPTY reads -1.  BSQ_U64: the value as int64 in
+ *              0 .. 2^32 - 2, EMPTY as -1.  Any other type: BSQ_ERR_DTYPE.
+ *     merge    the sketch of a row equals the bucket-wise UNSIGNED min of the sketches of pieces that together cover all its windows
+ *              (pieces of the row that overlap by k - 1 characters; EMPTY is the largest value): sketches of a sequence too long for
+ *              one row, or of a set of sequences, are merged without the characters.
+ *
+ * Limits, checked before anything is launched: 1 <= k <= 32 and A^k <= 2^64 (DNA4 up to k = 32, DNA5 27, AMINO20 14; the check itself
+ * cannot overflow); 1 <= S <= 2^14; B <= 2^31 - 1; form 0 .. 2 (1 takes S <= 1024), reserved 0, total_chars >= 0 -- otherwise
+ * BSQ_ERR_INVALID_ARG.  B == 0 is BSQ_OK with nothing launched; stream-ordered, never synchronises.  Every refusal leaves `out`
+ * untouched and sets bsq_last_error().
+ *
+ * Known answers (DNA4, k = 3, S = 4, seed 0; E = 4294967295):
+ *                 ACGTAC                      ACGNACGT                    AC, ""    TTTTTTT
+ *     plain       1282424135 2136608625 E E   1282424135 2136608625 E E   all E     E E 1516739009 E
+ *     canonical   1955840499 2136608625 E E   E 2136608625 E E            all E     773537092 E E E
+ * DNA4, k = 31, S = 2, seed 1, plain, the 33 characters ACGTACGTACGTACGTACGTACGTACGTACGTA: 1033262189 1590760883.
+ *
+ * THE COMPARISON of two sketch matrices a (Ba, S) and b (Bb, S) of one element type (BSQ_I32 or BSQ_U64), both C-contiguous.  Only the
+ * low 32 bits of an element are read, so -1 is EMPTY in both types.
+ *     match[i, j]  = #{t : a[i,t] == b[j,t] and a[i,t] != EMPTY}
+ *     either[i, j] = #{t : a[i,t] != EMPTY or b[j,t] != EMPTY}
+ * Both are int32 (Ba, Bb), C-contiguous, every element written exactly once; `either` may be null.  a and b may be the same buffer.  The
+ * Jaccard estimate of rows i and j is match / either, and 0 where either == 0.  1 <= S <= 2^14, Ba and Bb <= 2^31 - 1 with at most
+ * 2^31 - 1 tiles of 64 x 64 outputs, else BSQ_ERR_INVALID_ARG; Ba == 0 or Bb == 0 is BSQ_OK with nothing launched.
+ *
+ * Kernels: a table of S u32 buckets in LDS per row, filled with EMPTY, LDS atomic min, one conversion and write-out -- the spectrum's
+ * structure.  k_minhash_wave (S <= 1024): a wave per row, four rows per workgroup.  k_minhash_block<1024 | 4096 | 16384>: a workgroup
+ * per row.  A lane takes 16 consecutive windows and rolls a 64-bit word (for canonical a second one).  form = 0 takes the wave form
+ * when S <= 1024 and (total_chars == 0 or total_chars / B < 2048, or < 4096 in a batch of at least 4096 rows: the spectrum's thresholds
+ * but for the last, a measured choice, bsq_sketch_dev.h), else the block form.  One row is never split across workgroups.  k_sketch_compare: a workgroup per 64 x 64 output tile, rows staged
+ * through LDS 32 buckets at a time, a 4 x 4 register tile per thread; an input element is read once per tile pair.
+ * Measured on an MI355X, int32 sketches, cold (scripts/minhash_lab.py, profiles/r19/minhash_lab.txt; bytes = characters + offsets +
+ * output against 8 TB/s): DNA4 k = 21 canonical -- 1 M reads x 150: 1.57 ms at S = 128 (0.06 of the roof), 1.68 ms at S = 1024 (0.33);
+ * 262 144 x 512: 400 / 424 us (0.08 / 0.36); 4 096 contigs of 2 000 .. 200 000: 792 / 793 us (0.07 / 0.07, block form; the wave form
+ * 1.34 ms).  AMINO20 k = 7, 65 536 rows of 50 .. 1024: 77 / 84 us (0.11 / 0.46).  The kernel is far under the byte roof at every shape:
+ * it is bound by the arithmetic of a window (two 64-bit multiplications of mix64, the rolling words, one LDS atomic: 300 - 520 G windows
+ * per second on rows of 512 characters and more, 87 G on reads of 150, where 9 of a wave's 64 lanes hold a window), not by bytes, and
+ * kmer_spectrum_packed of the same batch at its nearest legal width takes 0.31 - 0.71 of the sketch's time.  No counters-only run was
+ * taken.  Against kmer_tokenize_packed -> int64 mix64 -> scatter_reduce(amin) in torch at k = 12, where that composition exists
+ * (262 144 reads x 150, S = 1024, equal results): 337 us against 5.5 ms, 16x.  k_sketch_compare: 156 us for 1024 x 1024 x 1024 (62x the
+ * chunked torch broadcast, equal results), 208 us for 4096 x 4096 x 128 (102x), 6.4 ms for 8192 x 8192 x 1024: 9.6 - 10.7 T bucket
+ * pairs per second at the larger sizes. */
+typedef struct bsq_minhash {
+    int32_t k;           /* 1 .. 32, A^k <= 2^64 */
+    int32_t buckets;     /* S: 1 .. 2^14 */
+    int32_t canonical;   /* 0 / 1 */
+    int32_t form;        /* 0: the library chooses; 1: wave per row (S <= 1024); 2: workgroup per row */
+    uint64_t seed;
+    int64_t total_chars; /* hint for the choice of kernel only (0: unknown); never bounds a load */
+    int32_t reserved;    /* 0 */
+} bsq_minhash;
+bsq_status bsq_minhash_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_minhash *m, bsq_dtype t,
+                              void *out, void *hip_stream);
+/* CPU twin on host buffers (the same word, hash and element code; no device is needed). */
+bsq_status bsq_minhash_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_minhash *m, bsq_dtype t,
+                            void *out);
+/* Host only: the kernel bsq_minhash_device takes ("k_minhash_wave", "k_minhash_block<1024>", "...<4096>", "...<16384>"), from the
+ * predicate the launch uses; "" for arguments the device call refuses. */
+const char *bsq_minhash_kernel_name(const bsq_desc *d, const bsq_minhash *m, int64_t B, bsq_dtype t);
+bsq_status bsq_sketch_compare_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, int32_t *match,
+                                     int32_t *either_or_null, void *hip_stream);
+bsq_status bsq_sketch_compare_host(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, int32_t *match,
+                                   int32_t *either_or_null);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
