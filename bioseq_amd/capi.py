@@ -9,6 +9,8 @@ import ctypes
 import os
 import re
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbsq_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bsq.h")
@@ -331,6 +333,23 @@ def dtype_of(destchar):
     return got
 
 
+def destchar_arg(destchar, allowed, what):
+    """`dtype_of(destchar)` for a call that takes only the codes `allowed`, as ValueError: a character the library refuses, and
+    "destchar %r: <what>" for one outside `allowed`."""
+    try:
+        dt, tdt = dtype_of(destchar)
+    except RuntimeError as e:
+        raise ValueError("bad destchar %r: %s" % (destchar, e)) from None
+    if dt not in allowed:
+        raise ValueError("destchar %r: %s" % (destchar, what))
+    return dt, tdt
+
+
+def has_strands(desc) -> bool:
+    """Whether the alphabet has strands as the library reads them: four classes, A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)."""
+    return desc.nchars == 4 and [desc.lut[ord(c)] for c in "ACGT"] == [0, 1, 2, 3]
+
+
 def parse_layout(layout) -> bool:
     """True for the channels-first one-hot (B, C, padlen), False for the reference's (padlen, B, C) -- the names `onehot_packed` takes."""
     if layout in ("tbc", "seq_first", ""):
@@ -360,6 +379,29 @@ def readable_chars(chars, device):
         return chars
     import torch
     return torch.zeros(16, dtype=torch.uint8, device=device)
+
+
+def host_batch(chars, offsets):
+    """A packed batch as a CPU twin reads it, both flat: contiguous uint8 characters -- a 16-byte stand-in where there are none, as
+    `readable_chars` -- and contiguous int64 offsets."""
+    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8).ravel())
+    return (chars if chars.size else np.zeros(16, np.uint8)), np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).ravel())
+
+
+def _row_table_packed(chars, offsets, B, width, tdt, max_len, launch):
+    """The (B, width) device matrix of a per-row table reduction over a packed batch on the device.  max_len (None: unchecked): malformed
+    offsets and a row of more characters raise the library's errors; launch(chars pointer, out pointer, stream) enqueues the kernel."""
+    import torch
+    if max_len is not None and B > 0:
+        bad = ctypes.c_int64(-1)
+        with launching(chars.device) as stream:
+            check(load().bsq_validate_packed_device(offsets.data_ptr(), B, max_len, 0, 0, chars.numel(), ctypes.byref(bad), stream))
+    out = torch.empty((B, width), dtype=tdt, device=chars.device)
+    if B > 0:
+        src = readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        with launching(src.device) as stream:
+            check(launch(src.data_ptr(), out.data_ptr(), stream))
+    return out
 
 
 def raise_too_long(tokenizer, length, padlen, onehot):

@@ -1,13 +1,10 @@
 // k-mer spectrum of a packed batch on the device (gfx950): include/bsq.h ("k-mer spectrum") documents the rule, bsq_kmer_spectrum_dev.h
-// holds what the kernels and the CPU twin share.  Unlike every other kernel of the library these are per-row REDUCTIONS: a histogram of
-// V = A^k u32 bins in LDS, built with LDS atomics (ds_add_u32, no return value), converted and written out once -- the (B, V) matrix is
-// never cleared and never touched by a global atomic.
+// holds what the kernels and the CPU twin share.  Unlike the encode kernels of the library these are per-row REDUCTIONS, over the scaffold
+// of bsq_row_table.h (the table in LDS, its fill, the two forms, the row store, the launch): a histogram of V = A^k u32 bins, filled with
+// zeros, built with LDS atomics (ds_add_u32, no return value); the counted windows of a row are summed for `normalize`.
 //
-// k_kmer_spectrum_wave<T, S1>         V <= 1024: a wave per row, four rows per workgroup, each wave with its own histogram (16 KiB per
-//            workgroup).  The waves of a workgroup never meet after the table is staged: a wave orders its own clear, atomics and reads
-//            with a wavefront-scope fence (LDS serves one wave's instructions in order).
-// k_kmer_spectrum_block<T, BINS, S1>  a 256-thread workgroup per row, BINS = 1024 / 4096 / 16384 bins (4 / 16 / 64 KiB): long rows and
-//            every V above 1024.
+// k_kmer_spectrum_wave<T, S1>         row_table_wave: V <= 1024, a wave per row.
+// k_kmer_spectrum_block<T, BINS, S1>  row_table_block<BINS>: a workgroup per row, long rows and every V above 1024.
 // Both sweep a row in pieces of (lanes x 16) windows: a lane takes 16 consecutive windows.
 //            <S1> stride 1: two 16-byte loads, then the rolling id and mapped-run counter k_kmer_bp<s1> uses: roll16 (bsq_kmer_lane.h);
 //            otherwise one 16-byte load (k <= 16) and a Horner sum per window.
@@ -26,13 +23,14 @@
 #include "bsq_kmer_dev.h"
 #include "bsq_kmer_lane.h"
 #include "bsq_kmer_spectrum_dev.h"
+#include "bsq_row_table.h"
 
 namespace {
 
-using namespace bsq_dev;  // kThreads, store16, u32x4_unaligned
+using bsq_dev::kThreads;
 using bsq_kmerd::Geometry;
-using bsq_kmerd::stage_lut;
-using bsq_specd::Form;
+using bsq_rowtab::Form;
+using bsq_rowtab::load16;
 
 constexpr int kRun = 16;                // windows of a lane's run
 struct SpecParams {
@@ -55,19 +53,6 @@ __device__ __forceinline__ uint32_t rc_fast(uint32_t v, int32_t k) {
 __device__ __forceinline__ void count_window(uint32_t *hist, uint32_t id, const SpecParams &p) {
     atomicAdd(hist + id, 1u);
     if (p.both) atomicAdd(hist + rc_fast(id, p.k), 1u);
-}
-
-// 16 bytes from chars + a, zero where the byte lies outside [0, total) or at / behind `lim` bytes from a
-__device__ __forceinline__ void load16(const uint8_t *chars, int64_t a, int64_t total, int32_t lim, uint32_t (&w)[4]) {
-    if (a >= 0 && a + 16 <= total) {
-        const u32x4_unaligned x = *reinterpret_cast<const u32x4_unaligned *>(chars + a);
-        w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
-    } else {
-        w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c < lim && a + c >= 0 && a + c < total) w[c >> 2] |= static_cast<uint32_t>(chars[a + c]) << (8 * (c & 3));
-    }
 }
 
 // The windows [0, n) of the row at `start` into `hist`, by NL lanes (lane: 0 .. NL - 1); the lane's number of counted windows.
@@ -117,59 +102,19 @@ __device__ __forceinline__ uint32_t sweep(const SpecParams &p, const int8_t *s_l
     return counted;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
-// hist[0 .. V) -> row[0 .. V) as T, by NL lanes: 16-byte stores where the row starts on a 16-byte boundary, element stores otherwise
-// and for the last V % (16 / sizeof(T)) elements; every element exactly once.
-template <typename T, int NL>
-__device__ __forceinline__ void write_row(T *row, const uint32_t *hist, int32_t V, uint32_t sum, bool normalize, int lane) {
-    constexpr int E = 16 / sizeof(T);
-    const int32_t nvec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0 ? V / E : 0;  // (uniform over the row's lanes)
-    for (int32_t g = lane; g < nvec; g += NL) {
-        union {
-            T v[E];
-            uint4 u;
-        } x;
-#pragma unroll
-        for (int e = 0; e < E; ++e) x.v[e] = bsq_specd::element<T>(hist[g * E + e], sum, normalize);
-        store16<true>(row + g * E, x.u);
-    }
-    for (int32_t e = nvec * E + lane; e < V; e += NL) __builtin_nontemporal_store(bsq_specd::element<T>(hist[e], sum, normalize), row + e);
-}
-
-// what orders one wave's LDS accesses: nothing of another wave is waited for
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int32_t windows_of(const SpecParams &p, int64_t i, int64_t *start) {
-    *start = p.offsets[i];
-    return static_cast<int32_t>(bsq_specd::row_windows(p.offsets[i + 1] - *start, p.k, p.stride));
-}
-
 template <typename T, bool S1>
 __global__ __launch_bounds__(kThreads) void k_kmer_spectrum_wave(const SpecParams p) {
     __shared__ int8_t s_lut[256];
-    __shared__ __align__(16) uint32_t s_hist[kThreads / 64][bsq_specd::kWaveMaxV];
-    stage_lut(s_lut, p.lut);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t *hist = s_hist[wave];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave;  // (wave-uniform)
-    if (i >= p.B) return;  // (no workgroup barrier follows)
-    for (int32_t v = lane; v < p.V; v += 64) hist[v] = 0;
-    wave_sync();
-    int64_t start;
-    const int32_t n = windows_of(p, i, &start);
-    const uint32_t sum = wave_sum(sweep<S1, 64>(p, s_lut, hist, start, p.offsets[p.B], n, lane)) << (p.both ? 1 : 0);
-    wave_sync();
-    write_row<T, 64>(static_cast<T *>(p.out) + i * p.V, hist, p.V, sum, p.normalize != 0, lane);
+    bsq_rowtab::row_table_wave<T, true>(
+        p, p.V, 0u, s_lut, [k = p.k, stride = p.stride](int64_t L) { return static_cast<int32_t>(bsq_specd::row_windows(L, k, stride)); },
+        [=](uint32_t *hist, int64_t start, int64_t total, int32_t n, int lane) { return sweep<S1, 64>(p, s_lut, hist, start, total, n, lane); },
+        [both = p.both, normalize = p.normalize != 0](uint32_t counted) {
+            return [sum = counted << (both ? 1 : 0), normalize](uint32_t count) { return bsq_specd::element<T>(count, sum, normalize); };
+        });
 }
 
+// The block form stays here, not behind row_table_block: a row's counted windows meet in one LDS word (s_sum), which the sketch must not
+// have, and through the scaffold's callables this kernel measured ~1 % slower on long both-strand rows (LAB_NOTES, round 20).
 template <typename T, int BINS, bool S1>
 __global__ __launch_bounds__(kThreads) void k_kmer_spectrum_block(const SpecParams p) {
     __shared__ int8_t s_lut[256];
@@ -179,23 +124,14 @@ __global__ __launch_bounds__(kThreads) void k_kmer_spectrum_block(const SpecPara
     const int64_t i = blockIdx.x;  // (< B)
     for (int32_t v = tid; v < p.V; v += kThreads) s_hist[v] = 0;
     if (tid == 0) s_sum = 0;
-    stage_lut(s_lut, p.lut);  // (its barrier also orders the clear before the atomics)
-    int64_t start;
-    const int32_t n = windows_of(p, i, &start);
-    const uint32_t mine = wave_sum(sweep<S1, kThreads>(p, s_lut, s_hist, start, p.offsets[p.B], n, tid));
+    bsq_kmerd::stage_lut(s_lut, p.lut);  // (its barrier also orders the clear before the atomics)
+    const int64_t start = p.offsets[i];
+    const int32_t n = static_cast<int32_t>(bsq_specd::row_windows(p.offsets[i + 1] - start, p.k, p.stride));
+    const uint32_t mine = bsq_rowtab::wave_sum(sweep<S1, kThreads>(p, s_lut, s_hist, start, p.offsets[p.B], n, tid));
     if ((tid & 63) == 0 && mine) atomicAdd(&s_sum, mine);
     __syncthreads();
-    const uint32_t sum = s_sum << (p.both ? 1 : 0);
-    write_row<T, kThreads>(static_cast<T *>(p.out) + i * p.V, s_hist, p.V, sum, p.normalize != 0, tid);
-}
-
-bsq_status check_all(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
-                     const bsq_kmer_spectrum *o, bsq_dtype t, const void *out, Geometry *g) {
-    const char *why = "";
-    const bsq_status st = bsq_specd::check(d, km, o, B, t, g, &why);
-    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
-    if (B > 0 && (!chars || !offsets || !out)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "chars, offsets or out is null");
-    return BSQ_OK;
+    const auto element = [sum = s_sum << (p.both ? 1 : 0), normalize = p.normalize != 0](uint32_t count) { return bsq_specd::element<T>(count, sum, normalize); };
+    bsq_rowtab::write_row<T, kThreads>(static_cast<T *>(p.out) + i * p.V, s_hist, p.V, tid, element);
 }
 
 // f(T{}) with the element type of a spectrum (check() has refused every other one)
@@ -233,7 +169,7 @@ const char *bsq_kmer_spectrum_kernel_name(const bsq_desc *d, const bsq_kmer *km,
 bsq_status bsq_kmer_spectrum_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
                                     const bsq_kmer_spectrum *o, bsq_dtype t, void *out, void *hip_stream) {
     Geometry g;
-    bsq_status st = check_all(d, chars, offsets, B, km, o, t, out, &g);
+    bsq_status st = bsq_rowtab::check_all(B, chars, offsets, out, [&](const char **why) { return bsq_specd::check(d, km, o, B, t, &g, why); });
     if (st != BSQ_OK || B == 0) return st;
     SpecParams p;
     std::memcpy(p.lut, d->lut, 256);
@@ -250,19 +186,13 @@ bsq_status bsq_kmer_spectrum_device(const bsq_desc *d, const uint8_t *chars, con
     p.normalize = o->normalize;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const Form form = bsq_specd::form_of(g.V, B, o->total_chars, o->form);
-    // one wave (wave form) or one workgroup (block form) per row: B <= 2^31 - 1 (bsq_specd::check) fits the grid
-    const dim3 grid(static_cast<unsigned>(form == Form::wave ? (B + kThreads / 64 - 1) / (kThreads / 64) : B)), block(kThreads);
     st = with_spectrum_type(t, [&](auto tag) {
         using T = decltype(tag);
         return bsq_internal::with_flags(
             [&](auto s1) {
                 constexpr bool S1 = decltype(s1)::value;
-                switch (form) {
-                case Form::wave: hipLaunchKernelGGL((k_kmer_spectrum_wave<T, S1>), grid, block, 0, s, p); break;
-                case Form::block1024: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 1024, S1>), grid, block, 0, s, p); break;
-                case Form::block4096: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 4096, S1>), grid, block, 0, s, p); break;
-                default: hipLaunchKernelGGL((k_kmer_spectrum_block<T, 16384, S1>), grid, block, 0, s, p); break;
-                }
+                bsq_rowtab::launch(form, B, s, p, k_kmer_spectrum_wave<T, S1>, k_kmer_spectrum_block<T, 1024, S1>, k_kmer_spectrum_block<T, 4096, S1>,
+                                   k_kmer_spectrum_block<T, 16384, S1>);
                 return BSQ_OK;
             },
             g.stride == 1);
@@ -273,7 +203,7 @@ bsq_status bsq_kmer_spectrum_device(const bsq_desc *d, const uint8_t *chars, con
 bsq_status bsq_kmer_spectrum_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_kmer *km,
                                   const bsq_kmer_spectrum *o, bsq_dtype t, void *out) {
     Geometry g;
-    const bsq_status st = check_all(d, chars, offsets, B, km, o, t, out, &g);
+    const bsq_status st = bsq_rowtab::check_all(B, chars, offsets, out, [&](const char **why) { return bsq_specd::check(d, km, o, B, t, &g, why); });
     if (st != BSQ_OK || B == 0) return st;
     return with_spectrum_type(t, [&](auto tag) {
         using T = decltype(tag);

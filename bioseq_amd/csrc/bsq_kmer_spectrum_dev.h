@@ -7,13 +7,12 @@
 
 #include "bsq.h"
 #include "bsq_kmer_dev.h"
+#include "bsq_row_table.h"
 
 namespace bsq_specd {
 
 constexpr int64_t kMaxV = int64_t(1) << 14;        // columns of the dense (B, V) matrix: the largest histogram one workgroup keeps in LDS
 constexpr int64_t kMaxWindows = int64_t(1) << 23;  // windows a row counts: both strands of every one still sum below 2^24 + 1 (exact in f32)
-constexpr int64_t kMaxRows = (int64_t(1) << 31) - 1;  // rows of a call: a row is a workgroup (or a wave) of one launch
-constexpr int64_t kWaveMaxV = 1024;                // the wave form: four V x u32 histograms per workgroup, 16 KiB
 // The choice between the forms at V <= 1024, from the mean row length total_chars / B (scripts/kmer_spectrum_lab.py on an MI355X,
 // profiles/r14/kmer_spectrum_lab.txt: DNA4, k = 4, f32 counts, cold; wave / block time, < 1: the wave form wins):
 //     128 Mi characters in rows of L     L = 1024: 0.36   2048: 0.52   4096: 0.79   8192: 0.93   16384: 1.01   65536: 2.28
@@ -49,32 +48,14 @@ BSQ_KMER_HD T element(uint32_t count, uint32_t sum, bool normalize) {
     return static_cast<T>(count);
 }
 
-enum class Form { none, wave, block1024, block4096, block16384 };
-
-// The kernel a call takes: a pure predicate of (V, B, total_chars, form); Form::none: form = 1 cannot take this V.
+// The kernel a call takes and its name (bsq_row_table.h): a pure predicate of (V, B, total_chars, form); Form::none: form = 1 cannot take this V.
+using bsq_rowtab::Form;
+using bsq_rowtab::kMaxRows;  // rows of a call: a row is a workgroup (or a wave) of one launch
 inline Form form_of(int64_t V, int64_t B, int64_t total_chars, int32_t form) {
-    const bool wave_fits = V <= kWaveMaxV;
-    bool wave;
-    if (form == 1) {
-        if (!wave_fits) return Form::none;
-        wave = true;
-    } else if (form == 2) {
-        wave = false;
-    } else {
-        wave = wave_fits && (total_chars == 0 || B == 0 || total_chars / B < (B >= kManyRows ? kBlockCharsMany : kBlockChars));
-    }
-    if (wave) return Form::wave;
-    return V <= 1024 ? Form::block1024 : (V <= 4096 ? Form::block4096 : Form::block16384);
+    return bsq_rowtab::form_of(V, B, total_chars, form, {kBlockChars, kManyRows, kBlockCharsMany});
 }
-inline const char *form_name(Form f) {
-    switch (f) {
-    case Form::wave: return "k_kmer_spectrum_wave";
-    case Form::block1024: return "k_kmer_spectrum_block<1024>";
-    case Form::block4096: return "k_kmer_spectrum_block<4096>";
-    case Form::block16384: return "k_kmer_spectrum_block<16384>";
-    default: return "";
-    }
-}
+constexpr const char *kFormNames[4] = {"k_kmer_spectrum_wave", "k_kmer_spectrum_block<1024>", "k_kmer_spectrum_block<4096>", "k_kmer_spectrum_block<16384>"};
+inline const char *form_name(Form f) { return bsq_rowtab::form_name(f, kFormNames); }
 
 // The argument rules that do not depend on a pointer to the batch: BSQ_OK and the geometry, or a status and a reason.  Host only.
 inline bsq_status check(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_spectrum *o, int64_t B, bsq_dtype t, bsq_kmerd::Geometry *g,
@@ -85,7 +66,7 @@ inline bsq_status check(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_sp
     if (g->V > kMaxV) return *why = "nchars^k exceeds 2^14: a dense (B, nchars^k) spectrum is not built beyond that", BSQ_ERR_INVALID_ARG;
     if ((o->both_strands | 1) != 1 || (o->normalize | 1) != 1 || o->form < 0 || o->form > 2 || o->reserved != 0 || o->total_chars < 0)
         return *why = "both_strands and normalize must be 0 / 1, form 0 .. 2, reserved 0 and total_chars >= 0", BSQ_ERR_INVALID_ARG;
-    if (o->both_strands && !(d->nchars == 4 && d->lut['A'] == 0 && d->lut['C'] == 1 && d->lut['G'] == 2 && d->lut['T'] == 3))
+    if (o->both_strands && !bsq_rowtab::has_strands(d))
         return *why = "both_strands needs the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)", BSQ_ERR_INVALID_ARG;
     if (t < BSQ_I8 || t > BSQ_F64) return *why = "bad bsq_dtype", BSQ_ERR_DTYPE;
     if (t == BSQ_I8 || t == BSQ_I16)

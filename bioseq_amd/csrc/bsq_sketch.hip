@@ -1,14 +1,11 @@
 // MinHash sketches of a packed batch and the all-pairs comparison of sketches on the device (gfx950): include/bsq.h ("MinHash sketch")
-// documents the rule, bsq_sketch_dev.h holds what the kernels and the CPU twins (bsq_sketch_host.cpp) share.  The sketch kernels are the
-// spectrum's per-row reductions (bsq_kmer_spectrum.hip) with `min` in place of `add`, over a wide rolling word in place of a dense id: a
-// table of S u32 buckets in LDS, initialised to EMPTY, updated with LDS atomics (ds_min_u32, no return value), converted and written out
-// once -- the (B, S) matrix is never cleared and never touched by a global atomic.
+// documents the rule, bsq_sketch_dev.h holds what the kernels and the CPU twins (bsq_sketch_host.cpp) share.  The sketch kernels are per-row
+// reductions over the scaffold of bsq_row_table.h (the table in LDS, its fill, the two forms, the row store, the launch), as the spectrum's
+// are (bsq_kmer_spectrum.hip), with `min` in place of `add` over a wide rolling word in place of a dense id: a table of S u32 buckets,
+// filled with EMPTY, updated with LDS atomics (ds_min_u32, no return value); nothing is counted per row.
 //
-// k_minhash_wave<T, MODE>         S <= 1024: a wave per row, four rows per workgroup, each wave with its own table (16 KiB per workgroup).
-//            The waves of a workgroup never meet after the byte table is staged: a wave orders its own fill, atomics and reads with a
-//            wavefront-scope fence (LDS serves one wave's instructions in order).
-// k_minhash_block<T, BINS, MODE>  a 256-thread workgroup per row, BINS = 1024 / 4096 / 16384 buckets (4 / 16 / 64 KiB): long rows and every
-//            S above 1024.
+// k_minhash_wave<T, MODE>         row_table_wave: S <= 1024, a wave per row.
+// k_minhash_block<T, BINS, MODE>  row_table_block<BINS>: a workgroup per row, long rows and every S above 1024.
 // Both sweep a row in pieces of (lanes x 16) windows: a lane takes 16 consecutive windows, 16 + k - 1 <= 47 characters from three 16-byte
 // loads -- the 16 that start a window, the next 16 (the warm-up of k > 17 only) and, k - 1 further than the first, the 16 that end one --
 // so that every register index is static.  MODE 0: any alphabet, the word rolls by a multiplication; 1: four classes, the word rolls by
@@ -28,14 +25,15 @@
 #include "bsq_device.h"
 #include "bsq_internal.h"
 #include "bsq_kmer_lane.h"
+#include "bsq_row_table.h"
 #include "bsq_sketch_dev.h"
 
 namespace {
 
-using namespace bsq_dev;  // kThreads, store16, u32x4_unaligned
+using bsq_dev::kThreads;
 using bsq_kmerd::byte_of;
-using bsq_kmerd::stage_lut;
-using bsq_sketchd::Form;
+using bsq_rowtab::Form;
+using bsq_rowtab::load16;
 using bsq_sketchd::Geometry;
 using bsq_sketchd::kEmpty;
 
@@ -49,25 +47,6 @@ struct SketchParams {
     int32_t S, k, A;
     int8_t lut[256];
 };
-
-// 16 bytes from chars + a, zero where the byte lies outside [0, total) or at / behind `lim` bytes from a (bsq_kmer_spectrum.hip's, restated)
-__device__ __forceinline__ void load16(const uint8_t *chars, int64_t a, int64_t total, int32_t lim, uint32_t (&w)[4]) {
-    if (a >= 0 && a + 16 <= total) {
-        const u32x4_unaligned x = *reinterpret_cast<const u32x4_unaligned *>(chars + a);
-        w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
-    } else {
-        w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c < lim && a + c >= 0 && a + c < total) w[c >> 2] |= static_cast<uint32_t>(chars[a + c]) << (8 * (c & 3));
-    }
-}
-
-// what orders one wave's LDS accesses: nothing of another wave is waited for (bsq_kmer_spectrum.hip's, restated)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // The rolling words of a lane: fw the Horner sum of the last k characters, rc (MODE 2) that of their reverse complement, run the mapped
 // characters in a row up to the current one (a window is whole from run >= k on).  An unmapped character enters as digit 0.
@@ -131,60 +110,29 @@ __device__ __forceinline__ void sweep(const SketchParams &p, const int8_t *s_lut
     }
 }
 
-// tab[0 .. S) -> row[0 .. S) as T, by NL lanes: 16-byte stores where the row starts on a 16-byte boundary, element stores otherwise
-// and for the last S % (16 / sizeof(T)) elements; every element exactly once.
-template <typename T, int NL>
-__device__ __forceinline__ void write_row(T *row, const uint32_t *tab, int32_t S, int lane) {
-    constexpr int E = 16 / sizeof(T);
-    const int32_t nvec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0 ? S / E : 0;  // (uniform over the row's lanes)
-    for (int32_t g = lane; g < nvec; g += NL) {
-        union {
-            T v[E];
-            uint4 u;
-        } x;
-#pragma unroll
-        for (int e = 0; e < E; ++e) x.v[e] = bsq_sketchd::element<T>(tab[g * E + e]);
-        store16<true>(row + g * E, x.u);
-    }
-    for (int32_t e = nvec * E + lane; e < S; e += NL) __builtin_nontemporal_store(bsq_sketchd::element<T>(tab[e]), row + e);
-}
-
-__device__ __forceinline__ int32_t windows_of(const SketchParams &p, int64_t i, int64_t *start) {
-    *start = p.offsets[i];
-    return static_cast<int32_t>(bsq_sketchd::row_windows(p.offsets[i + 1] - *start, p.k));
+// A row through the scaffold (bsq_row_table.h): BINS = 0 the wave form, else the block form of that many buckets.  Nothing is counted.
+template <typename T, int BINS, int MODE>
+__device__ __forceinline__ void minhash_row(const SketchParams &p) {
+    __shared__ int8_t s_lut[256];
+    constexpr int NL = BINS ? kThreads : 64;
+    const auto windows = [k = p.k](int64_t L) { return static_cast<int32_t>(bsq_sketchd::row_windows(L, k)); };
+    const auto sweep_row = [=](uint32_t *tab, int64_t start, int64_t total, int32_t n, int lane) {
+        sweep<MODE, NL>(p, s_lut, tab, start, total, n, lane);
+        return 0u;
+    };
+    const auto finish = [](uint32_t) { return [](uint32_t v) { return bsq_sketchd::element<T>(v); }; };
+    if constexpr (BINS == 0) bsq_rowtab::row_table_wave<T, false>(p, p.S, kEmpty, s_lut, windows, sweep_row, finish);
+    else bsq_rowtab::row_table_block<T, BINS>(p, p.S, kEmpty, s_lut, windows, sweep_row, finish);
 }
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(kThreads) void k_minhash_wave(const SketchParams p) {
-    __shared__ int8_t s_lut[256];
-    __shared__ __align__(16) uint32_t s_tab[kThreads / 64][bsq_sketchd::kWaveMaxS];
-    stage_lut(s_lut, p.lut);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t *tab = s_tab[wave];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave;  // (wave-uniform)
-    if (i >= p.B) return;  // (no workgroup barrier follows)
-    for (int32_t v = lane; v < p.S; v += 64) tab[v] = kEmpty;
-    wave_sync();
-    int64_t start;
-    const int32_t n = windows_of(p, i, &start);
-    sweep<MODE, 64>(p, s_lut, tab, start, p.offsets[p.B], n, lane);
-    wave_sync();
-    write_row<T, 64>(static_cast<T *>(p.out) + i * p.S, tab, p.S, lane);
+    minhash_row<T, 0, MODE>(p);
 }
 
 template <typename T, int BINS, int MODE>
 __global__ __launch_bounds__(kThreads) void k_minhash_block(const SketchParams p) {
-    __shared__ int8_t s_lut[256];
-    __shared__ __align__(16) uint32_t s_tab[BINS];
-    const int tid = threadIdx.x;
-    const int64_t i = blockIdx.x;  // (< B)
-    for (int32_t v = tid; v < p.S; v += kThreads) s_tab[v] = kEmpty;
-    stage_lut(s_lut, p.lut);  // (its barrier also orders the fill before the atomics)
-    int64_t start;
-    const int32_t n = windows_of(p, i, &start);
-    sweep<MODE, kThreads>(p, s_lut, s_tab, start, p.offsets[p.B], n, tid);
-    __syncthreads();
-    write_row<T, kThreads>(static_cast<T *>(p.out) + i * p.S, s_tab, p.S, tid);
+    minhash_row<T, BINS, MODE>(p);
 }
 
 // ---- the comparison ----
@@ -267,31 +215,17 @@ __global__ __launch_bounds__(kThreads) void k_sketch_compare(const T *a, int64_t
     }
 }
 
-bsq_status check_all(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_minhash *m, bsq_dtype t, const void *out,
-                     Geometry *g) {
-    const char *why = "";
-    const bsq_status st = bsq_sketchd::check(d, m, B, t, g, &why);
-    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
-    if (B > 0 && (!chars || !offsets || !out)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "chars, offsets or out is null");
-    return BSQ_OK;
-}
-
 template <typename T, int MODE>
-void launch_minhash(Form form, dim3 grid, hipStream_t s, const SketchParams &p) {
-    const dim3 block(kThreads);
-    switch (form) {
-    case Form::wave: hipLaunchKernelGGL((k_minhash_wave<T, MODE>), grid, block, 0, s, p); break;
-    case Form::block1024: hipLaunchKernelGGL((k_minhash_block<T, 1024, MODE>), grid, block, 0, s, p); break;
-    case Form::block4096: hipLaunchKernelGGL((k_minhash_block<T, 4096, MODE>), grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((k_minhash_block<T, 16384, MODE>), grid, block, 0, s, p); break;
-    }
+void launch_minhash(Form form, int64_t B, hipStream_t s, const SketchParams &p) {
+    bsq_rowtab::launch(form, B, s, p, k_minhash_wave<T, MODE>, k_minhash_block<T, 1024, MODE>, k_minhash_block<T, 4096, MODE>,
+                       k_minhash_block<T, 16384, MODE>);
 }
 
 template <typename T>
-void launch_minhash(Form form, dim3 grid, hipStream_t s, const SketchParams &p, int mode) {
-    if (mode == 0) launch_minhash<T, 0>(form, grid, s, p);
-    else if (mode == 1) launch_minhash<T, 1>(form, grid, s, p);
-    else launch_minhash<T, 2>(form, grid, s, p);
+void launch_minhash(Form form, int64_t B, hipStream_t s, const SketchParams &p, int mode) {
+    if (mode == 0) launch_minhash<T, 0>(form, B, s, p);
+    else if (mode == 1) launch_minhash<T, 1>(form, B, s, p);
+    else launch_minhash<T, 2>(form, B, s, p);
 }
 
 }  // namespace
@@ -308,7 +242,7 @@ const char *bsq_minhash_kernel_name(const bsq_desc *d, const bsq_minhash *m, int
 bsq_status bsq_minhash_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_minhash *m, bsq_dtype t,
                               void *out, void *hip_stream) {
     Geometry g;
-    const bsq_status st = check_all(d, chars, offsets, B, m, t, out, &g);
+    const bsq_status st = bsq_rowtab::check_all(B, chars, offsets, out, [&](const char **why) { return bsq_sketchd::check(d, m, B, t, &g, why); });
     if (st != BSQ_OK || B == 0) return st;
     SketchParams p;
     std::memcpy(p.lut, d->lut, 256);
@@ -324,11 +258,9 @@ bsq_status bsq_minhash_device(const bsq_desc *d, const uint8_t *chars, const int
     p.A = g.A;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const Form form = bsq_sketchd::form_of(g.S, B, m->total_chars, m->form);
-    // one wave (wave form) or one workgroup (block form) per row: B <= 2^31 - 1 (bsq_sketchd::check) fits the grid
-    const dim3 grid(static_cast<unsigned>(form == Form::wave ? (B + kThreads / 64 - 1) / (kThreads / 64) : B));
     const int mode = g.canonical ? 2 : (g.A == 4 ? 1 : 0);
-    if (t == BSQ_I32) launch_minhash<int32_t>(form, grid, s, p, mode);
-    else launch_minhash<uint64_t>(form, grid, s, p, mode);
+    if (t == BSQ_I32) launch_minhash<int32_t>(form, B, s, p, mode);
+    else launch_minhash<uint64_t>(form, B, s, p, mode);
     return bsq_internal::check_launch(bsq_sketchd::form_name(form));
 }
 

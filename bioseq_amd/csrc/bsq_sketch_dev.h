@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "bsq.h"
+#include "bsq_row_table.h"
 
 #if defined(__HIPCC__)
 #define BSQ_SKETCH_HD __host__ __device__ inline __attribute__((always_inline))
@@ -18,8 +19,6 @@ namespace bsq_sketchd {
 constexpr int32_t kMaxK = 32;                          // a word is one unsigned 64-bit value: A^k <= 2^64
 constexpr int64_t kMaxBuckets = int64_t(1) << 14;      // S: the largest u32 table one workgroup keeps in LDS (64 KiB)
 constexpr int64_t kMaxWindows = int64_t(1) << 30;      // windows a row sketches: window indices stay far inside 32 bits
-constexpr int64_t kMaxRows = (int64_t(1) << 31) - 1;   // rows of a call: a row is a workgroup (or a wave) of one launch
-constexpr int64_t kWaveMaxS = 1024;                    // the wave form: four S x u32 tables per workgroup, 16 KiB
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;               // a bucket no window fell into
 constexpr uint64_t kDomain = 0x534B455443485F5Full;    // the sketch's own hash domain ("SKETCH__")
 // The choice between the forms at S <= 1024, from the mean row length total_chars / B.  The starting values were the spectrum's
@@ -100,32 +99,14 @@ BSQ_SKETCH_HD bool window_word(const Geometry &g, const Lut &lut, const uint8_t 
     return true;
 }
 
-enum class Form { none, wave, block1024, block4096, block16384 };
-
-// The kernel a call takes: a pure predicate of (S, B, total_chars, form); Form::none: form = 1 cannot take this S.
+// The kernel a call takes and its name (bsq_row_table.h): a pure predicate of (S, B, total_chars, form); Form::none: form = 1 cannot take this S.
+using bsq_rowtab::Form;
+using bsq_rowtab::kMaxRows;  // rows of a call: a row is a workgroup (or a wave) of one launch
 inline Form form_of(int64_t S, int64_t B, int64_t total_chars, int32_t form) {
-    const bool wave_fits = S <= kWaveMaxS;
-    bool wave;
-    if (form == 1) {
-        if (!wave_fits) return Form::none;
-        wave = true;
-    } else if (form == 2) {
-        wave = false;
-    } else {
-        wave = wave_fits && (total_chars == 0 || B == 0 || total_chars / B < (B >= kManyRows ? kBlockCharsMany : kBlockChars));
-    }
-    if (wave) return Form::wave;
-    return S <= 1024 ? Form::block1024 : (S <= 4096 ? Form::block4096 : Form::block16384);
+    return bsq_rowtab::form_of(S, B, total_chars, form, {kBlockChars, kManyRows, kBlockCharsMany});
 }
-inline const char *form_name(Form f) {
-    switch (f) {
-    case Form::wave: return "k_minhash_wave";
-    case Form::block1024: return "k_minhash_block<1024>";
-    case Form::block4096: return "k_minhash_block<4096>";
-    case Form::block16384: return "k_minhash_block<16384>";
-    default: return "";
-    }
-}
+constexpr const char *kFormNames[4] = {"k_minhash_wave", "k_minhash_block<1024>", "k_minhash_block<4096>", "k_minhash_block<16384>"};
+inline const char *form_name(Form f) { return bsq_rowtab::form_name(f, kFormNames); }
 
 // The argument rules that do not depend on a pointer to the batch: BSQ_OK and the geometry, or a status and a reason.  Host only.
 inline bsq_status check(const bsq_desc *d, const bsq_minhash *m, int64_t B, bsq_dtype t, Geometry *g, const char **why) {
@@ -144,7 +125,7 @@ inline bsq_status check(const bsq_desc *d, const bsq_minhash *m, int64_t B, bsq_
     if (m->buckets < 1 || m->buckets > kMaxBuckets) return *why = "buckets must lie in 1 .. 2^14", BSQ_ERR_INVALID_ARG;
     if ((m->canonical | 1) != 1 || m->form < 0 || m->form > 2 || m->reserved != 0 || m->total_chars < 0)
         return *why = "canonical must be 0 / 1, form 0 .. 2, reserved 0 and total_chars >= 0", BSQ_ERR_INVALID_ARG;
-    if (m->canonical && !(d->nchars == 4 && d->lut['A'] == 0 && d->lut['C'] == 1 && d->lut['G'] == 2 && d->lut['T'] == 3))
+    if (m->canonical && !bsq_rowtab::has_strands(d))
         return *why = "canonical needs the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)", BSQ_ERR_INVALID_ARG;
     if (t != BSQ_I32 && t != BSQ_U64) return *why = "a sketch takes BSQ_I32 or BSQ_U64", BSQ_ERR_DTYPE;
     if (form_of(m->buckets, B, m->total_chars, m->form) == Form::none)

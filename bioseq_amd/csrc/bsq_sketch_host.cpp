@@ -7,10 +7,6 @@
 #include "bsq.h"
 #include "bsq_sketch_dev.h"
 
-namespace bsq_internal {
-bsq_status set_error(bsq_status st, const char *msg);  // (bsq_internal.h, which includes the HIP runtime's header)
-}
-
 namespace {
 
 using bsq_sketchd::Geometry;
@@ -56,11 +52,8 @@ extern "C" {
 bsq_status bsq_minhash_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, const bsq_minhash *m, bsq_dtype t,
                             void *out) {
     Geometry g;
-    const char *why = "";
-    const bsq_status st = bsq_sketchd::check(d, m, B, t, &g, &why);
-    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
-    if (B > 0 && (!chars || !offsets || !out)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "chars, offsets or out is null");
-    if (B == 0) return BSQ_OK;
+    const bsq_status st = bsq_rowtab::check_all(B, chars, offsets, out, [&](const char **why) { return bsq_sketchd::check(d, m, B, t, &g, why); });
+    if (st != BSQ_OK || B == 0) return st;
     if (t == BSQ_I32) minhash_rows(d, g, chars, offsets, B, static_cast<int32_t *>(out));
     else minhash_rows(d, g, chars, offsets, B, static_cast<uint64_t *>(out));
     return BSQ_OK;

@@ -141,12 +141,10 @@ def kmer_tokenize_host(tok, chars, offsets, k, padlen, destchar="q", batch_first
     dt, _ = _dtype(desc, km, destchar)
     if int(padlen) <= 0:
         raise ValueError("padlen must be positive")
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    chars, offsets = capi.host_batch(chars, offsets)
     B = offsets.size - 1
     out = np.empty((B, int(padlen)) if batch_first else (int(padlen), B), dtype=_NUMPY[dt])
-    keep = chars if chars.size else np.zeros(16, np.uint8)
-    capi.check(_lib.bsq_kmer_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
+    capi.check(_lib.bsq_kmer_tokenize_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
                                            ctypes.byref(km), dt, out.ctypes.data))
     return out
 
@@ -244,14 +242,12 @@ def kmer_mlm_tokenize_host(tok, chars, offsets, k, padlen, destchar="q", batch_f
                                            ignore_index, seed, first_row)
     if int(padlen) <= 0:
         raise ValueError("padlen must be positive")
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    chars, offsets = capi.host_batch(chars, offsets)
     B = offsets.size - 1
     shape = (B, int(padlen)) if batch_first else (int(padlen), B)
     inputs, labels = np.empty(shape, dtype=_NUMPY[dt]), np.empty(shape, dtype=_NUMPY[ldt])
-    keep = chars if chars.size else np.zeros(16, np.uint8)
     if B > 0:
-        capi.check(_lib.bsq_kmer_mlm_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
+        capi.check(_lib.bsq_kmer_mlm_tokenize_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, int(padlen), int(bool(batch_first)),
                                                    ctypes.byref(km), ctypes.byref(m), dt, inputs.ctypes.data, ldt, labels.ctypes.data))
     return inputs, labels
 
@@ -291,26 +287,17 @@ def kmer_mlm_tokenize_packed(tok, chars, offsets, k, padlen, destchar="q", batch
 _SPECTRUM_MAX_WINDOWS = 1 << 23  # (include/bsq.h, "k-mer spectrum": a row counts its first 2 ** 23 windows)
 
 
-def _strands(desc):
-    """Whether the alphabet has strands as the spectrum reads them: four classes, A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)."""
-    return desc.nchars == 4 and [desc.lut[ord(c)] for c in "ACGT"] == [0, 1, 2, 3]
-
-
 def _spectrum(tok, k, stride, destchar, both_strands, normalize, form, total_chars=0):
     """(desc, km, bsq_kmer_spectrum, dtype code, torch dtype, V) with the library's argument rules applied as ValueError."""
     desc, km = _kmer(tok, k, stride)
     V = int(_lib.bsq_kmer_spectrum_width(ctypes.byref(desc), ctypes.byref(km)))
     if V < 0:
         raise ValueError("k = %r with %d classes: %s" % (k, desc.nchars, _lib.bsq_last_error().decode()))
-    try:
-        dt, tdt = capi.dtype_of(destchar)
-    except RuntimeError as e:
-        raise ValueError("bad destchar %r: %s" % (destchar, e)) from None
-    allowed = (capi.F32, capi.F64) if normalize else (capi.I32, capi.U64, capi.F32, capi.F64)
-    if dt not in allowed:
-        raise ValueError("destchar %r: a spectrum of %s takes %s" % (destchar, "frequencies" if normalize else "counts",
-                                                                     "'f' or 'd'" if normalize else "'i', 'q', 'f' or 'd'"))
-    if both_strands and not _strands(desc):
+    if normalize:
+        dt, tdt = capi.destchar_arg(destchar, (capi.F32, capi.F64), "a spectrum of frequencies takes 'f' or 'd'")
+    else:
+        dt, tdt = capi.destchar_arg(destchar, (capi.I32, capi.U64, capi.F32, capi.F64), "a spectrum of counts takes 'i', 'q', 'f' or 'd'")
+    if both_strands and not capi.has_strands(desc):
         raise ValueError("both_strands needs an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
     form = 0 if form is None else int(form)
     if form not in (0, 1, 2) or (form == 1 and V > 1024):
@@ -331,7 +318,7 @@ def kmer_canonical_columns(tok, k):
     """The sorted int64 columns v with v <= rc(v) (host numpy): `spectrum[:, cols]` of a `both_strands` spectrum is the canonical-k-mer
     profile -- (4 ** k + 4 ** (k / 2)) / 2 columns for even k, 4 ** k / 2 for odd k.  ValueError for an alphabet without strands."""
     desc, km = _kmer(tok, k)
-    if not _strands(desc):
+    if not capi.has_strands(desc):
         raise ValueError("canonical k-mers need an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
     V = kmer_spectrum_width(tok, k)
     v = np.arange(V, dtype=np.int64)
@@ -351,13 +338,11 @@ def kmer_spectrum_kernel_name(tok, k, B, destchar="f", *, stride=1, both_strands
 def kmer_spectrum_host(tok, chars, offsets, k, destchar="f", *, stride=1, both_strands=False, normalize=False):
     """The library's CPU twin (`bsq_kmer_spectrum_host`, the window and element code of the kernels) on numpy arrays: a (B, V) matrix."""
     desc, km, o, dt, _, V = _spectrum(tok, k, stride, destchar, both_strands, normalize, None)
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    chars, offsets = capi.host_batch(chars, offsets)
     B = offsets.size - 1
     out = np.empty((B, V), dtype=_NUMPY[dt])
-    keep = chars if chars.size else np.zeros(16, np.uint8)
     if B > 0:
-        capi.check(_lib.bsq_kmer_spectrum_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, ctypes.byref(km), ctypes.byref(o), dt,
+        capi.check(_lib.bsq_kmer_spectrum_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, ctypes.byref(km), ctypes.byref(o), dt,
                                                out.ctypes.data))
     return out
 
@@ -372,21 +357,11 @@ def kmer_spectrum_packed(tok, chars, offsets, k, destchar="f", *, stride=1, both
     divided by its sum (destchar 'f' or 'd'; an empty row stays zero); counts take 'i', 'q', 'f' or 'd'.  form: None = the library
     chooses from `chars.numel()` / B, 1 = a wave per row, 2 = a workgroup per row.  validate: malformed offsets and a row of more than
     2 ** 23 windows raise the library's errors instead of being clamped."""
-    import torch
     B = capi.packed_on_device(chars, offsets, "kmer_spectrum_packed works on packed batches resident on the device (chars, offsets tensors)")
     desc, km, o, dt, tdt, V = _spectrum(tok, k, stride, destchar, both_strands, normalize, form, chars.numel())
-    if validate and B > 0:
-        bad = ctypes.c_int64(-1)
-        with capi.launching(chars.device) as stream:
-            capi.check(_lib.bsq_validate_packed_device(offsets.data_ptr(), B, (_SPECTRUM_MAX_WINDOWS - 1) * km.stride + km.k, 0, 0, chars.numel(),
-                                                       ctypes.byref(bad), stream))
-    out = torch.empty((B, V), dtype=tdt, device=chars.device)
-    if B > 0:
-        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
-        with capi.launching(src.device) as stream:
-            capi.check(_lib.bsq_kmer_spectrum_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, ctypes.byref(km), ctypes.byref(o), dt,
-                                                     out.data_ptr(), stream))
-    return out
+    max_len = (_SPECTRUM_MAX_WINDOWS - 1) * km.stride + km.k if validate else None
+    return capi._row_table_packed(chars, offsets, B, V, tdt, max_len, lambda src, out, stream: _lib.bsq_kmer_spectrum_device(
+        ctypes.byref(desc), src, offsets.data_ptr(), B, ctypes.byref(km), ctypes.byref(o), dt, out, stream))
 
 
 __all__ = ["kmer_tokenize_packed", "kmer_tokenize_host", "kmer_vocab_size", "kmer_special_ids", "kmer_count", "kmer_padlen",

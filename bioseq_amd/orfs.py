@@ -142,11 +142,10 @@ def orfs_packed(chars, offsets, *, index=None, frame="six", table=1, unknown="X"
 
 
 def _host_batch(chars, offsets):
-    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8).ravel())
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).ravel())
+    ch, offs = capi.host_batch(chars, offsets)
     if offs.size < 1:
         raise ValueError("offsets must hold at least one entry")
-    return (ch if ch.size else np.zeros(16, dtype=np.uint8)), offs
+    return ch, offs
 
 
 def find_orfs_host(chars, offsets, *, min_len=30, stop="*", start=None, max_orfs=None):

@@ -128,17 +128,15 @@ def pack_tokenize_host(tok, chars, offsets, padlen, destchar="q", *, mode="nextf
     """The library's CPU twin of `pack_tokenize_packed` on numpy arrays: the same named tuple, of numpy arrays and Python ints."""
     desc, code, padlen, rows = _args(tok, padlen, mode, rows)
     dt, _ = capi.dtype_of(destchar)
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = _host_offsets(offsets)
+    chars, offsets = capi.host_batch(chars, _host_offsets(offsets))
     B = offsets.size - 1
     starts, n_rows, n_placed = pack_plan_host(tok, offsets, padlen, mode, rows)
     R = n_rows if rows is None else rows
     tokens = np.empty((R, padlen), dtype=_NUMPY[dt])
     seg = np.empty((R, padlen), dtype=np.int32) if segment_ids else None
     pos = np.empty((R, padlen), dtype=np.int32) if position_ids else None
-    keep = chars if chars.size else np.zeros(16, np.uint8)
     if R > 0:
-        capi.check(_lib.bsq_pack_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, starts.ctypes.data, R, padlen, dt,
+        capi.check(_lib.bsq_pack_tokenize_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, starts.ctypes.data, R, padlen, dt,
                                                tokens.ctypes.data, seg.ctypes.data if segment_ids else None,
                                                pos.ctypes.data if position_ids else None))
     if rows is None:
@@ -152,8 +150,7 @@ def pack_mlm_tokenize_host(tok, chars, offsets, padlen, destchar="q", *, mode="n
     desc, code, padlen, rows = _args(tok, padlen, mode, rows)
     m = _mlm_params(frac, mask_prob, random_prob, tok.alphabet_size() if mask_token is None else mask_token, ignore_index, seed, first_row)
     (dt, _), (ldt, _) = capi.dtype_of(destchar), capi.dtype_of(label_dtype)
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = _host_offsets(offsets)
+    chars, offsets = capi.host_batch(chars, _host_offsets(offsets))
     B = offsets.size - 1
     starts, n_rows, n_placed = pack_plan_host(tok, offsets, padlen, mode, rows)
     R = n_rows if rows is None else rows
@@ -163,9 +160,8 @@ def pack_mlm_tokenize_host(tok, chars, offsets, padlen, destchar="q", *, mode="n
     labels = np.full((R, padlen), np.int64(ignore_index)).astype(_NUMPY[ldt])
     seg = np.zeros((R, padlen), dtype=np.int32) if segment_ids else None
     pos = np.zeros((R, padlen), dtype=np.int32) if position_ids else None
-    keep = chars if chars.size else np.zeros(16, np.uint8)
     if R > 0 and B > 0:
-        capi.check(_lib.bsq_pack_mlm_tokenize_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, starts.ctypes.data, R, padlen,
+        capi.check(_lib.bsq_pack_mlm_tokenize_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, starts.ctypes.data, R, padlen,
                                                    ctypes.byref(m), dt, inputs.ctypes.data, ldt, labels.ctypes.data,
                                                    seg.ctypes.data if segment_ids else None, pos.ctypes.data if position_ids else None))
     if rows is None:

@@ -32,11 +32,6 @@ _MAX_WINDOWS = 1 << 30  # (include/bsq.h, "MinHash sketch": a row sketches its f
 _NUMPY = {capi.I32: np.int32, capi.U64: np.uint64}
 
 
-def _strands(desc):
-    """Whether the alphabet has strands as the sketch reads them: four classes, A, C, G, T = 0, 1, 2, 3 (DNA, DNA4)."""
-    return desc.nchars == 4 and [desc.lut[ord(c)] for c in "ACGT"] == [0, 1, 2, 3]
-
-
 def _minhash(tok, k, buckets, destchar, canonical, seed, form, total_chars=0):
     """(desc, bsq_minhash, dtype code, torch dtype) with the library's argument rules applied as ValueError (no device is touched)."""
     desc = capi.desc_of(tok)
@@ -45,13 +40,8 @@ def _minhash(tok, k, buckets, destchar, canonical, seed, form, total_chars=0):
         raise ValueError("k = %r with %d classes: k must lie in 1 .. 32 and nchars ** k within 2 ** 64" % (k, desc.nchars))
     if not 1 <= buckets <= 1 << 14:
         raise ValueError("buckets must lie in 1 .. 2 ** 14, got %r" % (buckets,))
-    try:
-        dt, tdt = capi.dtype_of(destchar)
-    except RuntimeError as e:
-        raise ValueError("bad destchar %r: %s" % (destchar, e)) from None
-    if dt not in (capi.I32, capi.U64):
-        raise ValueError("destchar %r: a sketch takes 'i' (int32) or 'q' (int64)" % (destchar,))
-    if canonical and not _strands(desc):
+    dt, tdt = capi.destchar_arg(destchar, (capi.I32, capi.U64), "a sketch takes 'i' (int32) or 'q' (int64)")
+    if canonical and not capi.has_strands(desc):
         raise ValueError("canonical needs an alphabet with strands: the four classes A, C, G, T = 0, 1, 2, 3 (DNA, DNA4), not %r" % (tok.key,))
     form = 0 if form is None else int(form)
     if form not in (0, 1, 2) or (form == 1 and buckets > 1024):
@@ -72,13 +62,11 @@ def minhash_host(tok, chars, offsets, k, buckets=1024, destchar="i", *, canonica
     """The library's CPU twin (`bsq_minhash_host`, the word, hash and element code of the kernels) on numpy arrays: a (B, buckets) matrix,
     int32 for 'i' and uint64 for 'q' (EMPTY = all bits set: -1 as a signed value)."""
     desc, m, dt, _ = _minhash(tok, k, buckets, destchar, canonical, seed, None)
-    chars = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    chars, offsets = capi.host_batch(chars, offsets)
     B = offsets.size - 1
     out = np.empty((B, m.buckets), dtype=_NUMPY[dt])
-    keep = chars if chars.size else np.zeros(16, np.uint8)
     if B > 0:
-        capi.check(_lib.bsq_minhash_host(ctypes.byref(desc), keep.ctypes.data, offsets.ctypes.data, B, ctypes.byref(m), dt, out.ctypes.data))
+        capi.check(_lib.bsq_minhash_host(ctypes.byref(desc), chars.ctypes.data, offsets.ctypes.data, B, ctypes.byref(m), dt, out.ctypes.data))
     return out
 
 
@@ -92,19 +80,10 @@ def minhash_packed(tok, chars, offsets, k, buckets=1024, destchar="i", *, canoni
     equal sketches.  seed: another hash family.  form: None = the library chooses from `chars.numel()` / B, 1 = a wave per row
     (buckets <= 1024), 2 = a workgroup per row.  validate: malformed offsets and a row of more than 2 ** 30 windows raise the library's
     errors instead of being clamped."""
-    import torch
     B = capi.packed_on_device(chars, offsets, "minhash_packed works on packed batches resident on the device (chars, offsets tensors)")
     desc, m, dt, tdt = _minhash(tok, k, buckets, destchar, canonical, seed, form, chars.numel())
-    if validate and B > 0:
-        bad = ctypes.c_int64(-1)
-        with capi.launching(chars.device) as stream:
-            capi.check(_lib.bsq_validate_packed_device(offsets.data_ptr(), B, _MAX_WINDOWS - 1 + m.k, 0, 0, chars.numel(), ctypes.byref(bad), stream))
-    out = torch.empty((B, m.buckets), dtype=tdt, device=chars.device)
-    if B > 0:
-        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
-        with capi.launching(src.device) as stream:
-            capi.check(_lib.bsq_minhash_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, ctypes.byref(m), dt, out.data_ptr(), stream))
-    return out
+    return capi._row_table_packed(chars, offsets, B, m.buckets, tdt, _MAX_WINDOWS - 1 + m.k if validate else None, lambda src, out, stream:
+                                  _lib.bsq_minhash_device(ctypes.byref(desc), src, offsets.data_ptr(), B, ctypes.byref(m), dt, out, stream))
 
 
 def _pair_shape(a, b):

@@ -206,8 +206,7 @@ def translate_host(chars, offsets, *, index=None, frame=0, table=1, unknown="X",
     kernels compile): (chars uint8[total], offsets int64[rows + 1]).  validate=False: a bad index or frame code gives an empty row
     instead of IndexError, and a `capacity` too small cuts the batch instead of raising."""
     t, rows = _rule(frame, table, unknown, stop)
-    ch = np.ascontiguousarray(np.asarray(chars, dtype=np.uint8).ravel())
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).ravel())
+    ch, offs = capi.host_batch(chars, offsets)
     n_store = offs.size - 1
     if n_store < 0:
         raise ValueError("offsets must hold at least one entry")
@@ -229,8 +228,6 @@ def translate_host(chars, offsets, *, index=None, frame=0, table=1, unknown="X",
     out = np.empty(max(capacity, 1), dtype=np.uint8)
     out_offs = np.empty(n_out + 1, dtype=np.int64)
     status = ctypes.c_int64(-1)
-    if not ch.size:
-        ch = np.zeros(16, dtype=np.uint8)
     capi.check(_lib.bsq_translate_packed_host(ch.ctypes.data, offs.ctypes.data, n_store, idx.ctypes.data if idx is not None else None,
                                               frames.ctypes.data if frames is not None and n else None, n, ctypes.byref(t),
                                               out.ctypes.data, capacity, out_offs.ctypes.data, ctypes.byref(status)))

@@ -213,6 +213,37 @@ def test_guard_bytes_offsets_not_at_zero_and_an_empty_batch(gpu, bsq):
         assert st in (capi.ERR_INVALID_ARG, capi.ERR_DTYPE) and bool((buf == 0xAB).all()), (k, dt)
 
 
+@pytest.mark.parametrize("k, form, kernel", [(1, 1, WAVE), (1, 2, BLOCK % 1024), (5, 0, BLOCK % 4096), (6, 0, BLOCK % 16384)])
+def test_row_store_paths_on_an_output_one_element_off(gpu, bsq, k, form, kernel):
+    """The shared row store (csrc/bsq_row_table.h, write_row) in every form: DNA5, V = 5 ** k (no multiple of 16 / sizeof(T)), into a
+    (5, V) block that starts one element behind a 16-byte boundary inside a guard-filled buffer, so that rows start on and off such a
+    boundary (16-byte stores and the tail of V % (16 / sizeof(T)) elements; element stores) -- five rows: a wave workgroup's four and one
+    in a second, partly filled one; lengths on the first window, a lane's run of 16 windows, a wave's sweep step and a workgroup's.
+    Bit-exact against the library's CPU twin."""
+    import torch
+    from bioseq_amd import capi, kmers
+    L, tok = capi.load(), _tok(bsq, "DNA5")
+    d, km, V = capi.desc_of(tok), capi.Kmer(k, 1), 5 ** k
+    rng = np.random.default_rng(50 + k)
+    guard = 256
+    for lens in ([0, k - 1, k, k + 15, k + 16], [64 * 16 + k, 256 * 16 + k, 0, k + 15, k]):
+        chars, offs = _batch(rng, "DNA5", lens)
+        dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+        for dc, dt in (("i", I32), ("d", F64)):
+            norm = int(dc == "d")
+            assert kmers.kmer_spectrum_kernel_name(tok, k, 5, dc, normalize=norm, form=form or None, total_chars=chars.size) == kernel
+            exp = kmers.kmer_spectrum_host(tok, chars, offs, k, dc, normalize=bool(norm))
+            skew, n = exp.itemsize, exp.nbytes
+            buf = torch.full((n + 2 * guard + skew,), 0xAB, dtype=torch.uint8, device=gpu)
+            assert (buf.data_ptr() + guard) % 16 == 0
+            o = capi.KmerSpectrum(0, norm, form, 0, chars.size)
+            capi.check(L.bsq_kmer_spectrum_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), 5, ctypes.byref(km), ctypes.byref(o), dt,
+                                                  buf.data_ptr() + guard + skew, ctypes.c_void_p(capi.raw_stream(gpu))))
+            raw = buf.cpu().numpy()
+            assert (raw[:guard + skew] == 0xAB).all() and (raw[guard + skew + n:] == 0xAB).all(), "a guard byte of out was overwritten"
+            assert raw[guard + skew:guard + skew + n].tobytes() == exp.tobytes(), (k, form, dc, lens)
+
+
 def test_bincount_of_the_kmer_ids_is_the_count_spectrum(gpu, bsq):
     """An independent device path: per row, torch.bincount of the ids < V of kmer_tokenize_packed at the same k and stride."""
     import torch

@@ -212,6 +212,36 @@ def test_write_once_guards_and_a_sub_batch(gpu, bsq):
         assert st in (capi.ERR_INVALID_ARG, capi.ERR_DTYPE) and bool((buf == 0x5A).all())
 
 
+@pytest.mark.parametrize("S, form, kernel", [(5, 1, WAVE), (5, 2, BLOCK % 1024), (4095, 0, BLOCK % 4096), (16383, 0, BLOCK % 16384)])
+def test_row_store_paths_on_an_output_one_element_off(gpu, bsq, S, form, kernel):
+    """The shared row store (csrc/bsq_row_table.h, write_row) in every form: S no multiple of 16 / sizeof(T), into a (5, S) block that
+    starts one element behind a 16-byte boundary inside a guard-filled buffer, so that rows start on and off such a boundary (16-byte
+    stores and the tail of S % (16 / sizeof(T)) elements; element stores) -- five rows: a wave workgroup's four and one in a second,
+    partly filled one; lengths on the first window, a lane's run of 16 windows, a wave's sweep step and a workgroup's.  Bit-exact
+    against the library's CPU twin."""
+    import torch
+    from bioseq_amd import capi, sketch
+    L, tok, k = capi.load(), _tok(bsq, "DNA4"), 21
+    d = capi.desc_of(tok)
+    rng = np.random.default_rng(50 + S)
+    guard = 256
+    for lens in ([0, k - 1, k, k + 15, k + 16], [64 * 16 + k, 256 * 16 + k, 0, k + 15, k]):
+        chars, offs = _batch(rng, "DNA4", lens)
+        dch, dof = _dev(chars, gpu), _dev(offs, gpu)
+        for dc, dt in (("i", I32), ("q", U64)):
+            assert sketch.minhash_kernel_name(tok, k, 5, S, dc, canonical=True, form=form or None, total_chars=chars.size) == kernel
+            exp = sketch.minhash_host(tok, chars, offs, k, S, dc, canonical=True, seed=9)
+            skew, n = exp.itemsize, exp.nbytes
+            buf = torch.full((n + 2 * guard + skew,), 0x5A, dtype=torch.uint8, device=gpu)
+            assert (buf.data_ptr() + guard) % 16 == 0
+            m = capi.MinHash(k, S, 1, form, 9, chars.size, 0)
+            capi.check(L.bsq_minhash_device(ctypes.byref(d), dch.data_ptr(), dof.data_ptr(), 5, ctypes.byref(m), dt, buf.data_ptr() + guard + skew,
+                                            ctypes.c_void_p(capi.raw_stream(gpu))))
+            raw = buf.cpu().numpy()
+            assert (raw[:guard + skew] == 0x5A).all() and (raw[guard + skew + n:] == 0x5A).all(), "a guard byte of out was overwritten"
+            assert raw[guard + skew:guard + skew + n].tobytes() == exp.tobytes(), (S, form, dc, lens)
+
+
 def test_python_surface_and_refusals(gpu, bsq):
     import torch
     from bioseq_amd import sketch
