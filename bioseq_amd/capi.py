@@ -75,6 +75,11 @@ class MinHash(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("total_chars", ctypes.c_int64), ("reserved", ctypes.c_int32)]
 
 
+class SketchPairs(ctypes.Structure):
+    """struct bsq_sketch_pairs"""
+    _fields_ = [("min_match", ctypes.c_int32), ("jaccard_q16", ctypes.c_int32), ("upper", ctypes.c_int32), ("segments", ctypes.c_int32)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -197,6 +202,11 @@ def load():
         "bsq_minhash_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(MinHash), i64, c_int]),
         "bsq_sketch_compare_device": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp, vp]),
         "bsq_sketch_compare_host": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp]),
+        "bsq_sketch_pairs_segments": (i32, [i64, i64, i32]),
+        "bsq_sketch_pairs_count_device": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, vp, vp]),
+        "bsq_sketch_pairs_emit_device": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, i64, vp, vp, vp, vp, vp]),
+        "bsq_sketch_pairs_host": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, i64, vp, vp, vp, vp]),
+        "bsq_sketch_pairs_kernel_name": (ctypes.c_char_p, [i64, i64, i32]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

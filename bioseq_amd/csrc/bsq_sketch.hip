@@ -16,6 +16,8 @@
 //            through LDS in chunks of 32 buckets (bucket-major, so that a thread's four rows of a side are one 16-byte read), a thread
 //            keeps a 4 x 4 register tile of equal-bucket counts and one of both-EMPTY counts (from a 32-bit EMPTY mask per row and chunk:
 //            a popcount per pair and chunk), which give `match` and `either`.  An input element is read once per tile pair.
+// k_sketch_pairs<T, EMIT>   the thresholded pair list (include/bsq.h, "sketch pairs"): the same tile arithmetic (cmp_tile) by a workgroup per
+//            (strip of 64 rows, segment of j tiles), with a ragged, ordered output; its comment stands in front of it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -25,17 +27,19 @@
 #include "bsq_device.h"
 #include "bsq_internal.h"
 #include "bsq_kmer_lane.h"
+#include "bsq_ragged_out.h"
 #include "bsq_row_table.h"
 #include "bsq_sketch_dev.h"
 
 namespace {
 
-using bsq_dev::kThreads;
+// (kThreads = 256 is bsq_ragged_out.h's, which also has a Form of its own: the row table's is named in full)
 using bsq_kmerd::byte_of;
-using bsq_rowtab::Form;
 using bsq_rowtab::load16;
 using bsq_sketchd::Geometry;
 using bsq_sketchd::kEmpty;
+using bsq_sketchd::PairsRule;
+static_assert(kThreads == bsq_dev::kThreads, "one workgroup size");
 
 constexpr int kRun = 16;  // windows of a lane's run
 struct SketchParams {
@@ -144,17 +148,16 @@ constexpr int kChunkS = 32;                   // buckets staged at a time
 constexpr int kPitch = kTile + 4;
 __device__ __forceinline__ int cmp_slot(int row) { return (row & 15) * 4 + (row >> 4); }
 
+// The tile (i0, j0) by the whole workgroup, what k_sketch_compare and k_sketch_pairs share: the staging and the 4 x 4 register tile.
+// eq counts the buckets in which the two rows hold the same 32 bits, both the two rows' EMPTY ones among them (and the padding, which
+// is EMPTY on both sides); both counts those: match = eq - both, either = buckets staged - both.  Returns the buckets staged.  Thread
+// (tx, ty) holds rows i0 + ty + 16 r against rows j0 + tx + 16 c; the last barrier of the call stands behind every read of the stage.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void k_sketch_compare(const T *a, int64_t Ba, const T *b, int64_t Bb, int32_t S, uint32_t tiles_j,
-                                                             int32_t *match, int32_t *either) {
+__device__ __forceinline__ int32_t cmp_tile(const T *a, int64_t Ba, const T *b, int64_t Bb, int32_t S, int64_t i0, int64_t j0,
+                                            int32_t (&eq)[4][4], int32_t (&both)[4][4]) {
     __shared__ __align__(16) uint32_t s_a[kChunkS * kPitch], s_b[kChunkS * kPitch];
     __shared__ uint32_t s_ea[kTile], s_eb[kTile];  // bit t: the row's bucket t of the chunk is EMPTY
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const uint32_t ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int64_t i0 = static_cast<int64_t>(ti) * kTile, j0 = static_cast<int64_t>(tj) * kTile;
-    // eq counts the buckets in which the two rows hold the same 32 bits, both the two rows' EMPTY ones among them (and the padding, which
-    // is EMPTY on both sides); both counts those: match = eq - both, either = buckets staged - both
-    int32_t eq[4][4], both[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -201,6 +204,17 @@ __global__ __launch_bounds__(kThreads) void k_sketch_compare(const T *a, int64_t
         }
         __syncthreads();
     }
+    return staged;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_sketch_compare(const T *a, int64_t Ba, const T *b, int64_t Bb, int32_t S, uint32_t tiles_j,
+                                                             int32_t *match, int32_t *either) {
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const uint32_t ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
+    const int64_t i0 = static_cast<int64_t>(ti) * kTile, j0 = static_cast<int64_t>(tj) * kTile;
+    int32_t eq[4][4], both[4][4];
+    const int32_t staged = cmp_tile(a, Ba, b, Bb, S, i0, j0, eq, both);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t i = i0 + ty + 16 * r;
@@ -215,14 +229,133 @@ __global__ __launch_bounds__(kThreads) void k_sketch_compare(const T *a, int64_t
     }
 }
 
+// ---- the pair list (include/bsq.h, "sketch pairs") ----
+// k_sketch_pairs<T, EMIT>   a workgroup per (strip of 64 rows of a, segment of consecutive j tiles): it walks its tiles in ascending j
+//            with cmp_tile and, after each, ORs its 16 pass flags into a 64-bit hit mask per row in LDS (two words, LDS atomics).  The rank
+//            of column c inside its row is the row's running cursor (LDS) + popc(mask below c): no global atomic decides a rank, so the
+//            order is (i, j).  EMIT = false: the per-(row, segment) counts -> seg_offsets[1 + row * nseg + segment].  EMIT = true: the
+//            cursor starts at seg_offsets[row * nseg + segment], the scanned start, and every passing pair of rank < max_pairs is stored.
+//            upper: tiles left of the strip's diagonal tile are skipped, the diagonal tile keeps j > i.
+// The counts of the n = Ba * nseg (row, segment) entries become starts in place by the scaffold of bsq_ragged_out.h, whose offsets array
+// seg_offsets is (entry k + 1: the length of k, then its end), so that entry row * nseg + segment is where that (row, segment) starts and
+// the (i, segment, j) order is the (i, j) order:
+// k_sketch_pairs_sums       the sums of every 64 counts -> the stream's scratch (lengths_step);
+// k_sketch_pairs_scan       beyond 2^20 entries: those sums scanned once by one workgroup (scan_inclusive_block);
+// k_sketch_pairs_place<SCANNED>   counts -> ends in place, a workgroup per 64 entries (place_offsets), seg_offsets[0] <- 0, and
+//            pair_offsets[i] <- entry i * nseg, the one in front of row i (i <= Ba: the last is the total), by the thread that wrote it.
+// One workgroup scanning all n entries (scan_inclusive_block on seg_offsets itself) took 360 us at n = 262 144, more than the count of
+// 4096 x 4096 x 128 itself (profiles/r20/sketch_pairs_lab.txt): hence the split.
+struct PairsOut {
+    int64_t *row, *col;
+    int32_t *match, *either;
+    int64_t max_pairs;
+};
+
+template <typename T, bool EMIT>
+__global__ __launch_bounds__(kThreads) void k_sketch_pairs(const T *a, int64_t Ba, const T *b, int64_t Bb, int32_t S, const PairsRule r,
+                                                           int64_t *seg_offsets, const PairsOut out) {
+    __shared__ uint32_t s_hit[kTile][2];  // bit c of a row: column j0 + c of the tile passes
+    __shared__ int64_t s_cur[kTile];      // the pairs of a row in front of the tile: from the segment's first tile (count), of all (emit)
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const uint32_t nseg = static_cast<uint32_t>(r.nseg), strip = blockIdx.x / nseg, seg = blockIdx.x - strip * nseg;
+    const int64_t i0 = static_cast<int64_t>(strip) * kTile;
+    int64_t tj = bsq_sketchd::segment_first_tile(seg, nseg, r.tiles_j);
+    const int64_t tj_end = bsq_sketchd::segment_first_tile(seg + 1, nseg, r.tiles_j);
+    if (r.upper && tj < strip) tj = strip;
+    if constexpr (EMIT) {  // ranks grow with (row, segment): where the first row's start is cut, every pair of the workgroup is (uniform)
+        if (seg_offsets[i0 * nseg + seg] >= out.max_pairs) return;
+    }
+    if (tid < kTile) {  // (row tid is this thread's from here to the end: no barrier is needed for s_cur and the clearing of s_hit)
+        int64_t start = 0;
+        if constexpr (EMIT) {
+            if (i0 + tid < Ba) start = seg_offsets[(i0 + tid) * nseg + seg];
+        }
+        s_cur[tid] = start;
+        s_hit[tid][0] = s_hit[tid][1] = 0;
+    }
+    for (; tj < tj_end; ++tj) {
+        const int64_t j0 = tj * kTile;
+        int32_t eq[4][4], both[4][4];
+        const int32_t staged = cmp_tile(a, Ba, b, Bb, S, i0, j0, eq, both);  // (its barriers: s_cur and the cleared s_hit are visible)
+        const bool diagonal = r.upper && tj == strip;
+        uint32_t flags = 0;  // bit 4 r + c
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int64_t i = i0 + ty + 16 * rr;
+            uint32_t lo = 0, hi = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t j = j0 + tx + 16 * c;
+                const bool hit = i < Ba && j < Bb && (!diagonal || j > i) &&
+                                 bsq_sketchd::pair_passes(eq[rr][c] - both[rr][c], staged - both[rr][c], r.min_match, r.jaccard_q16);
+                flags |= static_cast<uint32_t>(hit) << (4 * rr + c);
+                (c < 2 ? lo : hi) |= static_cast<uint32_t>(hit) << (tx + 16 * (c & 1));
+            }
+            if (lo) atomicOr(&s_hit[ty + 16 * rr][0], lo);
+            if (hi) atomicOr(&s_hit[ty + 16 * rr][1], hi);
+        }
+        __syncthreads();
+        if constexpr (EMIT) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                if ((flags >> (4 * rr)) & 15u) {
+                    const int row = ty + 16 * rr;
+                    const uint64_t mask = s_hit[row][0] | static_cast<uint64_t>(s_hit[row][1]) << 32;
+                    const int64_t first = s_cur[row];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int64_t at = first + __popcll(mask & ((uint64_t(1) << (tx + 16 * c)) - 1));
+                        // (unsigned: a start that is not the count call's -- a negative one -- writes nothing either)
+                        if (((flags >> (4 * rr + c)) & 1u) && static_cast<uint64_t>(at) < static_cast<uint64_t>(out.max_pairs)) {
+                            out.row[at] = i0 + row;
+                            out.col[at] = j0 + tx + 16 * c;
+                            out.match[at] = eq[rr][c] - both[rr][c];
+                            if (out.either) out.either[at] = staged - both[rr][c];
+                        }
+                    }
+                }
+            }
+            __syncthreads();  // (every read of s_cur and s_hit is done)
+        }
+        if (tid < kTile) {
+            s_cur[tid] += __popc(s_hit[tid][0]) + __popc(s_hit[tid][1]);
+            s_hit[tid][0] = s_hit[tid][1] = 0;
+        }
+    }
+    if constexpr (!EMIT) {
+        if (tid < kTile && i0 + tid < Ba) seg_offsets[1 + (i0 + tid) * nseg + seg] = s_cur[tid];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_sketch_pairs_sums(int64_t n, int64_t *seg_offsets, int64_t *sums) {
+    const int64_t k = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    lengths_step(k, n, seg_offsets, sums, [=](int64_t e) { return seg_offsets[e + 1]; });  // (writes the count back where it read it)
+}
+
+__global__ __launch_bounds__(1024) void k_sketch_pairs_scan(int64_t *sums, int64_t groups) { scan_inclusive_block(sums, groups); }
+
+template <bool SCANNED>
+__global__ __launch_bounds__(kThreads) void k_sketch_pairs_place(int64_t n, int64_t nseg, int64_t *seg_offsets, const int64_t *sums,
+                                                                 int64_t *pair_offsets) {
+    __shared__ int64_t s_part[kThreads / 64];
+    __shared__ int64_t s_d0[kPlaceS];
+    place_offsets<SCANNED>(n, seg_offsets, sums, s_part, s_d0);
+    const int64_t k = static_cast<int64_t>(blockIdx.x) * kPlaceS + threadIdx.x;
+    if (threadIdx.x < kPlaceS && k < n) {  // (the thread that wrote the end of entry k; nobody reads entry 0 in this launch)
+        if (k == 0) seg_offsets[0] = 0;
+        if (k % nseg == 0) pair_offsets[k / nseg] = s_d0[threadIdx.x];
+        if (k == n - 1) pair_offsets[n / nseg] = seg_offsets[n];
+    }
+}
+
 template <typename T, int MODE>
-void launch_minhash(Form form, int64_t B, hipStream_t s, const SketchParams &p) {
+void launch_minhash(bsq_rowtab::Form form, int64_t B, hipStream_t s, const SketchParams &p) {
     bsq_rowtab::launch(form, B, s, p, k_minhash_wave<T, MODE>, k_minhash_block<T, 1024, MODE>, k_minhash_block<T, 4096, MODE>,
                        k_minhash_block<T, 16384, MODE>);
 }
 
 template <typename T>
-void launch_minhash(Form form, int64_t B, hipStream_t s, const SketchParams &p, int mode) {
+void launch_minhash(bsq_rowtab::Form form, int64_t B, hipStream_t s, const SketchParams &p, int mode) {
     if (mode == 0) launch_minhash<T, 0>(form, B, s, p);
     else if (mode == 1) launch_minhash<T, 1>(form, B, s, p);
     else launch_minhash<T, 2>(form, B, s, p);
@@ -257,7 +390,7 @@ bsq_status bsq_minhash_device(const bsq_desc *d, const uint8_t *chars, const int
     p.k = g.k;
     p.A = g.A;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const Form form = bsq_sketchd::form_of(g.S, B, m->total_chars, m->form);
+    const bsq_rowtab::Form form = bsq_sketchd::form_of(g.S, B, m->total_chars, m->form);
     const int mode = g.canonical ? 2 : (g.A == 4 ? 1 : 0);
     if (t == BSQ_I32) launch_minhash<int32_t>(form, B, s, p, mode);
     else launch_minhash<uint64_t>(form, B, s, p, mode);
@@ -280,6 +413,70 @@ bsq_status bsq_sketch_compare_device(const void *a, int64_t Ba, const void *b, i
         hipLaunchKernelGGL((k_sketch_compare<uint64_t>), grid, block, 0, s, static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb,
                            static_cast<int32_t>(S), static_cast<uint32_t>(tiles_j), match, either_or_null);
     return bsq_internal::check_launch("k_sketch_compare");
+}
+
+const char *bsq_sketch_pairs_kernel_name(int64_t Ba, int64_t Bb, int32_t segments) {
+    const int32_t nseg = bsq_sketch_pairs_segments(Ba, Bb, segments);
+    if (nseg == 0 || Ba > bsq_sketchd::kMaxRows || Bb > bsq_sketchd::kMaxRows) return "";
+    if (Ba == 0 || Bb == 0) return "hipMemsetAsync";
+    return form_of(Ba * nseg) != Form::ScanPlace ? "k_sketch_pairs<count>+k_sketch_pairs_sums+k_sketch_pairs_place;k_sketch_pairs<emit>"
+                                                 : "k_sketch_pairs<count>+k_sketch_pairs_sums+k_sketch_pairs_scan+k_sketch_pairs_place;k_sketch_pairs<emit>";
+}
+
+bsq_status bsq_sketch_pairs_count_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                         int64_t *seg_offsets, int64_t *pair_offsets, void *hip_stream) {
+    const char *why = "";
+    PairsRule r;
+    const bsq_status st = bsq_sketchd::check_pairs(a, Ba, b, Bb, S, t, rule, &r, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (!seg_offsets || !pair_offsets) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "seg_offsets or pair_offsets is null");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (Ba == 0 || Bb == 0) {  // (one segment: Ba + 1 entries each)
+        hipError_t e = hipMemsetAsync(pair_offsets, 0, static_cast<size_t>(Ba + 1) * sizeof(int64_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(seg_offsets, 0, static_cast<size_t>(Ba + 1) * sizeof(int64_t), s);
+        return e != hipSuccess ? bsq_internal::set_hip_error("hipMemsetAsync(sketch pairs)", e) : BSQ_OK;
+    }
+    const dim3 grid(static_cast<unsigned>(r.strips * r.nseg)), block(kThreads);  // (at most tiles_i * tiles_j: check_compare)
+    const PairsOut none{nullptr, nullptr, nullptr, nullptr, 0};
+    const int64_t n = Ba * r.nseg, nseg = r.nseg;  // the (row, segment) entries
+    return with_wave_sums(n, s, "k_sketch_pairs<count> / k_sketch_pairs_sums / k_sketch_pairs_place", [&](int64_t *sums) {
+        if (t == BSQ_I32)
+            hipLaunchKernelGGL((k_sketch_pairs<int32_t, false>), grid, block, 0, s, static_cast<const int32_t *>(a), Ba, static_cast<const int32_t *>(b),
+                               Bb, static_cast<int32_t>(S), r, seg_offsets, none);
+        else
+            hipLaunchKernelGGL((k_sketch_pairs<uint64_t, false>), grid, block, 0, s, static_cast<const uint64_t *>(a), Ba,
+                               static_cast<const uint64_t *>(b), Bb, static_cast<int32_t>(S), r, seg_offsets, none);
+        hipLaunchKernelGGL(k_sketch_pairs_sums, lengths_grid(n), block, 0, s, n, seg_offsets, sums);
+        if (form_of(n) != Form::ScanPlace) {
+            hipLaunchKernelGGL(k_sketch_pairs_place<false>, place_grid(n), block, 0, s, n, nseg, seg_offsets, sums, pair_offsets);
+        } else {
+            hipLaunchKernelGGL(k_sketch_pairs_scan, dim3(1), dim3(1024), 0, s, sums, (n + kPlaceS - 1) / kPlaceS);
+            hipLaunchKernelGGL(k_sketch_pairs_place<true>, place_grid(n), block, 0, s, n, nseg, seg_offsets, sums, pair_offsets);
+        }
+    });
+}
+
+bsq_status bsq_sketch_pairs_emit_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                        const int64_t *seg_offsets, int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match,
+                                        int32_t *either_or_null, void *hip_stream) {
+    const char *why = "";
+    PairsRule r;
+    const bsq_status st = bsq_sketchd::check_pairs(a, Ba, b, Bb, S, t, rule, &r, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (!seg_offsets || max_pairs < 0) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "seg_offsets is null or max_pairs negative");
+    if (max_pairs > 0 && (!row || !col || !match)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "an output array is null");
+    if (Ba == 0 || Bb == 0 || max_pairs == 0) return BSQ_OK;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const dim3 grid(static_cast<unsigned>(r.strips * r.nseg)), block(kThreads);
+    const PairsOut out{row, col, match, either_or_null, max_pairs};
+    int64_t *segs = const_cast<int64_t *>(seg_offsets);  // (the emit instantiation only reads them)
+    if (t == BSQ_I32)
+        hipLaunchKernelGGL((k_sketch_pairs<int32_t, true>), grid, block, 0, s, static_cast<const int32_t *>(a), Ba, static_cast<const int32_t *>(b), Bb,
+                           static_cast<int32_t>(S), r, segs, out);
+    else
+        hipLaunchKernelGGL((k_sketch_pairs<uint64_t, true>), grid, block, 0, s, static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb,
+                           static_cast<int32_t>(S), r, segs, out);
+    return bsq_internal::check_launch("k_sketch_pairs<emit>");
 }
 
 }  // extern "C"

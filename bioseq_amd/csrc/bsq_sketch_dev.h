@@ -1,7 +1,8 @@
-// MinHash sketches of a packed batch and the all-pairs comparison of sketches (include/bsq.h, "MinHash sketch"): what the kernels of
-// bsq_sketch.hip and the CPU twins of bsq_sketch_host.cpp share -- the limits, the wide geometry of a (tokenizer, bsq_minhash) pair, the
-// reverse complement of a 64-bit word, the hash, the bucket and value of a hash, the value of one output element, the choice of kernel
-// and the argument rules.  Plain C++ over <cstdint> and bsq.h alone: the host twins compile without the HIP headers.
+// MinHash sketches of a packed batch, the all-pairs comparison of sketches and the thresholded pair list (include/bsq.h, "MinHash
+// sketch", "sketch pairs"): what the kernels of bsq_sketch.hip and the CPU twins of bsq_sketch_host.cpp share -- the limits, the wide
+// geometry of a (tokenizer, bsq_minhash) pair, the reverse complement of a 64-bit word, the hash, the bucket and value of a hash, the
+// value of one output element, the choice of kernel, the selection of a pair, the segments of a strip and the argument rules.  Plain C++
+// over <cstdint> and bsq.h alone: the host twins compile without the HIP headers.
 #pragma once
 #include <cstdint>
 
@@ -149,6 +150,66 @@ inline bsq_status check_compare(const void *a, int64_t Ba, const void *b, int64_
     if (Ba > kMaxRows || Bb > kMaxRows || ((Ba + kCmpTile - 1) / kCmpTile) * ((Bb + kCmpTile - 1) / kCmpTile) > kMaxRows)
         return *why = "too many rows: the 64 x 64 tiles of the (Ba, Bb) output must number at most 2^31 - 1", BSQ_ERR_INVALID_ARG;
     if (Ba > 0 && Bb > 0 && (!a || !b || !match)) return *why = "a, b or match is null", BSQ_ERR_INVALID_ARG;
+    return BSQ_OK;
+}
+
+// ---- sketch pairs (include/bsq.h, "sketch pairs"): the selection, the segments and the argument rules ----
+constexpr int32_t kMaxSegments = 64;  // segments of the j tiles a strip of 64 rows of `a` is cut into
+constexpr int32_t kQ16 = 65536;       // jaccard_q16 = 65536: match == either
+// Workgroups (strip, segment) a call aims for when the library chooses the segments.  k_sketch_pairs takes ~250 VGPRs and 18.5 KB of LDS:
+// two workgroups per CU, 512 on an MI355X at once, so 4096 is eight rounds of that.  scripts/sketch_pairs_lab.py on an MI355X, the count
+// call, cross, int32 (profiles/r20/sketch_pairs_lab.txt; us, * the choice):
+//     8192 x 8192 x 1024 (128 strips)   segments 1: 23110   2: 12053   4: 7012   8: 6934   16: 6721   32*: 6567   64: 6303
+//     4096 x 4096 x 128  (64 strips)    segments 1: 1259    2: 606     4: 307    8: 210    16: 212    32: 215     64*: 227
+//     262144 x 262144 x 128, upper (4096 strips)   segments 1*: 415 ms   2: 616 ms
+// Wide sketches would take still more workgroups and narrow ones fewer; either choice is within 8 % of the best of its row, and once
+// the strips alone reach the target a second segment costs half as much again.
+constexpr int64_t kPairsGroups = 4096;
+
+// pass(i, j): both products are at most 2^30, so the 32-bit arithmetic is exact
+BSQ_SKETCH_HD bool pair_passes(int32_t match, int32_t either, int32_t min_match, int32_t jaccard_q16) {
+    return match >= min_match && match * kQ16 >= jaccard_q16 * either;
+}
+
+// A checked bsq_sketch_pairs and the geometry of its call (made on the host)
+struct PairsRule {
+    int32_t min_match, jaccard_q16, upper;
+    int32_t nseg;      // segments of a strip: 1 .. min(64, tiles_j)
+    int64_t tiles_j;   // 64-row tiles of b
+    int64_t strips;    // 64-row strips of a
+};
+
+// the j tiles [first, last) of segment `seg` of `nseg`: consecutive, every segment at least one tile (nseg <= tiles_j)
+BSQ_SKETCH_HD int64_t segment_first_tile(int64_t seg, int64_t nseg, int64_t tiles_j) { return seg * tiles_j / nseg; }
+
+// segments of a call: `segments` > 0 forces min(segments, tiles_j); 0: enough that strips * nseg reaches kPairsGroups, 1 once the strips
+// alone do, never more than 64 or the number of j tiles.  An empty side gives 1.
+inline int32_t pairs_segments(int64_t Ba, int64_t Bb, int32_t segments) {
+    const int64_t strips = (Ba + kCmpTile - 1) / kCmpTile, tiles_j = (Bb + kCmpTile - 1) / kCmpTile;
+    if (strips == 0 || tiles_j == 0) return 1;
+    int64_t n = segments > 0 ? segments : (kPairsGroups + strips - 1) / strips;
+    if (n > kMaxSegments) n = kMaxSegments;
+    if (n > tiles_j) n = tiles_j;
+    return static_cast<int32_t>(n);
+}
+
+// The rules both calls and the CPU twin share: BSQ_OK and the checked rule, or a status and a reason.  Host only.
+inline bsq_status check_pairs(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                              PairsRule *r, const char **why) {
+    if (!rule) return *why = "the rule is null", BSQ_ERR_INVALID_ARG;
+    const bsq_status st = check_compare(a, Ba, b, Bb, S, t, &rule->min_match, why);  // (the outputs are the caller's to check)
+    if (st != BSQ_OK) return st;
+    if (rule->min_match < 0 || rule->min_match > S) return *why = "min_match must lie in 0 .. S", BSQ_ERR_INVALID_ARG;
+    if (rule->jaccard_q16 < 0 || rule->jaccard_q16 > kQ16) return *why = "jaccard_q16 must lie in 0 .. 65536", BSQ_ERR_INVALID_ARG;
+    if ((rule->upper | 1) != 1) return *why = "upper must be 0 / 1", BSQ_ERR_INVALID_ARG;
+    if (rule->upper && Ba != Bb) return *why = "upper lists the pairs i < j of ONE matrix: Ba must equal Bb", BSQ_ERR_INVALID_ARG;
+    if (rule->segments < 0 || rule->segments > kMaxSegments) return *why = "segments must lie in 0 .. 64", BSQ_ERR_INVALID_ARG;
+    r->min_match = rule->min_match;
+    r->jaccard_q16 = rule->jaccard_q16;
+    r->upper = rule->upper;
+    r->nseg = pairs_segments(Ba, Bb, rule->segments);
+    r->tiles_j = (Bb + kCmpTile - 1) / kCmpTile;
+    r->strips = (Ba + kCmpTile - 1) / kCmpTile;
     return BSQ_OK;
 }
 

@@ -1,6 +1,7 @@
-// MinHash sketches and their comparison, the CPU side (include/bsq.h, "MinHash sketch"): the twins bsq_minhash_host and
-// bsq_sketch_compare_host -- plain loops over the rule text of bsq_sketch_dev.h, the text the kernels of bsq_sketch.hip compile.  Plain
-// C++: neither this file nor that header needs the HIP headers.
+// MinHash sketches, their comparison and the thresholded pair list, the CPU side (include/bsq.h, "MinHash sketch", "sketch pairs"): the
+// twins bsq_minhash_host, bsq_sketch_compare_host and bsq_sketch_pairs_host -- plain loops over the rule text of bsq_sketch_dev.h, the
+// text the kernels of bsq_sketch.hip compile -- and the host-only bsq_sketch_pairs_segments.  Plain C++: neither this file nor that
+// header needs the HIP headers.
 #include <cstdint>
 #include <vector>
 
@@ -45,6 +46,33 @@ void compare_rows(const T *a, int64_t Ba, const T *b, int64_t Bb, int64_t S, int
         }
 }
 
+// the pairs that pass, in (i, j) order: their number per row -> pair_offsets (a CSR), those of rank < max_pairs -> the arrays
+template <typename T>
+void pair_rows(const T *a, int64_t Ba, const T *b, int64_t Bb, int64_t S, const bsq_sketchd::PairsRule &r, int64_t *pair_offsets,
+               int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match, int32_t *either) {
+    int64_t rank = 0;
+    for (int64_t i = 0; i < Ba; ++i) {
+        pair_offsets[i] = rank;
+        for (int64_t j = r.upper ? i + 1 : 0; j < Bb; ++j) {
+            int32_t m = 0, e = 0;
+            for (int64_t t = 0; t < S; ++t) {
+                const uint32_t x = static_cast<uint32_t>(a[i * S + t]), y = static_cast<uint32_t>(b[j * S + t]);
+                m += x == y && x != kEmpty;
+                e += x != kEmpty || y != kEmpty;
+            }
+            if (!bsq_sketchd::pair_passes(m, e, r.min_match, r.jaccard_q16)) continue;
+            if (rank < max_pairs) {
+                row[rank] = i;
+                col[rank] = j;
+                match[rank] = m;
+                if (either) either[rank] = e;
+            }
+            ++rank;
+        }
+    }
+    pair_offsets[Ba] = rank;
+}
+
 }  // namespace
 
 extern "C" {
@@ -67,6 +95,30 @@ bsq_status bsq_sketch_compare_host(const void *a, int64_t Ba, const void *b, int
     if (Ba == 0 || Bb == 0) return BSQ_OK;
     if (t == BSQ_I32) compare_rows(static_cast<const int32_t *>(a), Ba, static_cast<const int32_t *>(b), Bb, S, match, either_or_null);
     else compare_rows(static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb, S, match, either_or_null);
+    return BSQ_OK;
+}
+
+int32_t bsq_sketch_pairs_segments(int64_t Ba, int64_t Bb, int32_t segments) {
+    if (Ba < 0 || Bb < 0 || segments < 0 || segments > bsq_sketchd::kMaxSegments) return 0;
+    return bsq_sketchd::pairs_segments(Ba, Bb, segments);
+}
+
+bsq_status bsq_sketch_pairs_host(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                 int64_t *pair_offsets, int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match, int32_t *either_or_null) {
+    const char *why = "";
+    bsq_sketchd::PairsRule r;
+    const bsq_status st = bsq_sketchd::check_pairs(a, Ba, b, Bb, S, t, rule, &r, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (!pair_offsets || max_pairs < 0) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "pair_offsets is null or max_pairs negative");
+    if (max_pairs > 0 && (!row || !col || !match)) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "an output array is null");
+    if (Ba == 0 || Bb == 0) {
+        for (int64_t i = 0; i <= Ba; ++i) pair_offsets[i] = 0;
+        return BSQ_OK;
+    }
+    if (t == BSQ_I32)
+        pair_rows(static_cast<const int32_t *>(a), Ba, static_cast<const int32_t *>(b), Bb, S, r, pair_offsets, max_pairs, row, col, match, either_or_null);
+    else
+        pair_rows(static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb, S, r, pair_offsets, max_pairs, row, col, match, either_or_null);
     return BSQ_OK;
 }
 

@@ -12,7 +12,13 @@ fraction J of their k-mers agree in about that fraction of their non-empty bucke
 * `sketch_compare`    `match` and `either` counts of every pair of rows of two sketch matrices, (Ba, Bb) int32, one launch -- no
                       `Ba * Bb * buckets` boolean tensor;
 * `sketch_compare_host`    its CPU twin;
-* `sketch_jaccard`    match / either as float32, 0 where either == 0.
+* `sketch_jaccard`    match / either as float32, 0 where either == 0;
+* `sketch_pairs`      the pairs of rows at least `min_jaccard` similar as an ordered list (row, col, match, either, pair_offsets) --
+                      the comparison's arithmetic with a ragged output, so a store of 262 144 sketches is searched against itself
+                      without the 550 GB its dense matrices would take (`bsq_sketch_pairs_count_device`, `bsq_sketch_pairs_emit_device`;
+                      include/bsq.h, "sketch pairs");
+* `sketch_pairs_host`, `sketch_pairs_kernel_name`    its CPU twin, its launches;
+* `sketch_duplicates`  (keep, first) from the pair list of a matrix with itself: every row with an earlier near-duplicate is dropped.
 
 The sketch of a sequence equals the bucket-wise UNSIGNED minimum of the sketches of pieces that together cover all its windows (EMPTY
 is the largest value), so sketches of longer sequences, or of sets of sequences, are merged without the characters.
@@ -145,4 +151,126 @@ def sketch_jaccard(a, b=None):
     return torch.where(e > 0, m.to(torch.float32) / e.clamp(min=1).to(torch.float32), torch.zeros((), dtype=torch.float32, device=m.device))
 
 
-__all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard"]
+_HOST_CODES = {np.dtype(np.int32): capi.I32, np.dtype(np.int64): capi.U64, np.dtype(np.uint64): capi.U64}
+
+
+def _pairs_rule(S, min_jaccard, min_match, max_pairs, segments, upper):
+    """(bsq_sketch_pairs, max_pairs or None) with the library's argument rules applied as ValueError (no device is touched)."""
+    if not 0.0 <= float(min_jaccard) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError("min_jaccard must lie in 0 .. 1, got %r" % (min_jaccard,))
+    if isinstance(min_match, bool) or int(min_match) != min_match or not 0 <= int(min_match) <= S:
+        raise ValueError("min_match must be an integer in 0 .. %d (the sketch width), got %r" % (S, min_match))
+    if max_pairs is not None and (int(max_pairs) != max_pairs or int(max_pairs) < 0):
+        raise ValueError("max_pairs must be None or an integer >= 0, got %r" % (max_pairs,))
+    segments = 0 if segments is None else segments
+    if isinstance(segments, bool) or int(segments) != segments or not 0 <= int(segments) <= 64:
+        raise ValueError("segments must be None or an integer in 1 .. 64, got %r" % (segments,))
+    rule = capi.SketchPairs(int(min_match), int(float(min_jaccard) * 65536 + 0.5), int(upper), int(segments))
+    return rule, None if max_pairs is None else int(max_pairs)
+
+
+def sketch_pairs_host(a, b=None, *, min_jaccard=0.5, min_match=1, max_pairs=None, either=True):
+    """The library's CPU twin of `sketch_pairs` (`bsq_sketch_pairs_host`) on numpy matrices of int32, int64 or uint64: (row, col, match,
+    either or None, pair_offsets) as numpy arrays, with `sketch_pairs`' meaning of every argument."""
+    a = np.ascontiguousarray(a)
+    upper = b is None
+    b = a if upper else np.ascontiguousarray(b)
+    if a.dtype not in _HOST_CODES:
+        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
+    Ba, Bb, S = _pair_shape(a, b)
+    rule, cap = _pairs_rule(S, min_jaccard, min_match, max_pairs, None, upper)
+    offs = np.zeros(Ba + 1, np.int64)
+
+    def call(n, *arrays):  # the twin counts and lists in one call; with max_pairs = 0 it only counts and takes no arrays
+        capi.check(_lib.bsq_sketch_pairs_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, _HOST_CODES[a.dtype], ctypes.byref(rule), offs.ctypes.data, n,
+                                              *(None if x is None else x.ctypes.data for x in arrays)))
+
+    if cap is None:
+        call(0, None, None, None, None)
+        cap = int(offs[-1])
+    row, col = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+    match, eith = np.zeros(cap, np.int32), np.zeros(cap, np.int32) if either else None
+    call(cap, row, col, match, eith)
+    return row, col, match, eith, offs
+
+
+def sketch_pairs(a, b=None, *, min_jaccard=0.5, min_match=1, max_pairs=None, either=True, segments=None):
+    """The pairs of rows of two sketch matrices that are at least `min_jaccard` similar, as a list -- never the dense (Ba, Bb) matrices
+    of `sketch_compare`: (row, col, match, either or None, pair_offsets), device tensors on torch's current stream.
+
+    a (Ba, S), b (Bb, S): contiguous int32 or int64 device tensors as `minhash_packed` returns them.  The pair (i, j) is listed when
+    match[i, j] >= min_match and match[i, j] / either[i, j] >= min_jaccard (decided in integers: match * 65536 >= T * either with
+    T = floor(min_jaccard * 65536 + 0.5), so the CPU twin `sketch_pairs_host` selects the same pairs bit for bit).  b=None lists the pairs
+    i < j of `a` with itself and computes half the tiles.  Pairs come in ascending (i, j); row and col are int64, match and either
+    int32, and pair_offsets (int64, Ba + 1) is the CSR of the ranks over the rows of a: pair_offsets[-1] is the number of pairs that
+    pass.  min_match=0 lets two rows without a filled bucket pass every threshold.
+
+    max_pairs=None reads that total back (8 bytes) and sizes the arrays exactly.  max_pairs=N reads nothing back: the arrays hold N
+    entries, the pairs of rank < N and zeros behind the last one, and pair_offsets[-1] > N tells later that the list was cut.
+    segments: None, or 1 .. 64 to force how a strip's tiles are split over workgroups (the result does not depend on it).
+
+    Train / test leakage: `sketch_pairs(train, test, min_jaccard=...)[1].unique()` are the test rows to drop."""
+    import torch
+    upper = b is None
+    b = a if upper else b
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda and a.device == b.device):
+        raise ValueError("sketch_pairs works on sketch matrices resident on one device")
+    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("sketches are contiguous int32 or int64 tensors")
+    Ba, Bb, S = _pair_shape(a, b)
+    rule, cap = _pairs_rule(S, min_jaccard, min_match, max_pairs, segments, upper)
+    dev, dt = a.device, capi.I32 if a.dtype == torch.int32 else capi.U64
+    nseg = _lib.bsq_sketch_pairs_segments(Ba, Bb, rule.segments)
+    if nseg < 1:
+        raise ValueError("the library refuses these sizes (include/bsq.h, \"sketch pairs\")")
+    segs = torch.empty(Ba * nseg + 1, dtype=torch.int64, device=dev)
+    offs = torch.empty(Ba + 1, dtype=torch.int64, device=dev)
+    with capi.launching(dev) as stream:
+        capi.check(_lib.bsq_sketch_pairs_count_device(a.data_ptr(), Ba, b.data_ptr(), Bb, S, dt, ctypes.byref(rule), segs.data_ptr(), offs.data_ptr(),
+                                                      stream))
+        if cap is None:
+            n, make = int(offs[-1].item()), torch.empty
+        else:  # entries at and past the total stay zero
+            n, make = cap, torch.zeros
+        row, col = make(n, dtype=torch.int64, device=dev), make(n, dtype=torch.int64, device=dev)
+        match = make(n, dtype=torch.int32, device=dev)
+        eith = make(n, dtype=torch.int32, device=dev) if either else None
+        if n:
+            capi.check(_lib.bsq_sketch_pairs_emit_device(a.data_ptr(), Ba, b.data_ptr(), Bb, S, dt, ctypes.byref(rule), segs.data_ptr(), n,
+                                                         row.data_ptr(), col.data_ptr(), match.data_ptr(), eith.data_ptr() if either else None,
+                                                         stream))
+    return row, col, match, eith, offs
+
+
+def sketch_duplicates(a, *, min_jaccard=0.9, min_match=1, max_pairs=None):
+    """De-duplication of one sketch matrix from its pair list: (keep, first).  first[j] (int64, B) is the smallest i < j that
+    `sketch_pairs(a, min_jaccard=..., min_match=...)` lists with j, or j itself; keep = first == arange(B) (bool).  `a[keep]` drops EVERY
+    row that has an earlier near-duplicate: of a chain A ~ B ~ C it loses B and C even when A and C are not similar.  A device tensor
+    gives device tensors (`scatter_reduce(amin)` over the list), a numpy matrix goes through the CPU twin and gives numpy.
+
+    max_pairs=None sizes the list exactly (one 8-byte read-back on the device) and returns (keep, first).  max_pairs=N reads nothing
+    back on the device, so a cut list cannot raise there; the call then returns (keep, first, total) with `total` the number of pairs
+    that pass (a 0-d tensor): where total > N the list was cut and the answer is partial -- rows may be kept that have a duplicate.
+    On numpy input the total is known: a cut list raises ValueError, and the result is always (keep, first)."""
+    if isinstance(a, np.ndarray):
+        row, col, _, _, offs = sketch_pairs_host(a, min_jaccard=min_jaccard, min_match=min_match, max_pairs=max_pairs, either=False)
+        if offs[-1] > row.size:
+            raise ValueError("%d pairs pass, max_pairs = %d: the list was cut" % (offs[-1], row.size))
+        first = np.arange(a.shape[0], dtype=np.int64)
+        np.minimum.at(first, col, row)
+        return first == np.arange(a.shape[0]), first
+    import torch
+    row, col, _, _, offs = sketch_pairs(a, min_jaccard=min_jaccard, min_match=min_match, max_pairs=max_pairs, either=False)
+    ident = torch.arange(a.shape[0], dtype=torch.int64, device=a.device)
+    first = ident.scatter_reduce(0, col, row, "amin")  # (the zeros behind a short list: first[0] <- min(0, 0))
+    keep = first == ident
+    return (keep, first) if max_pairs is None else (keep, first, offs[-1])
+
+
+def sketch_pairs_kernel_name(Ba, Bb, segments=None):
+    """The launches of `sketch_pairs` for these sizes (host only: profiling labels, tests), the count's before the ';'."""
+    return _lib.bsq_sketch_pairs_kernel_name(int(Ba), int(Bb), 0 if segments is None else int(segments)).decode()
+
+
+__all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard",
+           "sketch_pairs", "sketch_pairs_host", "sketch_duplicates", "sketch_pairs_kernel_name"]

@@ -43,7 +43,8 @@ extern "C" {
                            * bsq_codon_table, bsq_translate_length, bsq_translate_packed_device, bsq_translate_packed_host, bsq_translate_kernel_name,
                            * bsq_orf, bsq_orf_count_device, bsq_orf_emit_device, bsq_orf_count_host, bsq_orf_emit_host, bsq_orf_kernel_name,
                            * bsq_minhash, bsq_minhash_device, bsq_minhash_host, bsq_minhash_kernel_name, bsq_sketch_compare_device,
-                           * bsq_sketch_compare_host; nothing removed */
+                           * bsq_sketch_compare_host, bsq_sketch_pairs, bsq_sketch_pairs_segments, bsq_sketch_pairs_count_device,
+                           * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -705,6 +706,77 @@ bsq_status bsq_sketch_compare_device(const void *a, int64_t Ba, const void *b, i
                                      int32_t *either_or_null, void *hip_stream);
 bsq_status bsq_sketch_compare_host(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, int32_t *match,
                                    int32_t *either_or_null);
+
+/* ---- sketch pairs: the pairs of rows of two sketch matrices whose similarity reaches a threshold, as a list -- near-duplicate search
+ * and train / test leakage checks without the dense (Ba, Bb) matrices of the comparison, which at 262 144 x 262 144 rows would be
+ * 550 GB.  The arithmetic is the comparison's; the output is ragged, ordered and cut at a capacity, as the ORFs' is.
+ *
+ * THE RULE.  a (Ba, S) and b (Bb, S) are what bsq_sketch_compare_device takes (BSQ_I32 or BSQ_U64, C-contiguous, the low 32 bits read,
+ * 1 <= S <= 2^14), and match[i, j], either[i, j] are exactly the comparison's.  A bsq_sketch_pairs selects pairs:
+ *     pass(i, j)   <=>  match >= min_match  and  match * 65536 >= jaccard_q16 * either.
+ *                  min_match lies in 0 .. S; jaccard_q16 = floor(min_jaccard * 65536 + 0.5) lies in 0 .. 65536 (the rounding of the
+ *                  masked-LM draws).  Both products are at most 2^30: 32-bit integers, no float, the same selection everywhere.  With
+ *                  min_match = 0 and jaccard_q16 = 0 every pair passes and the list is the dense matrix in row-major order; with
+ *                  min_match = 0 two rows that are EMPTY throughout pass any threshold (0 >= 0): min_match >= 1 keeps them out.
+ *     upper        0 / 1.  1: a and b are ONE matrix (Ba == Bb, else BSQ_ERR_INVALID_ARG) and only the pairs i < j are listed; the
+ *                  tiles wholly below the diagonal are not computed -- half the work.
+ *     order        the listed pairs in ascending (i, j): that order is part of the contract.  pair_offsets (int64, Ba + 1 entries) is
+ *                  the CSR of their ranks over the rows of a; pair_offsets[Ba] is the total, also when the list is cut.
+ *     outputs      row[k], col[k] (int64), match[k], either[k] (int32; `either` may be null) of the pair of rank k, for every rank
+ *                  < max_pairs.  Nothing is written at or past index max_pairs.
+ *     segments     0 .. 64: into how many runs of consecutive 64-row tiles of b a strip of 64 rows of a is cut, a workgroup per
+ *                  (strip, run).  0: the library chooses -- enough that strips x segments reaches 4096 workgroups, 1 once the strips
+ *                  alone do, never more than 64 or the number of tiles; n: min(n, tiles).  The result does not depend on it.
+ * Limits: the comparison's.  Ba == 0 or Bb == 0 is BSQ_OK: pair_offsets (and seg_offsets) are zeroed, nothing else is written.  Every
+ * call is stream-ordered and never synchronises; a refusal writes nothing and sets bsq_last_error().
+ *
+ * bsq_sketch_pairs_segments: the segments a call with these sizes takes (host only); 0 for sizes or a `segments` the calls refuse.
+ * bsq_sketch_pairs_count_device: seg_offsets (device int64, Ba * segments + 1 entries, caller-owned: it must live until the emit call
+ * has run) <- entry i * segments + s = the pairs listed in front of row i's run s; pair_offsets[i] <- entry i * segments.
+ * bsq_sketch_pairs_emit_device: the arrays, from the seg_offsets the count call wrote for the same inputs and rule.  A caller that sized
+ * its arrays from pair_offsets[Ba] passes that as max_pairs; one that must not read back passes a bound and learns from
+ * pair_offsets[Ba] later whether the list was cut.  The arrays may be null when max_pairs == 0.
+ * bsq_sketch_pairs_host: the CPU twin (the rule text of csrc/bsq_sketch_dev.h in plain loops), count and emit in one call.
+ *
+ * Kernels: k_sketch_pairs<count | emit>, a workgroup per (strip, run) that walks its tiles in ascending j with the staging and the
+ * 4 x 4 register tile of k_sketch_compare; after each tile the 16 pass flags of a thread are ORed into a 64-bit hit mask per row in
+ * LDS, and the rank of a column is the row's running cursor plus the popcount of the mask below it -- no global atomic, no dense
+ * intermediate.  The per-(row, run) counts become starts in place as the row lengths of a ragged batch do (csrc/bsq_ragged_out.h):
+ * k_sketch_pairs_sums adds up every 64 of them, k_sketch_pairs_place turns counts into offsets and writes pair_offsets, and beyond
+ * 2^20 (row, run) entries k_sketch_pairs_scan scans the sums once between the two.  Count and emit each recompute the comparison.
+ * Measured on an MI355X, int32 sketches of random reads with 3 % planted near-duplicates, min_jaccard 0.5, buffers alternating
+ * (scripts/sketch_pairs_lab.py, profiles/r20/sketch_pairs_lab.txt), count + emit against k_sketch_compare alone and against the
+ * composition sketch_compare -> threshold -> torch.nonzero of the same build (equal results): 4096 x 4096 x 128: 227 + 217 us, 2.05x
+ * the dense kernel, 0.98x the composition; 8192 x 8192 x 1024: 6.58 + 6.58 ms, 2.04x and 1.83x (the composition computes the comparison
+ * once, and 0.5 GB of dense matrices are cheap to threshold); 131 072 x 131 072 x 128, the last power of two whose dense matrices
+ * (137 GB) fit: 208 + 211 ms, 1.91x and 1.08x.  So the list costs about the time of the composition or up to twice that, and takes no
+ * memory to speak of.  262 144 x 262 144 x 128, upper, which has no dense form: 415 + 418 ms, 10.6 T bucket pairs per second over the
+ * tiles computed (k_sketch_compare: 10.0 - 10.7), with one segment; two segments take 616 + 620 ms.  No counters-only run was taken.
+ *
+ * Known answers (the plain sketches of the MinHash section's batch ACGTAC, ACGNACGT, AC, "", TTTTTTT: DNA4, k = 3, S = 4, seed 0, as a
+ * and as b; rows 0 and 1 are equal with two filled buckets, rows 2 and 3 EMPTY throughout, row 4 has one filled bucket of its own):
+ *     upper, min_match 1, jaccard_q16 32768    (0,1) match 2 either 2                     pair_offsets 0 1 1 1 1 1
+ *     min_match 1, jaccard_q16 65536           (0,0) (0,1) (1,0) (1,1) (4,4)              pair_offsets 0 2 4 4 4 5
+ *     min_match 0, jaccard_q16 65536           those and (2,2) (2,3) (3,2) (3,3)          pair_offsets 0 2 4 6 8 9
+ *     min_match 0, jaccard_q16 0               all 25, (0,4): match 0 either 3            pair_offsets 0 5 10 15 20 25 */
+typedef struct bsq_sketch_pairs {
+    int32_t min_match;   /* 0 .. S */
+    int32_t jaccard_q16; /* 0 .. 65536: floor(min_jaccard * 65536 + 0.5) */
+    int32_t upper;       /* 0 / 1: the pairs i < j of one matrix */
+    int32_t segments;    /* 0: the library chooses; 1 .. 64 */
+} bsq_sketch_pairs;
+int32_t bsq_sketch_pairs_segments(int64_t Ba, int64_t Bb, int32_t segments);
+bsq_status bsq_sketch_pairs_count_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                         int64_t *seg_offsets, int64_t *pair_offsets, void *hip_stream);
+bsq_status bsq_sketch_pairs_emit_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                        const int64_t *seg_offsets, int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match,
+                                        int32_t *either_or_null, void *hip_stream);
+bsq_status bsq_sketch_pairs_host(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule,
+                                 int64_t *pair_offsets, int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match, int32_t *either_or_null);
+/* Host only: the launches of the two device calls, the count's before the ';'
+ * ("k_sketch_pairs<count>+k_sketch_pairs_sums+k_sketch_pairs_place;k_sketch_pairs<emit>", with "+k_sketch_pairs_scan" in front of the
+ * place launch beyond 2^20 (row, run) entries; "hipMemsetAsync" for an empty side); "" for sizes or a `segments` the calls refuse. */
+const char *bsq_sketch_pairs_kernel_name(int64_t Ba, int64_t Bb, int32_t segments);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
