@@ -207,6 +207,11 @@ def load():
         "bsq_sketch_pairs_emit_device": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, i64, vp, vp, vp, vp, vp]),
         "bsq_sketch_pairs_host": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, i64, vp, vp, vp, vp]),
         "bsq_sketch_pairs_kernel_name": (ctypes.c_char_p, [i64, i64, i32]),
+        "bsq_sketch_clusters_device": (i32, [vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp, vp, vp]),
+        "bsq_sketch_clusters_host": (i32, [vp, i64, i64, c_int, ctypes.POINTER(SketchPairs), vp]),
+        "bsq_cluster_pairs_device": (i32, [vp, vp, i64, i64, vp, vp, vp]),
+        "bsq_cluster_pairs_host": (i32, [vp, vp, i64, i64, vp]),
+        "bsq_sketch_clusters_kernel_name": (ctypes.c_char_p, [i64, i32]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -18,6 +18,8 @@
 //            a popcount per pair and chunk), which give `match` and `either`.  An input element is read once per tile pair.
 // k_sketch_pairs<T, EMIT>   the thresholded pair list (include/bsq.h, "sketch pairs"): the same tile arithmetic (cmp_tile) by a workgroup per
 //            (strip of 64 rows, segment of j tiles), with a ragged, ordered output; its comment stands in front of it.
+// k_cluster_init, k_sketch_link<T>, k_cluster_link_pairs, k_cluster_labels   the clusters (include/bsq.h, "sketch clusters"): the same
+//            walk of upper tiles, every passing pair a union in a lock-free union-find; their comment stands in front of them.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -348,6 +350,113 @@ __global__ __launch_bounds__(kThreads) void k_sketch_pairs_place(int64_t n, int6
     }
 }
 
+// ---- the clusters (include/bsq.h, "sketch clusters") ----
+// The connected components of the "passes" graph by a lock-free union-find over `parent` (int64, a word per row), whose find and
+// union text is bsq_sketch_dev.h's; three launches on one stream:
+// k_cluster_init        parent[i] <- i.
+// k_sketch_link<T>      k_sketch_pairs' geometry, upper: a workgroup per (strip of 64 rows, run of j tiles) walks its tiles in ascending j
+//            with cmp_tile; every passing (i, j) is a union.  A tile without a hit costs one barrier more.  A tile with hits: the roots
+//            of its 64 rows and 64 columns are found once (128 finds -> LDS); a hit whose two cached roots are equal is dropped there;
+//            the others are united in a union-find of the tile's 128 nodes in LDS, and each node that ends below another hands ONE
+//            union of the two cached roots to global memory -- at most 127 per tile, none in a store whose rows are one component already.
+// k_cluster_link_pairs  the same union, an edge of an explicit list per lane (grid-stride).
+// k_cluster_labels      behind the kernel boundary parent is final: labels[i] <- the root of i.
+// Workgroups of one link launch talk through `parent` alone, so EVERY access to it there is an agent-scope atomic on the global address
+// space (GlobalParent: relaxed loads, stores and compare-and-swaps, which are served by L2 and never by a CU's L1 or the scalar cache); the
+// word is all that is communicated, so relaxed order is enough, and a parent that is no longer current was once true and costs a retry.
+// No lane waits for another: every loop ends by the invariant parent[x] <= x or repeats after a swap that lost to a union that won.
+struct GlobalParent {
+    using Word = __attribute__((address_space(1))) int64_t;
+    int64_t *p;
+    __device__ __forceinline__ Word *at(int64_t x) const { return (Word *)(p + x); }
+    __device__ __forceinline__ int64_t load(int64_t x) const { return __hip_atomic_load(at(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ void store(int64_t x, int64_t v) const { __hip_atomic_store(at(x), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ bool swap_root(int64_t hi, int64_t lo) const {
+        int64_t expected = hi;
+        return __hip_atomic_compare_exchange_strong(at(hi), &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// the tile's 128 nodes in LDS (rows 0 .. 63, columns 64 .. 127): the same text over workgroup-scope atomics
+struct TileParent {
+    int32_t *p;
+    __device__ __forceinline__ int64_t load(int64_t x) const { return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ void store(int64_t x, int64_t v) const {
+        __hip_atomic_store(p + x, static_cast<int32_t>(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ bool swap_root(int64_t hi, int64_t lo) const {
+        int32_t expected = static_cast<int32_t>(hi);
+        return __hip_atomic_compare_exchange_strong(p + hi, &expected, static_cast<int32_t>(lo), __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+};
+
+__global__ __launch_bounds__(kThreads) void k_cluster_init(int64_t n, int64_t *parent) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    if (i < n) parent[i] = i;
+}
+
+__global__ __launch_bounds__(kThreads) void k_cluster_labels(int64_t n, int64_t *parent, int64_t *labels) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    if (i < n) labels[i] = bsq_sketchd::uf_find<false>(GlobalParent{parent}, i);
+}
+
+__global__ __launch_bounds__(kThreads) void k_cluster_link_pairs(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, int64_t *parent) {
+    const GlobalParent global{parent};
+    for (int64_t k = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; k < n_pairs; k += static_cast<int64_t>(gridDim.x) * kThreads) {
+        const int64_t i = row[k], j = col[k];
+        if (bsq_sketchd::edge_links(i, j, n)) bsq_sketchd::uf_union(global, i, j);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_sketch_link(const T *a, int64_t B, int32_t S, const PairsRule r, int64_t *parent) {
+    __shared__ int64_t s_root[2 * kTile];  // the root of row i0 + t (t < 64), of column j0 + t - 64, found once per tile with hits
+    __shared__ int32_t s_node[2 * kTile];  // the tile's own union-find over those 128 nodes
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const uint32_t nseg = static_cast<uint32_t>(r.nseg), strip = blockIdx.x / nseg, seg = blockIdx.x - strip * nseg;
+    const int64_t i0 = static_cast<int64_t>(strip) * kTile;
+    int64_t tj = bsq_sketchd::segment_first_tile(seg, nseg, r.tiles_j);
+    const int64_t tj_end = bsq_sketchd::segment_first_tile(seg + 1, nseg, r.tiles_j);
+    if (tj < strip) tj = strip;  // (upper: the tiles left of the diagonal tile are another strip's)
+    const GlobalParent global{parent};
+    const TileParent local{s_node};
+    for (; tj < tj_end; ++tj) {
+        const int64_t j0 = tj * kTile;
+        int32_t eq[4][4], both[4][4];
+        const int32_t staged = cmp_tile(a, B, a, B, S, i0, j0, eq, both);  // (its barriers stand behind the last tile's reads of s_root and s_node)
+        const bool diagonal = tj == strip;
+        uint32_t flags = 0;  // bit 4 r + c
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int64_t i = i0 + ty + 16 * rr;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t j = j0 + tx + 16 * c;
+                const bool hit = i < B && j < B && (!diagonal || j > i) &&
+                                 bsq_sketchd::pair_passes(eq[rr][c] - both[rr][c], staged - both[rr][c], r.min_match, r.jaccard_q16);
+                flags |= static_cast<uint32_t>(hit) << (4 * rr + c);
+            }
+        }
+        if (!__syncthreads_or(flags != 0)) continue;  // (uniform)
+        if (tid < 2 * kTile) {
+            const int64_t node = tid < kTile ? i0 + tid : j0 + tid - kTile;
+            s_root[tid] = node < B ? bsq_sketchd::uf_find<true>(global, node) : -1;  // (a node outside the matrix has no hit)
+            s_node[tid] = tid;
+        }
+        __syncthreads();
+        for (uint32_t left = flags; left; left &= left - 1) {  // a thread's hits, one set bit at a time
+            const int bit = __ffs(left) - 1, row = ty + 16 * (bit >> 2), col = kTile + tx + 16 * (bit & 3);
+            if (s_root[row] != s_root[col]) bsq_sketchd::uf_union(local, row, col);
+        }
+        __syncthreads();
+        if (tid < 2 * kTile) {  // (s_node is final: plain finds)
+            const int64_t top = bsq_sketchd::uf_find<false>(local, tid);
+            if (top != tid && s_root[tid] != s_root[top]) bsq_sketchd::uf_union(global, s_root[tid], s_root[top]);
+        }
+    }
+}
+
 template <typename T, int MODE>
 void launch_minhash(bsq_rowtab::Form form, int64_t B, hipStream_t s, const SketchParams &p) {
     bsq_rowtab::launch(form, B, s, p, k_minhash_wave<T, MODE>, k_minhash_block<T, 1024, MODE>, k_minhash_block<T, 4096, MODE>,
@@ -477,6 +586,52 @@ bsq_status bsq_sketch_pairs_emit_device(const void *a, int64_t Ba, const void *b
         hipLaunchKernelGGL((k_sketch_pairs<uint64_t, true>), grid, block, 0, s, static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb,
                            static_cast<int32_t>(S), r, segs, out);
     return bsq_internal::check_launch("k_sketch_pairs<emit>");
+}
+
+const char *bsq_sketch_clusters_kernel_name(int64_t B, int32_t segments) {
+    if (B <= 0 || B > bsq_sketchd::kMaxRows || bsq_sketch_pairs_segments(B, B, segments) == 0) return "";
+    const int64_t tiles = (B + kTile - 1) / kTile;
+    return tiles * tiles > bsq_sketchd::kMaxRows ? "" : "k_cluster_init+k_sketch_link+k_cluster_labels";
+}
+
+bsq_status bsq_sketch_clusters_device(const void *a, int64_t B, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule, int64_t *parent_scratch,
+                                      int64_t *labels, void *hip_stream) {
+    const char *why = "";
+    PairsRule r;
+    const bsq_status st = bsq_sketchd::check_clusters(a, B, S, t, rule, &r, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (B == 0) return BSQ_OK;
+    if (!parent_scratch || !labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "parent_scratch or labels is null");
+    if (parent_scratch == labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "labels must not be the parent scratch");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const dim3 rows(static_cast<unsigned>((B + kThreads - 1) / kThreads)), grid(static_cast<unsigned>(r.strips * r.nseg)), block(kThreads);
+    hipLaunchKernelGGL(k_cluster_init, rows, block, 0, s, B, parent_scratch);
+    if (t == BSQ_I32)
+        hipLaunchKernelGGL((k_sketch_link<int32_t>), grid, block, 0, s, static_cast<const int32_t *>(a), B, static_cast<int32_t>(S), r, parent_scratch);
+    else
+        hipLaunchKernelGGL((k_sketch_link<uint64_t>), grid, block, 0, s, static_cast<const uint64_t *>(a), B, static_cast<int32_t>(S), r, parent_scratch);
+    hipLaunchKernelGGL(k_cluster_labels, rows, block, 0, s, B, parent_scratch, labels);
+    return bsq_internal::check_launch("k_cluster_init / k_sketch_link / k_cluster_labels");
+}
+
+bsq_status bsq_cluster_pairs_device(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, int64_t *parent_scratch, int64_t *labels,
+                                    void *hip_stream) {
+    const char *why = "";
+    const bsq_status st = bsq_sketchd::check_cluster_pairs(row, col, n_pairs, n, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (n == 0) return BSQ_OK;
+    if (!parent_scratch || !labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "parent_scratch or labels is null");
+    if (parent_scratch == labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "labels must not be the parent scratch");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const dim3 nodes(static_cast<unsigned>((n + kThreads - 1) / kThreads)), block(kThreads);
+    hipLaunchKernelGGL(k_cluster_init, nodes, block, 0, s, n, parent_scratch);
+    if (n_pairs > 0) {  // (a lane per edge up to 2^20 workgroups, a stride of the grid beyond)
+        const int64_t groups = (n_pairs + kThreads - 1) / kThreads, most = int64_t(1) << 20;
+        hipLaunchKernelGGL(k_cluster_link_pairs, dim3(static_cast<unsigned>(groups < most ? groups : most)), block, 0, s, row, col, n_pairs, n,
+                           parent_scratch);
+    }
+    hipLaunchKernelGGL(k_cluster_labels, nodes, block, 0, s, n, parent_scratch, labels);
+    return bsq_internal::check_launch("k_cluster_init / k_cluster_link_pairs / k_cluster_labels");
 }
 
 }  // extern "C"

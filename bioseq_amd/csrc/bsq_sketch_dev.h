@@ -1,7 +1,8 @@
 // MinHash sketches of a packed batch, the all-pairs comparison of sketches and the thresholded pair list (include/bsq.h, "MinHash
 // sketch", "sketch pairs"): what the kernels of bsq_sketch.hip and the CPU twins of bsq_sketch_host.cpp share -- the limits, the wide
 // geometry of a (tokenizer, bsq_minhash) pair, the reverse complement of a 64-bit word, the hash, the bucket and value of a hash, the
-// value of one output element, the choice of kernel, the selection of a pair, the segments of a strip and the argument rules.  Plain C++
+// value of one output element, the choice of kernel, the selection of a pair, the segments of a strip, the find and union of the
+// clusters ("sketch clusters") and the argument rules.  Plain C++
 // over <cstdint> and bsq.h alone: the host twins compile without the HIP headers.
 #pragma once
 #include <cstdint>
@@ -210,6 +211,67 @@ inline bsq_status check_pairs(const void *a, int64_t Ba, const void *b, int64_t 
     r->nseg = pairs_segments(Ba, Bb, rule->segments);
     r->tiles_j = (Bb + kCmpTile - 1) / kCmpTile;
     r->strips = (Ba + kCmpTile - 1) / kCmpTile;
+    return BSQ_OK;
+}
+
+// ---- sketch clusters (include/bsq.h, "sketch clusters"): the union-find, the edge rule and the argument rules ----
+// One text of find and union over a `parent` array reached through an accessor P: load(x), store(x, v) and swap_root(hi, lo), which
+// sets parent[hi] from hi to lo and says whether it did.  The kernels pass accessors made of agent-scope atomics on global memory
+// and of workgroup-scope atomics on LDS (bsq_sketch.hip), the CPU twins the plain SeqParent below.  The invariant is parent[x] <= x:
+// a root is hooked under a SMALLER root only, and only while it is a root (the swap expects parent[hi] == hi), so there is no cycle
+// and the last root of a component is its smallest member, in whatever order the unions arrive.  A node that has left the roots never
+// returns to them: path halving (HALVE) may store any ancestor over its parent, a stale one included, and the swap on it fails
+// either way.  Nothing here waits: a failed swap means that another union has just succeeded on that root.
+template <bool HALVE, typename P>
+BSQ_SKETCH_HD int64_t uf_find(const P &m, int64_t x) {
+    int64_t p = m.load(x);
+    while (p != x) {
+        const int64_t g = m.load(p);
+        if (HALVE && g != p) m.store(x, g);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+template <typename P>
+BSQ_SKETCH_HD void uf_union(const P &m, int64_t a, int64_t b) {
+    for (;;) {
+        a = uf_find<true>(m, a);
+        b = uf_find<true>(m, b);
+        if (a == b) return;
+        const int64_t lo = a < b ? a : b, hi = a < b ? b : a;
+        if (m.swap_root(hi, lo)) return;
+        a = lo;  // (hi has just been hooked elsewhere: again, from where this attempt stood)
+        b = hi;
+    }
+}
+
+// the accessor of the CPU twins: one thread, so the swap always finds what find left
+struct SeqParent {
+    int64_t *p;
+    int64_t load(int64_t x) const { return p[x]; }
+    void store(int64_t x, int64_t v) const { p[x] = v; }
+    bool swap_root(int64_t hi, int64_t lo) const { return p[hi] = lo, true; }
+};
+
+// an entry of an explicit edge list links two nodes: not a self-edge, both ends inside 0 .. n - 1 (anything else is ignored unread)
+BSQ_SKETCH_HD bool edge_links(int64_t row, int64_t col, int64_t n) {
+    return row != col && static_cast<uint64_t>(row) < static_cast<uint64_t>(n) && static_cast<uint64_t>(col) < static_cast<uint64_t>(n);
+}
+
+// The rules of the clustering calls: the pair list's, on one matrix, with upper == 1.  Host only.
+inline bsq_status check_clusters(const void *a, int64_t B, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule, PairsRule *r, const char **why) {
+    const bsq_status st = check_pairs(a, B, a, B, S, t, rule, r, why);
+    if (st != BSQ_OK) return st;
+    if (rule->upper != 1) return *why = "sketch clusters take a rule with upper == 1: the links i < j of ONE matrix", BSQ_ERR_INVALID_ARG;
+    return BSQ_OK;
+}
+
+inline bsq_status check_cluster_pairs(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, const char **why) {
+    if (n_pairs < 0 || n < 0) return *why = "negative n_pairs or n", BSQ_ERR_INVALID_ARG;
+    if (n > kMaxRows) return *why = "n exceeds 2^31 - 1", BSQ_ERR_INVALID_ARG;
+    if (n_pairs > 0 && (!row || !col)) return *why = "row or col is null", BSQ_ERR_INVALID_ARG;
     return BSQ_OK;
 }
 

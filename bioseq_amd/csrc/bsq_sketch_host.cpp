@@ -1,7 +1,8 @@
-// MinHash sketches, their comparison and the thresholded pair list, the CPU side (include/bsq.h, "MinHash sketch", "sketch pairs"): the
-// twins bsq_minhash_host, bsq_sketch_compare_host and bsq_sketch_pairs_host -- plain loops over the rule text of bsq_sketch_dev.h, the
-// text the kernels of bsq_sketch.hip compile -- and the host-only bsq_sketch_pairs_segments.  Plain C++: neither this file nor that
-// header needs the HIP headers.
+// MinHash sketches, their comparison, the thresholded pair list and the clusters, the CPU side (include/bsq.h, "MinHash sketch",
+// "sketch pairs", "sketch clusters"): the twins bsq_minhash_host, bsq_sketch_compare_host, bsq_sketch_pairs_host,
+// bsq_sketch_clusters_host and bsq_cluster_pairs_host -- plain loops over the rule text of bsq_sketch_dev.h, the text the kernels of
+// bsq_sketch.hip compile -- and the host-only bsq_sketch_pairs_segments.  Plain C++: neither this file nor that header needs the HIP
+// headers.
 #include <cstdint>
 #include <vector>
 
@@ -73,6 +74,32 @@ void pair_rows(const T *a, int64_t Ba, const T *b, int64_t Bb, int64_t S, const 
     pair_offsets[Ba] = rank;
 }
 
+// parent[x] <- x for every node; after the unions, every node's root: `labels` is the parent array, rewritten in ascending order
+// (a root is smaller than its members, so a parent read by a later find is a final label already)
+void cluster_begin(int64_t n, int64_t *labels) {
+    for (int64_t i = 0; i < n; ++i) labels[i] = i;
+}
+void cluster_end(int64_t n, int64_t *labels) {
+    const bsq_sketchd::SeqParent parent{labels};
+    for (int64_t i = 0; i < n; ++i) labels[i] = bsq_sketchd::uf_find<false>(parent, i);
+}
+
+// every pair i < j that passes is a union
+template <typename T>
+void cluster_rows(const T *a, int64_t B, int64_t S, const bsq_sketchd::PairsRule &r, int64_t *labels) {
+    const bsq_sketchd::SeqParent parent{labels};
+    for (int64_t i = 0; i < B; ++i)
+        for (int64_t j = i + 1; j < B; ++j) {
+            int32_t m = 0, e = 0;
+            for (int64_t t = 0; t < S; ++t) {
+                const uint32_t x = static_cast<uint32_t>(a[i * S + t]), y = static_cast<uint32_t>(a[j * S + t]);
+                m += x == y && x != kEmpty;
+                e += x != kEmpty || y != kEmpty;
+            }
+            if (bsq_sketchd::pair_passes(m, e, r.min_match, r.jaccard_q16)) bsq_sketchd::uf_union(parent, i, j);
+        }
+}
+
 }  // namespace
 
 extern "C" {
@@ -119,6 +146,34 @@ bsq_status bsq_sketch_pairs_host(const void *a, int64_t Ba, const void *b, int64
         pair_rows(static_cast<const int32_t *>(a), Ba, static_cast<const int32_t *>(b), Bb, S, r, pair_offsets, max_pairs, row, col, match, either_or_null);
     else
         pair_rows(static_cast<const uint64_t *>(a), Ba, static_cast<const uint64_t *>(b), Bb, S, r, pair_offsets, max_pairs, row, col, match, either_or_null);
+    return BSQ_OK;
+}
+
+bsq_status bsq_sketch_clusters_host(const void *a, int64_t B, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule, int64_t *labels) {
+    const char *why = "";
+    bsq_sketchd::PairsRule r;
+    const bsq_status st = bsq_sketchd::check_clusters(a, B, S, t, rule, &r, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (B == 0) return BSQ_OK;
+    if (!labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "labels is null");
+    cluster_begin(B, labels);
+    if (t == BSQ_I32) cluster_rows(static_cast<const int32_t *>(a), B, S, r, labels);
+    else cluster_rows(static_cast<const uint64_t *>(a), B, S, r, labels);
+    cluster_end(B, labels);
+    return BSQ_OK;
+}
+
+bsq_status bsq_cluster_pairs_host(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, int64_t *labels) {
+    const char *why = "";
+    const bsq_status st = bsq_sketchd::check_cluster_pairs(row, col, n_pairs, n, &why);
+    if (st != BSQ_OK) return bsq_internal::set_error(st, why);
+    if (n == 0) return BSQ_OK;
+    if (!labels) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "labels is null");
+    cluster_begin(n, labels);
+    const bsq_sketchd::SeqParent parent{labels};
+    for (int64_t k = 0; k < n_pairs; ++k)
+        if (bsq_sketchd::edge_links(row[k], col[k], n)) bsq_sketchd::uf_union(parent, row[k], col[k]);
+    cluster_end(n, labels);
     return BSQ_OK;
 }
 

@@ -18,7 +18,14 @@ fraction J of their k-mers agree in about that fraction of their non-empty bucke
                       without the 550 GB its dense matrices would take (`bsq_sketch_pairs_count_device`, `bsq_sketch_pairs_emit_device`;
                       include/bsq.h, "sketch pairs");
 * `sketch_pairs_host`, `sketch_pairs_kernel_name`    its CPU twin, its launches;
-* `sketch_duplicates`  (keep, first) from the pair list of a matrix with itself: every row with an earlier near-duplicate is dropped.
+* `sketch_duplicates`  (keep, first) from the pair list of a matrix with itself: every row with an earlier near-duplicate is dropped;
+* `sketch_clusters`   the single-linkage clusters of a matrix as one int64 label per row -- the connected components of the pairs that
+                      pass, by a lock-free union-find inside the comparison's tile walk, with no pair list (`bsq_sketch_clusters_device`;
+                      include/bsq.h, "sketch clusters");
+* `cluster_pairs`     the same labels from an explicit edge list (`bsq_cluster_pairs_device`): merged lists, pairs from elsewhere;
+* `sketch_clusters_host`, `cluster_pairs_host`, `sketch_clusters_kernel_name`    their CPU twins, the launches;
+* `cluster_table`, `cluster_split`    (representatives, sizes, dense ids) of a label array; a seeded split in which every cluster goes to
+                      one side whole.
 
 The sketch of a sequence equals the bucket-wise UNSIGNED minimum of the sketches of pieces that together cover all its windows (EMPTY
 is the largest value), so sketches of longer sequences, or of sets of sequences, are merged without the characters.
@@ -272,5 +279,162 @@ def sketch_pairs_kernel_name(Ba, Bb, segments=None):
     return _lib.bsq_sketch_pairs_kernel_name(int(Ba), int(Bb), 0 if segments is None else int(segments)).decode()
 
 
+def sketch_clusters_host(a, *, min_jaccard=0.9, min_match=1):
+    """The library's CPU twin of `sketch_clusters` (`bsq_sketch_clusters_host`) on a numpy matrix of int32, int64 or uint64: the int64
+    labels as a numpy array."""
+    a = np.ascontiguousarray(a)
+    if a.dtype not in _HOST_CODES:
+        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
+    B, _, S = _pair_shape(a, a)
+    rule, _ = _pairs_rule(S, min_jaccard, min_match, None, None, True)
+    labels = np.empty(B, np.int64)
+    if B:
+        capi.check(_lib.bsq_sketch_clusters_host(a.ctypes.data, B, S, _HOST_CODES[a.dtype], ctypes.byref(rule), labels.ctypes.data))
+    return labels
+
+
+def sketch_clusters(a, *, min_jaccard=0.9, min_match=1, segments=None):
+    """The near-duplicate clusters of one sketch matrix: labels (int64, B), labels[i] = the smallest row index that row i reaches over
+    links, where rows i and j are linked when `sketch_pairs(a, min_jaccard=..., min_match=...)` would list them.  A row linked to nothing
+    is its own label; `labels[labels] == labels` and `labels <= arange(B)` always hold, and `labels == arange(B)` marks one
+    representative per cluster.  A device tensor (contiguous int32 or int64, as `minhash_packed` returns it) gives a device tensor on
+    torch's current stream, three launches (`sketch_clusters_kernel_name`), nothing read back and no pair list at any point: a store
+    that is one cluster of 100 000 rows costs what any other costs.  A numpy matrix goes through the CPU twin (`sketch_clusters_host`)
+    and gives numpy; the two agree bit for bit.  segments: as in `sketch_pairs` (the result does not depend on it).
+
+    Single linkage: this is the clustering by connected components.  Chains merge -- of A ~ B ~ C all three share one label even when
+    A and C are not similar -- so the two ends of a large cluster need not resemble each other; that is what a leakage-free split wants
+    (nothing similar to a test row stays in the training set) and not what a choice of representatives at a fixed radius wants.
+    `sketch_duplicates` is unchanged and remains the "earliest neighbour" filter.
+
+    A train set together with a test set: `labels = sketch_clusters(torch.cat([train, test]))`, then `cluster_split(labels, ...)` for a
+    new split of both, or compare `labels[:len(train)]` with `labels[len(train):]` for the clusters that straddle the old one."""
+    if isinstance(a, np.ndarray):
+        _pairs_rule(1 << 14, 0.0, 0, None, segments, True)  # (the twin has no segments: the argument is checked all the same)
+        return sketch_clusters_host(a, min_jaccard=min_jaccard, min_match=min_match)
+    import torch
+    if not (isinstance(a, torch.Tensor) and a.is_cuda):
+        raise ValueError("sketch_clusters works on a sketch matrix resident on the device, or on a numpy matrix")
+    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous():
+        raise ValueError("sketches are contiguous int32 or int64 tensors")
+    B, _, S = _pair_shape(a, a)
+    rule, _ = _pairs_rule(S, min_jaccard, min_match, None, segments, True)
+    if _lib.bsq_sketch_pairs_segments(B, B, rule.segments) < 1:
+        raise ValueError("the library refuses these sizes (include/bsq.h, \"sketch clusters\")")
+    parent = torch.empty(B, dtype=torch.int64, device=a.device)
+    labels = torch.empty(B, dtype=torch.int64, device=a.device)
+    if B:
+        with capi.launching(a.device) as stream:
+            capi.check(_lib.bsq_sketch_clusters_device(a.data_ptr(), B, S, capi.I32 if a.dtype == torch.int32 else capi.U64, ctypes.byref(rule),
+                                                       parent.data_ptr(), labels.data_ptr(), stream))
+    return labels
+
+
+def _edge_count(n):
+    if isinstance(n, bool) or int(n) != n or not 0 <= int(n) < 2 ** 31:
+        raise ValueError("n must be an integer in 0 .. 2 ** 31 - 1, got %r" % (n,))
+    return int(n)
+
+
+def cluster_pairs_host(row, col, n):
+    """The library's CPU twin of `cluster_pairs` (`bsq_cluster_pairs_host`) on numpy index arrays: the int64 labels of n nodes."""
+    n = _edge_count(n)
+    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
+    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
+        raise ValueError("row and col are int64 arrays of one length")
+    labels = np.empty(n, np.int64)
+    if n:
+        capi.check(_lib.bsq_cluster_pairs_host(row.ctypes.data if row.size else None, col.ctypes.data if row.size else None, row.size, n,
+                                               labels.ctypes.data))
+    return labels
+
+
+def cluster_pairs(row, col, n):
+    """The clusters of an explicit edge list: labels (int64, n) with `sketch_clusters`' meaning, where entry k links nodes row[k] and
+    col[k].  This is how lists are merged before clustering -- `torch.cat` the row and col arrays of `sketch_pairs` at several
+    thresholds or sketch widths, of a train list and a train x test list with the columns offset by `len(train)`, or of pairs found
+    elsewhere.  An entry with row == col is ignored (the zeros behind a list cut at `max_pairs`), and so is one with an index outside
+    0 .. n - 1.  Device int64 tensors give a device tensor on torch's current stream, nothing read back; numpy arrays go through the CPU
+    twin."""
+    if isinstance(row, np.ndarray) and isinstance(col, np.ndarray):
+        return cluster_pairs_host(row, col, n)
+    import torch
+    n = _edge_count(n)
+    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda and row.device == col.device):
+        raise ValueError("cluster_pairs works on index tensors resident on one device, or on numpy arrays")
+    if row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or row.shape != col.shape or not row.is_contiguous() or not col.is_contiguous():
+        raise ValueError("row and col are contiguous int64 tensors of one length")
+    parent = torch.empty(n, dtype=torch.int64, device=row.device)
+    labels = torch.empty(n, dtype=torch.int64, device=row.device)
+    if n:
+        with capi.launching(row.device) as stream:
+            capi.check(_lib.bsq_cluster_pairs_device(row.data_ptr(), col.data_ptr(), row.numel(), n, parent.data_ptr(), labels.data_ptr(), stream))
+    return labels
+
+
+def sketch_clusters_kernel_name(B, segments=None):
+    """The launches of `sketch_clusters` for B rows joined by '+' (host only: profiling labels, tests); '' for B = 0, which launches
+    nothing, and for sizes the library refuses."""
+    return _lib.bsq_sketch_clusters_kernel_name(int(B), 0 if segments is None else int(segments)).decode()
+
+
+def cluster_table(labels):
+    """(representatives, sizes, dense_id) of a label array: the rows with labels == arange, ascending (int64); their member counts
+    (int64); and dense_id[i], the rank of labels[i] among the representatives -- consecutive cluster numbers 0 .. C - 1 in order of each
+    cluster's first row.  Plain torch on a tensor (on its device), plain numpy on an array."""
+    if isinstance(labels, np.ndarray):
+        reps = np.nonzero(labels == np.arange(labels.size, dtype=np.int64))[0].astype(np.int64)
+        return reps, np.bincount(labels, minlength=labels.size).astype(np.int64)[reps], np.searchsorted(reps, labels).astype(np.int64)
+    import torch
+    reps = torch.nonzero(labels == torch.arange(labels.numel(), dtype=torch.int64, device=labels.device)).reshape(-1)
+    return reps, torch.bincount(labels, minlength=labels.numel())[reps], torch.searchsorted(reps, labels)
+
+
+_GOLDEN, _MIX_A, _MIX_B = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+
+
+def cluster_split(labels, fractions, seed=0):
+    """The split index (int64, 0 .. len(fractions) - 1) of every row, THE SAME FOR ALL ROWS OF A CLUSTER: a leakage-free train / test
+    (/ validation) split over the labels of `sketch_clusters` or `cluster_pairs`.  The split of a row is decided by (seed, label) alone,
+    so rows keep their split when unrelated rows are added after them, and another seed gives another split.
+
+    The fractions are over CLUSTERS, not rows: each cluster goes to split s with probability fractions[s], whatever its size, so a store
+    with one very large cluster has row shares that differ from the fractions (`cluster_table` gives the sizes).  They must be positive
+    and sum to 1 within 1e-6, else ValueError.
+
+    Integers only: h = the first output of splitmix64 from the state (seed + label) mod 2^64, that is mix64((seed + label +
+    0x9E3779B97F4A7C15) mod 2^64) with the finalizer of include/bsq.h ("MinHash sketch"); u = h >> 32; the split is the first s with
+    u < floor((fractions[0] + ... + fractions[s]) * 2^32), and the last split takes the rest.  The numpy form computes in uint64, the
+    torch form (any device) in int64 with wrap-around products and masked shifts; they give identical arrays."""
+    fr = [float(f) for f in fractions]
+    if not fr or not all(f > 0.0 for f in fr) or not abs(sum(fr) - 1.0) <= 1e-6:  # (a NaN fails the comparisons)
+        raise ValueError("fractions must be positive and sum to 1, got %r" % (fractions,))
+    bounds, run = [], 0.0
+    for f in fr[:-1]:
+        run += f
+        bounds.append(min(int(run * 4294967296.0), 1 << 32))
+    state = (int(seed) + _GOLDEN) & (2 ** 64 - 1)
+    if isinstance(labels, np.ndarray):
+        z = labels.astype(np.int64).view(np.uint64) + np.uint64(state)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(_MIX_A)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(_MIX_B)
+        u = (z ^ (z >> np.uint64(31))) >> np.uint64(32)
+        return np.searchsorted(np.array(bounds, np.uint64), u, side="right").astype(np.int64)
+    import torch
+
+    def signed(c):  # the int64 that holds these 64 bits
+        return c - (1 << 64) if c >> 63 else c
+
+    def shr(z, k):  # the logical shift: an arithmetic one with the copies of the sign masked off
+        return (z >> k) & ((1 << (64 - k)) - 1)
+
+    z = labels.to(torch.int64) + signed(state)
+    z = (z ^ shr(z, 30)) * signed(_MIX_A)
+    z = (z ^ shr(z, 27)) * signed(_MIX_B)
+    u = shr(z ^ shr(z, 31), 32)
+    return torch.searchsorted(torch.tensor(bounds, dtype=torch.int64, device=labels.device), u, right=True)
+
+
 __all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard",
-           "sketch_pairs", "sketch_pairs_host", "sketch_duplicates", "sketch_pairs_kernel_name"]
+           "sketch_pairs", "sketch_pairs_host", "sketch_duplicates", "sketch_pairs_kernel_name", "sketch_clusters", "sketch_clusters_host",
+           "cluster_pairs", "cluster_pairs_host", "sketch_clusters_kernel_name", "cluster_table", "cluster_split"]

@@ -44,7 +44,9 @@ extern "C" {
                            * bsq_orf, bsq_orf_count_device, bsq_orf_emit_device, bsq_orf_count_host, bsq_orf_emit_host, bsq_orf_kernel_name,
                            * bsq_minhash, bsq_minhash_device, bsq_minhash_host, bsq_minhash_kernel_name, bsq_sketch_compare_device,
                            * bsq_sketch_compare_host, bsq_sketch_pairs, bsq_sketch_pairs_segments, bsq_sketch_pairs_count_device,
-                           * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name; nothing removed */
+                           * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name, bsq_sketch_clusters_device,
+                           * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name;
+                           * nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -777,6 +779,69 @@ bsq_status bsq_sketch_pairs_host(const void *a, int64_t Ba, const void *b, int64
  * ("k_sketch_pairs<count>+k_sketch_pairs_sums+k_sketch_pairs_place;k_sketch_pairs<emit>", with "+k_sketch_pairs_scan" in front of the
  * place launch beyond 2^20 (row, run) entries; "hipMemsetAsync" for an empty side); "" for sizes or a `segments` the calls refuse. */
 const char *bsq_sketch_pairs_kernel_name(int64_t Ba, int64_t Bb, int32_t segments);
+
+/* ---- sketch clusters: the single-linkage clusters of one sketch matrix -- the connected components of the graph whose edges are the
+ * pairs the pair rule passes -- as one label per row: what a leakage-free train / test split is made over (every row of a cluster goes
+ * to one side), computed inside the comparison's tile walk.  No pair list exists at any point, so a store that is one cluster of
+ * 100 000 near-identical rows (5 * 10^9 pairs, 120 GB as a list) costs B int64 labels like any other.
+ *
+ * THE RULE.  a (B, S) is what the comparison takes (BSQ_I32 or BSQ_U64, C-contiguous, the low 32 bits read, 1 <= S <= 2^14; the limits
+ * are the comparison's).  The bsq_sketch_pairs must have upper == 1, anything else is BSQ_ERR_INVALID_ARG.
+ *     link         rows i and j are linked when pass(i, j) of "sketch pairs" holds (pass is symmetric: i < j is all that is looked at).
+ *     labels[i]    (int64, B entries) the smallest row index reachable from i over links.  A row linked to nothing is its own label;
+ *                  labels[labels[i]] == labels[i] and labels[i] <= i always hold.  Single linkage: chains merge, so the two ends of a
+ *                  cluster need not be similar to each other.
+ *     determinism  the labels depend on the matrix and the thresholds alone: not on `segments`, on scheduling or on the order in which
+ *                  links are met.  The CPU twin and the kernels agree bit for bit.
+ * B == 0 is BSQ_OK and writes nothing.  Every call is stream-ordered and never synchronises; a refusal writes nothing and sets
+ * bsq_last_error().
+ *
+ * bsq_sketch_clusters_device: parent_scratch is a caller-owned device int64[B], distinct from labels; it is initialised inside the call
+ * on every call, never assumed clean, and holds nothing of use afterwards.
+ * bsq_sketch_clusters_host: the CPU twin in plain loops (csrc/bsq_sketch_host.cpp) over the shared pass test and union-find text of
+ * csrc/bsq_sketch_dev.h.
+ * bsq_cluster_pairs_device, bsq_cluster_pairs_host: the same labels from an explicit edge list row[k] -- col[k] (int64, n_pairs entries)
+ * over n nodes (n <= 2^31 - 1): how lists are merged -- several thresholds, several sketch widths, a train list and a test list with
+ * offset columns, pairs from elsewhere.  An entry with row == col is ignored, so the zeros behind a list cut at max_pairs are harmless;
+ * an entry with an index outside 0 .. n - 1 is ignored too and never dereferenced.  n == 0 is BSQ_OK and writes nothing.
+ *
+ * Kernels: k_cluster_init (parent[i] <- i), one link launch, k_cluster_labels (labels[i] <- the root of i; the kernel boundary makes
+ * parent final).  k_sketch_link<T> has k_sketch_pairs' geometry -- a workgroup per (strip, run) walks upper tiles in ascending j with
+ * the same staging and register tile, the diagonal tile keeps j > i -- and every passing (i, j) is a union in a lock-free union-find
+ * over parent: find both roots, stop if they are equal, else compare-and-swap the LARGER root's parent from itself to the smaller
+ * root, and go round again when the swap fails.  parent[x] <= x always holds, which rules out cycles and makes the last root the
+ * component's smallest member whatever the interleaving.  No lane waits for another lane, wave or workgroup: there is no lock, no
+ * flag and no grid-wide barrier, and every retry follows a swap that failed because another union succeeded.  Every access to parent
+ * inside the link launch is an agent-scope relaxed atomic on the global address space (loads, path-halving stores, swaps): per-XCD
+ * L2s are not coherent with each other and a CU's L1 is never refreshed by other CUs' stores.  A tile without a hit costs one barrier.
+ * For a tile with hits the workgroup first finds the root of each of its 64 rows and 64 columns once (128 finds, kept in LDS); a hit
+ * whose two cached roots are equal is dropped without touching global memory, the others are united in a union-find of the tile's 128
+ * nodes in LDS, and each node that ends below another hands one union of the two cached roots to global memory: at most 127 per tile,
+ * none in a store that is one component already.  k_cluster_link_pairs: the same union, an edge per lane.
+ * Measured on an MI355X, int32 sketches, min_jaccard 0.5, buffers alternating, whole calls (scripts/sketch_clusters_lab.py,
+ * profiles/r21/sketch_clusters_lab.txt), against the count call of the pair list alone on the same input and against the composition
+ * sketch_pairs (count + emit) -> label propagation in torch, scatter_reduce(amin) over both directions of the list until nothing
+ * changes (equal labels).  Random reads with 3 % planted near-duplicates: 4096 x 128: 153 us, 0.88x the count call, 0.35x the
+ * composition; 8192 x 1024: 6.47 ms, 1.00x and 0.51x; 131 072 x 128: 155 ms, 1.01x and 0.50x; 262 144 x 128: 417 ms, 1.00x and 0.50x --
+ * the walk of the tiles is all the call costs, the unions are not seen, and the call takes half of what listing the pairs takes before
+ * anything is done with them.  One row repeated (every pair passes, one cluster): 188 us, 6.62 ms, 174 ms and 474 ms, 1.07x, 1.01x, 1.11x
+ * and 1.13x the count call: where the call is slowest, it pays an eighth over the bare walk for 128 finds per tile.  There the
+ * composition exists only while its list fits -- 4096 rows (8.4 M pairs): 6.1 ms, 33x the call; 8192 rows (33.6 M pairs): 33 ms, 5x --
+ * and stops at 131 072 rows, whose list would be 172 GB.  No counters-only run was taken.
+ *
+ * Known answers (the plain sketches of the MinHash section's batch: rows 0 and 1 equal, rows 2 and 3 EMPTY throughout, row 4 on its own):
+ *     min_match 1, jaccard_q16 32768    labels 0 0 2 3 4
+ *     min_match 0, jaccard_q16 65536    labels 0 0 2 2 4
+ *     min_match 0, jaccard_q16 0        labels 0 0 0 0 0 */
+bsq_status bsq_sketch_clusters_device(const void *a, int64_t B, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule, int64_t *parent_scratch,
+                                      int64_t *labels, void *hip_stream);
+bsq_status bsq_sketch_clusters_host(const void *a, int64_t B, int64_t S, bsq_dtype t, const bsq_sketch_pairs *rule, int64_t *labels);
+bsq_status bsq_cluster_pairs_device(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, int64_t *parent_scratch, int64_t *labels,
+                                    void *hip_stream);
+bsq_status bsq_cluster_pairs_host(const int64_t *row, const int64_t *col, int64_t n_pairs, int64_t n, int64_t *labels);
+/* Host only: the launches of bsq_sketch_clusters_device joined by '+' ("k_cluster_init+k_sketch_link+k_cluster_labels"); "" for B == 0,
+ * which launches nothing, and for sizes or a `segments` the call refuses. */
+const char *bsq_sketch_clusters_kernel_name(int64_t B, int32_t segments);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
