@@ -47,7 +47,7 @@ __device__ __forceinline__ uint32_t entry_of(const DParams &p, const uint16_t *s
     case 4: v = static_cast<int32_t>(*reinterpret_cast<const uint32_t *>(a)); break;
     default: v = static_cast<int32_t>(static_cast<uint32_t>(*reinterpret_cast<const uint64_t *>(a))); break;
     }
-    const int32_t idx = v - kTabLo;
+    const int64_t idx = static_cast<int64_t>(v) - kTabLo;  // (in int32, v - kTabLo overflows for v >= 2^31 - 128)
     return (idx >= 0 && idx < kTabN) ? s_tab[idx] : 0xFFFFu;
 }
 
