@@ -80,6 +80,11 @@ class SketchPairs(ctypes.Structure):
     _fields_ = [("min_match", ctypes.c_int32), ("jaccard_q16", ctypes.c_int32), ("upper", ctypes.c_int32), ("segments", ctypes.c_int32)]
 
 
+class Edit(ctypes.Structure):
+    """struct bsq_edit"""
+    _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -212,6 +217,9 @@ def load():
         "bsq_cluster_pairs_device": (i32, [vp, vp, i64, i64, vp, vp, vp]),
         "bsq_cluster_pairs_host": (i32, [vp, vp, i64, i64, vp]),
         "bsq_sketch_clusters_kernel_name": (ctypes.c_char_p, [i64, i32]),
+        "bsq_edit_pairs_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp, vp]),
+        "bsq_edit_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp]),
+        "bsq_edit_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Edit)]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -45,8 +45,8 @@ extern "C" {
                            * bsq_minhash, bsq_minhash_device, bsq_minhash_host, bsq_minhash_kernel_name, bsq_sketch_compare_device,
                            * bsq_sketch_compare_host, bsq_sketch_pairs, bsq_sketch_pairs_segments, bsq_sketch_pairs_count_device,
                            * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name, bsq_sketch_clusters_device,
-                           * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name;
-                           * nothing removed */
+                           * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name,
+                           * bsq_edit, bsq_edit_pairs_device, bsq_edit_pairs_host, bsq_edit_pairs_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -842,6 +842,74 @@ bsq_status bsq_cluster_pairs_host(const int64_t *row, const int64_t *col, int64_
 /* Host only: the launches of bsq_sketch_clusters_device joined by '+' ("k_cluster_init+k_sketch_link+k_cluster_labels"); "" for B == 0,
  * which launches nothing, and for sizes or a `segments` the call refuses. */
 const char *bsq_sketch_clusters_kernel_name(int64_t B, int32_t segments);
+
+/* ---- edit distance of row pairs: the exact unit-cost edit distance of listed pairs of rows of resident packed stores, one launch --
+ * the alignment step that follows a k-mer filter (cd-hit, mmseqs cluster): a candidate list of "sketch pairs" becomes a list verified
+ * at a sequence identity, which bsq_cluster_pairs_device turns into labels, without a character leaving the device.
+ *
+ * THE RULE.  Store A is (chars_a, offsets_a, Ba), store B (chars_b, offsets_b, Bb): packed batches as everywhere else (uint8
+ * characters, int64 offsets with B + 1 entries; a length read as negative counts as 0).  B may be the same store as A.  row[k] (an
+ * index into A) and col[k] (into B) are int64 arrays of n_pairs entries; dist[k] is int32.
+ *     class        of a byte: d->lut[byte] where that is >= 0, otherwise d->nchars -- every unmapped byte shares one extra class.  Two
+ *                  characters are equal when their classes are: case and alias groups fold as the tokenizer folds them, N equals N in
+ *                  DNA4 (and '-', and every other unmapped byte), and dist of a row with itself is 0 whatever it holds.
+ *     dist[k]      the Levenshtein distance between the class strings of row row[k] of A and row col[k] of B: substitution, insertion
+ *                  and deletion cost 1 each, the alignment is global; BOS, EOS and PAD play no part (d->bos, eos, padchar are not read).
+ *     max_len      1 .. 4096: the caller's bound on the SHORTER side of every pair.  A pair with min(la, lb) > max_len gets
+ *                  dist = BSQ_EDIT_TOO_LONG (-1).  The longer side may have any length up to 2^31 - 2 (beyond: -1 as well).  The
+ *                  shorter side is the pattern (A's row when the lengths are equal); the distance is symmetric, so the result does
+ *                  not depend on which store holds it.
+ *     bad index    row[k] outside 0 .. Ba - 1 or col[k] outside 0 .. Bb - 1: dist = BSQ_EDIT_BAD_INDEX (-2); such an index is never
+ *                  dereferenced.  The zeros behind a list cut at max_pairs are the valid pair (0, 0).
+ *     form         lanes per pair and the longest shorter side they hold: 1: 4 lanes, 256; 2: 16 lanes, 1024; 3: 64 lanes, 4096;
+ *                  0: the smallest form that holds max_len.  A forced form that cannot hold max_len is BSQ_ERR_INVALID_ARG.  The
+ *                  result never depends on the form.
+ *     identity     (for callers; bioseq_amd.align.verify_pairs) with L = max(la, lb) and T = floor(min_identity * 65536 + 0.5) a pair
+ *                  passes when dist >= 0 and dist * 65536 <= (65536 - T) * L, in 64-bit integers: 1 - dist / L >= min_identity.  Two
+ *                  empty rows pass any threshold.
+ * Limits: an alphabet of 1 .. 30 classes (every key but BYTES: the tables of a workgroup's four waves, (nchars + 1) x 64 words each, fit
+ * the 64 KiB of LDS a launch gets without asking), Ba, Bb, n_pairs <= 2^31 - 1; anything else, a null pointer that would be read and a
+ * bsq_edit outside the rules above are BSQ_ERR_INVALID_ARG.  A null bsq_edit means {4096, 0}.  n_pairs == 0 is BSQ_OK and writes
+ * nothing.  The device call is stream-ordered and never synchronises; a refusal writes nothing and sets bsq_last_error().
+ *
+ * Kernels: k_edit_pairs<4 | 16 | 64>, Myers' bit-vector algorithm in Hyyro's blocked form (csrc/bsq_edit_dev.h has the block step, the
+ * text the CPU twin runs in plain loops).  The pattern is cut into blocks of 64 characters; lane b of the pair's group of G lanes owns
+ * block b -- its vertical deltas in registers, its column of the pair's match table ((nchars + 1) x G 64-bit words in LDS, laid out
+ * [class][lane], written by plain read-modify-write of the owning lane alone).  The group walks anti-diagonals: at step t lane b
+ * takes text column t - b, so a pair costs n + blocks - 1 steps and a wave (64 / G pairs) runs until its slowest group is done, the
+ * others masked off.  The text is fetched G characters at a time, a byte per lane, one tile ahead of its use, and mapped to classes
+ * once; the class of a column and the horizontal delta that leaves a block travel up the lanes together in one 32-bit value, one
+ * ds_bpermute per step, which also feeds lane 0 from the tile.  No global atomic, no barrier after the byte table is staged, no
+ * waiting on other waves.  A step is one dependent chain of about twenty 64-bit operations and one LDS read, so resident waves are
+ * what hides it: DNA4 (5 classes) takes 10.3 KiB of LDS per workgroup, AMINO20 (21 classes) 42.3 KiB.
+ * Measured on an MI355X, whole calls, buffers alternating, seeded random rows (scripts/edit_distance_lab.py,
+ * profiles/r22/edit_distance_lab.txt; a cell is one entry of a pair's la x lb table): 1 048 576 pairs of 150-character DNA4 reads,
+ * form 1: 870 us, 1.2 G pairs and 27 T cells per second; 262 144 pairs of AMINO20 rows of 50 .. 1024 residues, form 3: 18.9 ms, 13.8 M
+ * pairs and 4.0 T cells per second -- such rows keep 1 .. 16 of the 64 lanes busy -- and with max_len = 1024, form 2: 5.65 ms, 46 M pairs
+ * and 13.4 T cells per second; 4096 pairs of 4096 x 4096, form 3 with every lane busy: 1.61 ms, 42.7 T cells per second.  The host twin
+ * on one thread runs 20 - 28 G cells per second on a 1/64 sample of the same lists (for scale).  Two sessions agree within 0.4 %.  No
+ * counters-only run was taken.
+ *
+ * Known answers (the plain dynamic programme, not the kernel; DNA4; the batch ACGTAC, ACGNACGT, AC, "", TTTTTTT as A and as B):
+ *     dist of every (i, j)     0 3 4 6 6 / 3 0 6 8 7 / 4 6 0 2 7 / 6 8 2 0 7 / 6 7 7 7 0
+ *     acgtNN- against ACGTnxA  1 (case folds; N, -, n, x share the unmapped class; only '-' against A differs)
+ *     max_len = 5, pair (0, 1) -1 (both sides longer than 5);  pair (0, 2): 4 (the shorter side, AC, fits);  row = 5 or col = -1: -2
+ *     identity, pair (0, 1)    dist 3, L 8: passes min_identity 0.625 (3 * 65536 == (65536 - 40960) * 8) and fails at T = 40961 */
+#define BSQ_EDIT_TOO_LONG (-1)
+#define BSQ_EDIT_BAD_INDEX (-2)
+typedef struct bsq_edit {
+    int32_t max_len; /* 1 .. 4096: the bound on the shorter side of every pair */
+    int32_t form;    /* 0: the library chooses; 1, 2, 3: 4, 16, 64 lanes per pair */
+} bsq_edit;
+bsq_status bsq_edit_pairs_device(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                                 const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_edit *e,
+                                 int32_t *dist, void *hip_stream);
+/* CPU twin on host buffers (the same class and block-step text; no device is needed). */
+bsq_status bsq_edit_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                               const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_edit *e,
+                               int32_t *dist);
+/* Host only: the kernel the device call takes ("k_edit_pairs<4>", "k_edit_pairs<16>", "k_edit_pairs<64>"); "" for a bsq_edit it refuses. */
+const char *bsq_edit_pairs_kernel_name(const bsq_edit *e);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
