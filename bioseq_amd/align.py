@@ -14,6 +14,17 @@ groups fold as the tokenizer folds them, `N` equals `N` in DNA4.  include/bsq.h 
 * `edit_distance_host`, `edit_kernel_name`    the library's CPU twin (numpy), the kernel taken;
 * `pair_lengths`, `pair_identity`    (la, lb) of the listed pairs; 1 - dist / max(la, lb) as float32;
 * `verify_pairs`, `verify_pairs_host`    (keep, dist): keep[k] <=> identity >= min_identity, decided in integers.
+
+For proteins the measure is a scored alignment (`bsq_score_pairs_device`; include/bsq.h, "scored alignment of row pairs"): Gotoh's
+algorithm with a substitution matrix over the classes and affine gap costs, local or global.
+
+    S = align.blosum62_matrix(tok)
+    keep, score = align.verify_score_pairs(tok, chars, offsets, row, col, matrix=S, gap_open=11, gap_extend=1, min_ratio=0.5)
+
+* `score_matrix`, `blosum62_matrix`    match / mismatch and BLOSUM62 matrices over a tokenizer's classes (int8 numpy);
+* `score_pairs`, `score_pairs_host`, `score_kernel_name`    score (int32), optionally the ends of the best cell; the CPU twin; the kernel;
+* `self_scores`    the perfect score of every row, int64;
+* `verify_score_pairs`, `verify_score_pairs_host`    (keep, score): keep[k] <=> score / min(self_a, self_b) >= min_ratio, in integers.
 """
 from __future__ import annotations
 
@@ -170,5 +181,188 @@ def verify_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *,
     return (dist >= 0) & (dist.to(torch.int64) * 65536 <= (65536 - T) * L), dist
 
 
+# ---- scored alignment of row pairs (include/bsq.h, "scored alignment of row pairs")
+
+SCORE_TOO_LONG, SCORE_BAD_INDEX = -2**31 + 1, -2**31 + 2
+CODE_BELOW = -2**30  # every score <= this is a code
+_MODES = {"local": 0, "global": 1}
+_BLOSUM_LETTERS = "ARNDCQEGHILKMFPSTWYV"
+
+
+def score_matrix(tok, match, mismatch):
+    """The (C + 1, C + 1) int8 matrix with `match` where two classes are equal (the unmapped class against itself included) and
+    `mismatch` elsewhere; C is the number of classes of the tokenizer's alphabet."""
+    C = capi.desc_of(tok).nchars
+    for v in (match, mismatch):
+        if isinstance(v, bool) or int(v) != v or not -128 <= int(v) <= 127:
+            raise ValueError("match and mismatch are integers in -128 .. 127")
+    m = np.full((C + 1, C + 1), int(mismatch), np.int8)
+    np.fill_diagonal(m, int(match))
+    return m
+
+
+def blosum62_matrix(tok):
+    """BLOSUM62 over the tokenizer's classes as a (21, 21) int8 matrix: the 20 letters on the classes the tokenizer gives them, the
+    unmapped class on the X row and column (X / X = -1).  ValueError unless the alphabet has 20 classes and the letters land on 20
+    distinct ones."""
+    desc = capi.desc_of(tok)
+    cls = [desc.lut[ord(c)] for c in _BLOSUM_LETTERS]
+    if desc.nchars != 20 or min(cls) < 0 or len(set(cls)) != 20:
+        raise ValueError("blosum62_matrix needs an alphabet whose 20 classes are the 20 amino acids, got %r" % (tok.key,))
+    raw = np.zeros((21, 21), np.int8)
+    capi.check(_lib.bsq_blosum62_scores(raw.ctypes.data))
+    at = np.array(cls + [20])
+    out = np.empty((21, 21), np.int8)
+    out[np.ix_(at, at)] = raw
+    return out
+
+
+def _score(tok, matrix, gap_open, gap_extend, mode, max_len, form):
+    """(desc, bsq_score) with the library's argument rules applied as ValueError (no device is touched)."""
+    desc, e = _edit(tok, max_len, form)
+    if mode not in _MODES:
+        raise ValueError("mode is 'local' or 'global', got %r" % (mode,))
+    for name, v in (("gap_open", gap_open), ("gap_extend", gap_extend)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 127:
+            raise ValueError("%s must be an integer in 0 .. 127, got %r" % (name, v))
+    m = np.asarray(matrix)
+    C = desc.nchars + 1
+    if m.dtype.kind not in "iu" or m.shape != (C, C) or m.min() < -128 or m.max() > 127:
+        raise ValueError("matrix is a (%d, %d) integer array of int8 values (classes of %r and the unmapped one)" % (C, C, tok.key))
+    s = capi.Score(e.max_len, e.form, _MODES[mode], int(gap_open), int(gap_extend))
+    np.ctypeslib.as_array(s.matrix)[:C, :C] = m.astype(np.int8)
+    if not _lib.bsq_score_pairs_kernel_name(ctypes.byref(s), 0):  # (whatever the rules above do not restate)
+        raise ValueError("the library refuses these arguments (include/bsq.h, \"scored alignment of row pairs\")")
+    return desc, s
+
+
+def score_kernel_name(*, mode="local", ends=False, max_len=MAX_LEN, form=None, gap_open=0, gap_extend=0):
+    """The kernel `score_pairs` takes (host only: profiling labels, tests); "" for what the library refuses."""
+    s = capi.Score(int(max_len), 0 if form is None else int(form), _MODES.get(mode, -1), int(gap_open), int(gap_extend))
+    return _lib.bsq_score_pairs_kernel_name(ctypes.byref(s), int(bool(ends))).decode()
+
+
+def score_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local", ends=False,
+                     max_len=MAX_LEN, form=None):
+    """The library's CPU twin (`bsq_score_pairs_host`: the cell of the kernels in plain loops) on numpy arrays: score as an int32
+    array, or (score, ends) with ends int32 of shape (n, 2); every argument means what it means to `score_pairs`."""
+    desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, form)
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    row, col = _host_lists(row, col)
+    ca, oa = capi.host_batch(chars, offsets)
+    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
+    score = np.empty(row.size, np.int32)
+    en = np.empty((row.size, 2), np.int32) if ends else None
+    if row.size:
+        capi.check(_lib.bsq_score_pairs_host(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
+                                             row.ctypes.data, col.ctypes.data, row.size, ctypes.byref(s), score.ctypes.data,
+                                             en.ctypes.data if ends else None))
+    return (score, en) if ends else score
+
+
+def score_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local", ends=False,
+                max_len=MAX_LEN, form=None):
+    """score[k] = the alignment score of row row[k] of the store (chars, offsets) and row col[k] of the store (chars_b, offsets_b) -- the
+    same store when those are None -- by Gotoh's algorithm: an int32 device tensor on torch's current stream, one launch, nothing read
+    back.  With ends=True, (score, ends) with ends int32 of shape (n, 2): (end_a, end_b) of the best cell.
+
+    matrix[class of A's character][class of B's character] is a (C + 1, C + 1) integer array of int8 values (`score_matrix`,
+    `blosum62_matrix`); a gap of L characters costs gap_open + L * gap_extend (BLAST's 11 / 1 is gap_open=11, gap_extend=1).  mode:
+    "local" (Smith-Waterman: max(0, best cell); ends of the first best cell, smallest end_a then end_b, (0, 0) for score 0) or
+    "global" (Needleman-Wunsch; ends (la, lb)).  Stores, lists, max_len and form as for `edit_distance_pairs`; the longer side may
+    have up to 2^20 characters.  Codes: `SCORE_TOO_LONG`, `SCORE_BAD_INDEX` (every score <= `CODE_BELOW` is one), ends (-1, -1)."""
+    import torch
+    desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, form)
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    what = "score_pairs works on packed batches resident on the device (chars, offsets tensors)"
+    Ba = capi.packed_on_device(chars, offsets, what)
+    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, what)
+    if chars_b is not None and chars_b.device != chars.device:
+        raise ValueError("both stores must live on one device")
+    _device_lists(row, col, chars.device)
+    score = torch.empty(row.numel(), dtype=torch.int32, device=chars.device)
+    en = torch.empty((row.numel(), 2), dtype=torch.int32, device=chars.device) if ends else None
+    if row.numel():
+        ca = capi.readable_chars(chars, chars.device)  # (every row may be empty)
+        cb = ca if chars_b is None else capi.readable_chars(chars_b, chars.device)
+        ob = offsets if offsets_b is None else offsets_b
+        with capi.launching(chars.device) as stream:
+            capi.check(_lib.bsq_score_pairs_device(ctypes.byref(desc), ca.data_ptr(), offsets.data_ptr(), Ba, cb.data_ptr(), ob.data_ptr(), Bb,
+                                                   row.data_ptr(), col.data_ptr(), row.numel(), ctypes.byref(s), score.data_ptr(),
+                                                   en.data_ptr() if ends else None, stream))
+    return (score, en) if ends else score
+
+
+def self_scores(tok, chars, offsets, matrix):
+    """The score of every row against itself with no gap -- the sum of matrix[c][c] over the row's classes -- as int64: in torch on the
+    device for tensors (class table -> diagonal -> cumulative sum -> difference at the offsets, nothing read back), in numpy for arrays."""
+    desc = capi.desc_of(tok)
+    m = np.asarray(matrix)
+    if m.shape != (desc.nchars + 1, desc.nchars + 1):
+        raise ValueError("matrix is a (%d, %d) array" % (desc.nchars + 1, desc.nchars + 1))
+    lut = np.array(list(desc.lut), np.int64)
+    per_byte = np.diagonal(m).astype(np.int64)[np.where(lut >= 0, lut, desc.nchars)]  # the self-score of every byte value
+    if isinstance(chars, np.ndarray) or not hasattr(chars, "device"):
+        sums = np.concatenate([np.zeros(1, np.int64), np.cumsum(per_byte[np.asarray(chars, np.uint8).ravel()])])
+        o = np.asarray(offsets, np.int64).ravel()
+        return sums[o[1:]] - sums[o[:-1]]
+    import torch
+    table = torch.from_numpy(per_byte).to(chars.device)
+    sums = torch.cat([torch.zeros(1, dtype=torch.int64, device=chars.device), torch.cumsum(table[chars.to(torch.int64)], 0)])
+    return sums[offsets[1:]] - sums[offsets[:-1]]
+
+
+def _valid_take(xp, values, idx):
+    """values[idx], 0 where idx lies outside values (numpy or torch by `xp`)."""
+    if values.shape[0] == 0:
+        return xp.zeros_like(idx)
+    ok = (idx >= 0) & (idx < values.shape[0])
+    return xp.where(ok, values[xp.where(ok, idx, xp.zeros_like(idx))], xp.zeros_like(idx))
+
+
+def _ratio_q16(min_ratio, min_score):
+    if not 0.0 <= float(min_ratio) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError("min_ratio must lie in 0 .. 1, got %r" % (min_ratio,))
+    if isinstance(min_score, bool) or int(min_score) != min_score:
+        raise ValueError("min_score is an integer, got %r" % (min_score,))
+    return int(float(min_ratio) * 65536 + 0.5), int(min_score)
+
+
+def _score_keep(xp, score64, self_a, self_b, T, min_score):
+    least = xp.minimum(self_a, self_b)
+    return (score64 > CODE_BELOW) & (score64 >= min_score) & (least > 0) & (score64 * 65536 >= T * least)
+
+
+def verify_score_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                            min_ratio=0.5, min_score=1, max_len=MAX_LEN):
+    """`verify_score_pairs` on numpy arrays through the CPU twin: (keep, score) as numpy arrays, the same bits."""
+    T, min_score = _ratio_q16(min_ratio, min_score)
+    score = score_pairs_host(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend, mode=mode,
+                             max_len=max_len)
+    row, col = _host_lists(row, col)
+    sa = self_scores(tok, np.asarray(chars, np.uint8), offsets, matrix)
+    sb = sa if chars_b is None else self_scores(tok, np.asarray(chars_b, np.uint8), offsets_b, matrix)
+    return _score_keep(np, score.astype(np.int64), _valid_take(np, sa, row), _valid_take(np, sb, col), T, min_score), score
+
+
+def verify_score_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                       min_ratio=0.5, min_score=1, max_len=MAX_LEN):
+    """(keep, score) of a candidate list: score as `score_pairs` gives it, and keep[k] (bool) true when the score is no code, reaches
+    min_score, and its ratio to the perfect score of the weaker row reaches min_ratio: with least = min(self_a, self_b) of
+    `self_scores`, least > 0 and score * 65536 >= T * least, T = floor(min_ratio * 65536 + 0.5), in 64-bit integers, in torch on the
+    device, nothing read back -- `verify_score_pairs_host` keeps the same pairs bit for bit.  `row[keep]`, `col[keep]` is the verified
+    list, which `sketch.cluster_pairs` takes."""
+    import torch
+    T, min_score = _ratio_q16(min_ratio, min_score)
+    score = score_pairs(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend, mode=mode,
+                        max_len=max_len)
+    sa = self_scores(tok, chars, offsets, matrix)
+    sb = sa if chars_b is None else self_scores(tok, chars_b, offsets_b, matrix)
+    return _score_keep(torch, score.to(torch.int64), _valid_take(torch, sa, row), _valid_take(torch, sb, col), T, min_score), score
+
+
 __all__ = ["TOO_LONG", "BAD_INDEX", "MAX_LEN", "edit_distance_pairs", "edit_distance_host", "edit_kernel_name", "pair_lengths", "pair_identity",
-           "verify_pairs", "verify_pairs_host"]
+           "verify_pairs", "verify_pairs_host", "SCORE_TOO_LONG", "SCORE_BAD_INDEX", "CODE_BELOW", "score_matrix", "blosum62_matrix", "score_pairs",
+           "score_pairs_host", "score_kernel_name", "self_scores", "verify_score_pairs", "verify_score_pairs_host"]

@@ -85,6 +85,12 @@ class Edit(ctypes.Structure):
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32)]
 
 
+class Score(ctypes.Structure):
+    """struct bsq_score"""
+    _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32), ("mode", ctypes.c_int32), ("gap_open", ctypes.c_int32),
+                ("gap_extend", ctypes.c_int32), ("matrix", (ctypes.c_int8 * 32) * 32)]
+
+
 class Batch(ctypes.Structure):
     """struct bsq_batch: one packed batch of a multi-batch call (device pointers)"""
     _fields_ = [("chars", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("B", ctypes.c_int64), ("out", ctypes.c_void_p)]
@@ -220,6 +226,10 @@ def load():
         "bsq_edit_pairs_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp, vp]),
         "bsq_edit_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp]),
         "bsq_edit_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Edit)]),
+        "bsq_score_pairs_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp, vp]),
+        "bsq_score_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp]),
+        "bsq_score_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Score), c_int]),
+        "bsq_blosum62_scores": (i32, [vp]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

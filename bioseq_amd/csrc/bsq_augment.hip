@@ -171,6 +171,14 @@ bsq_status bsq_blosum62_normrows(double *out21x20) {
     return BSQ_OK;
 }
 
+// the scores themselves, 21 x 21: the X column is the X row (the matrix is symmetric), X against X is -1
+bsq_status bsq_blosum62_scores(int8_t *out21x21) {
+    if (!out21x21) return BSQ_ERR_INVALID_ARG;
+    for (int r = 0; r < kRows; ++r)
+        for (int c = 0; c < kRows; ++c) out21x21[r * kRows + c] = c < kCols ? kBlosum62[r][c] : (r < kCols ? kBlosum62[kRows - 1][r] : int8_t(-1));
+    return BSQ_OK;
+}
+
 bsq_status bsq_augment_device(uint8_t *chars, const int64_t *offsets, int64_t B, int32_t chain_len, double frac,
                               uint64_t seed, void *hip_stream) {
     if (!offsets || B < 0 || chain_len < 0) return bsq_internal::set_error(BSQ_ERR_INVALID_ARG, "bad augment arguments");

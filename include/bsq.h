@@ -46,7 +46,8 @@ extern "C" {
                            * bsq_sketch_compare_host, bsq_sketch_pairs, bsq_sketch_pairs_segments, bsq_sketch_pairs_count_device,
                            * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name, bsq_sketch_clusters_device,
                            * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name,
-                           * bsq_edit, bsq_edit_pairs_device, bsq_edit_pairs_host, bsq_edit_pairs_kernel_name; nothing removed */
+                           * bsq_edit, bsq_edit_pairs_device, bsq_edit_pairs_host, bsq_edit_pairs_kernel_name, bsq_score, bsq_score_pairs_device,
+                           * bsq_score_pairs_host, bsq_score_pairs_kernel_name, bsq_blosum62_scores; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -910,6 +911,96 @@ bsq_status bsq_edit_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const 
                                int32_t *dist);
 /* Host only: the kernel the device call takes ("k_edit_pairs<4>", "k_edit_pairs<16>", "k_edit_pairs<64>"); "" for a bsq_edit it refuses. */
 const char *bsq_edit_pairs_kernel_name(const bsq_edit *e);
+
+/* ---- scored alignment of row pairs: Gotoh's algorithm -- a substitution matrix over the tokenizer's classes and affine gap costs -- as
+ * a local (Smith-Waterman) or global (Needleman-Wunsch) score of listed pairs of rows of resident packed stores, one launch, nothing
+ * read back.  The measure protein tools accept a pair by (cd-hit, mmseqs cluster), where the unit-cost edit distance above is the one
+ * for DNA reads.
+ *
+ * THE RULE.  Stores, pair lists, the class of a byte (d->lut[byte], every unmapped byte in the extra class d->nchars), max_len and form
+ * mean exactly what they mean for bsq_edit_pairs_device.  x = A's row (la characters), y = B's row (lb), o = gap_open,
+ * e = gap_extend, S = matrix, indexed [class of A's character][class of B's character]; entries at an index > nchars are not read.
+ * A gap of L characters costs o + L * e (BLAST's 11 / 1 is {11, 1}).
+ *     E[i][j] = max(E[i][j-1], H[i][j-1] - o) - e
+ *     F[i][j] = max(F[i-1][j], H[i-1][j] - o) - e
+ *     H[i][j] = max(H[i-1][j-1] + S[x_i][y_j], E[i][j], F[i][j])          and also 0 in local mode
+ *     global boundaries   H[0][0] = 0, H[i][0] = -(o + i e), H[0][j] = -(o + j e), E[i][0] = F[0][j] = minus infinity
+ *     local boundaries    every boundary H is 0 (E and F as above)
+ *     score        global: H[la][lb];  local: max(0, max H)
+ *     ends         ends[k] = (end_a, end_b), the characters of each row up to and including the best cell.  Among the cells that reach
+ *                  the maximum: the smallest end_a, then the smallest end_b.  A score of 0 has ends (0, 0); in global mode the ends are
+ *                  (la, lb); a pair that gets a code has (-1, -1).  ends may be null: nothing but score is written then.
+ *     codes        global scores are negative, so the codes sit at the bottom of the range: BSQ_SCORE_TOO_LONG (INT32_MIN + 1) where
+ *                  the shorter side exceeds max_len or the longer side 2^20; BSQ_SCORE_BAD_INDEX (INT32_MIN + 2) for an index outside
+ *                  its store, which is never dereferenced.  Every value <= -2^30 is a code.
+ *     range        with |S| <= 128, o and e <= 127, a shorter side <= 4096 and a longer side <= 2^20 every real cell has |H| < 2^27.
+ *                  Minus infinity is -2^29: it only decays, by at most 127 a step, so it never wraps and never overtakes a real
+ *                  value.  The kernels and the twin compute in plain int32 with no saturation.
+ *     symmetry     score(A, B; S) = score(B, A; S transposed), with the ends swapped wherever one cell alone reaches the maximum (among
+ *                  several, each call takes the smallest end in ITS store A first).  The shorter row is the pattern (A's when the
+ *                  lengths are equal) and S is read accordingly, so the result does not depend on which store holds it.
+ * Limits and refusals are the edit distance's (1 .. 30 classes, Ba, Bb, n_pairs <= 2^31 - 1, null pointers that would be read); a null
+ * bsq_score, a mode outside 0 .. 1, a gap cost outside 0 .. 127, and a max_len or form the edit distance refuses are
+ * BSQ_ERR_INVALID_ARG and write nothing.  n_pairs == 0 is BSQ_OK.  The device call is stream-ordered and never synchronises.
+ *
+ * Kernels: k_score_pairs<4 | 16 | 64, global | local | local+ends> (csrc/bsq_score.hip; csrc/bsq_score_dev.h has the cell, the text the
+ * CPU twin runs in plain loops).  The edit kernel's skeleton: lane b of a pair's group owns pattern rows 64 b + 1 .. 64 b + 64, the
+ * group walks anti-diagonals, the text comes a tile ahead and is mapped to classes once.  A lane keeps H[i][j-1] and E[i][j-1] of its
+ * 64 rows in 128 registers, ALL 64 rows in one pass (no form is narrowed), and the rows' classes packed four to a register; the
+ * diagonal, H above and F run down the rows as scalars.  The bottom row's H and F and the column's class move up one lane per step in
+ * three ds_bpermute (per 64 cells; the class shares its word with the tile's class for lane 0, as in the edit kernel).  The substitution
+ * score is one LDS byte per cell from a 32 x 32 table at [column class][row class], staged once per workgroup in both orientations.  A
+ * step's cells run under the wave's execution mask, not as selects: a lane outside its columns skips them.  Ends: one max per cell
+ * over keys (H << 6) | (63 - row), one comparison per lane and column, one reduction per group under the tie rule, in the local+ends
+ * instantiation only; ends = NULL and global mode pay nothing.
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / LDS bytes / scratch bytes, the range over G = 4, 16, 64):
+ * global 224 - 225 / 2304 / 0, local 225 - 228 / 2304 / 0,
+ * local+ends 230 - 233 / 2304 / 0: two waves per SIMD, no scratch in any of the nine instantiations.
+ *
+ * Measured on an MI355X, whole calls, buffers alternating, seeded random rows (scripts/score_pairs_lab.py,
+ * profiles/r23/score_pairs_lab.txt; a cell is one entry of a pair's la x lb table; local / local+ends / global, then the edit distance
+ * on the same lists): 1 048 576 pairs of 150-character DNA4 reads, +2 / -3 {5, 2}, form 1: 11.5 / 12.9 / 10.0 ms, 2.0 / 1.8 / 2.4 T cells
+ * per second (edit distance 0.87 ms); 262 144 pairs of AMINO20 rows of 50 .. 1024 residues, BLOSUM62 {11, 1}, form 3: 254 / 280 / 223 ms,
+ * 0.30 / 0.27 / 0.34 T cells per second -- such rows keep 1 .. 16 of the 64 lanes busy -- and with max_len = 1024, form 2: 73.9 / 82.2 /
+ * 64.1 ms, 3.5 M pairs and 1.0 / 0.92 / 1.2 T cells per second (edit distance 19.0 and 5.7 ms); 4096 pairs of 4096 x 4096, form 3 with
+ * every lane busy: 21.0 / 23.1 / 18.1 ms, 3.3 / 3.0 / 3.8 T cells per second (edit distance 1.6 ms: a bit per cell against two words).
+ * The host twin on one thread runs 0.17 - 0.68 G cells per second on a 1/64 sample of the same lists (for scale).  What bounds the
+ * kernel is vector issue, not the LDS byte reads: the 64-cell block of a step is 645 / 750 / 824 vector instructions (global / local /
+ * local+ends: 10 - 13 per cell, four of them the subtractions of the gap costs) beside 64 LDS reads, and the measured 2650 / 3070 /
+ * 3370 cycles per step of a full wave at 2.4 GHz are those counts times the four cycles a wave's vector instruction takes.  No
+ * counters-only run was taken, and no cheaper lookup was tried: the reads are not the limit.
+ *
+ * Known answers (a cell-by-cell Gotoh programme, not the kernel).  DNA4, the batch ACGTAC, ACGNACGT, AC, "", TTTTTTT as A and as B,
+ * S = +2 where the classes are equal (N / N = +2) and -3 otherwise, {5, 2}:
+ *     global score of every (i, j)    12 -2 -9 -17 -20 / -2 16 -13 -21 -23 / -9 -13 4 -9 -21 / -17 -21 -9 0 -19 / -20 -23 -21 -19 14
+ *     local (score, end_a, end_b)     row 0: (12,6,6) (8,4,8) (4,2,2) (0,0,0) (2,4,1)    row 1: (8,8,4) (16,8,8) (4,2,2) (0,0,0) (2,8,1)
+ *                                     row 2: (4,2,2) (4,2,2) (4,2,2) (0,0,0) (0,0,0)     row 3: all (0,0,0)
+ *                                     row 4: (2,1,4) (2,1,8) (0,0,0) (0,0,0) (14,7,7)
+ *     S = 0 / -1, {0, 1}, global      minus the edit distance: minus the matrix printed in the section above
+ * BLOSUM62 (bsq_blosum62_scores), A = HEAGAWGHEE, B = PAWHEAE:  {11, 1}: local 17, ends (3, 6), global 1;  {0, 8}: local 20, ends
+ * (9, 5), global -8.  Swapping the stores swaps the ends.  The self-scores (the sum of S[c][c] over a row) are 62 and 44. */
+#define BSQ_SCORE_TOO_LONG (INT32_MIN + 1)
+#define BSQ_SCORE_BAD_INDEX (INT32_MIN + 2)
+typedef struct bsq_score {
+    int32_t max_len;        /* 1 .. 4096: the bound on the SHORTER side of every pair */
+    int32_t form;           /* 0: the library chooses; 1, 2, 3: 4, 16, 64 lanes per pair (shorter sides up to 256, 1024, 4096) */
+    int32_t mode;           /* 0 local, 1 global */
+    int32_t gap_open;       /* 0 .. 127 */
+    int32_t gap_extend;     /* 0 .. 127: a gap of L characters costs gap_open + L * gap_extend */
+    int8_t matrix[32][32];  /* matrix[class of A's character][class of B's character]; entries at an index > nchars are not read */
+} bsq_score;
+bsq_status bsq_score_pairs_device(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                                  const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_score *s,
+                                  int32_t *score, int32_t *ends /* n_pairs x 2, may be null */, void *hip_stream);
+/* CPU twin on host buffers (the same class and cell text; no device is needed). */
+bsq_status bsq_score_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                                const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_score *s,
+                                int32_t *score, int32_t *ends /* may be null */);
+/* Host only: the kernel the device call takes ("k_score_pairs<16, local+ends>", ...; global mode does not depend on with_ends); "" for a
+ * bsq_score the calls refuse. */
+const char *bsq_score_pairs_kernel_name(const bsq_score *s, int with_ends);
+/* The BLOSUM62 scores as 21 x 21 int8: rows and columns ARNDCQEGHILKMFPSTWYV + X (the table of the augmentation above); X / X = -1. */
+bsq_status bsq_blosum62_scores(int8_t *out21x21);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
