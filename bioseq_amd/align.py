@@ -25,6 +25,18 @@ algorithm with a substitution matrix over the classes and affine gap costs, loca
 * `score_pairs`, `score_pairs_host`, `score_kernel_name`    score (int32), optionally the ends of the best cell; the CPU twin; the kernel;
 * `self_scores`    the perfect score of every row, int64;
 * `verify_score_pairs`, `verify_score_pairs_host`    (keep, score): keep[k] <=> score / min(self_a, self_b) >= min_ratio, in integers.
+
+What cd-hit and mmseqs threshold on is the alignment itself: sequence identity over it and coverage of the rows by it
+(`bsq_align_stats_device`; include/bsq.h, "alignment statistics of row pairs"): start, end, identical columns and length of one optimal
+alignment, carried through the same recurrence in one launch, no traceback.
+
+    row, col, *_ = sketch.sketch_pairs(sk, min_jaccard=0.05)
+    keep, score, stats = align.verify_align_pairs(tok, chars, offsets, row, col, matrix=S, gap_open=11, gap_extend=1, min_identity=0.3, min_coverage=0.8)
+    labels = sketch.cluster_pairs(row[keep], col[keep], B)
+
+* `stats_pairs`, `stats_pairs_host`, `stats_kernel_name`    (score, stats): stats[k] = (start_a, start_b, end_a, end_b, matches, columns);
+* `stats_identity`, `stats_coverage`    matches / columns (or / a length), (end - start) / length, float32;
+* `verify_align_pairs`, `verify_align_pairs_host`    (keep, score, stats): identity and coverage thresholds, in integers.
 """
 from __future__ import annotations
 
@@ -363,6 +375,195 @@ def verify_score_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=No
     return _score_keep(torch, score.to(torch.int64), _valid_take(torch, sa, row), _valid_take(torch, sb, col), T, min_score), score
 
 
+# ---- alignment statistics of row pairs (include/bsq.h, "alignment statistics of row pairs")
+
+STATS_MAX_LEN = 2048
+_STATS_FORM_HOLDS = {1: 128, 2: 512, 3: 2048}
+_IDENTITY_OVER = ("columns", "shorter", "longer")
+_COVERAGE = ("both", "shorter", "longer", "a", "b")
+
+
+def _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form):
+    """(desc, bsq_score) for the statistics calls: `_score`'s rules with the narrower max_len and forms."""
+    if isinstance(max_len, bool) or int(max_len) != max_len or not 1 <= int(max_len) <= STATS_MAX_LEN:
+        raise ValueError("max_len must be an integer in 1 .. %d, got %r" % (STATS_MAX_LEN, max_len))
+    form = 0 if form is None else form
+    if isinstance(form, bool) or form not in (0, 1, 2, 3) or (form and _STATS_FORM_HOLDS[form] < int(max_len)):
+        raise ValueError("form must be None or 1, 2, 3 (shorter sides up to 128, 512, 2048), got %r at max_len %d" % (form, int(max_len)))
+    desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, None)
+    s.form = int(form)
+    if not _lib.bsq_align_stats_kernel_name(ctypes.byref(s)):  # (whatever the rules above do not restate)
+        raise ValueError("the library refuses these arguments (include/bsq.h, \"alignment statistics of row pairs\")")
+    return desc, s
+
+
+def stats_kernel_name(*, mode="local", max_len=STATS_MAX_LEN, form=None, gap_open=0, gap_extend=0):
+    """The kernel `stats_pairs` takes (host only: profiling labels, tests); "" for what the library refuses."""
+    s = capi.Score(int(max_len), 0 if form is None else int(form), _MODES.get(mode, -1), int(gap_open), int(gap_extend))
+    return _lib.bsq_align_stats_kernel_name(ctypes.byref(s)).decode()
+
+
+def stats_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                     max_len=STATS_MAX_LEN, form=None):
+    """The library's CPU twin (`bsq_align_stats_host`: the cell of the kernels in plain loops) on numpy arrays: (score int32, stats int32
+    of shape (n, 6)); every argument means what it means to `stats_pairs`."""
+    desc, s = _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form)
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    row, col = _host_lists(row, col)
+    ca, oa = capi.host_batch(chars, offsets)
+    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
+    score = np.empty(row.size, np.int32)
+    stats = np.empty((row.size, 6), np.int32)
+    if row.size:
+        capi.check(_lib.bsq_align_stats_host(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
+                                             row.ctypes.data, col.ctypes.data, row.size, ctypes.byref(s), score.ctypes.data, stats.ctypes.data))
+    return score, stats
+
+
+def stats_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                max_len=STATS_MAX_LEN, form=None):
+    """(score, stats) of the listed pairs: score exactly as `score_pairs` gives it, and stats int32 of shape (n, 6), the row
+    (start_a, start_b, end_a, end_b, matches, columns) of one optimal alignment that ends in the best cell -- device tensors on torch's
+    current stream, one launch, nothing read back.
+
+    The alignment covers A's characters [start_a, end_a) and B's [start_b, end_b); `matches` of its `columns` columns (gap columns
+    included) pair characters of one class.  Global mode: starts (0, 0), ends (la, lb).  A local score of 0 gives six zeros, a code six
+    times -1.  Stores, lists, matrix, gap costs and mode as for `score_pairs`; max_len is 1 .. 2048 here (the kernel keeps three times
+    the state per row) and form 1, 2, 3 holds shorter sides up to 128, 512, 2048.  `stats_identity`, `stats_coverage` and
+    `verify_align_pairs` turn the statistics into the thresholds of cd-hit and mmseqs."""
+    import torch
+    desc, s = _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form)
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    what = "stats_pairs works on packed batches resident on the device (chars, offsets tensors)"
+    Ba = capi.packed_on_device(chars, offsets, what)
+    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, what)
+    if chars_b is not None and chars_b.device != chars.device:
+        raise ValueError("both stores must live on one device")
+    _device_lists(row, col, chars.device)
+    score = torch.empty(row.numel(), dtype=torch.int32, device=chars.device)
+    stats = torch.empty((row.numel(), 6), dtype=torch.int32, device=chars.device)
+    if row.numel():
+        ca = capi.readable_chars(chars, chars.device)  # (every row may be empty)
+        cb = ca if chars_b is None else capi.readable_chars(chars_b, chars.device)
+        ob = offsets if offsets_b is None else offsets_b
+        with capi.launching(chars.device) as stream:
+            capi.check(_lib.bsq_align_stats_device(ctypes.byref(desc), ca.data_ptr(), offsets.data_ptr(), Ba, cb.data_ptr(), ob.data_ptr(), Bb,
+                                                   row.data_ptr(), col.data_ptr(), row.numel(), ctypes.byref(s), score.data_ptr(),
+                                                   stats.data_ptr(), stream))
+    return score, stats
+
+
+def _xp(a):
+    if isinstance(a, np.ndarray):
+        return np
+    import torch
+    return torch
+
+
+def _ratio32(xp, num, den, bad):
+    """num / den as float32 (computed in float64), NaN where `bad` or den <= 0."""
+    if xp is np:
+        out = np.full(num.shape, np.nan, np.float64)
+        ok = ~bad & (den > 0)
+        out[ok] = num[ok].astype(np.float64) / den[ok].astype(np.float64)
+        return out.astype(np.float32)
+    ok = ~bad & (den > 0)
+    q = num.to(xp.float64) / xp.where(ok, den, xp.ones_like(den)).to(xp.float64)
+    return xp.where(ok, q, xp.full_like(q, float("nan"))).to(xp.float32)
+
+
+def stats_identity(stats, over="columns", la=None, lb=None):
+    """matches / D as float32: D = the alignment's columns (over="columns", BLAST's identity), or min(la, lb) ("shorter", cd-hit's) or
+    max(la, lb) ("longer") with la and lb from `pair_lengths`.  NaN for a pair with a code and where D is 0.  numpy or torch by `stats`."""
+    if over not in _IDENTITY_OVER:
+        raise ValueError("over is one of %r, got %r" % (_IDENTITY_OVER, over))
+    if over != "columns" and (la is None or lb is None):
+        raise ValueError("over=%r needs la and lb (pair_lengths)" % (over,))
+    xp = _xp(stats)
+    if xp is np:
+        st = stats.astype(np.int64)
+    else:
+        st = stats.to(xp.int64)
+    den = st[:, 5] if over == "columns" else (xp.minimum(la, lb) if over == "shorter" else xp.maximum(la, lb))
+    return _ratio32(xp, st[:, 4], den, st[:, 5] < 0)
+
+
+def stats_coverage(stats, la, lb):
+    """(cov_a, cov_b): the share of each row the alignment covers, (end - start) / length as float32; NaN for a code and a length of 0."""
+    xp = _xp(stats)
+    st = stats.astype(np.int64) if xp is np else stats.to(xp.int64)
+    bad = st[:, 5] < 0
+    return _ratio32(xp, st[:, 2] - st[:, 0], la, bad), _ratio32(xp, st[:, 3] - st[:, 1], lb, bad)
+
+
+def _align_thresholds(min_identity, min_coverage, identity_over, coverage, min_score):
+    if identity_over not in ("columns", "shorter"):
+        raise ValueError("identity_over is 'columns' or 'shorter', got %r" % (identity_over,))
+    if coverage not in _COVERAGE:
+        raise ValueError("coverage is one of %r, got %r" % (_COVERAGE, coverage))
+    if not 0.0 <= float(min_coverage) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError("min_coverage must lie in 0 .. 1, got %r" % (min_coverage,))
+    if isinstance(min_score, bool) or int(min_score) != min_score:
+        raise ValueError("min_score is an integer, got %r" % (min_score,))
+    return _identity_q16(min_identity), int(float(min_coverage) * 65536 + 0.5), int(min_score)
+
+
+def _align_keep(xp, score64, st, la, lb, Ti, Tc, min_score, identity_over, coverage):
+    """The rule of `verify_align_pairs` on int64 arrays (numpy or torch by `xp`)."""
+    D = st[:, 5] if identity_over == "columns" else xp.minimum(la, lb)
+    keep = (score64 > CODE_BELOW) & (score64 >= min_score) & (D > 0) & (st[:, 4] * 65536 >= Ti * D)
+    ok_a, ok_b = (st[:, 2] - st[:, 0]) * 65536 >= Tc * la, (st[:, 3] - st[:, 1]) * 65536 >= Tc * lb
+    a_short = la <= lb  # (A's row is the shorter one when the lengths are equal, as in the kernels)
+    if coverage == "both":
+        cov = ok_a & ok_b
+    elif coverage == "a":
+        cov = ok_a
+    elif coverage == "b":
+        cov = ok_b
+    elif coverage == "shorter":
+        cov = xp.where(a_short, ok_a, ok_b)
+    else:
+        cov = xp.where(a_short, ok_b, ok_a)
+    return keep & cov
+
+
+def verify_align_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                            min_identity=0.9, min_coverage=0.8, identity_over="columns", coverage="both", min_score=1, max_len=STATS_MAX_LEN):
+    """`verify_align_pairs` on numpy arrays through the CPU twin: (keep, score, stats) as numpy arrays, the same bits."""
+    Ti, Tc, min_score = _align_thresholds(min_identity, min_coverage, identity_over, coverage, min_score)
+    score, stats = stats_pairs_host(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend,
+                                    mode=mode, max_len=max_len)
+    row, col = _host_lists(row, col)
+    oa = np.asarray(offsets, np.int64).ravel()
+    ob = oa if offsets_b is None else np.asarray(offsets_b, np.int64).ravel()
+    la, lb = _valid_lengths(np, oa, row), _valid_lengths(np, ob, col)
+    return _align_keep(np, score.astype(np.int64), stats.astype(np.int64), la, lb, Ti, Tc, min_score, identity_over, coverage), score, stats
+
+
+def verify_align_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
+                       min_identity=0.9, min_coverage=0.8, identity_over="columns", coverage="both", min_score=1, max_len=STATS_MAX_LEN):
+    """(keep, score, stats) of a candidate list: score and stats as `stats_pairs` gives them, and keep[k] (bool) true when the pair
+    passes the thresholds protein clustering tools publish -- sequence identity over the alignment and coverage of the rows by it:
+
+    * the score is no code and reaches min_score;
+    * matches * 65536 >= Ti * D and D > 0, D = columns (identity_over="columns", `mmseqs --min-seq-id`) or min(la, lb) ("shorter",
+      `cd-hit -c`), Ti = floor(min_identity * 65536 + 0.5);
+    * (end - start) * 65536 >= Tc * length, Tc likewise from min_coverage, for the rows `coverage` names: "both" (`mmseqs -c` in its
+      default coverage mode), "shorter", "longer" (A's row is the shorter one when the lengths are equal), "a" or "b".
+
+    Decided in 64-bit integers, in torch on the device, nothing read back: `verify_align_pairs_host` keeps the same pairs bit for bit.
+    `row[keep]`, `col[keep]` is the verified list, which `sketch.cluster_pairs` takes."""
+    import torch
+    Ti, Tc, min_score = _align_thresholds(min_identity, min_coverage, identity_over, coverage, min_score)
+    score, stats = stats_pairs(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend, mode=mode,
+                               max_len=max_len)
+    la, lb = _valid_lengths(torch, offsets, row), _valid_lengths(torch, offsets if offsets_b is None else offsets_b, col)
+    return _align_keep(torch, score.to(torch.int64), stats.to(torch.int64), la, lb, Ti, Tc, min_score, identity_over, coverage), score, stats
+
+
 __all__ = ["TOO_LONG", "BAD_INDEX", "MAX_LEN", "edit_distance_pairs", "edit_distance_host", "edit_kernel_name", "pair_lengths", "pair_identity",
            "verify_pairs", "verify_pairs_host", "SCORE_TOO_LONG", "SCORE_BAD_INDEX", "CODE_BELOW", "score_matrix", "blosum62_matrix", "score_pairs",
-           "score_pairs_host", "score_kernel_name", "self_scores", "verify_score_pairs", "verify_score_pairs_host"]
+           "score_pairs_host", "score_kernel_name", "self_scores", "verify_score_pairs", "verify_score_pairs_host", "STATS_MAX_LEN", "stats_pairs",
+           "stats_pairs_host", "stats_kernel_name", "stats_identity", "stats_coverage", "verify_align_pairs", "verify_align_pairs_host"]

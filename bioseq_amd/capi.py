@@ -230,6 +230,9 @@ def load():
         "bsq_score_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp]),
         "bsq_score_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Score), c_int]),
         "bsq_blosum62_scores": (i32, [vp]),
+        "bsq_align_stats_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp, vp]),
+        "bsq_align_stats_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp]),
+        "bsq_align_stats_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Score)]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -47,7 +47,8 @@ extern "C" {
                            * bsq_sketch_pairs_emit_device, bsq_sketch_pairs_host, bsq_sketch_pairs_kernel_name, bsq_sketch_clusters_device,
                            * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name,
                            * bsq_edit, bsq_edit_pairs_device, bsq_edit_pairs_host, bsq_edit_pairs_kernel_name, bsq_score, bsq_score_pairs_device,
-                           * bsq_score_pairs_host, bsq_score_pairs_kernel_name, bsq_blosum62_scores; nothing removed */
+                           * bsq_score_pairs_host, bsq_score_pairs_kernel_name, bsq_blosum62_scores, bsq_align_stats_device,
+                           * bsq_align_stats_host, bsq_align_stats_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -1001,6 +1002,102 @@ bsq_status bsq_score_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const
 const char *bsq_score_pairs_kernel_name(const bsq_score *s, int with_ends);
 /* The BLOSUM62 scores as 21 x 21 int8: rows and columns ARNDCQEGHILKMFPSTWYV + X (the table of the augmentation above); X / X = -1. */
 bsq_status bsq_blosum62_scores(int8_t *out21x21);
+
+/* ---- alignment statistics of row pairs: where the best alignment of the section above starts, how many of its columns are identical and
+ * how long it is -- what cd-hit (-c) and mmseqs cluster (--min-seq-id, -c) threshold on: sequence identity over the alignment and
+ * coverage of each sequence by it.  No traceback: the three quantities are carried forward through Gotoh's recurrence beside H, E and
+ * F (as parasail's _stats kernels do), in linear space, one launch, nothing read back.
+ *
+ * THE RULE.  Stores, pair lists, the class of a byte, matrix, gap_open (o), gap_extend (e), mode, the codes, the range and the symmetry
+ * wording are those of "scored alignment of row pairs"; i runs over A's row, j over B's, whichever row the kernel takes as pattern.
+ * Every one of H[i][j], E[i][j], F[i][j] carries a tuple (start_a, start_b, matches, diag) of ONE optimal path into that state:
+ *     E[i][j]      (consumes B's character: a gap in A) takes the tuple of H[i][j-1] when H[i][j-1] - o >= E[i][j-1] -- opening wins the
+ *                  tie -- and otherwise that of E[i][j-1].  A gap step leaves the tuple as it is.
+ *     F[i][j]      (consumes A's character) likewise from H[i-1][j] and F[i-1][j].
+ *     H[i][j]      the candidates are d = H[i-1][j-1] + S[x_i][y_j], E[i][j] and F[i][j]; on ties the diagonal wins, then E, then F.  The
+ *                  diagonal's tuple is that of H[i-1][j-1] with diag + 1, and matches + 1 when the two CLASSES are equal (the unmapped
+ *                  class equals itself, as in the edit distance; S plays no part in `matches`).
+ *     local mode   when the maximum is <= 0, H = 0 and the tuple is (i, j, 0, 0): an alignment that continues from this cell starts
+ *                  after i characters of A and j of B.  The boundary cells H[i][0] and H[0][j] carry (i, 0, 0, 0) and (0, j, 0, 0).
+ *     global mode  the starts are always (0, 0); the origin and the boundary cells H[i][0], H[0][j] (pure gaps) carry zeros.
+ *     boundary E and F are minus infinity and never win, so their tuples are never read.
+ * The result of a pair is score[k], exactly the value bsq_score_pairs_device gives, and
+ *     stats[k] = (start_a, start_b, end_a, end_b, matches, columns)   int32
+ *     ends         (end_a, end_b) is the best cell under the tie rule of the section above; (la, lb) in global mode
+ *     tuple        that of H at the best cell
+ *     columns      (end_a - start_a) + (end_b - start_b) - diag: the alignment's length, gap columns included (not carried: computed
+ *                  at the end).  The alignment covers A's characters [start_a, end_a) and B's [start_b, end_b).
+ *     zero         a local score of 0 gives six zeros; with an empty side local mode gives zeros, global mode (0, 0, la, lb, 0, la + lb)
+ *     codes        a pair whose score is a code (BSQ_SCORE_TOO_LONG, BSQ_SCORE_BAD_INDEX) has six times -1
+ *     max_len      1 .. 2048 for THIS call (bsq_score::max_len; a shorter side beyond it gets BSQ_SCORE_TOO_LONG, the longer side stays
+ *                  <= 2^20).  The bound is the register budget: a lane keeps six registers per pattern row here where the score keeps
+ *                  two, so it owns 32 rows instead of 64.
+ *     form         1: 4 lanes, shorter sides up to 128; 2: 16 lanes, 512; 3: 64 lanes, 2048; 0: the smallest that holds max_len
+ *     symmetry     the tie rules are in A / B terms: the result depends neither on the form nor on which row is the pattern.
+ *                  stats(A, B; S) and stats(B, A; S transposed) have one score, and mirrored statistics wherever no tie is broken.
+ *     identity     (for callers; bioseq_amd.align.verify_align_pairs) with Ti = floor(min_identity * 65536 + 0.5) and Tc likewise a
+ *                  pair passes when the score is no code and >= min_score, matches * 65536 >= Ti * D with D = columns or min(la, lb)
+ *                  and D > 0, and (end - start) * 65536 >= Tc * length for the rows whose coverage is asked, in 64-bit integers.
+ * Limits and refusals are those of the section above with max_len and form as stated here; score and stats must not be null when
+ * n_pairs > 0.  A refusal writes nothing; n_pairs == 0 is BSQ_OK.  The device call is stream-ordered and never synchronises.
+ *
+ * Kernels: k_align_stats<4 | 16 | 64, local | global> (csrc/bsq_align_stats.hip; csrc/bsq_align_stats_dev.h has the cell with its
+ * tuples, the packing and the unpacking, the text the CPU twin runs in plain loops).  k_score_pairs' skeleton: the shorter row is the
+ * pattern, lane b owns rows 32 b + 1 .. 32 b + 32, the group walks anti-diagonals, the text comes a tile ahead, the cells run under
+ * the execution mask, the score table is in LDS in both orientations.  A tuple is two 32-bit words: the text-side start (< 2^20, 20
+ * bits) below the pattern-side start (12 bits) -- a start is strictly below its length wherever the state can still reach a positive
+ * score; a reset in the last column of a text of 2^20 characters stores a masked value that nothing reads -- and matches below diag,
+ * 13 bits each (both <= 2048), so that a diagonal step is one add of (1 << 13) + equal.  Global mode never makes the first word.  A
+ * lane keeps H, E and the tuples of both for its 32 rows: 192 registers in local mode, 128 in global mode.  Per step the bottom row's
+ * H and F, their tuples and the column's class move up one lane: seven ds_bpermute per 32 cells (five in global mode).  The tie
+ * between E and F in H depends on which row is the pattern: one value per lane, added before the comparison, not a second kernel.
+ * The best cell's tuple follows the column's largest key (H << 5) | (31 - row) down the rows; one reduction per group under the tie
+ * rule, one lane writes score and the six statistics with plain vector stores.
+ * Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / LDS bytes / scratch bytes):
+ *     k_align_stats<4, local>  253 / 0 / 2304 / 0     k_align_stats<16, local>  255 / 0 / 2304 / 0     k_align_stats<64, local>  250 / 0 / 2304 / 0
+ *     k_align_stats<4, global> 187 / 0 / 2304 / 0     k_align_stats<16, global> 187 / 0 / 2304 / 0     k_align_stats<64, global> 186 / 0 / 2304 / 0
+ * two waves per SIMD and no scratch in all six.  It takes two measures to get there in local mode: the rows' classes stay packed four
+ * to a register inside the loop, and the best cell's tuple is selected per cell (picking it out of the registers by row number once per
+ * column costs 55 registers more and one wave per SIMD).  64 rows per lane also build without scratch, but at one wave per SIMD with
+ * more than 220 register copies parked in AGPRs (local) -- not measured, and the contract stays 2048.
+ *
+ * Measured on an MI355X, whole calls, buffers alternating, seeded random rows, in turns with bsq_score_pairs_device with ends
+ * (local+ends, and global) on the same lists at the same max_len -- that kernel is unchanged by this section -- (scripts/align_stats_lab.py,
+ * profiles/r24/align_stats_lab.txt; local / global, the score in brackets): 1 048 576 pairs of 150-character DNA4 reads, +2 / -3 {5, 2},
+ * max_len 256: 78.5 / 49.8 ms, 0.30 / 0.47 T cells per second (12.8 / 10.0 ms: 6.1 and 5.0 times the score's time -- 150 rows are 5 of
+ * form 2's 16 lanes here and 3 of form 1's 4 there, so a wave holds 4 pairs where the score's holds 16); 262 144 pairs of AMINO20 rows of
+ * 50 .. 1024 residues, BLOSUM62 {11, 1}, max_len 1024: 432 / 271 ms, 0.61 / 0.97 M pairs and 0.17 / 0.28 T cells per second (81.9 /
+ * 63.7 ms: 5.3 and 4.3 times; 64 lanes per pair against 16); 4096 pairs of 2048 x 2048, every lane busy: 18.0 / 11.3 ms, 0.95 / 1.52 T
+ * cells per second (11.5 / 9.0 ms with half of the score's 64 lanes idle; against its 3.0 / 3.8 T cells per second at 4096 x 4096 the
+ * cost per cell is 3.2 and 2.5 times).  The 32-cell block is about 39 vector instructions per cell in local mode and 24 in global mode
+ * against the score's 13 and 10, and the measured 5100 cycles per full local step of a wave at 2.4 GHz, two waves a SIMD, are that
+ * count times four: vector issue bounds it.  The host twin on one thread runs 0.18 - 0.41 G cells per second on a 1/64 sample.  No
+ * counters-only run was taken.  An 8-lane form (shorter sides up to 256) would halve the reads' time; it is not part of this contract.
+ *
+ * Known answers (tests/align_stats_twin.py, a cell-by-cell programme of the rule over full tables, not the kernel).  DNA4, the batch
+ * ACGTAC, ACGNACGT, AC, "", TTTTTTT as A and as B, S = +2 / -3 (N / N = +2), {5, 2}; scores as in the section above:
+ *     local stats      row 0: (0,0,6,6,6,6) (0,4,4,8,4,4) (0,0,2,2,2,2) zeros (3,0,4,1,1,1)
+ *                      row 1: (4,0,8,4,4,4) (0,0,8,8,8,8) (0,0,2,2,2,2) zeros (7,0,8,1,1,1)
+ *                      row 2: (0,0,2,2,2,2) three times, then zeros twice          row 3: zeros
+ *                      row 4: (0,3,1,4,1,1) (0,7,1,8,1,1) zeros zeros (0,0,7,7,7,7)
+ *     global           starts (0,0), ends (la, lb); (matches, columns) of every (i, j):
+ *                      (6,6) (5,8) (2,6) (0,6) (1,7) / (5,8) (8,8) (2,8) (0,8) (1,8) / (2,6) (2,8) (2,2) (0,2) (0,7) /
+ *                      (0,6) (0,8) (0,2) (0,0) (0,7) / (1,7) (1,8) (0,7) (0,7) (7,7)
+ *     acgtNN- against ACGTnxA, global: score 9, (0,0,7,7,6,7) -- case folds, N, n and x share the unmapped class, '-' against A differs
+ * BLOSUM62, A = HEAGAWGHEE, B = PAWHEAE:  {11, 1}: local 17, (0,3,3,6,3,3) -- HEA / HEA --, global 1, (0,0,10,7,3,10);  {0, 8}: local 20,
+ * (4,1,9,5,4,5), global -8, (0,0,10,7,3,10).  Swapping the stores swaps start_a with start_b and end_a with end_b in all four.
+ * Identity: AAAAAAAA against AAAACCAA, +1 / -1 {3, 1}, global: (0,0,8,8,6,8) passes min_identity 0.75 over the columns
+ * (6 * 65536 == 49152 * 8) and fails at Ti = 49153. */
+bsq_status bsq_align_stats_device(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                                  const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_score *s,
+                                  int32_t *score, int32_t *stats /* n_pairs x 6 */, void *hip_stream);
+/* CPU twin on host buffers (the same class, cell and packing text; no device is needed). */
+bsq_status bsq_align_stats_host(const bsq_desc *d, const uint8_t *chars_a, const int64_t *offsets_a, int64_t Ba, const uint8_t *chars_b,
+                                const int64_t *offsets_b, int64_t Bb, const int64_t *row, const int64_t *col, int64_t n_pairs, const bsq_score *s,
+                                int32_t *score, int32_t *stats /* n_pairs x 6 */);
+/* Host only: the kernel the device call takes ("k_align_stats<16, local>", ...); "" for a bsq_score the calls refuse, a max_len > 2048
+ * included. */
+const char *bsq_align_stats_kernel_name(const bsq_score *s);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
