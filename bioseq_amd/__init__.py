@@ -31,7 +31,7 @@ except ImportError as _e:  # fail loudly: the HIP extension IS the product
 
 from .cbioseq import Threading, Tokenizer, get_host_threads, get_num_threads, set_host_threads, set_num_threads  # noqa: F401
 from . import synth  # noqa: F401
-from . import blosum, kmers, masking, multi, orfs, packing, sharding, sketch, translate, views  # noqa: F401
+from . import blosum, bpe, kmers, masking, multi, orfs, packing, sharding, sketch, translate, views  # noqa: F401
 from .flatfile import FlatFile, FlatFileIterator, getstats  # noqa: F401  (bioseq.FlatFile / getstats, /root/reference/src/fxstats.cpp:166-219)
 
 __version__ = "0.1.0"
@@ -172,4 +172,4 @@ __all__ = ["onehot_encode", "cbioseq", "f_encode", "Tokenizer", "make_embedding"
            "pos_tokenizers", "default_tokenizers", "total_tokenizer_dict", "get_tokenizer_dict", "DNATokenizer",
            "AmineTokenizer", "Reduced6Tokenizer", "Reduced8Tokenizer", "Reduced10Tokenizer", "Reduced14Tokenizer",
            "DayhoffTokenizer", "LIATokenizer", "LIBTokenizer", "torchify", "set_num_threads", "get_num_threads",
-           "Threading", "device_count", "synth", "blosum", "kmers", "masking", "multi", "orfs", "packing", "sharding", "sketch", "translate", "views", "FlatFile", "FlatFileIterator", "getstats", "loaders", "set_host_threads", "get_host_threads"]
+           "Threading", "device_count", "synth", "blosum", "bpe", "kmers", "masking", "multi", "orfs", "packing", "sharding", "sketch", "translate", "views", "FlatFile", "FlatFileIterator", "getstats", "loaders", "set_host_threads", "get_host_threads"]

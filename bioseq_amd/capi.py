@@ -85,6 +85,11 @@ class Edit(ctypes.Structure):
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32)]
 
 
+class Bpe(ctypes.Structure):
+    """struct bsq_bpe"""
+    _fields_ = [("max_chars", ctypes.c_int32), ("form", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class Score(ctypes.Structure):
     """struct bsq_score"""
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32), ("mode", ctypes.c_int32), ("gap_open", ctypes.c_int32),
@@ -233,6 +238,16 @@ def load():
         "bsq_align_stats_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp, vp]),
         "bsq_align_stats_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Score), vp, vp]),
         "bsq_align_stats_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Score)]),
+        "bsq_bpe_table_bytes": (i64, [i32, i64]),
+        "bsq_bpe_table_build": (i32, [dp, vp, i64, vp]),
+        "bsq_bpe_vocab_size": (i64, [dp, i64]),
+        "bsq_bpe_unk_id": (i64, [dp, i64]),
+        "bsq_bpe_bos_id": (i64, [dp, i64]),
+        "bsq_bpe_eos_id": (i64, [dp, i64]),
+        "bsq_bpe_pad_id": (i64, [dp, i64]),
+        "bsq_bpe_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), c_int, vp, vp, vp]),
+        "bsq_bpe_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), c_int, vp, vp]),
+        "bsq_bpe_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Bpe)]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -48,7 +48,9 @@ extern "C" {
                            * bsq_sketch_clusters_host, bsq_cluster_pairs_device, bsq_cluster_pairs_host, bsq_sketch_clusters_kernel_name,
                            * bsq_edit, bsq_edit_pairs_device, bsq_edit_pairs_host, bsq_edit_pairs_kernel_name, bsq_score, bsq_score_pairs_device,
                            * bsq_score_pairs_host, bsq_score_pairs_kernel_name, bsq_blosum62_scores, bsq_align_stats_device,
-                           * bsq_align_stats_host, bsq_align_stats_kernel_name; nothing removed */
+                           * bsq_align_stats_host, bsq_align_stats_kernel_name, bsq_bpe, bsq_bpe_table_bytes, bsq_bpe_table_build,
+                           * bsq_bpe_vocab_size, bsq_bpe_unk_id, bsq_bpe_bos_id, bsq_bpe_eos_id, bsq_bpe_pad_id, bsq_bpe_tokenize_device,
+                           * bsq_bpe_tokenize_host, bsq_bpe_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -1098,6 +1100,84 @@ bsq_status bsq_align_stats_host(const bsq_desc *d, const uint8_t *chars_a, const
 /* Host only: the kernel the device call takes ("k_align_stats<16, local>", ...); "" for a bsq_score the calls refuse, a max_len > 2048
  * included. */
 const char *bsq_align_stats_kernel_name(const bsq_score *s);
+
+/* ---- BPE ids of a packed batch: byte-pair encoding, the vocabulary DNABERT-2, GENA-LM, GROVER and ProtGPT2 are trained on -- an ordered
+ * list of merges applied to every row of a resident packed batch in one launch, the id rows written as bsq_kmer_tokenize_device writes
+ * its own.  No pre-tokenisation, no dropout, no fuse_unk: a row is one word.
+ *
+ * THE RULE.  A tokenizer description d with C = d->nchars classes and merges[0 .. M) (int32 pairs (l, r), M x 2, row-major).
+ *     ids          0 .. C - 1 the classes, C + m the product of merge m, V = C + M; UNK = V, then BOS, EOS, PAD exactly as bsq_kmer orders
+ *                  them behind UNK (BOS = V + 1 and EOS = V + 1 + bos where the flag is set, else -1; PAD = V + 1 + bos + eos, stored at
+ *                  pad positions when d->padchar, else 0 is stored); vocab = V + 1 + bos + eos + padchar.
+ *     legal table  0 <= l, r < C + m for merge m (a merge names only classes and earlier products), all pairs distinct, V + 4 <= 65536
+ *                  (every id fits 16 bits; ProtGPT2's 50 257 do).  Anything else is BSQ_ERR_INVALID_ARG from bsq_bpe_table_build:
+ *                  nothing illegal ever reaches a kernel.
+ *     a row        of L characters is the symbol string of its classes; every unmapped byte (lut < 0) is one UNK, which is never fused
+ *                  and never part of a pair (a barrier).  While some adjacent pair is in `merges`: take the pair occurrence of lowest
+ *                  rank m, leftmost among equals, and replace it by C + m.  The result is n ids.
+ *     equivalently (what the kernels and the CPU twin run) a merge names only earlier ids, so a pair created by merge m has a rank above
+ *                  m and the ranks applied strictly increase.  One step: m = the lowest rank present; replace ALL its occurrences left
+ *                  to right without overlap.  Occurrences overlap only when l == r: in a maximal run of consecutive candidate positions
+ *                  the ones at even distance from the run's start are taken (AAAAA under (A, A) gives AA AA A).
+ *     tokens       (B, P) when batch_first, else (P, B), C-contiguous, every element written exactly once: row = [BOS] id_0 .. id_{n'-1}
+ *                  [EOS] PAD ... with n' = min(n, max(P - bos - eos, 0)).  All six bsq_dtype, refused with BSQ_ERR_DTYPE by
+ *                  bsq_dtype_holds(t, 0, vocab - 1).
+ *     lengths      int32 (B): n BEFORE the clamp, so a caller sees a cut row.  A row of more than max_chars characters gets
+ *                  BSQ_BPE_TOO_LONG (-1) and the token row of an empty row: nothing is silently truncated.  A negative L (malformed
+ *                  offsets) counts as 0.
+ * Limits: 1 <= max_chars <= 8192, form 0 .. 2 (1 needs max_chars <= 1024), reserved == 0, B <= 2^31 - 1, P >= 1; otherwise, and for a
+ * null pointer that would be read, BSQ_ERR_INVALID_ARG.  A null bsq_bpe means {8192, 0, 0}.  B == 0 is BSQ_OK with nothing launched.
+ * The device call is stream-ordered and never synchronises; every refusal leaves the outputs untouched and sets bsq_last_error().
+ *
+ * The table: bsq_bpe_table_build validates the merges and writes bsq_bpe_table_bytes(C, M) bytes of an opaque lookup table into HOST
+ * memory; the caller uploads them once and owns the device copy (the library allocates nothing on the device).  It is an
+ * open-addressing hash of (l << 16 | r) to the rank: capacity = the power of two >= max(2 M, 16), eight bytes per slot, at most 1 MiB.
+ * table_dev / table_host and M of a tokenize call must be what one build produced; the probe loop is bounded by the capacity and the
+ * step loop by the row's length, so a damaged table ends in wrong ids, never in a wait.
+ *
+ * Kernels (csrc/bsq_bpe.hip; csrc/bsq_bpe_dev.h has the lookup and the run-parity selection, the text the CPU twin shares): one row is
+ * never split across workgroups.  k_bpe_wave: a wave per row, four rows per workgroup, max_chars <= 1024 (form 0 takes it there, so a
+ * smaller bound is a cheaper call); k_bpe_block: a 256-thread workgroup per row, up to 8192.  The row's symbols stay dense in LDS as
+ * 16-bit ids with the rank of each adjacent pair beside them; position 64 q + lane belongs to lane `lane`, so a step is a min-reduction
+ * of the ranks, one ballot per 64 positions for the candidate mask, the run-parity selection on those 64-bit masks (a carry crosses
+ * the 64-position boundary), a prefix sum of the kept counts, the compaction, and a re-lookup of only the pairs next to a new symbol.
+ * No global atomic, no waiting on another workgroup, vector stores and plain C++ only.
+ * Measured on an MI355X, whole calls, int16 rows, buffers alternating, merges trained on a sample of the same uniform-letter rows
+ * (scripts/bpe_lab.py, profiles/r25/bpe_lab.txt): 1 048 576 DNA4 reads of 150 at 4096 merges 19.0 ms (56 steps a row); 262 144 rows of 512
+ * 18.0 ms (130 steps); 65 536 AMINO20 rows of 50 .. 1024 at 8000 merges 17.6 ms (224 steps); 4096 rows of 8192, block form, 26.3 ms (800
+ * steps); the poly-A batches of these shapes 0.2 .. 1.4 ms (one or two steps).  That is 500 .. 800 times the host twin on one thread and
+ * 15 .. 195 times Hugging Face's encode_batch on 16 threads, on a 1/64 sample.  A call costs rows x steps, not bytes.  One session; no
+ * counters-only run was taken.
+ *
+ * Known answers (DNA4, no flags, merges (A,A) (C,G) (AA,A) (CG,T) (AA,AA) (T,T): 4 = AA, 5 = CG, 6 = AAA, 7 = CGT, 8 = AAAA, 9 = TT,
+ * UNK = 10):  AAAAAAA -> 8 6;  AAAAA -> 4 6;  ACGTACGT -> 0 7 0 7;  AAACGTNAAAA -> 6 7 10 8;  TTTTT -> 9 9 3;  CGCGT -> 5 7;  N -> 10;
+ * "" -> nothing. */
+#define BSQ_BPE_TOO_LONG (-1)
+typedef struct bsq_bpe {
+    int32_t max_chars; /* 1 .. 8192: the caller's bound on a row's characters; a longer row gets lengths = -1 */
+    int32_t form;      /* 0: the library chooses (wave up to 1024, else block); 1: wave per row; 2: workgroup per row */
+    int32_t reserved;  /* 0 */
+} bsq_bpe;
+/* Bytes of the lookup table of C classes and M merges, or a negative bsq_status (-BSQ_ERR_INVALID_ARG) for C < 1, M < 0 or
+ * C + M + 4 > 65536. */
+int64_t bsq_bpe_table_bytes(int32_t C, int64_t M);
+/* Host only: validates merges (M x 2 int32) against THE RULE and writes the table into host_out (bsq_bpe_table_bytes(d->nchars, M)
+ * bytes).  A refusal writes nothing. */
+bsq_status bsq_bpe_table_build(const bsq_desc *d, const int32_t *merges, int64_t M, void *host_out);
+/* vocab / the ids above; a negative bsq_status for a null descriptor or an illegal M.  bos / eos: -1 where the tokenizer has none. */
+int64_t bsq_bpe_vocab_size(const bsq_desc *d, int64_t M);
+int64_t bsq_bpe_unk_id(const bsq_desc *d, int64_t M);
+int64_t bsq_bpe_bos_id(const bsq_desc *d, int64_t M);
+int64_t bsq_bpe_eos_id(const bsq_desc *d, int64_t M);
+int64_t bsq_bpe_pad_id(const bsq_desc *d, int64_t M);
+bsq_status bsq_bpe_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, int32_t batch_first,
+                                   const void *table_dev, int64_t M, const bsq_bpe *bpe, bsq_dtype t, void *tokens, int32_t *lengths,
+                                   void *hip_stream);
+/* CPU twin on host buffers (the same lookup, selection and element text; no device is needed). */
+bsq_status bsq_bpe_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, int32_t batch_first,
+                                 const void *table_host, int64_t M, const bsq_bpe *bpe, bsq_dtype t, void *tokens, int32_t *lengths);
+/* Host only: the kernel the device call takes ("k_bpe_wave", "k_bpe_block"); "" for a bsq_bpe the calls refuse. */
+const char *bsq_bpe_kernel_name(const bsq_bpe *bpe);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
