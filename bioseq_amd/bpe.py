@@ -11,7 +11,9 @@ pre-tokenisation, no dropout, no fuse_unk.  include/bsq.h ("BPE ids of a packed 
 * `bpe_tokenize_host`     the library's CPU twin (numpy in, numpy out; no device);
 * `bpe_vocab_size`, `bpe_special_ids`, `bpe_strings`, `bpe_decode`, `bpe_external_ids`  the sizes an embedding table needs, the
                           vocabulary-file strings, ids -> strings (host), and the map from these ids to a published vocabulary's;
-* `bpe_kernel_name`       the kernel a call takes;
+* `bpe_mlm_tokenize_packed`  (inputs, labels, lengths): masked-LM batches over those ids, drawn on the device in the same launch;
+* `bpe_mlm_tokenize_host`  its CPU twin;
+* `bpe_kernel_name`, `bpe_mlm_kernel_name`  the kernel a call takes;
 * `bpe_train_host`        a plain deterministic trainer for samples of a few MB (not a corpus-scale trainer).
 
 Rows longer than `max_chars` (at most 8192) get length -1 and an empty token row: crop first with `views.crop_packed`.
@@ -255,6 +257,94 @@ def bpe_tokenize_packed(vocab, chars, offsets, padlen, destchar="q", batch_first
     return tokens, lengths
 
 
+def _bpe_mlm(vocab, destchar, label_destchar, frac, mask_prob, random_prob, mask_token, ignore_index, seed, first_row, max_chars, form):
+    """(bsq_bpe, bsq_bpe_mlm, input dtype, label dtype, torch dtypes) with the library's argument rules applied as ValueError."""
+    bpe, dt, tdt = _bpe(vocab, destchar, max_chars, form)
+    for name, p in (("frac", frac), ("mask_prob", mask_prob), ("random_prob", random_prob)):
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError("%s must lie in [0, 1], got %r" % (name, p))
+    if float(mask_prob) + float(random_prob) > 1.0 + 1e-12:
+        raise ValueError("mask_prob + random_prob must not exceed 1")
+    size = bpe_vocab_size(vocab)
+    m = capi.BpeMlm(float(frac), float(mask_prob), float(random_prob), size if mask_token is None else int(mask_token), int(ignore_index),
+                    int(seed) & (2 ** 64 - 1), int(first_row))
+    if m.first_row < 0 or m.mask_token < 0:
+        raise ValueError("first_row and mask_token must be >= 0")
+    ldt, ltdt = capi.dtype_of(label_destchar)
+    top = max(size - 1, m.mask_token)
+    if not _lib.bsq_dtype_holds(dt, 0, top):
+        raise ValueError("destchar %r cannot hold ids up to %d (vocabulary and mask token)" % (destchar, top))
+    last = vocab.desc.nchars + vocab.M - 1
+    if not _lib.bsq_dtype_holds(ldt, min(m.ignore_index, 0), max(m.ignore_index, last)):
+        raise ValueError("label_destchar %r cannot hold plain ids up to %d and ignore_index %d" % (label_destchar, last, m.ignore_index))
+    return bpe, m, dt, ldt, tdt, ltdt
+
+
+def bpe_mlm_kernel_name(vocab=None, *, max_chars=None, form=None):
+    """The kernel `bpe_mlm_tokenize_packed` takes for this bound (host only: profiling labels, tests); `vocab` plays no part."""
+    max_chars = MAX_CHARS if max_chars is None else int(max_chars)
+    name = _lib.bsq_bpe_mlm_kernel_name(ctypes.byref(capi.Bpe(max_chars, 0 if form is None else int(form), 0))).decode()
+    if not name:
+        raise ValueError("max_chars must lie in 1 .. %d and form be None, 1 (max_chars <= %d) or 2" % (MAX_CHARS, WAVE_MAX_CHARS))
+    return name
+
+
+def bpe_mlm_tokenize_host(vocab, chars, offsets, padlen, destchar="q", batch_first=True, *, label_destchar="q", frac=0.15, mask_prob=0.8,
+                          random_prob=0.1, mask_token=None, ignore_index=-100, seed=0, first_row=0, max_chars=None, form=None):
+    """The library's CPU twin (`bsq_bpe_mlm_tokenize_host`: the twin's merge loop and the element code of the kernels) on numpy arrays:
+    (inputs, labels, lengths) as numpy arrays.  max_chars: None = 8192; form is checked and changes nothing on the host."""
+    bpe, m, dt, ldt, _, _ = _bpe_mlm(vocab, destchar, label_destchar, frac, mask_prob, random_prob, mask_token, ignore_index, seed, first_row,
+                                     max_chars, form)
+    padlen = int(padlen)
+    if padlen <= 0:
+        raise ValueError("padlen must be positive")
+    chars, offsets = capi.host_batch(chars, offsets)
+    B = offsets.size - 1
+    shape = (B, padlen) if batch_first else (padlen, B)
+    inputs, labels = np.empty(shape, dtype=_NUMPY[dt]), np.empty(shape, dtype=_NUMPY[ldt])
+    lengths = np.empty(B, dtype=np.int32)
+    if B > 0:
+        capi.check(_lib.bsq_bpe_mlm_tokenize_host(ctypes.byref(vocab.desc), chars.ctypes.data, offsets.ctypes.data, B, padlen, int(bool(batch_first)),
+                                                  vocab.table.ctypes.data, vocab.M, ctypes.byref(bpe), ctypes.byref(m), dt, inputs.ctypes.data, ldt,
+                                                  labels.ctypes.data, lengths.ctypes.data))
+    return inputs, labels, lengths
+
+
+def bpe_mlm_tokenize_packed(vocab, chars, offsets, padlen, destchar="q", batch_first=True, *, label_destchar="q", frac=0.15, mask_prob=0.8,
+                            random_prob=0.1, mask_token=None, ignore_index=-100, seed=0, first_row=0, max_chars=None, form=None):
+    """Masked-LM batches over the BPE ids of a packed batch on the device: (inputs, labels, lengths) device tensors on torch's current
+    stream, one launch (`bsq_bpe_mlm_tokenize_device`; include/bsq.h, "BPE masked-LM", has the draw).  inputs and labels are (B, padlen)
+    when batch_first else (padlen, B), with `bpe_tokenize_packed`'s positions; lengths is `bpe_tokenize_packed`'s.
+
+    A share `frac` of a row's tokens is selected (UNK, BOS, EOS and PAD never are); a selected token becomes `mask_token` (None:
+    `bpe_vocab_size`) with probability mask_prob, a uniform id of the classes and merge products with random_prob, else keeps its id;
+    labels hold the plain id at selected tokens and ignore_index elsewhere.  A token's fate depends on (seed, first_row + its row, its
+    index in the row) and its own id only: not on padlen, the layout, the element types, max_chars, form, the batch's size or the
+    stream, so a shard drawn with its `first_row` is the same rows of the whole batch.  max_chars / form: exactly as `bpe_tokenize_packed`."""
+    import torch
+    B = capi.packed_on_device(chars, offsets, "bpe_mlm_tokenize_packed works on packed batches resident on the device (chars, offsets tensors)")
+    if max_chars is None:
+        longest = int((offsets[1:] - offsets[:-1]).max().item()) if B > 0 else 0
+        max_chars = WAVE_MAX_CHARS if longest <= WAVE_MAX_CHARS and form != 2 else MAX_CHARS
+    bpe, m, dt, ldt, tdt, ltdt = _bpe_mlm(vocab, destchar, label_destchar, frac, mask_prob, random_prob, mask_token, ignore_index, seed, first_row,
+                                          max_chars, form)
+    padlen = int(padlen)
+    if padlen <= 0:
+        raise ValueError("padlen must be positive")
+    shape = (B, padlen) if batch_first else (padlen, B)
+    inputs = torch.empty(shape, dtype=tdt, device=chars.device)
+    labels = torch.empty(shape, dtype=ltdt, device=chars.device)
+    lengths = torch.empty(B, dtype=torch.int32, device=chars.device)
+    if B > 0:
+        src = capi.readable_chars(chars, offsets.device)  # (every sequence may be empty)
+        table = vocab.device_table(src.device)
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_bpe_mlm_tokenize_device(ctypes.byref(vocab.desc), src.data_ptr(), offsets.data_ptr(), B, padlen, int(bool(batch_first)),
+                                                        table.data_ptr(), vocab.M, ctypes.byref(bpe), ctypes.byref(m), dt, inputs.data_ptr(), ldt,
+                                                        labels.data_ptr(), lengths.data_ptr(), stream))
+    return inputs, labels, lengths
+
+
 def _taken(a, key, best):
     """The positions of `a` where the pair `best` is replaced, left to right without overlap: in a run of consecutive occurrences (they
     exist only when l == r) those at even distance from the run's start."""
@@ -314,4 +404,4 @@ def bpe_train_host(tok, chars, offsets, n_merges):
 
 
 __all__ = ["BPEVocab", "bpe_tokenize_packed", "bpe_tokenize_host", "bpe_vocab_size", "bpe_special_ids", "bpe_strings", "bpe_decode",
-           "bpe_external_ids", "bpe_kernel_name", "bpe_train_host", "TOO_LONG", "MAX_CHARS", "WAVE_MAX_CHARS"]
+           "bpe_external_ids", "bpe_kernel_name", "bpe_train_host", "bpe_mlm_tokenize_packed", "bpe_mlm_tokenize_host", "bpe_mlm_kernel_name", "TOO_LONG", "MAX_CHARS", "WAVE_MAX_CHARS"]

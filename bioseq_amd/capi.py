@@ -90,6 +90,12 @@ class Bpe(ctypes.Structure):
     _fields_ = [("max_chars", ctypes.c_int32), ("form", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class BpeMlm(ctypes.Structure):
+    """struct bsq_bpe_mlm"""
+    _fields_ = [("frac", ctypes.c_double), ("mask_prob", ctypes.c_double), ("random_prob", ctypes.c_double), ("mask_token", ctypes.c_int64),
+                ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
+
+
 class Score(ctypes.Structure):
     """struct bsq_score"""
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32), ("mode", ctypes.c_int32), ("gap_open", ctypes.c_int32),
@@ -248,6 +254,9 @@ def load():
         "bsq_bpe_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), c_int, vp, vp, vp]),
         "bsq_bpe_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), c_int, vp, vp]),
         "bsq_bpe_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Bpe)]),
+        "bsq_bpe_mlm_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), ctypes.POINTER(BpeMlm), c_int, vp, c_int, vp, vp, vp]),
+        "bsq_bpe_mlm_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), ctypes.POINTER(BpeMlm), c_int, vp, c_int, vp, vp]),
+        "bsq_bpe_mlm_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Bpe)]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

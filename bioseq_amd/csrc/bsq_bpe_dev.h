@@ -119,6 +119,44 @@ BSQ_BPE_HD int32_t element(const Geometry &g, const Sym *sym, int32_t n, int64_t
     return g.pad_store;
 }
 
+// The CPU twins' merge loop (bsq_bpe_host.cpp, bsq_bpe_mlm_host.cpp), host only.  One row: seq[0 .. L) -> its ids in sym[0 .. n); returns n.  rk[i]: the rank of the pair at i; taken: a word per 64 positions.
+inline int32_t encode_row_host(const Geometry &g, const Entry *table, const int8_t *lut, const uint8_t *seq, int32_t L, uint16_t *sym, uint16_t *rk,
+                   uint64_t *taken) {
+    for (int32_t i = 0; i < L; ++i) {
+        const int32_t id = lut[seq[i]];
+        sym[i] = static_cast<uint16_t>(id < 0 ? g.V : id);
+        rk[i] = static_cast<uint16_t>(kDirty);
+    }
+    int32_t n = L;
+    for (int32_t step = 0; step < L; ++step) {  // (every step removes a symbol)
+        uint32_t mn = kNoRank;
+        for (int32_t i = 0; i < n; ++i) {
+            if (rk[i] == kDirty) rk[i] = static_cast<uint16_t>(pair_rank(g, table, sym, i, n));
+            mn = rk[i] < mn ? rk[i] : mn;
+        }
+        if (mn == kNoRank) break;
+        const int32_t nrows = (n + 63) >> 6;
+        bool prev = false;
+        for (int32_t w = 0; w < nrows; ++w) {
+            uint64_t cand = 0;
+            for (int32_t b = 0; b < 64 && 64 * w + b < n; ++b) cand |= static_cast<uint64_t>(rk[64 * w + b] == mn) << b;
+            taken[w] = select_taken(cand, prev);
+            prev = (taken[w] >> 63) != 0;
+        }
+        int32_t j = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            if (i > 0 && ((taken[(i - 1) >> 6] >> ((i - 1) & 63)) & 1)) continue;  // fused into the symbol in front
+            const bool tk = (taken[i >> 6] >> (i & 63)) & 1;
+            const bool next_tk = i + 1 < n && ((taken[(i + 1) >> 6] >> ((i + 1) & 63)) & 1);
+            sym[j] = tk ? static_cast<uint16_t>(g.C + mn) : sym[i];
+            rk[j] = (tk || next_tk) ? static_cast<uint16_t>(kDirty) : rk[i];
+            ++j;
+        }
+        n = j;
+    }
+    return n;
+}
+
 // 0 for a bsq_bpe the calls refuse, 1 the wave form, 2 the block form; bpe == nullptr: the defaults {8192, 0, 0}
 inline int32_t form_of(const bsq_bpe *bpe) {
     const int32_t max_chars = bpe ? bpe->max_chars : kMaxChars, form = bpe ? bpe->form : 0;

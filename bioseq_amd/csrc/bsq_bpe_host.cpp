@@ -1,6 +1,6 @@
 // BPE ids of a packed batch, the CPU side (include/bsq.h, "BPE ids of a packed batch"): the table builder, the sizes and ids, the twin
-// bsq_bpe_tokenize_host -- plain loops over a row's positions around the lookup, the selection and the element of bsq_bpe_dev.h, the
-// text the kernels of bsq_bpe.hip compile -- and the host-only bsq_bpe_kernel_name.  Plain C++: neither this file nor that header needs
+// bsq_bpe_tokenize_host -- bsq_bpe_dev.h's encode_row_host (plain loops over a row's positions around the lookup and the selection, the
+// text the kernels compile) and its element -- and the host-only bsq_bpe_kernel_name.  Plain C++: neither this file nor that header needs
 // the HIP headers.
 #include <cstdint>
 #include <vector>
@@ -15,44 +15,6 @@ bsq_status set_error(bsq_status st, const char *msg);  // (bsq_internal.h, which
 namespace {
 
 using namespace bsq_bped;
-
-// One row: seq[0 .. L) -> its ids in sym[0 .. n); returns n.  rk[i]: the rank of the pair at i; taken: a word per 64 positions.
-int32_t encode_row(const Geometry &g, const Entry *table, const int8_t *lut, const uint8_t *seq, int32_t L, uint16_t *sym, uint16_t *rk,
-                   uint64_t *taken) {
-    for (int32_t i = 0; i < L; ++i) {
-        const int32_t id = lut[seq[i]];
-        sym[i] = static_cast<uint16_t>(id < 0 ? g.V : id);
-        rk[i] = static_cast<uint16_t>(kDirty);
-    }
-    int32_t n = L;
-    for (int32_t step = 0; step < L; ++step) {  // (every step removes a symbol)
-        uint32_t mn = kNoRank;
-        for (int32_t i = 0; i < n; ++i) {
-            if (rk[i] == kDirty) rk[i] = static_cast<uint16_t>(pair_rank(g, table, sym, i, n));
-            mn = rk[i] < mn ? rk[i] : mn;
-        }
-        if (mn == kNoRank) break;
-        const int32_t nrows = (n + 63) >> 6;
-        bool prev = false;
-        for (int32_t w = 0; w < nrows; ++w) {
-            uint64_t cand = 0;
-            for (int32_t b = 0; b < 64 && 64 * w + b < n; ++b) cand |= static_cast<uint64_t>(rk[64 * w + b] == mn) << b;
-            taken[w] = select_taken(cand, prev);
-            prev = (taken[w] >> 63) != 0;
-        }
-        int32_t j = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            if (i > 0 && ((taken[(i - 1) >> 6] >> ((i - 1) & 63)) & 1)) continue;  // fused into the symbol in front
-            const bool tk = (taken[i >> 6] >> (i & 63)) & 1;
-            const bool next_tk = i + 1 < n && ((taken[(i + 1) >> 6] >> ((i + 1) & 63)) & 1);
-            sym[j] = tk ? static_cast<uint16_t>(g.C + mn) : sym[i];
-            rk[j] = (tk || next_tk) ? static_cast<uint16_t>(kDirty) : rk[i];
-            ++j;
-        }
-        n = j;
-    }
-    return n;
-}
 
 int64_t geometry_value(const bsq_desc *d, int64_t M, int which) {
     Geometry g;
@@ -76,7 +38,7 @@ void run_rows(const Geometry &g, const bsq_desc *d, const uint8_t *chars, const 
         int64_t L = offsets[b + 1] - offsets[b];
         L = L < 0 ? 0 : L;  // (a length as read from the offsets: a negative one counts as 0)
         const bool too_long = L > max_chars;
-        const int32_t n = too_long ? 0 : encode_row(g, table, d->lut, chars + offsets[b], static_cast<int32_t>(L), sym.data(), rk.data(), taken.data());
+        const int32_t n = too_long ? 0 : encode_row_host(g, table, d->lut, chars + offsets[b], static_cast<int32_t>(L), sym.data(), rk.data(), taken.data());
         lengths[b] = too_long ? BSQ_BPE_TOO_LONG : n;
         for (int64_t t = 0; t < P; ++t) out[batch_first ? b * P + t : t * B + b] = static_cast<T>(element(g, sym.data(), n, P, t));
     }

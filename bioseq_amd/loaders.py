@@ -13,7 +13,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import blosum, kmers, masking, packing, views
+from . import blosum, capi, kmers, masking, packing, views
+from . import bpe as bpe_ids
 from . import translate as translation
 from .flatfile import FlatFile
 
@@ -89,6 +90,20 @@ class FlatFileDataset(torch.utils.data.Dataset):
     they encode any unmapped character.  revcomp_frac > 0 is allowed with it whatever the tokenizer: the strand draw in front of the
     frame makes the batch a sample of the six frames.  Translation draws nothing: no key or counter is added, no existing draw shifts.
 
+    bpe=vocab (keyword; off by default; token rows only; a `bpe.BPEVocab` over this dataset's tokenizer): a token is a BPE id
+    (bpe.bpe_tokenize_packed, one launch; `token_dtype`, batch-first) from `get_batch`, `__getitems__`, `__getitem__` and `batches()`.
+    max_seq_len = `bpe_padlen` when given (a smaller number cuts rows, as padlen does everywhere), else longest + bos + eos with
+    `longest` the crop, the store's maxseqlen, or a third of it under translate=: no merge can lengthen a row.  `longest` is also the
+    call's max_chars, so no batch reads anything back; above 8192 it is a ValueError: give crop=.  A store whose lengths are not
+    trusted (opened with a smaller maxseqlen than its longest sequence) has every batch's lengths checked, and a row that is too long
+    raises, as validated batches do.  It composes with crop, revcomp_frac, translate, shuffle, group and prefetch.  With cnn=True,
+    augment > 0, masked=True, kmer=, pack= or spectrum= it raises ValueError.
+
+    bpe_mlm=True (keyword; off by default; only with bpe=): the BPE batches are masked-LM batches drawn on the device at rate `maskfrac`
+    (bpe.bpe_mlm_tokenize_packed, the same single launch) -- (inputs, labels): BERT's 80/10/10 replacement with mask token =
+    bpe.bpe_vocab_size, labels int64 with ignore_index -100.  Keyed like kmer_mlm=True: a fresh key per call and per `batches()` epoch,
+    a row keyed by its index in the epoch's order, so `group` and `prefetch` hand out the same masks.
+
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
     (tokens, segment_ids, position_ids), each (rows, max_seq_len), rows being what the batch needs (one 8-byte read-back per batch:
@@ -111,7 +126,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
                  crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False,
                  kmer_mlm=False, kmer_span=None, spectrum=None, spectrum_stride=1, spectrum_both_strands=False, spectrum_normalize=True,
-                 translate=None, codon_table=1):
+                 translate=None, codon_table=1, bpe=None, bpe_padlen=None, bpe_mlm=False):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -193,6 +208,31 @@ class FlatFileDataset(torch.utils.data.Dataset):
             # (k, stride, nchars ** k and the strands are checked here)
             kmers.kmer_spectrum_kernel_name(tokenizer, self.spectrum, 1, "f", stride=self.spectrum_stride,
                                             both_strands=self.spectrum_both_strands, normalize=self.spectrum_normalize)
+
+        self.bpe, self.bpe_mlm = bpe, bool(bpe_mlm)
+        if self.bpe_mlm and bpe is None:
+            raise ValueError("bpe_mlm=True masks the BPE batches of bpe=: give bpe=vocab with it")
+        if bpe is not None:
+            if cnn or augment or masked or kmer is not None or pack is not None or spectrum is not None:
+                raise ValueError("bpe= gives BPE token rows of the plain batch: it cannot be combined with cnn=True, augment > 0, masked=True, "
+                                 "kmer=, pack= or spectrum= (masked-LM batches over BPE ids: bpe_mlm=True)")
+            if not isinstance(bpe, bpe_ids.BPEVocab) or bytes(bpe.desc) != bytes(capi.desc_of(tokenizer)):
+                raise ValueError("bpe= must be a BPEVocab over this dataset's tokenizer (the same alphabet and eos / bos / padchar flags)")
+            longest = self.crop if self.crop is not None else ff.maxseqlen
+            if self.translate is not None:
+                longest //= 3
+            if longest > bpe_ids.MAX_CHARS:
+                raise ValueError("bpe= takes rows of at most %d characters and this store's reach %d: give crop=" % (bpe_ids.MAX_CHARS, longest))
+            self._bpe_max_chars = max(1, longest)
+            if bpe_padlen is not None and int(bpe_padlen) <= 0:
+                raise ValueError("bpe_padlen must be a positive number of positions, got %r" % (bpe_padlen,))
+            width = longest + int(tokenizer.includes_bos()) + int(tokenizer.includes_eos())
+            self.max_seq_len = self.maxseqlen = int(bpe_padlen) if bpe_padlen is not None else max(1, width)
+            # (token_dtype and maskfrac are checked here)
+            if self.bpe_mlm:
+                bpe_ids._bpe_mlm(bpe, token_dtype, "q", maskfrac, 0.8, 0.1, None, -100, 0, 0, self._bpe_max_chars, None)
+            else:
+                bpe_ids._bpe(bpe, token_dtype, self._bpe_max_chars, None)
 
     def __len__(self):
         return self.ff.nseqs()
@@ -280,6 +320,18 @@ class FlatFileDataset(torch.utils.data.Dataset):
                                               stride=self.kmer_stride, frac=self.maskfrac, span=self.kmer_span, seed=mask_seed,
                                               first_row=first_row, validate=not self._trusted_lengths)
 
+    def _bpe_lengths_checked(self, lengths):
+        """A store whose lengths are not trusted may hold a row of more than max_chars characters: its batch raises (one read-back)."""
+        if not self._trusted_lengths and bool((lengths < 0).any()):
+            raise RuntimeError("a sequence is longer than the %d characters bpe= was set up for (the store's maxseqlen)" % self._bpe_max_chars)
+
+    def _encode_bpe_mlm(self, chars, offs, mask_seed, first_row):
+        inputs, labels, lengths = bpe_ids.bpe_mlm_tokenize_packed(self.bpe, chars, offs, self.max_seq_len, self.token_dtype, True,
+                                                                  frac=self.maskfrac, seed=mask_seed, first_row=first_row,
+                                                                  max_chars=self._bpe_max_chars)
+        self._bpe_lengths_checked(lengths)
+        return inputs, labels
+
     def _encode(self, chars, offs):
         """augment_seq, then encode (bioseq/loaders.py:83-84, :102-103) on the batch's own copy.  Token rows go through the
         one-call entry `blosum.augment_tokenize_packed` (one launch for int8 rows; the entry runs the two launches for the
@@ -291,6 +343,10 @@ class FlatFileDataset(torch.utils.data.Dataset):
         if self.kmer is not None:
             return kmers.kmer_tokenize_packed(self.tokenizer, chars, offs, self.kmer, self.max_seq_len, self.token_dtype, True,
                                               stride=self.kmer_stride, validate=not trusted)
+        if self.bpe is not None:
+            tokens, lengths = bpe_ids.bpe_tokenize_packed(self.bpe, chars, offs, self.max_seq_len, self.token_dtype, True, max_chars=self._bpe_max_chars)
+            self._bpe_lengths_checked(lengths)
+            return tokens
         if self.spectrum is not None:
             return kmers.kmer_spectrum_packed(self.tokenizer, chars, offs, self.spectrum, "f", stride=self.spectrum_stride,
                                               both_strands=self.spectrum_both_strands, normalize=self.spectrum_normalize, validate=not trusted)
@@ -317,6 +373,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_pack_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
         if self.kmer_mlm:
             return self._encode_kmer_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
+        if self.bpe_mlm:
+            return self._encode_bpe_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
         return self._encode(*self._packed_device(start, stop))
 
     def _index(self, i):
@@ -346,6 +404,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_pack_mlm(*packed, self._mask_key(), 0)
         if self.kmer_mlm:
             return self._encode_kmer_mlm(*packed, self._mask_key(), 0)
+        if self.bpe_mlm:
+            return self._encode_bpe_mlm(*packed, self._mask_key(), 0)
         return self._encode(*packed)
 
     def batches(self, batch_size, shuffle=True, drop_last=False, generator=None, prefetch=None, group=1):
@@ -382,11 +442,11 @@ class FlatFileDataset(torch.utils.data.Dataset):
             raise ValueError("group > 1 cannot be combined with pack=: a super-batch's row blocks are not the batches' own packings")
         if self.spectrum is not None and int(group) > 1:
             raise ValueError("group > 1 cannot be combined with spectrum=")
-        pairs = self.masked or self.pack is not None or self.kmer_mlm  # a batch is a tuple of tensors
+        pairs = self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm  # a batch is a tuple of tensors
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
-        mask_seed = self._mask_key() if self.masked or self.pack_mlm or self.kmer_mlm else None
+        mask_seed = self._mask_key() if self.masked or self.pack_mlm or self.kmer_mlm or self.bpe_mlm else None
         crop_seed = self._crop_key() if self._views else None
 
         def encode(first):
@@ -400,13 +460,15 @@ class FlatFileDataset(torch.utils.data.Dataset):
                 return self._encode_pack_mlm(*packed, mask_seed, first)
             if self.kmer_mlm:
                 return self._encode_kmer_mlm(*packed, mask_seed, first)
+            if self.bpe_mlm:
+                return self._encode_bpe_mlm(*packed, mask_seed, first)
             return self._encode(*packed)
 
         def hand_out(big):
             rows = big[0].shape[0] if pairs else big.shape[0]
             if rows <= batch_size or self.pack is not None:
                 yield big
-            elif self.masked or self.kmer_mlm:
+            elif self.masked or self.kmer_mlm or self.bpe_mlm:
                 for r in range(0, rows, batch_size):
                     yield big[0][r:r + batch_size], big[1][r:r + batch_size]
             else:
@@ -471,7 +533,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
             s, e, st = index.indices(len(self))
             return self.__getitems__(list(range(s, e, st)))
         index = self._index(index)
-        if self.masked or self.pack is not None or self.kmer_mlm:
+        if self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm:
             return tuple(t[0] for t in self.get_batch(index, index + 1))
         return self.get_batch(index, index + 1)[0]
 

@@ -50,7 +50,8 @@ extern "C" {
                            * bsq_score_pairs_host, bsq_score_pairs_kernel_name, bsq_blosum62_scores, bsq_align_stats_device,
                            * bsq_align_stats_host, bsq_align_stats_kernel_name, bsq_bpe, bsq_bpe_table_bytes, bsq_bpe_table_build,
                            * bsq_bpe_vocab_size, bsq_bpe_unk_id, bsq_bpe_bos_id, bsq_bpe_eos_id, bsq_bpe_pad_id, bsq_bpe_tokenize_device,
-                           * bsq_bpe_tokenize_host, bsq_bpe_kernel_name; nothing removed */
+                           * bsq_bpe_tokenize_host, bsq_bpe_kernel_name, bsq_bpe_mlm, bsq_bpe_mlm_tokenize_device, bsq_bpe_mlm_tokenize_host,
+                           * bsq_bpe_mlm_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -1135,7 +1136,8 @@ const char *bsq_align_stats_kernel_name(const bsq_score *s);
  * table_dev / table_host and M of a tokenize call must be what one build produced; the probe loop is bounded by the capacity and the
  * step loop by the row's length, so a damaged table ends in wrong ids, never in a wait.
  *
- * Kernels (csrc/bsq_bpe.hip; csrc/bsq_bpe_dev.h has the lookup and the run-parity selection, the text the CPU twin shares): one row is
+ * Kernels (csrc/bsq_bpe.hip; csrc/bsq_bpe_row.h has the merge loop, which the masked-LM kernels share, and csrc/bsq_bpe_dev.h the lookup
+ * and the run-parity selection, the text the CPU twin shares): one row is
  * never split across workgroups.  k_bpe_wave: a wave per row, four rows per workgroup, max_chars <= 1024 (form 0 takes it there, so a
  * smaller bound is a cheaper call); k_bpe_block: a 256-thread workgroup per row, up to 8192.  The row's symbols stay dense in LDS as
  * 16-bit ids with the rank of each adjacent pair beside them; position 64 q + lane belongs to lane `lane`, so a step is a min-reduction
@@ -1178,6 +1180,70 @@ bsq_status bsq_bpe_tokenize_host(const bsq_desc *d, const uint8_t *chars, const 
                                  const void *table_host, int64_t M, const bsq_bpe *bpe, bsq_dtype t, void *tokens, int32_t *lengths);
 /* Host only: the kernel the device call takes ("k_bpe_wave", "k_bpe_block"); "" for a bsq_bpe the calls refuse. */
 const char *bsq_bpe_kernel_name(const bsq_bpe *bpe);
+
+/* ---- BPE masked-LM: masked-LM batches over the ids of bsq_bpe, the objective DNABERT-2, GENA-LM and GROVER are pretrained with (BERT's,
+ * over BPE tokens).  Inputs, labels and lengths of a packed batch in ONE launch, with bsq_bpe's ids and positions.
+ *
+ * THE DRAW.  n is the number of ids of the row and id_j its ids (bsq_bpe's rule), V = C + M, UNK = V; row = first_row + i for row i of
+ * the batch.  With mix64 the splitmix64 finalizer and T_x = floor(p_x * 65536 + 0.5):
+ *     h_row       = mix64((seed ^ 0x4250454D4C4D534B) + 0x9E3779B97F4A7C15 * (row + 1))    "BPEMLMSK": a domain of its own
+ *     w(q)        = mix64(h_row + 0xD1342543DE82EF95 * (q + 1))                             one word per 4 token indices
+ *     selected(j) <=>  0 <= j < n  and  id_j != UNK  and  ((w(j >> 2) >> (16 * (j & 3))) & 0xFFFF) < T_frac
+ *     v           = mix64(~h_row + 0xD1342543DE82EF95 * (j + 1))                            selected tokens only
+ *     cat16 = v & 0xFFFF,  rnd32 = (v >> 16) & 0xFFFFFFFF
+ *     input       = mask_token                 if cat16 < T_mask
+ *                   (rnd32 * V) >> 32          if cat16 < T_mask + T_random    (uniform over classes and merge products; 32 bits: V
+ *                                                                               reaches 65532)
+ *                   id_j                       otherwise
+ *     label       = id_j if selected(j) else ignore_index
+ * BOS, EOS, PAD and UNK positions are never selected: they carry bsq_bpe's value in the inputs and ignore_index in the labels.  The
+ * matrix shows the tokens j < n' = min(n, max(P - bos - eos, 0)).  A token's fate depends on (seed, row, j, the thresholds) and its
+ * own id only -- never on padlen, layout, element types, form, max_chars, batch size, shards or the stream.  frac = 0: the inputs are
+ * bsq_bpe_tokenize_device's output, bit for bit, and every label is ignore_index; frac = 1: every non-UNK token is selected.  lengths
+ * is exactly bsq_bpe_tokenize_device's: a row of more than max_chars characters gets -1, the inputs of an empty row and labels that are
+ * all ignore_index.
+ *
+ * Known answers (DNA4, no flags, the merges of bsq_bpe's known answers, V = UNK = 10, mask_token = vocab = 11, ignore_index = -100
+ * written as "-", mask_prob 0.8, random_prob 0.1, seed 7; the batch AAAAAAA, ACGTACGT, AAACGTNAAAA, TTTTT, whose plain ids are
+ * 8 6 / 0 7 0 7 / 6 7 10 8 / 9 9 3):
+ *     frac 0.5, first_row 0:    inputs 11 11 | 0 7 11 7 | 6 11 10 11 | 2 9 3        labels 8 6 | - - 0 7 | - 7 - 8 | 9 - -
+ *     frac 0.5, first_row 100:  inputs 8 11 | 0 11 0 11 | 11 7 10 11 | 11 9 3       labels - 6 | - 7 - 7 | 6 - - 8 | 9 - -
+ *     frac 1.0, first_row 0:    inputs 11 11 | 11 11 11 7 | 6 11 10 11 | 2 11 11    labels 8 6 | 0 7 0 7 | 6 7 - 8 | 9 9 3
+ * (the mask case, a random id -- 2 for label 9 --, a kept id -- 7 stays 7, 6 stays 6 -- and the UNK that is never selected).  On
+ * 65 536 tokens of id 0 at seed 1, row 0, frac 0.15: 9847 are selected (0.1503), 7888 of those become the mask token (0.801) and 858 a
+ * random id other than 0 (a random draw hits 0 with probability 1 / 10: about 953 random draws, 0.097 of the selected).
+ *
+ * Refused before anything is launched, with the outputs untouched and bsq_last_error() set, BSQ_ERR_INVALID_ARG: everything
+ * bsq_bpe_tokenize_device refuses, a null bsq_bpe_mlm, a probability outside [0, 1] or NaN, mask_prob + random_prob > 1, first_row < 0,
+ * mask_token < 0, both outputs NULL; BSQ_ERR_DTYPE, by bsq_dtype_holds: an input type that does not hold [0, max(vocab - 1,
+ * mask_token)], a label type that does not hold [min(ignore_index, 0), max(ignore_index, V - 1)].
+ * Conventions of the neighbouring entry points: stream-ordered, never synchronises, B == 0 is BSQ_OK with nothing launched, either
+ * output may be NULL (not both); all six bsq_dtypes for each output, every stored value exact in its type.
+ * Kernels (csrc/bsq_bpe_mlm.hip; csrc/bsq_bpe_mlm_dev.h has the value of one element, the text the CPU twin shares): k_bpe_mlm_wave (a
+ * wave per row, four rows per workgroup, max_chars <= 1024) and k_bpe_mlm_block (a workgroup per row, up to 8192) are the merge loop of
+ * k_bpe_wave / k_bpe_block (csrc/bsq_bpe_row.h, one text) followed by an output stage that reads the row's final ids from LDS once:
+ * per position the selection hash of its quad, for a selected token the replacement hash, then the two stores.  The element types are
+ * chosen at run time (a wave-uniform switch in front of each store), so there are two kernels, not 72.  No LDS beyond the merge
+ * loop's, no global atomic, nobody waits. */
+typedef struct bsq_bpe_mlm {
+    double frac;          /* share of the non-UNK tokens that are selected, in [0, 1] */
+    double mask_prob;     /* of the selected: replaced by mask_token (BERT: 0.8) */
+    double random_prob;   /* of the selected: replaced by a uniform id of 0 .. V - 1 (BERT: 0.1); the rest keep their id */
+    int64_t mask_token;   /* usually bsq_bpe_vocab_size(): one past the last id */
+    int64_t ignore_index; /* label of every position that is not selected (torch: -100) */
+    uint64_t seed;
+    int64_t first_row;    /* row key of the batch's first sequence (a shard or a piece of a larger batch: its first row there) */
+} bsq_bpe_mlm;            /* 56 bytes */
+bsq_status bsq_bpe_mlm_tokenize_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P,
+                                       int32_t batch_first, const void *table_dev, int64_t M, const bsq_bpe *bpe, const bsq_bpe_mlm *m,
+                                       bsq_dtype in_dtype, void *inputs_or_null, bsq_dtype label_dtype, void *labels_or_null, int32_t *lengths,
+                                       void *hip_stream);
+/* CPU twin on host buffers (the same merge loop and element text; no device is needed). */
+bsq_status bsq_bpe_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P, int32_t batch_first,
+                                     const void *table_host, int64_t M, const bsq_bpe *bpe, const bsq_bpe_mlm *m, bsq_dtype in_dtype,
+                                     void *inputs_or_null, bsq_dtype label_dtype, void *labels_or_null, int32_t *lengths);
+/* Host only: the kernel the device call takes ("k_bpe_mlm_wave", "k_bpe_mlm_block"); "" for a bsq_bpe the calls refuse. */
+const char *bsq_bpe_mlm_kernel_name(const bsq_bpe *bpe);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
