@@ -234,6 +234,10 @@ def load():
         "bsq_cluster_pairs_device": (i32, [vp, vp, i64, i64, vp, vp, vp]),
         "bsq_cluster_pairs_host": (i32, [vp, vp, i64, i64, vp]),
         "bsq_sketch_clusters_kernel_name": (ctypes.c_char_p, [i64, i32]),
+        "bsq_greedy_scratch_bytes": (i64, [i64, i64]),
+        "bsq_greedy_pairs_device": (i32, [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp]),
+        "bsq_greedy_pairs_host": (i32, [vp, vp, vp, i64, i64, vp, vp]),
+        "bsq_greedy_kernel_name": (ctypes.c_char_p, [i32, i32]),
         "bsq_edit_pairs_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp, vp]),
         "bsq_edit_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp]),
         "bsq_edit_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Edit)]),

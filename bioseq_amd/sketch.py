@@ -25,7 +25,11 @@ fraction J of their k-mers agree in about that fraction of their non-empty bucke
 * `cluster_pairs`     the same labels from an explicit edge list (`bsq_cluster_pairs_device`): merged lists, pairs from elsewhere;
 * `sketch_clusters_host`, `cluster_pairs_host`, `sketch_clusters_kernel_name`    their CPU twins, the launches;
 * `cluster_table`, `cluster_split`    (representatives, sizes, dense ids) of a label array; a seeded split in which every cluster goes to
-                      one side whole.
+                      one side whole;
+* `greedy_pairs`      greedy representatives of an edge list (cd-hit's rule: visit the nodes longest first, keep a node unless an
+                      earlier kept node is linked to it): rep[i] per node, no two kept nodes linked, every dropped node linked to a kept
+                      one (`bsq_greedy_pairs_device`; include/bsq.h, "greedy representatives");
+* `greedy_pairs_host`, `greedy_kernel_name`, `length_key`    its CPU twin, its launches, the "longest first" key of a packed batch.
 
 The sketch of a sequence equals the bucket-wise UNSIGNED minimum of the sketches of pieces that together cover all its windows (EMPTY
 is the largest value), so sketches of longer sequences, or of sets of sequences, are merged without the characters.
@@ -252,7 +256,8 @@ def sketch_pairs(a, b=None, *, min_jaccard=0.5, min_match=1, max_pairs=None, eit
 def sketch_duplicates(a, *, min_jaccard=0.9, min_match=1, max_pairs=None):
     """De-duplication of one sketch matrix from its pair list: (keep, first).  first[j] (int64, B) is the smallest i < j that
     `sketch_pairs(a, min_jaccard=..., min_match=...)` lists with j, or j itself; keep = first == arange(B) (bool).  `a[keep]` drops EVERY
-    row that has an earlier near-duplicate: of a chain A ~ B ~ C it loses B and C even when A and C are not similar.  A device tensor
+    row that has an earlier near-duplicate: of a chain A ~ B ~ C it loses B and C even when A and C are not similar (`greedy_pairs` over
+    the pair list keeps C there: every dropped row then has a kept neighbour).  A device tensor
     gives device tensors (`scatter_reduce(amin)` over the list), a numpy matrix goes through the CPU twin and gives numpy.
 
     max_pairs=None sizes the list exactly (one 8-byte read-back on the device) and returns (keep, first).  max_pairs=N reads nothing
@@ -306,6 +311,7 @@ def sketch_clusters(a, *, min_jaccard=0.9, min_match=1, segments=None):
     A and C are not similar -- so the two ends of a large cluster need not resemble each other; that is what a leakage-free split wants
     (nothing similar to a test row stays in the training set) and not what a choice of representatives at a fixed radius wants.
     `sketch_duplicates` is unchanged and remains the "earliest neighbour" filter.
+    `greedy_pairs` over a pair list is the choice of representatives (no two kept rows linked, every dropped row linked to a kept one).
 
     A train set together with a test set: `labels = sketch_clusters(torch.cat([train, test]))`, then `cluster_split(labels, ...)` for a
     new split of both, or compare `labels[:len(train)]` with `labels[len(train):]` for the clusters that straddle the old one."""
@@ -378,6 +384,114 @@ def sketch_clusters_kernel_name(B, segments=None):
     return _lib.bsq_sketch_clusters_kernel_name(int(B), 0 if segments is None else int(segments)).decode()
 
 
+def _greedy_host_args(row, col, n, key, weight):
+    n = _edge_count(n)
+    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
+    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
+        raise ValueError("row and col are int64 arrays of one length")
+    if key is not None:
+        key = np.ascontiguousarray(key)
+        if key.dtype != np.int64 or key.shape != (n,):
+            raise ValueError("key is an int64 array of n entries")
+    if weight is not None:
+        weight = np.ascontiguousarray(weight)
+        if weight.dtype != np.int32 or weight.shape != row.shape:
+            raise ValueError("weight is an int32 array of the list's length")
+    return row, col, n, key, weight
+
+
+def greedy_pairs_host(row, col, n, *, key=None, weight=None):
+    """The library's CPU twin of `greedy_pairs` (`bsq_greedy_pairs_host`, the plain sequential visit) on numpy arrays: rep (int64, n)."""
+    row, col, n, key, weight = _greedy_host_args(row, col, n, key, weight)
+    rep = np.empty(n, np.int64)
+    if n:
+        capi.check(_lib.bsq_greedy_pairs_host(row.ctypes.data if row.size else None, col.ctypes.data if row.size else None,
+                                              None if weight is None or not row.size else weight.ctypes.data, row.size, n,
+                                              None if key is None else key.ctypes.data, rep.ctypes.data))
+    return rep
+
+
+def _round_count(value, name):
+    if isinstance(value, bool) or int(value) != value or not 0 <= int(value) < 1 << 30:
+        raise ValueError("%s must be an integer in 0 .. 2 ** 30 - 1, got %r" % (name, value))
+    return int(value)
+
+
+def greedy_pairs(row, col, n, *, key=None, weight=None, max_rounds=None, rounds_per_call=16):
+    """Greedy representatives of an edge list (cd-hit's rule; include/bsq.h, "greedy representatives"): rep (int64, n).  Entry k links
+    nodes row[k] and col[k] (either orientation, duplicates allowed; an entry with row == col or an index outside 0 .. n - 1 is ignored,
+    as in `cluster_pairs`).  Node u comes before node v when (key[u], u) < (key[v], v); key=None is index order and `length_key(offsets)`
+    is "longest first".  The nodes are visited in that order and a node is kept as a representative unless one of its earlier neighbours
+    is kept.  rep[i] = i for a representative; for a member, the representative neighbour before i that comes first in the order, or,
+    with weight (int32, one per entry), the one whose entry has the largest weight (ties to the first in the order).  No entry joins two
+    representatives, every member has an entry to rep[i], `rep[rep] == rep`, and rep serves `cluster_table` and `cluster_split` as
+    labels; `rep == arange(n)` is the keep mask.  The result depends on the edges and the order alone.
+
+    Device int64 tensors give a device tensor on torch's current stream (`bsq_greedy_pairs_device`: rounds of two launches over the
+    list; random lists take about ten rounds, a path laid out in visiting order as many as it has nodes).  max_rounds=None: calls of
+    `rounds_per_call` rounds, each followed by an 8-byte read-back of the count of nodes left; while it is positive the run continues
+    where it stopped with twice the rounds per call; returns rep.  max_rounds=N: one call of N rounds, nothing read back; returns
+    (rep, undecided) with rep[i] = -1 where node i is not decided yet, final everywhere else, and `undecided` (a 0-d tensor) the
+    number of those.  numpy arrays go through the CPU twin (`greedy_pairs_host`) and give numpy -- rep, or (rep, 0) with max_rounds;
+    the two agree bit for bit."""
+    if max_rounds is not None:
+        max_rounds = _round_count(max_rounds, "max_rounds")
+    rounds_per_call = _round_count(rounds_per_call, "rounds_per_call")
+    if rounds_per_call < 1:
+        raise ValueError("rounds_per_call must be at least 1")
+    if isinstance(row, np.ndarray) and isinstance(col, np.ndarray):
+        rep = greedy_pairs_host(row, col, n, key=key, weight=weight)
+        return rep if max_rounds is None else (rep, np.int64(0))
+    import torch
+    n = _edge_count(n)
+    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda and row.device == col.device):
+        raise ValueError("greedy_pairs works on index tensors resident on one device, or on numpy arrays")
+    if row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or row.shape != col.shape or not row.is_contiguous() or not col.is_contiguous():
+        raise ValueError("row and col are contiguous int64 tensors of one length")
+    if key is not None and not (isinstance(key, torch.Tensor) and key.device == row.device and key.dtype == torch.int64 and key.shape == (n,)
+                                and key.is_contiguous()):
+        raise ValueError("key is a contiguous int64 tensor of n entries on the list's device")
+    if weight is not None and not (isinstance(weight, torch.Tensor) and weight.device == row.device and weight.dtype == torch.int32
+                                   and weight.shape == row.shape and weight.is_contiguous()):
+        raise ValueError("weight is a contiguous int32 tensor of the list's length on the list's device")
+    dev = row.device
+    rep = torch.empty(n, dtype=torch.int64, device=dev)
+    left = torch.zeros((), dtype=torch.int64, device=dev)
+    if n:
+        scratch = torch.empty((_lib.bsq_greedy_scratch_bytes(n, row.numel()) + 7) // 8, dtype=torch.int64, device=dev)
+        done, step = 0, rounds_per_call if max_rounds is None else max_rounds
+        with capi.launching(dev) as stream:
+            while True:
+                step = min(step, (1 << 30) - 1 - done)
+                capi.check(_lib.bsq_greedy_pairs_device(row.data_ptr(), col.data_ptr(), None if weight is None else weight.data_ptr(), row.numel(), n,
+                                                        None if key is None else key.data_ptr(), scratch.data_ptr(), done, step, rep.data_ptr(),
+                                                        left.data_ptr(), stream))
+                done += step
+                if max_rounds is not None or int(left.item()) == 0:
+                    break
+                if step == 0:
+                    raise RuntimeError("greedy_pairs: %d nodes left after 2 ** 30 - 1 rounds" % int(left.item()))
+                step *= 2
+    return rep if max_rounds is None else (rep, left)
+
+
+def greedy_kernel_name(*, key=False, weight=False):
+    """The launches `greedy_pairs` takes with or without a key and a weight (host only: profiling labels, tests): those of one round,
+    then, behind the ';', those of the assignment that ends every call."""
+    return _lib.bsq_greedy_kernel_name(int(bool(key)), int(bool(weight))).decode()
+
+
+def length_key(offsets):
+    """The key of cd-hit's order, "longest first": -(offsets[1:] - offsets[:-1]) as int64, a tensor for a tensor (on its device) and a
+    numpy array otherwise.  Rows of one length fall to the earlier row."""
+    if isinstance(offsets, np.ndarray) or not hasattr(offsets, "is_cuda"):
+        o = np.asarray(offsets, np.int64).ravel()
+        return np.ascontiguousarray(o[:-1] - o[1:])
+    import torch
+    o = offsets.to(torch.int64).reshape(-1)
+    return (o[:-1] - o[1:]).contiguous()
+
+
 def cluster_table(labels):
     """(representatives, sizes, dense_id) of a label array: the rows with labels == arange, ascending (int64); their member counts
     (int64); and dense_id[i], the rank of labels[i] among the representatives -- consecutive cluster numbers 0 .. C - 1 in order of each
@@ -437,4 +551,5 @@ def cluster_split(labels, fractions, seed=0):
 
 __all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard",
            "sketch_pairs", "sketch_pairs_host", "sketch_duplicates", "sketch_pairs_kernel_name", "sketch_clusters", "sketch_clusters_host",
-           "cluster_pairs", "cluster_pairs_host", "sketch_clusters_kernel_name", "cluster_table", "cluster_split"]
+           "cluster_pairs", "cluster_pairs_host", "sketch_clusters_kernel_name", "cluster_table", "cluster_split", "greedy_pairs",
+           "greedy_pairs_host", "greedy_kernel_name", "length_key"]

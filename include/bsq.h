@@ -51,7 +51,8 @@ extern "C" {
                            * bsq_align_stats_host, bsq_align_stats_kernel_name, bsq_bpe, bsq_bpe_table_bytes, bsq_bpe_table_build,
                            * bsq_bpe_vocab_size, bsq_bpe_unk_id, bsq_bpe_bos_id, bsq_bpe_eos_id, bsq_bpe_pad_id, bsq_bpe_tokenize_device,
                            * bsq_bpe_tokenize_host, bsq_bpe_kernel_name, bsq_bpe_mlm, bsq_bpe_mlm_tokenize_device, bsq_bpe_mlm_tokenize_host,
-                           * bsq_bpe_mlm_kernel_name; nothing removed */
+                           * bsq_bpe_mlm_kernel_name, bsq_greedy_scratch_bytes, bsq_greedy_pairs_device, bsq_greedy_pairs_host,
+                           * bsq_greedy_kernel_name; nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -847,6 +848,93 @@ bsq_status bsq_cluster_pairs_host(const int64_t *row, const int64_t *col, int64_
 /* Host only: the launches of bsq_sketch_clusters_device joined by '+' ("k_cluster_init+k_sketch_link+k_cluster_labels"); "" for B == 0,
  * which launches nothing, and for sizes or a `segments` the call refuses. */
 const char *bsq_sketch_clusters_kernel_name(int64_t B, int32_t segments);
+
+/* ---- greedy representatives: a non-redundant set of the nodes of an edge list, by the rule of cd-hit, UniRef50/90 and linclust --
+ * visit the nodes in an order (the longest sequence first), keep a node unless an earlier kept node is linked to it -- as one int64
+ * per node.  Where the clusters above are connected components (chains merge: a leakage-free split), this is the choice of
+ * representatives at a fixed radius: no two kept nodes are linked, and every dropped node is linked to a kept one.  It works on the
+ * pair lists the pipeline produces (sketch pairs, verified by edit distance, score or alignment statistics), on the device.
+ *
+ * THE RULE.
+ *     inputs       n nodes, 0 <= n <= 2^31 - 1.  An undirected edge list row[k] -- col[k] (int64, n_pairs entries, either orientation,
+ *                  duplicates allowed).  An entry with row == col is ignored, and so is one with an index outside 0 .. n - 1, which is
+ *                  never dereferenced (bsq_cluster_pairs_device's convention: the zeros behind a list cut at max_pairs are harmless).
+ *                  key: NULL or int64, n entries, any values.  weight: NULL or int32, one per list entry.
+ *     order        node u comes before node v when (key[u], u) < (key[v], v) lexicographically; key == NULL is index order.  Any int64
+ *                  array is a legal total order: nothing is sorted, and ties fall to the smaller index.
+ *     representatives   visit the nodes in that order: a node is a representative iff none of its neighbours that come before it is one.
+ *     rep[i]       (int64, n entries) a representative: i itself.  A member, without weight: among the representative neighbours that
+ *                  come BEFORE i, the one that comes first in the order (a representative neighbour that comes after i is never
+ *                  chosen).  A member, with weight: among the same neighbours, the one whose connecting entry has the largest weight,
+ *                  ties to the one that comes first in the order; of duplicate entries the largest weight counts.
+ *     consequences no list entry joins two representatives; every member has an entry to rep[i]; rep[rep[i]] == rep[i]; rep[i] never
+ *                  comes after i in the order; with key == NULL rep[i] <= i.  rep serves as the labels of a clustering unchanged
+ *                  (rep[i] == i marks the kept nodes).
+ *     determinism  the result depends on the list as a set of weighted edges and on the order alone: not on the order of the entries, on
+ *                  scheduling, or on how a run is cut into calls.  The CPU twin and the kernels agree bit for bit.
+ *
+ * bsq_greedy_scratch_bytes: host only, the bytes of the caller-owned device scratch of a run (64 + 28 n: 32-bit state and mark words, the
+ * assignment's words; no copy of the list is kept, so n_pairs does not enter); -BSQ_ERR_INVALID_ARG for sizes the call refuses.
+ * bsq_greedy_pairs_device: scratch is 8-byte aligned.  round0 == 0 starts a run and initialises the scratch inside the call (it is
+ * never assumed clean); round0 > 0 continues the run whose first round0 rounds are in the scratch (the same list, n and key).  The call
+ * runs rounds >= 0 rounds and then the assignment: rep[i] is final wherever it is not -1, and -1 for a node that is not decided yet --
+ * one whose own state is open, or a member one of whose earlier neighbours is still open, since that neighbour may yet become the
+ * representative the rule assigns.  *undecided (device int64) is the number of those -1 entries; when it is 0 the run is over and
+ * further rounds change nothing.  The call is stream-ordered and never synchronises.  n == 0 is BSQ_OK with nothing launched and
+ * nothing written.  BSQ_ERR_INVALID_ARG, with nothing launched and bsq_last_error() set: a null row or col with n_pairs > 0, a null or
+ * misaligned scratch, a null rep or undecided, a negative size or round number, n > 2^31 - 1, round0 + rounds > 2^30 - 1 (a round stamp
+ * would leave 31 bits).
+ * bsq_greedy_pairs_host: the CPU twin as the plain sequential visit (csrc/bsq_greedy_host.cpp: order the nodes, collect every node's
+ * earlier neighbours, one pass) -- not a restatement of the rounds.
+ *
+ * Kernels (csrc/bsq_greedy.hip).  The visit is the lexicographically first maximal independent set; it is computed in rounds that
+ * decide every node whose earlier neighbours allow it.  A node is UNDECIDED, REP or MEMBER (a 32-bit word); mark is a 32-bit word per
+ * node that holds round stamps, so nothing is cleared between rounds.  Round t, two launches: k_greedy_mark, an entry per lane
+ * (grid-stride), orients the entry as (u before v), skips it if v is decided or u is MEMBER, and raises mark[v] to 2 (t + 1) + 1 if u
+ * is REP, to 2 (t + 1) if u is UNDECIDED; k_greedy_decide, a node per lane: an UNDECIDED v becomes MEMBER if mark[v] == 2 (t + 1) + 1,
+ * stays if mark[v] == 2 (t + 1), else becomes REP, and the nodes that stay are counted.  A node is MEMBER from the first round in which
+ * an earlier neighbour is REP, which is final; each round decides at least the first undecided node, so n rounds always suffice (a
+ * path in index order needs them all; random lists of 20 000 nodes and 200 000 entries take 9 - 13, a complete graph 2).  Both
+ * launches of a round first read the count the previous round left -- final behind the kernel boundary -- and return without touching
+ * the list when it is 0: surplus rounds cost empty launches.  The assignment: k_greedy_clear, then one list pass per criterion that
+ * the arguments bring -- k_greedy_best<weight> (largest weight), k_greedy_best<key> (smallest key among those), k_greedy_best<index>
+ * (smallest index among those; the only pass with neither key nor weight) -- over the entries (u REP before v MEMBER), and k_greedy_rep,
+ * which writes rep and counts *undecided.  A word that another workgroup may write in the same launch (mark, the counts, the
+ * assignment's best words) is touched there only by agent-scope relaxed atomics on the global address space and not read; everything
+ * read crossed a kernel boundary.  No lane waits for another lane, wave or workgroup: no grid barrier, no flag, no lock, and no loop
+ * runs until a value changes.  No compacted copy of the live entries is kept: every round that runs reads the whole list.
+ * Measured on an MI355X, whole calls alternating in one process, medians of 7 windows (scripts/greedy_lab.py,
+ * profiles/r27/greedy_lab.txt), results asserted equal, against bsq_cluster_pairs_device on the same list, the same rounds composed in
+ * torch (scatter_reduce(amax) marks, masked updates, a read-back a round, a final scatter_reduce(amin)) and the CPU twin on one thread.
+ * Python's default loop (16 rounds a call, doubling, an 8-byte read-back a call): the lists "sketch pairs" gives on random reads with 3 %
+ * planted near-duplicates (127 - 7871 entries over 4096 - 262 144 nodes, 2 rounds) 179 - 197 us, 0.21 - 0.23x torch, 11 - 12x the 17 us
+ * of the cluster call -- launches only: one call of 2 rounds takes 46 us, the rest is 14 surplus rounds of two empty launches and the
+ * read-back; four cliques of 1500 nodes among 65 536 (4.6 M entries, 10 rounds) 873 us, 0.18x torch, 0.11x the cluster call (its unions
+ * contend: 7.9 ms), 1/69 of the twin; 2^21 nodes and 2^25 random entries (17 rounds, 2 read-backs) 10.8 ms, 0.31x torch, 6.7x the
+ * cluster call, 1/114 of the twin's 1.23 s -- 547 us a round where the list's 512 MiB take 67 us at 8 TB/s: the two scattered state reads
+ * and the atomic per live entry bound a round, not the list; with a key and a weight that list takes 34.6 ms (two more scattered 8-byte
+ * reads per entry and pass, three assignment passes).  The 300-node path in index order: 8.75 us a round, 2.65 ms in one call, 4.45 ms
+ * through the default loop (5 read-backs), 0.06x torch.  No counters-only run was taken.
+ *
+ * Known answers:
+ *     the path 0 -- 1 -- 2 -- 3 -- 4                                  rep 0 0 2 2 4
+ *     the same path, key (0, 0, 0, -1, 0)                              rep 0 0 3 3 3   (3 is visited first; 0 is kept, 1 falls to 0;
+ *                                                                                      2 and 4 fall to 3)
+ *     the triangle 0 -- 1, 0 -- 2, 1 -- 2 and the pendant 2 -- 3       rep 0 0 0 3
+ *     the entries 0 -- 2, 1 -- 2 (0 and 1 are both kept)               rep 0 1 0; with weights (1, 5) rep 0 1 1; with (5, 5) rep 0 1 0
+ *
+ * Out of scope: the rule inside the sketch tile walk (there is no list-free form: one cluster of 100 000 identical rows still needs
+ * bsq_sketch_clusters_device), assigning the rows of a second store to existing representatives (cd-hit-2d), re-assignment of members
+ * to later representatives. */
+int64_t bsq_greedy_scratch_bytes(int64_t n, int64_t n_pairs);
+bsq_status bsq_greedy_pairs_device(const int64_t *row, const int64_t *col, const int32_t *weight_or_null, int64_t n_pairs, int64_t n,
+                                   const int64_t *key_or_null, void *scratch, int64_t round0, int64_t rounds, int64_t *rep, int64_t *undecided,
+                                   void *hip_stream);
+bsq_status bsq_greedy_pairs_host(const int64_t *row, const int64_t *col, const int32_t *weight_or_null, int64_t n_pairs, int64_t n,
+                                 const int64_t *key_or_null, int64_t *rep);
+/* Host only: the launches of one round and of the assignment, the round's before the ';' ("k_greedy_mark+k_greedy_decide;k_greedy_clear+
+ * k_greedy_best<weight>+k_greedy_best<key>+k_greedy_best<index>+k_greedy_rep" with both; a run's first call launches k_greedy_init first). */
+const char *bsq_greedy_kernel_name(int32_t has_key, int32_t has_weight);
 
 /* ---- edit distance of row pairs: the exact unit-cost edit distance of listed pairs of rows of resident packed stores, one launch --
  * the alignment step that follows a k-mer filter (cd-hit, mmseqs cluster): a candidate list of "sketch pairs" becomes a list verified
