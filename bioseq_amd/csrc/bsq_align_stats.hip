@@ -1,11 +1,8 @@
-// Alignment statistics of row pairs on the device (include/bsq.h, "alignment statistics of row pairs"): k_align_stats<G, LOCAL>,
-// G = 4, 16 or 64 lanes per pair, local or global; a wave holds 64 / G pairs and a workgroup four waves that never meet after the
-// tables are staged.  The skeleton is k_score_pairs' (bsq_score.hip): the shorter row of a pair is the pattern, the group walks
-// anti-diagonals (lane b takes text column t - b at step t), the text is fetched G bytes at a time one tile ahead of its use and mapped
-// to classes once, a step's cells run under the wave's execution mask, the score table is in LDS in both orientations, a wave runs
-// until its slowest group is done.
+// Alignment statistics of row pairs on the device (include/bsq.h, "alignment statistics of row pairs"): k_align_stats<G, LOCAL>, local
+// or global, on the pair walk of bsq_pair_walk.h with 32 pattern rows a lane; as in k_score_pairs (bsq_score.hip) a step's cells run
+// under the wave's execution mask and the score table is in LDS in both orientations.
 //
-// What differs is what a lane keeps, and so how many rows it owns: lane b owns pattern rows 32 b + 1 .. 32 b + 32 and keeps, per row,
+// What differs from k_score_pairs is what a lane keeps, and so how many rows it owns: lane b owns pattern rows 32 b + 1 .. 32 b + 32 and keeps, per row,
 // H[i][j-1] and E[i][j-1] and the two-word tuples of both (bsq_align_stats_dev.h: starts in one word, matches and diag in the other) --
 // six registers a row, 192 in all, four in global mode where the starts are (0, 0) and their word is never made.  The diagonal, H above
 // and F run down the rows as scalars with their tuples through the cell of bsq_align_stats_dev.h.  What moves up one lane per step: the
@@ -18,7 +15,7 @@
 // the tie rule once, at the end, and lane 0 writes score and the six statistics with plain stores.
 // Registers: the rows' classes stay packed four to a word inside the loop (an empty asm statement per word and step keeps the compiler
 // from unpacking them once outside it, which k_score_pairs can afford and this kernel cannot: 32 registers); with that the local
-// instantiations take 250 - 255 VGPRs and the global ones 186 - 187, two waves per SIMD, no scratch (include/bsq.h has the table).
+// instantiations take 252 - 254 VGPRs and the global ones 178 - 197, two waves per SIMD, no scratch (include/bsq.h has the table).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -27,11 +24,12 @@
 #include "bsq_align_stats_dev.h"
 #include "bsq_device.h"
 #include "bsq_internal.h"
-#include "bsq_row_table.h"
+#include "bsq_pair_walk.h"
 
 namespace {
 
 using bsq_dev::kThreads;
+using bsq_pairs::Kind;
 using namespace bsq_alnstat;
 
 struct StatsParams {
@@ -53,85 +51,31 @@ template <int G, bool LOCAL>
 __global__ __launch_bounds__(kThreads) void k_align_stats(const StatsParams p) {
     __shared__ int8_t s_mat[2 * kDim * kDim];  // [0]: [B's class][A's class] for a pattern from A, [1]: [A's class][B's class]
     __shared__ uint8_t s_cls[256];
-    s_cls[threadIdx.x] = static_cast<uint8_t>(bsq_editd::class_of(p.lut, p.nchars, static_cast<uint8_t>(threadIdx.x)));  // (kThreads == 256)
-    for (int q = threadIdx.x; q < kDim * kDim; q += kThreads) {
-        const int c = q >> 5, r = q & 31;
-        const bool real = c <= p.nchars && r <= p.nchars;
-        s_mat[q] = real ? p.matrix[r][c] : static_cast<int8_t>(kPadScore);
-        s_mat[kDim * kDim + q] = real ? p.matrix[c][r] : static_cast<int8_t>(kPadScore);
-    }
+    bsq_pairs::stage_classes(p, s_cls);
+    bsq_pairs::stage_matrix<kDim>(p, s_mat, kPadScore);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = lane & (G - 1), base = lane & ~(G - 1);
-    const int64_t k = (static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave) * (64 / G) + lane / G;
+    const int lane = threadIdx.x & 63, b = lane & (G - 1), base = lane & ~(G - 1);
+    const int64_t k = bsq_pairs::pair_index<G>();
     const int32_t go = p.gap_open, ge = p.gap_extend;
 
-    // the pair of this lane's group: its pattern (m characters, nb lanes) and text (n characters); steps = 0: nothing to walk
-    const uint8_t *pat = nullptr, *text = nullptr;
-    int64_t pat_at = 0, pat_total = 0;
-    uint32_t m = 0, n = 0, nb = 0, steps = 0;
-    bool live = false, a_short = true;
-    if (k < p.n_pairs) {
-        const int64_t i = p.row[k], j = p.col[k];
-        int32_t now = 0, fill = -1, ea = -1, eb = -1, cols = -1;  // what lane 0 writes when the group walks nothing
-        if (i < 0 || i >= p.Ba || j < 0 || j >= p.Bb) {
-            now = BSQ_SCORE_BAD_INDEX;
-        } else {
-            const int64_t sa = p.offsets_a[i], sb = p.offsets_b[j];
-            int64_t la = p.offsets_a[i + 1] - sa, lb = p.offsets_b[j + 1] - sb;
-            la = la < 0 ? 0 : la;
-            lb = lb < 0 ? 0 : lb;
-            a_short = la <= lb;
-            const int64_t mm = a_short ? la : lb, nn = a_short ? lb : la;
-            if (mm > p.max_len || nn > kMaxLong) {
-                now = BSQ_SCORE_TOO_LONG;
-            } else if (mm == 0) {
-                now = boundary<LOCAL>(static_cast<int32_t>(nn), go, ge);
-                fill = 0;
-                ea = LOCAL ? 0 : static_cast<int32_t>(la), eb = LOCAL ? 0 : static_cast<int32_t>(lb), cols = ea + eb;
-            } else {
-                live = true;
-                m = static_cast<uint32_t>(mm), n = static_cast<uint32_t>(nn), nb = (m + kRows - 1) / kRows;
-                steps = n + nb - 1;
-                pat = a_short ? p.chars_a : p.chars_b;
-                pat_at = a_short ? sa : sb;
-                pat_total = a_short ? p.offsets_a[p.Ba] : p.offsets_b[p.Bb];
-                text = a_short ? p.chars_b + sb : p.chars_a + sa;
-            }
-        }
-        if (!live && b == 0) {
-            p.score[k] = now;
-            write_stats(p.stats + 6 * k, fill, fill, ea, eb, fill, cols);
-        }
+    // the pair of this lane's group: its pattern (m characters, nb lanes) and text (n characters; 0 where nothing is walked)
+    bsq_pairs::Pair pair;
+    const Kind kind = bsq_pairs::resolve(p, k, kMaxLong, pair);
+    const bool live = kind == Kind::live, a_short = pair.a_short;
+    if (kind != Kind::none && !live && b == 0) {
+        const bool empty = kind == Kind::empty;
+        const int32_t fill = empty ? 0 : -1, ea = !empty ? -1 : (LOCAL ? 0 : pair.la()), eb = !empty ? -1 : (LOCAL ? 0 : pair.lb());
+        p.score[k] = empty ? boundary<LOCAL>(static_cast<int32_t>(pair.n), go, ge) : (kind == Kind::bad_index ? BSQ_SCORE_BAD_INDEX : BSQ_SCORE_TOO_LONG);
+        write_stats(p.stats + 6 * k, fill, fill, ea, eb, fill, empty ? ea + eb : -1);
     }
-    uint32_t wave_steps = steps;
-#pragma unroll
-    for (int x = 32; x > 0; x >>= 1) {
-        const uint32_t o = __shfl_xor(wave_steps, x);
-        wave_steps = o > wave_steps ? o : wave_steps;
-    }
-    wave_steps = __builtin_amdgcn_readfirstlane(wave_steps);
+    const uint32_t m = pair.m, n = live ? pair.n : 0u, nb = (m + kRows - 1) / kRows;
+    const uint32_t wave_steps = bsq_pairs::wave_max(live ? n + nb - 1 : 0u);
     if (wave_steps == 0) return;  // (no workgroup barrier follows)
 
-    // the classes of this lane's rows, four to a word; behind the pattern's end the padding class
     const bool mine_any = live && static_cast<uint32_t>(b) < nb;
     const int32_t mine = !mine_any ? 0 : (static_cast<int32_t>(m) - kRows * b < kRows ? static_cast<int32_t>(m) - kRows * b : kRows);
     uint32_t pc[kRows / 4];
-#pragma unroll
-    for (int q = 0; q < kRows / 16; ++q) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (16 * q < mine) bsq_rowtab::load16(pat, pat_at + kRows * b + 16 * q, pat_total, mine - 16 * q, w);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            uint32_t packed = 0;
-#pragma unroll
-            for (int z = 0; z < 4; ++z) {
-                const int r = 16 * q + 4 * c + z;
-                const uint32_t cls = r < mine ? s_cls[(w[c] >> (8 * z)) & 0xFFu] : static_cast<uint32_t>(kPadClass);
-                packed |= cls << (8 * z);
-            }
-            pc[4 * q + c] = packed;
-        }
-    }
+    bsq_pairs::pack_classes<kRows>(pair, b, mine, s_cls, kPadClass, pc);
 
     int32_t H[kRows], E[kRows];
     Tup HT[kRows], ET[kRows];
@@ -152,14 +96,10 @@ __global__ __launch_bounds__(kThreads) void k_align_stats(const StatsParams p) {
     uint32_t out_cls = 0;                                   // the class of the column just done, for the lane above
     uint32_t bkey = kRows - 1, bcol = 0;                    // local: the best key (score 0 in row 0: no cell beats it with H = 0), its column
     Tup bT = {0, 0};                                        // and its tuple
-    auto fetch = [&](uint32_t at) -> uint32_t { return at < n ? text[at] : 0u; };  // (n == 0 for a lane without a text)
-    uint32_t ahead = fetch(b), tile = 0;
+    bsq_pairs::TextTile<G> tile(pair.text, n, b);
     for (uint32_t t = 0; t < wave_steps; ++t) {
-        if ((t & (G - 1)) == 0) {  // (uniform)
-            tile = s_cls[ahead];
-            ahead = fetch(t + G + b);
-        }
-        const uint32_t got = __shfl((tile << 8) | out_cls, b == 0 ? base + static_cast<int>(t & (G - 1)) : src);
+        tile.step(t, b, s_cls);
+        const uint32_t got = __shfl((tile.tile << 8) | out_cls, b == 0 ? base + static_cast<int>(t & (G - 1)) : src);
         int32_t up = __shfl(H[kRows - 1], src), f = __shfl(fbot, src);
         Tup uT, fT;
         uT.cnt = __shfl(HT[kRows - 1].cnt, src), fT.cnt = __shfl(fbotT.cnt, src);
@@ -253,19 +193,6 @@ __global__ __launch_bounds__(kThreads) void k_align_stats(const StatsParams p) {
     }
 }
 
-template <int G, bool LOCAL>
-void launch(const StatsParams &p, hipStream_t s) {
-    const int64_t per_group = (kThreads / 64) * (64 / G);
-    hipLaunchKernelGGL((k_align_stats<G, LOCAL>), dim3(static_cast<unsigned>((p.n_pairs + per_group - 1) / per_group)), dim3(kThreads), 0, s, p);
-}
-
-template <bool LOCAL>
-void launch_form(int32_t lanes, const StatsParams &p, hipStream_t s) {
-    if (lanes == 4) launch<4, LOCAL>(p, s);
-    else if (lanes == 16) launch<16, LOCAL>(p, s);
-    else launch<64, LOCAL>(p, s);
-}
-
 }  // namespace
 
 extern "C" {
@@ -279,16 +206,13 @@ bsq_status bsq_align_stats_device(const bsq_desc *d, const uint8_t *chars_a, con
     if (st != BSQ_OK) return bsq_internal::set_error(st, why);
     if (n_pairs == 0) return BSQ_OK;
     StatsParams p;
-    p.chars_a = chars_a, p.chars_b = chars_b, p.offsets_a = offsets_a, p.offsets_b = offsets_b;
-    p.row = row, p.col = col, p.score = score, p.stats = stats;
-    p.Ba = Ba, p.Bb = Bb, p.n_pairs = n_pairs;
-    p.max_len = sc->max_len, p.nchars = d->nchars, p.gap_open = sc->gap_open, p.gap_extend = sc->gap_extend;
-    for (int c = 0; c < 256; ++c) p.lut[c] = d->lut[c];
-    for (int r = 0; r < kDim; ++r)
-        for (int c = 0; c < kDim; ++c) p.matrix[r][c] = sc->matrix[r][c];
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (sc->mode == 0) launch_form<true>(lanes, p, s);
-    else launch_form<false>(lanes, p, s);
+    bsq_pairs::fill(p, d, chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, row, col, n_pairs, sc->max_len);
+    bsq_pairs::fill_scores(p, sc);
+    p.score = score, p.stats = stats;
+    bsq_pairs::for_lanes(lanes, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        bsq_pairs::launch<G>(sc->mode == 0 ? k_align_stats<G, true> : k_align_stats<G, false>, p, 0, static_cast<hipStream_t>(hip_stream));
+    });
     return bsq_internal::check_launch(kernel_name(lanes, sc->mode));
 }
 

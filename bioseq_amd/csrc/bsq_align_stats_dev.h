@@ -96,17 +96,14 @@ BSQ_EDIT_HD void stats_of(Tup t, int32_t end_pat, int32_t end_text, bool a_rows,
 
 // lanes per pair of the kernel a call takes (4, 16 or 64: shorter sides up to 128, 512, 2048), 0 for a bsq_score the call refuses
 inline int32_t lanes_of(const bsq_score *s) {
-    if (!s || s->max_len < 1 || s->max_len > kMaxLen || s->form < 0 || s->form > 3) return 0;
-    if (s->mode < 0 || s->mode > 1 || s->gap_open < 0 || s->gap_open > bsq_scored::kMaxGap || s->gap_extend < 0 || s->gap_extend > bsq_scored::kMaxGap) return 0;
-    const int32_t least = s->max_len <= 4 * kRows ? 1 : (s->max_len <= 16 * kRows ? 2 : 3);
-    if (s->form != 0 && s->form < least) return 0;
-    return 1 << (2 * (s->form != 0 ? s->form : least));
+    if (!s || s->mode < 0 || s->mode > 1 || s->gap_open < 0 || s->gap_open > bsq_scored::kMaxGap || s->gap_extend < 0 || s->gap_extend > bsq_scored::kMaxGap) return 0;
+    return bsq_pairs::lanes_of(s->max_len, s->form, kRows, kMaxLen);
 }
 inline const char *kernel_name(int32_t lanes, int32_t mode) {
     static const char *const names[3][2] = {{"k_align_stats<4, local>", "k_align_stats<4, global>"},
                                             {"k_align_stats<16, local>", "k_align_stats<16, global>"},
                                             {"k_align_stats<64, local>", "k_align_stats<64, global>"}};
-    const int f = lanes == 4 ? 0 : (lanes == 16 ? 1 : (lanes == 64 ? 2 : -1));
+    const int f = bsq_pairs::lanes_index(lanes);
     return f < 0 || mode < 0 || mode > 1 ? "" : names[f][mode];
 }
 
@@ -114,19 +111,10 @@ inline const char *kernel_name(int32_t lanes, int32_t mode) {
 inline bsq_status check(const bsq_desc *d, const void *chars_a, const void *offsets_a, int64_t Ba, const void *chars_b, const void *offsets_b,
                         int64_t Bb, const void *row, const void *col, int64_t n_pairs, const bsq_score *s, const void *score, const void *stats,
                         int32_t *lanes, const char **why) {
-    if (!d) return *why = "the descriptor is null", BSQ_ERR_INVALID_ARG;
-    if (d->nchars < 1 || d->nchars + 1 > bsq_scored::kMaxClasses) return *why = "the alphabet must have 1 .. 30 classes (BYTES has 256)", BSQ_ERR_INVALID_ARG;
-    if (!s) return *why = "the bsq_score is null", BSQ_ERR_INVALID_ARG;
     *lanes = lanes_of(s);
-    if (*lanes == 0)
-        return *why = "mode must be 0 or 1, gap_open and gap_extend lie in 0 .. 127, max_len in 1 .. 2048 and form be 0, or 1 .. 3 with max_len <= 128 / 512 / 2048",
-               BSQ_ERR_INVALID_ARG;
-    if (Ba < 0 || Bb < 0 || n_pairs < 0) return *why = "negative Ba, Bb or n_pairs", BSQ_ERR_INVALID_ARG;
-    if (Ba > bsq_scored::kMaxRows || Bb > bsq_scored::kMaxRows || n_pairs > bsq_scored::kMaxPairs) return *why = "Ba, Bb or n_pairs exceeds 2^31 - 1", BSQ_ERR_INVALID_ARG;
-    if (n_pairs > 0 && (!row || !col || !score || !stats)) return *why = "row, col, score or stats is null", BSQ_ERR_INVALID_ARG;
-    if (n_pairs > 0 && ((Ba > 0 && (!chars_a || !offsets_a)) || (Bb > 0 && (!chars_b || !offsets_b))))
-        return *why = "chars or offsets of a store with rows is null", BSQ_ERR_INVALID_ARG;
-    return BSQ_OK;
+    const char *rules = "mode must be 0 or 1, gap_open and gap_extend lie in 0 .. 127, max_len in 1 .. 2048 and form be 0, or 1 .. 3 with max_len <= 128 / 512 / 2048";
+    return bsq_pairs::check_pairs(d, chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, n_pairs, bsq_scored::refused(s, *lanes, rules),
+                                  row && col && score && stats ? nullptr : "row, col, score or stats is null", why);
 }
 
 }  // namespace bsq_alnstat

@@ -89,29 +89,22 @@ bsq_status bsq_align_stats_host(const bsq_desc *d, const uint8_t *chars_a, const
     if (st != BSQ_OK) return bsq_internal::set_error(st, why);
     Work w;
     for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t i = row[k], j = col[k];
         int32_t out[6] = {-1, -1, -1, -1, -1, -1};
-        if (i < 0 || i >= Ba || j < 0 || j >= Bb) {
+        bsq_pairs::Pair q;
+        const bsq_pairs::Kind kind = bsq_pairs::resolve(chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, row[k], col[k], s->max_len, kMaxLong, q);
+        if (kind == bsq_pairs::Kind::bad_index) {
             score[k] = BSQ_SCORE_BAD_INDEX;
+        } else if (kind == bsq_pairs::Kind::too_long) {
+            score[k] = BSQ_SCORE_TOO_LONG;
+        } else if (kind == bsq_pairs::Kind::empty) {  // an empty side: nothing aligns in local mode, one gap (or nothing) in global mode
+            const bool local = s->mode == 0;
+            score[k] = local ? 0 : boundary<false>(static_cast<int32_t>(q.n), s->gap_open, s->gap_extend);
+            out[0] = out[1] = out[4] = 0;
+            out[2] = local ? 0 : q.la(), out[3] = local ? 0 : q.lb();
+            out[5] = out[2] + out[3];
         } else {
-            int64_t la = offsets_a[i + 1] - offsets_a[i], lb = offsets_b[j + 1] - offsets_b[j];
-            la = la < 0 ? 0 : la;  // (a length as read from the offsets: a negative one counts as 0)
-            lb = lb < 0 ? 0 : lb;
-            const bool a_short = la <= lb;
-            const int64_t m = a_short ? la : lb, n = a_short ? lb : la;
-            if (m > s->max_len || n > kMaxLong) {
-                score[k] = BSQ_SCORE_TOO_LONG;
-            } else if (m == 0) {  // an empty side: nothing aligns in local mode, one gap (or nothing) in global mode
-                const bool local = s->mode == 0;
-                score[k] = local ? 0 : boundary<false>(static_cast<int32_t>(n), s->gap_open, s->gap_extend);
-                out[0] = out[1] = out[4] = 0;
-                out[2] = local ? 0 : static_cast<int32_t>(la), out[3] = local ? 0 : static_cast<int32_t>(lb);
-                out[5] = local ? 0 : static_cast<int32_t>(la + lb);
-            } else {
-                const uint8_t *x = chars_a + offsets_a[i], *y = chars_b + offsets_b[j];
-                score[k] = s->mode == 0 ? pair_stats<true>(d, s, a_short ? x : y, m, a_short ? y : x, n, a_short, w, out)
-                                        : pair_stats<false>(d, s, a_short ? x : y, m, a_short ? y : x, n, a_short, w, out);
-            }
+            score[k] = s->mode == 0 ? pair_stats<true>(d, s, q.pat + q.pat_at, q.m, q.text, q.n, q.a_short, w, out)
+                                    : pair_stats<false>(d, s, q.pat + q.pat_at, q.m, q.text, q.n, q.a_short, w, out);
         }
         for (int q = 0; q < 6; ++q) stats[6 * k + q] = out[q];
     }

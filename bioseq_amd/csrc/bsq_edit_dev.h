@@ -1,35 +1,20 @@
 // Edit distance of row pairs (include/bsq.h, "edit distance of row pairs"): what the kernels of bsq_edit.hip and the CPU twin of
-// bsq_edit_host.cpp share -- the limits, the class of a byte, one column of one 64-row block of Myers' bit-vector algorithm in Hyyro's
-// blocked form, the integer identity test, the choice of kernel and the argument rules.  Plain C++ over <cstdint> and bsq.h alone: the
-// host twin compiles without the HIP headers.
+// bsq_edit_host.cpp share beside the pair walk (bsq_pair_walk.h) -- the family's limits, one column of one 64-row block of Myers'
+// bit-vector algorithm in Hyyro's blocked form, the integer identity test, the choice of kernel and the argument rules.  Plain C++ over
+// <cstdint> and bsq.h alone: the host twin compiles without the HIP headers.
 #pragma once
 #include <cstdint>
 
 #include "bsq.h"
-
-#if defined(__HIPCC__)
-#define BSQ_EDIT_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define BSQ_EDIT_HD inline
-#endif
+#include "bsq_pair_walk.h"
 
 namespace bsq_editd {
 
-constexpr int32_t kMaxLen = 4096;                       // the shorter side: 64 lanes of 64 rows each
-constexpr int64_t kMaxLong = (int64_t(1) << 31) - 2;    // the longer side: the step counter n + blocks - 1 stays inside 32 bits
-constexpr int64_t kMaxPairs = (int64_t(1) << 31) - 1;   // pairs of a call: at least four of them per workgroup of one launch
-constexpr int64_t kMaxRows = (int64_t(1) << 31) - 1;    // rows of a store
-// classes of an alphabet, the unmapped one included: four waves' tables of classes x 64 words and the byte table fit the 64 KiB of LDS
-// a workgroup gets without asking (every alphabet of the package but BYTES)
-constexpr int32_t kMaxClasses = 31;
-constexpr int32_t kQ16 = 65536;
+using bsq_pairs::class_of;
 
-// the class of a byte: its id, or nchars for every byte the alphabet does not map
-template <typename Lut>
-BSQ_EDIT_HD uint32_t class_of(const Lut &lut, int32_t nchars, uint8_t byte) {
-    const int32_t id = lut[byte];
-    return static_cast<uint32_t>(id >= 0 ? id : nchars);
-}
+constexpr int32_t kMaxLen = 4096;                     // the shorter side: 64 lanes of 64 rows each
+constexpr int64_t kMaxLong = (int64_t(1) << 31) - 2;  // the longer side: the step counter n + blocks - 1 stays inside 32 bits
+constexpr int32_t kQ16 = 65536;
 
 // One text column through one block of 64 pattern rows.  pv / mv: the block's vertical +1 / -1 deltas, updated; eq: the rows whose class
 // is the column's; hin: the horizontal delta that enters the block's first row (-1, 0, +1); top: the bit of the block's last row (63, in
@@ -58,13 +43,7 @@ BSQ_EDIT_HD bool identity_passes(int32_t dist, int64_t la, int64_t lb, int32_t i
 }
 
 // lanes per pair of the kernel a call takes (4, 16 or 64), 0 for a bsq_edit the calls refuse; e == nullptr: the defaults {4096, 0}
-inline int32_t lanes_of(const bsq_edit *e) {
-    const int32_t max_len = e ? e->max_len : kMaxLen, form = e ? e->form : 0;
-    if (max_len < 1 || max_len > kMaxLen || form < 0 || form > 3) return 0;
-    const int32_t least = max_len <= 256 ? 1 : (max_len <= 1024 ? 2 : 3);
-    if (form != 0 && form < least) return 0;
-    return 1 << (2 * (form != 0 ? form : least));
-}
+inline int32_t lanes_of(const bsq_edit *e) { return bsq_pairs::lanes_of(e ? e->max_len : kMaxLen, e ? e->form : 0, 64, kMaxLen); }
 inline const char *kernel_name(int32_t lanes) {
     return lanes == 4 ? "k_edit_pairs<4>" : (lanes == 16 ? "k_edit_pairs<16>" : (lanes == 64 ? "k_edit_pairs<64>" : ""));
 }
@@ -73,16 +52,10 @@ inline const char *kernel_name(int32_t lanes) {
 inline bsq_status check(const bsq_desc *d, const void *chars_a, const void *offsets_a, int64_t Ba, const void *chars_b, const void *offsets_b,
                         int64_t Bb, const void *row, const void *col, int64_t n_pairs, const bsq_edit *e, const void *dist, int32_t *lanes,
                         const char **why) {
-    if (!d) return *why = "the descriptor is null", BSQ_ERR_INVALID_ARG;
-    if (d->nchars < 1 || d->nchars + 1 > kMaxClasses) return *why = "the alphabet must have 1 .. 30 classes (BYTES has 256)", BSQ_ERR_INVALID_ARG;
     *lanes = lanes_of(e);
-    if (*lanes == 0) return *why = "max_len must lie in 1 .. 4096 and form be 0, or 1 .. 3 with max_len <= 256 / 1024 / 4096", BSQ_ERR_INVALID_ARG;
-    if (Ba < 0 || Bb < 0 || n_pairs < 0) return *why = "negative Ba, Bb or n_pairs", BSQ_ERR_INVALID_ARG;
-    if (Ba > kMaxRows || Bb > kMaxRows || n_pairs > kMaxPairs) return *why = "Ba, Bb or n_pairs exceeds 2^31 - 1", BSQ_ERR_INVALID_ARG;
-    if (n_pairs > 0 && (!row || !col || !dist)) return *why = "row, col or dist is null", BSQ_ERR_INVALID_ARG;
-    if (n_pairs > 0 && ((Ba > 0 && (!chars_a || !offsets_a)) || (Bb > 0 && (!chars_b || !offsets_b))))
-        return *why = "chars or offsets of a store with rows is null", BSQ_ERR_INVALID_ARG;
-    return BSQ_OK;
+    return bsq_pairs::check_pairs(d, chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, n_pairs,
+                                  *lanes != 0 ? nullptr : "max_len must lie in 1 .. 4096 and form be 0, or 1 .. 3 with max_len <= 256 / 1024 / 4096",
+                                  row && col && dist ? nullptr : "row, col or dist is null", why);
 }
 
 }  // namespace bsq_editd

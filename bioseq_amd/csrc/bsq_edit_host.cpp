@@ -52,22 +52,11 @@ bsq_status bsq_edit_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const 
     const int64_t max_len = e ? e->max_len : bsq_editd::kMaxLen;
     std::vector<uint64_t> peq, pv, mv;
     for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t i = row[k], j = col[k];
-        if (i < 0 || i >= Ba || j < 0 || j >= Bb) {
-            dist[k] = BSQ_EDIT_BAD_INDEX;
-            continue;
-        }
-        int64_t la = offsets_a[i + 1] - offsets_a[i], lb = offsets_b[j + 1] - offsets_b[j];
-        la = la < 0 ? 0 : la;  // (a length as read from the offsets: a negative one counts as 0)
-        lb = lb < 0 ? 0 : lb;
-        const bool a_short = la <= lb;
-        const int64_t m = a_short ? la : lb, n = a_short ? lb : la;
-        if (m > max_len || n > bsq_editd::kMaxLong) {
-            dist[k] = BSQ_EDIT_TOO_LONG;
-            continue;
-        }
-        const uint8_t *x = chars_a + offsets_a[i], *y = chars_b + offsets_b[j];
-        dist[k] = pair_distance(d, a_short ? x : y, m, a_short ? y : x, n, peq, pv, mv);
+        bsq_pairs::Pair q;
+        const bsq_pairs::Kind kind = bsq_pairs::resolve(chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, row[k], col[k], max_len, bsq_editd::kMaxLong, q);
+        if (kind == bsq_pairs::Kind::bad_index) dist[k] = BSQ_EDIT_BAD_INDEX;
+        else if (kind == bsq_pairs::Kind::too_long) dist[k] = BSQ_EDIT_TOO_LONG;
+        else dist[k] = pair_distance(d, q.pat + q.pat_at, q.m, q.text, q.n, peq, pv, mv);
     }
     return BSQ_OK;
 }

@@ -1,8 +1,5 @@
-// Scored alignment of row pairs on the device (include/bsq.h, "scored alignment of row pairs"): k_score_pairs<G, MODE>, G = 4, 16 or 64
-// lanes per pair, MODE global, local or local with ends; a wave holds 64 / G pairs and a workgroup four waves that never meet after the
-// tables are staged.  The skeleton is the edit distance's (bsq_edit.hip): the shorter row of a pair is the pattern, lane b of the pair's
-// group owns pattern rows 64 b + 1 .. 64 b + 64, the group walks anti-diagonals (lane b takes text column t - b at step t), the text is
-// fetched G bytes at a time one tile ahead of its use and mapped to classes once, a wave runs until its slowest group is done.
+// Scored alignment of row pairs on the device (include/bsq.h, "scored alignment of row pairs"): k_score_pairs<G, MODE>, MODE global,
+// local or local with ends, on the pair walk of bsq_pair_walk.h with 64 pattern rows a lane.
 //
 // What a lane keeps: H[i][j-1] and E[i][j-1] of its 64 rows (128 registers) and the rows' classes, four to a register.  Within a step
 // the diagonal, H above and F run down the rows as scalars through the cell of bsq_score_dev.h.  What moves up one lane per step: the
@@ -24,12 +21,13 @@
 #include "bsq.h"
 #include "bsq_device.h"
 #include "bsq_internal.h"
-#include "bsq_row_table.h"
+#include "bsq_pair_walk.h"
 #include "bsq_score_dev.h"
 
 namespace {
 
 using bsq_dev::kThreads;
+using bsq_pairs::Kind;
 using namespace bsq_scored;
 
 constexpr int kGlobal = 0, kLocal = 1, kLocalEnds = 2;
@@ -50,74 +48,35 @@ __global__ __launch_bounds__(kThreads) void k_score_pairs(const ScoreParams p) {
     constexpr bool LOCAL = MODE != kGlobal;
     __shared__ int8_t s_mat[2 * kDim * kDim];  // [0]: [B's class][A's class] for a pattern from A, [1]: [A's class][B's class]
     __shared__ uint8_t s_cls[256];
-    s_cls[threadIdx.x] = static_cast<uint8_t>(bsq_editd::class_of(p.lut, p.nchars, static_cast<uint8_t>(threadIdx.x)));  // (kThreads == 256)
-    for (int q = threadIdx.x; q < kDim * kDim; q += kThreads) {
-        const int c = q >> 5, r = q & 31;
-        const bool real = c <= p.nchars && r <= p.nchars;
-        s_mat[q] = real ? p.matrix[r][c] : static_cast<int8_t>(kPadScore);
-        s_mat[kDim * kDim + q] = real ? p.matrix[c][r] : static_cast<int8_t>(kPadScore);
-    }
+    bsq_pairs::stage_classes(p, s_cls);
+    bsq_pairs::stage_matrix<kDim>(p, s_mat, kPadScore);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = lane & (G - 1), base = lane & ~(G - 1);
-    const int64_t k = (static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + wave) * (64 / G) + lane / G;
+    const int lane = threadIdx.x & 63, b = lane & (G - 1), base = lane & ~(G - 1);
+    const int64_t k = bsq_pairs::pair_index<G>();
     const int32_t go = p.gap_open, ge = p.gap_extend;
 
-    // the pair of this lane's group: its pattern (m characters, nb lanes) and text (n characters); steps = 0: nothing to walk
-    const uint8_t *pat = nullptr, *text = nullptr;
-    int64_t pat_at = 0, pat_total = 0;
-    uint32_t m = 0, n = 0, nb = 0, steps = 0;
-    int32_t la32 = 0, lb32 = 0;
-    bool live = false, a_short = true;
-    if (k < p.n_pairs) {
-        const int64_t i = p.row[k], j = p.col[k];
-        int32_t now = 0, ea = -1, eb = -1;  // what lane 0 writes when the group walks nothing
-        if (i < 0 || i >= p.Ba || j < 0 || j >= p.Bb) {
-            now = BSQ_SCORE_BAD_INDEX;
-        } else {
-            const int64_t sa = p.offsets_a[i], sb = p.offsets_b[j];
-            int64_t la = p.offsets_a[i + 1] - sa, lb = p.offsets_b[j + 1] - sb;
-            la = la < 0 ? 0 : la;
-            lb = lb < 0 ? 0 : lb;
-            a_short = la <= lb;
-            const int64_t mm = a_short ? la : lb, nn = a_short ? lb : la;
-            if (mm > p.max_len || nn > kMaxLong) {
-                now = BSQ_SCORE_TOO_LONG;
-            } else if (mm == 0) {
-                now = boundary<LOCAL>(static_cast<int32_t>(nn), go, ge);
-                ea = LOCAL ? 0 : static_cast<int32_t>(la), eb = LOCAL ? 0 : static_cast<int32_t>(lb);
-            } else {
-                live = true;
-                la32 = static_cast<int32_t>(la), lb32 = static_cast<int32_t>(lb);
-                m = static_cast<uint32_t>(mm), n = static_cast<uint32_t>(nn), nb = (m + 63) >> 6;
-                steps = n + nb - 1;
-                pat = a_short ? p.chars_a : p.chars_b;
-                pat_at = a_short ? sa : sb;
-                pat_total = a_short ? p.offsets_a[p.Ba] : p.offsets_b[p.Bb];
-                text = a_short ? p.chars_b + sb : p.chars_a + sa;
-            }
-        }
-        if (!live && b == 0) {
-            p.score[k] = now;
-            if (p.ends) p.ends[2 * k] = ea, p.ends[2 * k + 1] = eb;
-        }
+    // the pair of this lane's group: its pattern (m characters, nb lanes) and text (n characters; 0 where nothing is walked)
+    bsq_pairs::Pair pair;
+    const Kind kind = bsq_pairs::resolve(p, k, kMaxLong, pair);
+    const bool live = kind == Kind::live, a_short = pair.a_short;
+    if (kind != Kind::none && !live && b == 0) {
+        const bool empty = kind == Kind::empty;
+        p.score[k] = empty ? boundary<LOCAL>(static_cast<int32_t>(pair.n), go, ge) : (kind == Kind::bad_index ? BSQ_SCORE_BAD_INDEX : BSQ_SCORE_TOO_LONG);
+        if (p.ends) p.ends[2 * k] = !empty ? -1 : (LOCAL ? 0 : pair.la()), p.ends[2 * k + 1] = !empty ? -1 : (LOCAL ? 0 : pair.lb());
     }
-    uint32_t wave_steps = steps;
-#pragma unroll
-    for (int x = 32; x > 0; x >>= 1) {
-        const uint32_t o = __shfl_xor(wave_steps, x);
-        wave_steps = o > wave_steps ? o : wave_steps;
-    }
-    wave_steps = __builtin_amdgcn_readfirstlane(wave_steps);
+    const uint32_t m = pair.m, n = live ? pair.n : 0u, nb = (m + 63) >> 6;
+    const uint32_t wave_steps = bsq_pairs::wave_max(live ? n + nb - 1 : 0u);
     if (wave_steps == 0) return;  // (no workgroup barrier follows)
 
-    // the classes of this lane's rows, four to a word; behind the pattern's end the padding class
     const bool mine_any = live && static_cast<uint32_t>(b) < nb;
     const int32_t mine = !mine_any ? 0 : (static_cast<int32_t>(m) - 64 * b < 64 ? static_cast<int32_t>(m) - 64 * b : 64);
+    // the class packing and, below, the text tile of bsq_pair_walk.h, written out: with bsq_pairs::pack_classes and TextTile the step loop
+    // took other instruction forms and whole calls ran up to 4 % slower in local mode (profiles/r28/pair_walk_lab.txt)
     uint32_t pc[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         uint32_t w[4] = {0, 0, 0, 0};
-        if (16 * q < mine) bsq_rowtab::load16(pat, pat_at + 64 * b + 16 * q, pat_total, mine - 16 * q, w);
+        if (16 * q < mine) bsq_rowtab::load16(pair.pat, pair.pat_at + 64 * b + 16 * q, pair.pat_total, mine - 16 * q, w);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             uint32_t packed = 0;
@@ -144,6 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_score_pairs(const ScoreParams p) {
     uint32_t out_cls = 0;                                   // the class of the column just done, for the lane above
     int32_t best = 0;                                       // kLocal: the best H of this lane's cells
     uint32_t bkey = 63, bcol = 0;                           // kLocalEnds: the best key (score 0 in row 0: no cell beats it with H = 0), its column
+    const uint8_t *text = pair.text;
     auto fetch = [&](uint32_t at) -> uint32_t { return at < n ? text[at] : 0u; };  // (n == 0 for a lane without a text)
     uint32_t ahead = fetch(b), tile = 0;
     for (uint32_t t = 0; t < wave_steps; ++t) {
@@ -195,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void k_score_pairs(const ScoreParams p) {
 #pragma unroll
             for (int r = 1; r < 64; ++r) h = top == static_cast<uint32_t>(r) ? H[r] : h;
             p.score[k] = h;
-            if (p.ends) p.ends[2 * k] = la32, p.ends[2 * k + 1] = lb32;
+            if (p.ends) p.ends[2 * k] = pair.la(), p.ends[2 * k + 1] = pair.lb();
         }
     } else if (MODE == kLocal) {
 #pragma unroll
@@ -218,19 +178,6 @@ __global__ __launch_bounds__(kThreads) void k_score_pairs(const ScoreParams p) {
     }
 }
 
-template <int G, int MODE>
-void launch(const ScoreParams &p, hipStream_t s) {
-    const int64_t per_group = (kThreads / 64) * (64 / G);
-    hipLaunchKernelGGL((k_score_pairs<G, MODE>), dim3(static_cast<unsigned>((p.n_pairs + per_group - 1) / per_group)), dim3(kThreads), 0, s, p);
-}
-
-template <int MODE>
-void launch_form(int32_t lanes, const ScoreParams &p, hipStream_t s) {
-    if (lanes == 4) launch<4, MODE>(p, s);
-    else if (lanes == 16) launch<16, MODE>(p, s);
-    else launch<64, MODE>(p, s);
-}
-
 }  // namespace
 
 extern "C" {
@@ -244,18 +191,15 @@ bsq_status bsq_score_pairs_device(const bsq_desc *d, const uint8_t *chars_a, con
     if (st != BSQ_OK) return bsq_internal::set_error(st, why);
     if (n_pairs == 0) return BSQ_OK;
     ScoreParams p;
-    p.chars_a = chars_a, p.chars_b = chars_b, p.offsets_a = offsets_a, p.offsets_b = offsets_b;
-    p.row = row, p.col = col, p.score = score, p.ends = ends;
-    p.Ba = Ba, p.Bb = Bb, p.n_pairs = n_pairs;
-    p.max_len = sc->max_len, p.nchars = d->nchars, p.gap_open = sc->gap_open, p.gap_extend = sc->gap_extend;
-    for (int c = 0; c < 256; ++c) p.lut[c] = d->lut[c];
-    for (int r = 0; r < kDim; ++r)
-        for (int c = 0; c < kDim; ++c) p.matrix[r][c] = sc->matrix[r][c];
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    bsq_pairs::fill(p, d, chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, row, col, n_pairs, sc->max_len);
+    bsq_pairs::fill_scores(p, sc);
+    p.score = score, p.ends = ends;
     const int32_t which = which_of(sc, ends != nullptr);
-    if (which == kGlobal) launch_form<kGlobal>(lanes, p, s);
-    else if (which == kLocal) launch_form<kLocal>(lanes, p, s);
-    else launch_form<kLocalEnds>(lanes, p, s);
+    bsq_pairs::for_lanes(lanes, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        void (*const kernels[3])(ScoreParams) = {k_score_pairs<G, kGlobal>, k_score_pairs<G, kLocal>, k_score_pairs<G, kLocalEnds>};
+        bsq_pairs::launch<G>(kernels[which], p, 0, static_cast<hipStream_t>(hip_stream));
+    });
     return bsq_internal::check_launch(kernel_name(lanes, which));
 }
 

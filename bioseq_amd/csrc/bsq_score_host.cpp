@@ -72,24 +72,14 @@ bsq_status bsq_score_pairs_host(const bsq_desc *d, const uint8_t *chars_a, const
     std::vector<int32_t> H, E;
     std::vector<uint8_t> pc;
     for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t i = row[k], j = col[k];
         int32_t en[2] = {-1, -1};
-        if (i < 0 || i >= Ba || j < 0 || j >= Bb) {
-            score[k] = BSQ_SCORE_BAD_INDEX;
-        } else {
-            int64_t la = offsets_a[i + 1] - offsets_a[i], lb = offsets_b[j + 1] - offsets_b[j];
-            la = la < 0 ? 0 : la;  // (a length as read from the offsets: a negative one counts as 0)
-            lb = lb < 0 ? 0 : lb;
-            const bool a_short = la <= lb;
-            const int64_t m = a_short ? la : lb, n = a_short ? lb : la;
-            if (m > s->max_len || n > kMaxLong) {
-                score[k] = BSQ_SCORE_TOO_LONG;
-            } else {
-                const uint8_t *x = chars_a + offsets_a[i], *y = chars_b + offsets_b[j];
-                score[k] = s->mode == 0 ? pair_score<true>(d, s, a_short ? x : y, m, a_short ? y : x, n, a_short, H, E, pc, en)
-                                        : pair_score<false>(d, s, a_short ? x : y, m, a_short ? y : x, n, a_short, H, E, pc, en);
-            }
-        }
+        bsq_pairs::Pair q;
+        const bsq_pairs::Kind kind = bsq_pairs::resolve(chars_a, offsets_a, Ba, chars_b, offsets_b, Bb, row[k], col[k], s->max_len, kMaxLong, q);
+        if (kind == bsq_pairs::Kind::bad_index) score[k] = BSQ_SCORE_BAD_INDEX;
+        else if (kind == bsq_pairs::Kind::too_long) score[k] = BSQ_SCORE_TOO_LONG;
+        else
+            score[k] = s->mode == 0 ? pair_score<true>(d, s, q.pat + q.pat_at, q.m, q.text, q.n, q.a_short, H, E, pc, en)
+                                    : pair_score<false>(d, s, q.pat + q.pat_at, q.m, q.text, q.n, q.a_short, H, E, pc, en);
         if (ends) ends[2 * k] = en[0], ends[2 * k + 1] = en[1];
     }
     return BSQ_OK;

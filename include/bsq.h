@@ -1145,8 +1145,8 @@ bsq_status bsq_blosum62_scores(int8_t *out21x21);
  * The best cell's tuple follows the column's largest key (H << 5) | (31 - row) down the rows; one reduction per group under the tie
  * rule, one lane writes score and the six statistics with plain vector stores.
  * Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / LDS bytes / scratch bytes):
- *     k_align_stats<4, local>  253 / 0 / 2304 / 0     k_align_stats<16, local>  255 / 0 / 2304 / 0     k_align_stats<64, local>  250 / 0 / 2304 / 0
- *     k_align_stats<4, global> 187 / 0 / 2304 / 0     k_align_stats<16, global> 187 / 0 / 2304 / 0     k_align_stats<64, global> 186 / 0 / 2304 / 0
+ *     k_align_stats<4, local>  252 / 0 / 2304 / 0     k_align_stats<16, local>  254 / 0 / 2304 / 0     k_align_stats<64, local>  254 / 0 / 2304 / 0
+ *     k_align_stats<4, global> 178 / 0 / 2304 / 0     k_align_stats<16, global> 178 / 0 / 2304 / 0     k_align_stats<64, global> 197 / 0 / 2304 / 0
  * two waves per SIMD and no scratch in all six.  It takes two measures to get there in local mode: the rows' classes stay packed four
  * to a register inside the loop, and the best cell's tuple is selected per cell (picking it out of the registers by row number once per
  * column costs 55 registers more and one wave per SIMD).  64 rows per lane also build without scratch, but at one wave per SIMD with
