@@ -80,6 +80,11 @@ class SketchPairs(ctypes.Structure):
     _fields_ = [("min_match", ctypes.c_int32), ("jaccard_q16", ctypes.c_int32), ("upper", ctypes.c_int32), ("segments", ctypes.c_int32)]
 
 
+class Lsh(ctypes.Structure):
+    """struct bsq_lsh"""
+    _fields_ = [("rows_per_band", ctypes.c_int32), ("max_bucket", ctypes.c_int32), ("seed", ctypes.c_uint64), ("reserved", ctypes.c_int32)]
+
+
 class Edit(ctypes.Structure):
     """struct bsq_edit"""
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32)]
@@ -238,6 +243,15 @@ def load():
         "bsq_greedy_pairs_device": (i32, [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp]),
         "bsq_greedy_pairs_host": (i32, [vp, vp, vp, i64, i64, vp, vp]),
         "bsq_greedy_kernel_name": (ctypes.c_char_p, [i32, i32]),
+        "bsq_lsh_keys_device": (i32, [vp, i64, i64, c_int, ctypes.POINTER(Lsh), vp, i64, vp]),
+        "bsq_lsh_keys_host": (i32, [vp, i64, i64, c_int, ctypes.POINTER(Lsh), vp, i64]),
+        "bsq_lsh_count_device": (i32, [vp, i64, i64, ctypes.POINTER(Lsh), vp, vp]),
+        "bsq_lsh_emit_device": (i32, [vp, vp, i64, i64, ctypes.POINTER(Lsh), vp, i64, vp, vp]),
+        "bsq_sketch_compare_list_device": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp, i64, vp, vp, vp]),
+        "bsq_sketch_compare_list_host": (i32, [vp, i64, vp, i64, i64, c_int, vp, vp, i64, vp, vp]),
+        "bsq_lsh_pairs_host": (i32, [vp, i64, vp, i64, i64, c_int, ctypes.POINTER(Lsh), ctypes.POINTER(SketchPairs), i64, i64p, vp, i64, vp, vp, vp,
+                                     vp]),
+        "bsq_lsh_kernel_name": (ctypes.c_char_p, [i64, c_int]),
         "bsq_edit_pairs_device": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp, vp]),
         "bsq_edit_pairs_host": (i32, [dp, vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(Edit), vp]),
         "bsq_edit_pairs_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Edit)]),

@@ -29,7 +29,15 @@ fraction J of their k-mers agree in about that fraction of their non-empty bucke
 * `greedy_pairs`      greedy representatives of an edge list (cd-hit's rule: visit the nodes longest first, keep a node unless an
                       earlier kept node is linked to it): rep[i] per node, no two kept nodes linked, every dropped node linked to a kept
                       one (`bsq_greedy_pairs_device`; include/bsq.h, "greedy representatives");
-* `greedy_pairs_host`, `greedy_kernel_name`, `length_key`    its CPU twin, its launches, the "longest first" key of a packed batch.
+* `greedy_pairs_host`, `greedy_kernel_name`, `length_key`    its CPU twin, its launches, the "longest first" key of a packed batch;
+* `lsh_pairs`         the pair list without the all-pairs comparison: banded LSH over the sketch rows -- rows that agree on a whole band of
+                      `rows_per_band` buckets are candidates, and only candidates are compared -- so the cost follows the rows and the
+                      candidates, not Ba x Bb (`bsq_lsh_keys_device`, `bsq_lsh_count_device`, `bsq_lsh_emit_device`,
+                      `bsq_sketch_compare_list_device`; include/bsq.h, "LSH candidates of a sketch matrix");
+* `lsh_candidates`, `lsh_keys`, `sketch_compare_list`    its parts: the candidates before any threshold, the band keys, `match` and
+                      `either` of a GIVEN list of pairs (rescoring a list from elsewhere or from a narrower sketch);
+* `lsh_keys_host`, `sketch_compare_list_host`, `lsh_kernel_name`    their CPU twins, the launches;
+* `lsh_recall`, `lsh_rows_per_band`    the predicted recall of a banding and the choice of `rows_per_band` for a threshold.
 
 The sketch of a sequence equals the bucket-wise UNSIGNED minimum of the sketches of pieces that together cover all its windows (EMPTY
 is the largest value), so sketches of longer sequences, or of sets of sequences, are merged without the characters.
@@ -481,6 +489,269 @@ def greedy_kernel_name(*, key=False, weight=False):
     return _lib.bsq_greedy_kernel_name(int(bool(key)), int(bool(weight))).decode()
 
 
+# ---- LSH candidates of a sketch matrix (include/bsq.h, "LSH candidates of a sketch matrix") ----
+
+def lsh_recall(jaccard, rows_per_band, bands):
+    """1 - (1 - J ** r) ** T: the chance that two rows of Jaccard similarity J share the key of at least one of T bands of r buckets.
+    This is the independent-bucket approximation -- every bucket of two rows agrees with probability J, independently of the others --
+    which one-permutation sketches with EMPTY buckets follow only roughly; scripts/lsh_lab.py sets the measured recall beside it.
+    Pure Python."""
+    j, r, t = float(jaccard), int(rows_per_band), int(bands)
+    if not 0.0 <= j <= 1.0 or r < 1 or t < 0:
+        raise ValueError("jaccard must lie in 0 .. 1, rows_per_band be at least 1 and bands at least 0")
+    return 1.0 - (1.0 - j ** r) ** t
+
+
+def lsh_rows_per_band(S, min_jaccard, recall=0.95):
+    """The largest r in 1 .. S whose predicted recall `lsh_recall(min_jaccard, r, S // r)` reaches `recall` -- the fewest, widest bands
+    (the fewest chance collisions) that still find that share of the pairs at the threshold; 1, the most sensitive choice, when no r
+    reaches it.  Pure Python.  lsh_rows_per_band(128, 0.5) == 3: 42 bands, predicted recall 0.996 (r = 4: 0.873)."""
+    S = int(S)
+    if S < 1 or not 0.0 <= float(recall) <= 1.0:
+        raise ValueError("S must be at least 1 and recall lie in 0 .. 1")
+    good = [r for r in range(1, S + 1) if lsh_recall(min_jaccard, r, S // r) >= recall]
+    return max(good) if good else 1
+
+
+def _lsh_rule(S, rows_per_band, max_bucket, seed, max_candidates=None):
+    """(bsq_lsh, bands) with the library's argument rules applied as ValueError (no device is touched)."""
+    if isinstance(rows_per_band, bool) or int(rows_per_band) != rows_per_band or not 1 <= int(rows_per_band) <= S:
+        raise ValueError("rows_per_band must be an integer in 1 .. %d (the sketch width), got %r" % (S, rows_per_band))
+    if isinstance(max_bucket, bool) or int(max_bucket) != max_bucket or not 2 <= int(max_bucket) < 2 ** 31:
+        raise ValueError("max_bucket must be an integer in 2 .. 2 ** 31 - 1, got %r" % (max_bucket,))
+    if max_candidates is not None and (isinstance(max_candidates, bool) or int(max_candidates) != max_candidates or int(max_candidates) < 0):
+        raise ValueError("max_candidates must be None or an integer >= 0, got %r" % (max_candidates,))
+    return capi.Lsh(int(rows_per_band), int(max_bucket), int(seed) & (2 ** 64 - 1), 0), S // int(rows_per_band)
+
+
+def _host_sketches(a, b=None):
+    """contiguous numpy matrices of one accepted element type and width: (a, b or None, Ba, Bb, S, dtype code)"""
+    a = np.ascontiguousarray(a)
+    b = None if b is None else np.ascontiguousarray(b)
+    if a.dtype not in _HOST_CODES:
+        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
+    Ba, Bb, S = _pair_shape(a, a if b is None else b)
+    return a, b, Ba, Bb if b is not None else 0, S, _HOST_CODES[a.dtype]
+
+
+def _device_sketches(a, b, what):
+    """device matrices of one accepted element type, width and device: (Ba, Bb, S, dtype code)"""
+    import torch
+    other = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(other, torch.Tensor) and a.is_cuda and other.is_cuda and a.device == other.device):
+        raise ValueError("%s works on sketch matrices resident on one device, or on numpy matrices" % what)
+    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not other.is_contiguous():
+        raise ValueError("sketches are contiguous int32 or int64 tensors")
+    Ba, Bb, S = _pair_shape(a, other)
+    return Ba, Bb if b is not None else 0, S, capi.I32 if a.dtype == torch.int32 else capi.U64
+
+
+def _lsh_width(a, b, what):
+    other = a if b is None else b
+    if not (hasattr(a, "ndim") and hasattr(other, "ndim")):
+        raise ValueError("%s works on sketch matrices resident on one device, or on numpy matrices" % what)
+    return _pair_shape(a, other)[2]
+
+
+def _host_indices(row, col):
+    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
+    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
+        raise ValueError("row and col are int64 arrays of one length")
+    return row, col
+
+
+def lsh_kernel_name(S, destchar="i"):
+    """The launches of the LSH family for sketches of S buckets (host only: profiling labels, tests): those of `lsh_candidates`, then,
+    behind the ';', the kernel `sketch_compare_list` takes; '' for a width the library refuses."""
+    dt, _ = capi.destchar_arg(destchar, (capi.I32, capi.U64), "a sketch takes 'i' (int32) or 'q' (int64)")
+    return _lib.bsq_lsh_kernel_name(int(S), dt).decode()
+
+
+def lsh_keys_host(a, rows_per_band, seed=0):
+    """The library's CPU twin of `lsh_keys` (`bsq_lsh_keys_host`) on a numpy matrix of int32, int64 or uint64: (T, N) int64."""
+    a, _, N, _, S, dt = _host_sketches(a)
+    rule, T = _lsh_rule(S, rows_per_band, 2, seed)
+    keys = np.empty((T, N), np.int64)
+    if N:
+        capi.check(_lib.bsq_lsh_keys_host(a.ctypes.data, N, S, dt, ctypes.byref(rule), keys.ctypes.data, N))
+    return keys
+
+
+def lsh_keys(a, rows_per_band, seed=0):
+    """The band keys of a sketch matrix: (T, N) int64, T = S // rows_per_band, band-major -- keys[t, i] hashes buckets t r .. t r + r - 1
+    of row i (0 .. 2 ** 63 - 1), and is -1 where all of them are EMPTY.  Two rows share a key exactly when they agree on the whole band
+    (up to a 63-bit hash).  int32 and int64 sketches of one batch give equal keys; another seed gives another family.  A device tensor
+    gives a device tensor on torch's current stream, one launch, nothing read back; a numpy matrix goes through the CPU twin."""
+    if isinstance(a, np.ndarray):
+        return lsh_keys_host(a, rows_per_band, seed)
+    import torch
+    N, _, S, dt = _device_sketches(a, None, "lsh_keys")
+    rule, T = _lsh_rule(S, rows_per_band, 2, seed)
+    keys = torch.empty((T, N), dtype=torch.int64, device=a.device)
+    if N:
+        with capi.launching(a.device) as stream:
+            capi.check(_lib.bsq_lsh_keys_device(a.data_ptr(), N, S, dt, ctypes.byref(rule), keys.data_ptr(), N, stream))
+    return keys
+
+
+def sketch_compare_list_host(a, row, col, b=None, *, either=True):
+    """The library's CPU twin of `sketch_compare_list` (`bsq_sketch_compare_list_host`) on numpy arrays: (match, either or None)."""
+    a, b, Ba, Bb, S, dt = _host_sketches(a, b)
+    row, col = _host_indices(row, col)
+    n = row.size
+    match = np.empty(n, np.int32)
+    eith = np.empty(n, np.int32) if either else None
+    if n:
+        other = a if b is None else b
+        capi.check(_lib.bsq_sketch_compare_list_host(a.ctypes.data if Ba else None, Ba, other.ctypes.data if other.shape[0] else None, other.shape[0], S,
+                                                     dt, row.ctypes.data, col.ctypes.data, n, match.ctypes.data, eith.ctypes.data if either else None))
+    return match, eith
+
+
+def sketch_compare_list(a, row, col, b=None, *, either=True):
+    """`match` and `either` of LISTED pairs of rows: (match, either or None), int32, one entry per pair (row[p], col[p]) of a (Ba, S)
+    and b (Bb, S) -- b=None: of a with itself -- with `sketch_compare`'s meaning of both counts.  It rescores a candidate list, from
+    `lsh_candidates`, from elsewhere or from a narrower sketch, at the cost of the list and not of Ba x Bb.  An index outside its
+    matrix gives match = either = -1 and is never followed.  Device tensors (contiguous sketches, contiguous int64 indices) give device
+    tensors on torch's current stream, one launch, nothing read back; numpy arrays go through the CPU twin."""
+    if isinstance(a, np.ndarray):
+        return sketch_compare_list_host(a, row, col, b, either=either)
+    import torch
+    Ba, Bb, S, dt = _device_sketches(a, b, "sketch_compare_list")
+    other = a if b is None else b
+    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.device == a.device and col.device == a.device
+            and row.dtype == torch.int64 and col.dtype == torch.int64 and row.ndim == 1 and row.shape == col.shape
+            and row.is_contiguous() and col.is_contiguous()):
+        raise ValueError("row and col are contiguous int64 tensors of one length on the sketches' device")
+    n = row.numel()
+    match = torch.empty(n, dtype=torch.int32, device=a.device)
+    eith = torch.empty(n, dtype=torch.int32, device=a.device) if either else None
+    if n:
+        with capi.launching(a.device) as stream:
+            capi.check(_lib.bsq_sketch_compare_list_device(a.data_ptr() if Ba else None, Ba, other.data_ptr() if other.shape[0] else None,
+                                                           other.shape[0], S, dt, row.data_ptr(), col.data_ptr(), n, match.data_ptr(),
+                                                           eith.data_ptr() if either else None, stream))
+    return match, eith
+
+
+def _too_many(total, cap):
+    return ValueError("%d candidates before the union, max_candidates = %d: lower max_bucket (long runs then yield their centre's pairs "
+                      "only) or raise rows_per_band (fewer, more selective bands)" % (total, cap))
+
+
+def _lsh_host(a, b, lsh, rule, cap, either):
+    """bsq_lsh_pairs_host twice -- to count, then to list -- as `sketch_pairs_host` calls its twin"""
+    a, b, Ba, Bb, S, dt = _host_sketches(a, b)
+    offs = np.zeros(Ba + 1, np.int64)
+    total = ctypes.c_int64(0)
+
+    def call(n, *arrays):
+        capi.check(_lib.bsq_lsh_pairs_host(a.ctypes.data if Ba else None, Ba, None if b is None else b.ctypes.data, Bb, S, dt, ctypes.byref(lsh),
+                                           None if rule is None else ctypes.byref(rule), -1 if cap is None else cap, ctypes.byref(total),
+                                           offs.ctypes.data, n, *(None if x is None else x.ctypes.data for x in arrays)))
+
+    if b is None or Bb:  # (a `b` without rows: no pair, and no pointer that says "two matrices")
+        call(0, None, None, None, None)
+    if cap is not None and total.value > cap:
+        raise _too_many(total.value, cap)
+    n = int(offs[-1])
+    row, col = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    match = None if rule is None else np.zeros(n, np.int32)
+    eith = np.zeros(n, np.int32) if rule is not None and either else None
+    if n:
+        call(n, row, col, match, eith)
+    return row, col, match, eith, offs
+
+
+def _lsh_device(a, b, lsh, T, cap):
+    """the candidates (row, col) of device matrices, ascending and each once: keys, torch's stable sort of every band, count, scan,
+    emit, torch.unique of the codes"""
+    import torch
+    Ba, Bb, S, dt = _device_sketches(a, b, "lsh_pairs")
+    N, dev = Ba + Bb, a.device
+    if N >= 2 ** 31:
+        raise ValueError("the two matrices together have more than 2 ** 31 - 1 rows")
+    none = torch.empty(0, dtype=torch.int64, device=dev)
+    if N == 0:
+        return none, none
+    with capi.launching(dev) as stream:
+        keys = torch.empty((T, N), dtype=torch.int64, device=dev)
+        if Ba:
+            capi.check(_lib.bsq_lsh_keys_device(a.data_ptr(), Ba, S, dt, ctypes.byref(lsh), keys.data_ptr(), N, stream))
+        if Bb:
+            capi.check(_lib.bsq_lsh_keys_device(b.data_ptr(), Bb, S, dt, ctypes.byref(lsh), keys.data_ptr() + 8 * Ba, N, stream))
+        keys, order = torch.sort(keys, dim=1, stable=True)
+        counts = torch.empty(T * N, dtype=torch.int64, device=dev)
+        capi.check(_lib.bsq_lsh_count_device(keys.data_ptr(), T, N, ctypes.byref(lsh), counts.data_ptr(), stream))
+        ends = torch.cumsum(counts, 0)
+        total = int(ends[-1].item())
+        if cap is not None and total > cap:
+            raise _too_many(total, cap)
+        if total == 0:
+            return none, none
+        codes = torch.empty(total, dtype=torch.int64, device=dev)
+        capi.check(_lib.bsq_lsh_emit_device(keys.data_ptr(), order.data_ptr(), T, N, ctypes.byref(lsh), (ends - counts).data_ptr(), total,
+                                            codes.data_ptr(), stream))
+        del keys, order, counts, ends
+        codes = torch.unique(codes)  # (sorted: ascending (i, j))
+        row = torch.div(codes, N, rounding_mode="floor")
+        col = codes - row * N
+        if b is not None:
+            cross = (row < Ba) & (col >= Ba)
+            row, col = row[cross], col[cross] - Ba
+    return row.contiguous(), col.contiguous()
+
+
+def lsh_candidates(a, b=None, *, rows_per_band, max_bucket=32, max_candidates=None, seed=0):
+    """The LSH candidates of a sketch matrix, before any threshold: (row, col), int64, ascending (i, j), each pair once -- the pairs of
+    rows that share the key of at least one band (`lsh_keys`).  b=None: the pairs i < j of `a`; b given: the rule runs over `a` followed
+    by `b` and the pairs (i in a, j in b) are kept.  In a band, a group of up to `max_bucket` rows with one key yields all its pairs, a
+    larger group only the pairs of its smallest row with each other member (linclust's centre rule), so a store that is one read
+    repeated costs N - 1 candidates per band and not N * (N - 1) / 2.  max_candidates: raise ValueError, before the candidate list
+    is allocated, when the candidates before the union over the bands number more.  Arguments and the device / numpy split as in
+    `lsh_pairs`."""
+    S = _lsh_width(a, b, "lsh_candidates")
+    lsh, T = _lsh_rule(S, rows_per_band, max_bucket, seed, max_candidates)
+    cap = None if max_candidates is None else int(max_candidates)
+    if isinstance(a, np.ndarray):
+        return _lsh_host(a, b, lsh, None, cap, False)[:2]
+    return _lsh_device(a, b, lsh, T, cap)
+
+
+def lsh_pairs(a, b=None, *, rows_per_band, min_jaccard=0.5, min_match=1, max_bucket=32, max_candidates=None, either=True, seed=0):
+    """Near-duplicate search without the all-pairs comparison: (row, col, match, either or None, pair_offsets) with the shape and meaning
+    of `sketch_pairs`' result, over the LSH candidates of the matrices instead of over every pair.  The cost follows the number of rows
+    and of candidates, not Ba x Bb (include/bsq.h, "LSH candidates of a sketch matrix").
+
+    The sketch rows are cut into T = S // rows_per_band bands of `rows_per_band` buckets; two rows are candidates when they agree on a
+    whole band (`lsh_candidates`), and a candidate is listed when it passes `sketch_pairs`' rule -- match >= min_match and
+    match * 65536 >= floor(min_jaccard * 65536 + 0.5) * either over all S buckets.  With no group above `max_bucket` the result is
+    exactly `sketch_pairs`' list restricted to the pairs that share a band; identical rows with a filled bucket among the first
+    T * rows_per_band are always listed; rows that are EMPTY throughout never are.  `lsh_rows_per_band(S, min_jaccard)` chooses
+    rows_per_band for a predicted recall (`lsh_recall`) at the threshold.  b=None lists the pairs i < j of `a`; b given lists pairs
+    (i of a, j of b).  pair_offsets (int64, Ba + 1) is the CSR over the rows of a.  seed: another family of band keys.
+
+    Device tensors (contiguous int32 or int64, as `minhash_packed` returns them) give device tensors on torch's current stream: the
+    library's kernels for the keys, the candidates of the sorted bands and the counts of the listed pairs, torch for the stable sort of
+    every band, the scan, the union (`torch.unique`) and the compaction.  The call reads three sizes back (the candidates before the
+    union, the union's and the result's).  max_candidates=M raises ValueError before the candidate list is allocated when the candidates
+    before the union exceed M; None means no limit (8 bytes a candidate).  numpy matrices go through the CPU twin
+    (`bsq_lsh_pairs_host`) and give the same bytes."""
+    S = _lsh_width(a, b, "lsh_pairs")
+    lsh, T = _lsh_rule(S, rows_per_band, max_bucket, seed, max_candidates)
+    rule, _ = _pairs_rule(S, min_jaccard, min_match, None, None, False)
+    cap = None if max_candidates is None else int(max_candidates)
+    if isinstance(a, np.ndarray):
+        return _lsh_host(a, b, lsh, rule, cap, either)
+    import torch
+    row, col = _lsh_device(a, b, lsh, T, cap)
+    match, eith = sketch_compare_list(a, row, col, b)
+    keep = (match >= rule.min_match) & (match.to(torch.int64) * 65536 >= eith.to(torch.int64) * rule.jaccard_q16)
+    row, col, match = row[keep], col[keep], match[keep]
+    offs = torch.searchsorted(row, torch.arange(a.shape[0] + 1, dtype=torch.int64, device=a.device))
+    return row, col, match, eith[keep] if either else None, offs
+
+
 def length_key(offsets):
     """The key of cd-hit's order, "longest first": -(offsets[1:] - offsets[:-1]) as int64, a tensor for a tensor (on its device) and a
     numpy array otherwise.  Rows of one length fall to the earlier row."""
@@ -552,4 +823,5 @@ def cluster_split(labels, fractions, seed=0):
 __all__ = ["EMPTY", "minhash_packed", "minhash_host", "minhash_kernel_name", "sketch_compare", "sketch_compare_host", "sketch_jaccard",
            "sketch_pairs", "sketch_pairs_host", "sketch_duplicates", "sketch_pairs_kernel_name", "sketch_clusters", "sketch_clusters_host",
            "cluster_pairs", "cluster_pairs_host", "sketch_clusters_kernel_name", "cluster_table", "cluster_split", "greedy_pairs",
-           "greedy_pairs_host", "greedy_kernel_name", "length_key"]
+           "greedy_pairs_host", "greedy_kernel_name", "length_key", "lsh_pairs", "lsh_candidates", "lsh_keys", "lsh_keys_host",
+           "sketch_compare_list", "sketch_compare_list_host", "lsh_recall", "lsh_rows_per_band", "lsh_kernel_name"]

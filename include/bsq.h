@@ -52,7 +52,9 @@ extern "C" {
                            * bsq_bpe_vocab_size, bsq_bpe_unk_id, bsq_bpe_bos_id, bsq_bpe_eos_id, bsq_bpe_pad_id, bsq_bpe_tokenize_device,
                            * bsq_bpe_tokenize_host, bsq_bpe_kernel_name, bsq_bpe_mlm, bsq_bpe_mlm_tokenize_device, bsq_bpe_mlm_tokenize_host,
                            * bsq_bpe_mlm_kernel_name, bsq_greedy_scratch_bytes, bsq_greedy_pairs_device, bsq_greedy_pairs_host,
-                           * bsq_greedy_kernel_name; nothing removed */
+                           * bsq_greedy_kernel_name, bsq_lsh, bsq_lsh_keys_device, bsq_lsh_keys_host, bsq_lsh_count_device, bsq_lsh_emit_device,
+                           * bsq_sketch_compare_list_device, bsq_sketch_compare_list_host, bsq_lsh_pairs_host, bsq_lsh_kernel_name;
+                           * nothing removed */
 
 typedef int32_t bsq_status;
 enum {
@@ -935,6 +937,127 @@ bsq_status bsq_greedy_pairs_host(const int64_t *row, const int64_t *col, const i
 /* Host only: the launches of one round and of the assignment, the round's before the ';' ("k_greedy_mark+k_greedy_decide;k_greedy_clear+
  * k_greedy_best<weight>+k_greedy_best<key>+k_greedy_best<index>+k_greedy_rep" with both; a run's first call launches k_greedy_init first). */
 const char *bsq_greedy_kernel_name(int32_t has_key, int32_t has_weight);
+
+/* ---- LSH candidates of a sketch matrix: the sub-quadratic front of the near-duplicate search.  "sketch pairs" walks every tile of the
+ * Ba x Bb comparison; cd-hit, linclust and the dedup passes of language-model corpora never compare all pairs: they bucket rows by a
+ * few hashed sketch bands and compare only inside buckets.  This section is that step over the one-permutation MinHash rows of "MinHash
+ * sketch" -- banded locality-sensitive hashing -- and the call that scores a GIVEN list of sketch pairs.  The result has the shape and
+ * the meaning of the pair list's.
+ *
+ * THE RULE.
+ *     bands        a sketch matrix has N rows of S buckets (BSQ_I32 or BSQ_U64, C-contiguous, the low 32 bits read, 1 <= S <= 2^14,
+ *                  N <= 2^31 - 1).  r = rows_per_band, 1 <= r <= S; T = floor(S / r) bands; band t is buckets t r .. t r + r - 1; the
+ *                  trailing S - T r buckets play no part.
+ *     keys         v_q is a bucket's 32-bit unsigned value; EMPTY is 0xFFFFFFFF in either element type, so the int32 and the int64
+ *                  sketches of one batch give the same keys.  mix64 is splitmix64's finalizer ("MinHash sketch").
+ *                      s'   = mix64(seed ^ 0x4C53485F42414E44)                      ("LSH_BAND": a domain of its own)
+ *                      h    = mix64(s' + 0x9E3779B97F4A7C15 * (t + 1))
+ *                      h    = mix64(h ^ v_q)        for q = 0 .. r - 1, in this order
+ *                      key[t][i] = (int64)(h >> 1)  0 .. 2^63 - 1
+ *                      key[t][i] = -1               when all r buckets of the band are EMPTY: a void band, which collides with nothing
+ *                  A band with some but not all buckets EMPTY is an ordinary band -- EMPTY is a value like any other -- which matters
+ *                  for short reads, whose rows fill a fraction of 1024 buckets.
+ *     runs         the rows of each band sorted by (key, row index) ascending: a stable sort of the keys.  A run is a maximal stretch
+ *                  of equal non-void keys.  A run of n <= max_bucket rows yields all n (n - 1) / 2 pairs (i, j), i < j.  A run of
+ *                  n > max_bucket rows yields the n - 1 pairs (c, j), c the run's smallest row index (its first element after the
+ *                  stable sort): linclust's centre rule, which keeps the search linear on a store that is one amplicon repeated; under
+ *                  single linkage the run is still one cluster wherever the pairs pass.  max_bucket >= 2.
+ *     candidates   the union over the bands, each pair once.
+ *     result       the candidates that pass the integer rule of "sketch pairs" -- match >= min_match and match * 65536 >= jaccard_q16 *
+ *                  either, match and either over all S buckets exactly as the comparison defines them -- in ascending (i, j).
+ *                  Consequence: with no run above max_bucket the result is the pair list of "sketch pairs" (upper) restricted to the
+ *                  pairs that share a key in some band, and two identical rows with at least one filled bucket among the first T r
+ *                  are always listed.
+ *     two matrices b given: the rule runs over the concatenation a then b (N = Ba + Bb <= 2^31 - 1); only the candidates with
+ *                  i < Ba <= j are kept and reported as (i, j - Ba).  A long run's centre is then a row of a whenever the run holds one.
+ *
+ * bsq_lsh_keys_device / _host: keys[t * key_pitch + i] <- key[t][i], int64, band-major, so that each band's keys are contiguous for
+ * the sort; key_pitch >= N is the distance of two bands, which lets the keys of b be written behind those of a (keys + Ba, the same
+ * pitch) without a copy.  N == 0 is BSQ_OK and writes nothing.
+ * bsq_lsh_count_device: sorted_keys (device int64, bands x N, every band ascending: the values of the stable sort) -> counts (int64,
+ * bands x N): the candidates each sorted position owns.  The element at place q of a run of n owns q candidates if n <= max_bucket,
+ * else 1 if q > 0 and 0 if q == 0; a void key owns none.  Only max_bucket of the bsq_lsh is read.
+ * bsq_lsh_emit_device: order (int64, bands x N: the sort's indices) and starts (int64, bands x N: the exclusive scan of counts over
+ * all bands x N positions) -> codes[starts[p] ..] <- i * N + j of the candidates position p owns (i < j as the stable sort leaves
+ * them).  Nothing is written at or past index max_codes.  The codes of all bands are not yet a set: the union is the caller's.
+ * bsq_sketch_compare_list_device / _host: match[p], either[p] (int32; either may be null) of the listed pairs (row[p], col[p]) of a
+ * (Ba, S) and b (Bb, S), which may be one matrix; one launch.  An index outside its matrix gives match = either = -1 and is never
+ * followed: the edit distance's convention for bad indices, expressed in a count.  Public on its own: rescoring a list from elsewhere
+ * or from a narrower sketch.
+ * bsq_lsh_pairs_host: the whole rule sequentially (csrc/bsq_lsh_host.cpp: a stable sort of every band, a walk of its runs, the union,
+ * the counts, the pass rule) -- not a restatement of the kernels.  b_or_null == NULL: one matrix (Bb must be 0).  rule_or_null == NULL:
+ * the candidates alone, no threshold; otherwise min_match and jaccard_q16 are read and upper and segments must be 0.  *n_candidates <-
+ * the candidates before the union; when max_candidates >= 0 and that number exceeds it, nothing else is written (BSQ_OK).  Otherwise
+ * pair_offsets (Ba + 1 entries: the CSR over the rows of a; the last is the total), and row, col, match, either (match and either may
+ * be null) of every rank < max_pairs, as bsq_sketch_pairs_host writes them.
+ * Every device call is stream-ordered and never synchronises; a refusal writes nothing and sets bsq_last_error().  BSQ_ERR_INVALID_ARG:
+ * a null pointer where one is read, a negative size, S outside 1 .. 2^14, rows_per_band outside 1 .. S, max_bucket < 2, reserved != 0,
+ * more than 2^31 - 1 rows, key_pitch < N, bands > 2^14.  BSQ_ERR_DTYPE: an element type other than BSQ_I32 and BSQ_U64.
+ *
+ * Kernels (csrc/bsq_lsh.hip).  k_lsh_keys<T>: a workgroup per (64 rows, 64 bands); a lane takes one (row, band) with the band index
+ * fastest, so a wave reads consecutive r-bucket pieces of a row; the keys go through a [band][row] image in LDS and leave a wave per
+ * band, 512 contiguous bytes into the band-major matrix.  k_lsh_count, k_lsh_emit: a lane per sorted position; a key that differs from
+ * the one in front of it heads its run, any other finds its head from the sorted keys by doubling steps back and a bisection
+ * (O(log q) reads at place q) and its run's length class from the one position max_bucket behind the head -- no lane depends on which
+ * wave or workgroup holds the rest of its run.  k_sketch_compare_list<T, G>: G = 4 / 16 / 64 lanes per pair by the row's size (up to
+ * 128 bytes, up to 1 KiB, beyond), 16-byte loads of both rows, match and either added up in one word and reduced by lane exchanges:
+ * no atomics, no LDS; rows whose size is no multiple of 16 bytes take element loads.  No kernel uses scratch
+ * (profiles/r29/lsh_resources.txt).
+ * Measured on an MI355X (scripts/lsh_lab.py, profiles/r29/lsh_lab.txt), the whole Python call -- these kernels, torch's stable sort of
+ * the (T, N) keys, its scan and its unique, three read-backs -- against the pair list of "sketch pairs" of the same build in alternation,
+ * on that section's inputs (int32, S = 128, random reads with 3 % planted near-duplicates, min_jaccard 0.5, r = 3: 42 bands):
+ * 4096 rows 0.46 ms against 0.39; 16 384: 0.77 against 6.09; 65 536: 0.89 against 89.3; 262 144: 2.17 against 837 (386x); 1 Mi rows
+ * 11.6 ms and 4 Mi rows 23.5 ms, where the pair list is no longer run: 0.008, 0.011 and 0.006 us a row from 262 144 rows on, so the call
+ * is no longer quadratic.  Every pair of the pair list was returned at every size (the planted copies sit near J = 0.63, where the
+ * predicted recall is 0.99999; the prediction at the threshold itself, 0.9963, is not tested by these inputs).  At 4 Mi rows the sort is
+ * 17.9 of the 23.2 ms, count + scan + emit 3.7, keys 1.3 (2.8 TB/s of sketches read and keys written), unique 0.3 and the list compare
+ * 0.1 (126 K candidates: launch cost).  The list compare alone on 16.8 M pairs over 1 Mi rows: 1.19 ms on neighbouring pairs (14.5 TB/s
+ * of row bytes) and 1.54 ms with random columns (11.1 TB/s) -- above HBM's 8 TB/s because the list is sorted by row and the a side
+ * comes from L2; the random b rows are 5.6 TB/s of gathered 512-byte rows, which is what bounds it.  One row repeated: 0.60 ms at 4096
+ * rows, 3.1 ms at 262 144 and 14.7 ms at 1 Mi with the centre rule; without it (max_bucket = N) 4096 rows take 25 ms and 2.8 GB of
+ * codes.  No counters-only run was taken.
+ *
+ * Known answers (int32, S = 4, E = EMPTY, seed 0; rows 0 and 1 equal with two filled buckets, rows 2 and 3 EMPTY throughout, row 4
+ * with one filled bucket of its own, row 5 sharing bucket 0 with rows 0 and 1):
+ *     (7 E 9 E) (7 E 9 E) (E E E E) (E E E E) (E 5 E E) (7 E 3 E)
+ *     r = 1   key[0] 5027150649341863934 (rows 0, 1, 5), -1 (rows 2, 3, 4); key[1] 4172740380461416370 (row 4), -1 elsewhere;
+ *             key[2] 4432986889740121373 (rows 0, 1), 2075462142187623361 (row 5), -1 elsewhere; key[3] -1 throughout
+ *     r = 2   key[0] 5679660576557730032 (rows 0, 1, 5), 1824924355021282908 (row 4: a partly EMPTY band), -1 (rows 2, 3);
+ *             key[1] 7335292338109055888 (rows 0, 1), 7855000670364763218 (row 5), -1 elsewhere
+ *     r = 3   key[0] 140436569112452715 (rows 0, 1), 4637186175826648359 (row 4), 8262566470542649784 (row 5), -1 (rows 2, 3)
+ *     r = 2, seed 1   key[0] 2738558360980352134 (rows 0, 1, 5), 5308736278640590164 (row 4), -1 (rows 2, 3)
+ *     r = 1 or 2, max_bucket 32   candidates (0,1) (0,5) (1,5), 4 before the union; min_match 1, jaccard_q16 32768: (0,1) match 2
+ *                                 either 2, (0,5) match 1 either 2, (1,5) match 1 either 2; pair_offsets 0 2 3 3 3 3 3
+ *     r = 1, max_bucket 2         the run 0, 1, 5 is long, its centre 0: candidates (0,1) (0,5), 3 before the union;
+ *                                 pair_offsets 0 2 2 2 2 2 2
+ *     r = 4                       candidates (0,1); pair_offsets 0 1 1 1 1 1 1
+ *     a = rows 0, 1 and b = rows 2 .. 5, r = 1   candidates (0,3) (1,3), both match 1 either 2; pair_offsets 0 1 2
+ *
+ * Out of scope: a form that reads nothing back; bands in chunks to bound the candidate memory; bottom-s sketches and minimizers; a
+ * segmented sort of the library's own; the union-find inside the bucket walk without a list; multi-device sharding of the bands. */
+typedef struct bsq_lsh {
+    int32_t rows_per_band; /* r: 1 .. S */
+    int32_t max_bucket;    /* >= 2: a run of more rows yields its centre's pairs only */
+    uint64_t seed;
+    int32_t reserved;      /* 0 */
+} bsq_lsh;
+bsq_status bsq_lsh_keys_device(const void *a, int64_t N, int64_t S, bsq_dtype t, const bsq_lsh *lsh, int64_t *keys, int64_t key_pitch,
+                               void *hip_stream);
+bsq_status bsq_lsh_keys_host(const void *a, int64_t N, int64_t S, bsq_dtype t, const bsq_lsh *lsh, int64_t *keys, int64_t key_pitch);
+bsq_status bsq_lsh_count_device(const int64_t *sorted_keys, int64_t bands, int64_t N, const bsq_lsh *lsh, int64_t *counts, void *hip_stream);
+bsq_status bsq_lsh_emit_device(const int64_t *sorted_keys, const int64_t *order, int64_t bands, int64_t N, const bsq_lsh *lsh, const int64_t *starts,
+                               int64_t max_codes, int64_t *codes, void *hip_stream);
+bsq_status bsq_sketch_compare_list_device(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const int64_t *row,
+                                          const int64_t *col, int64_t n_pairs, int32_t *match, int32_t *either_or_null, void *hip_stream);
+bsq_status bsq_sketch_compare_list_host(const void *a, int64_t Ba, const void *b, int64_t Bb, int64_t S, bsq_dtype t, const int64_t *row,
+                                        const int64_t *col, int64_t n_pairs, int32_t *match, int32_t *either_or_null);
+bsq_status bsq_lsh_pairs_host(const void *a, int64_t Ba, const void *b_or_null, int64_t Bb, int64_t S, bsq_dtype t, const bsq_lsh *lsh,
+                              const bsq_sketch_pairs *rule_or_null, int64_t max_candidates, int64_t *n_candidates, int64_t *pair_offsets,
+                              int64_t max_pairs, int64_t *row, int64_t *col, int32_t *match_or_null, int32_t *either_or_null);
+/* Host only: the launches of the family for sketches of this width and element type, the list compare's behind the ';'
+ * ("k_lsh_keys+k_lsh_count+k_lsh_emit;k_sketch_compare_list<16>", "...<4, elements>" where a row is no multiple of 16 bytes); "" for an
+ * S or an element type the calls refuse. */
+const char *bsq_lsh_kernel_name(int64_t S, bsq_dtype t);
 
 /* ---- edit distance of row pairs: the exact unit-cost edit distance of listed pairs of rows of resident packed stores, one launch --
  * the alignment step that follows a k-mer filter (cd-hit, mmseqs cluster): a candidate list of "sketch pairs" becomes a list verified
