@@ -245,173 +245,17 @@ __device__ __forceinline__ ChunkCoord chunk_coord(const EParams &p, int64_t k, i
 // NIB (round 5): the id matrix holds NIBBLES -- the id of (t, b) in bits 4 (b & 1) ... of byte (t * Bp + b) / 2 (Bp is even), 15 = no one:
 // the scratch of alphabets with at most 15 classes at half its bytes (see two_pass_nibbles).  A template flag: as a runtime one its
 // shift / mask arithmetic cost the BYTE form 13 % on cfg4 f32 (670 -> 759 us).
+// The statements are bsq_expand_chunks_text.h, for block `blk` of one batch's grid: included by expand_chunks_body (k_expand_chunks_multi: the
+// block inside the batch's range) and by the one-batch kernel (blockIdx.x).  Included, not called from the kernel: as a call of that function
+// the one-batch kernel compiled to different code, and cfg3 ran 0.5 % slower.
 template <typename ST, bool NT, int MATH, bool GATE = false, bool NIB = false>
 __device__ __forceinline__ void expand_chunks_body(const uint32_t blk, const EParams &p) {
-    constexpr int PIECE = kChunk;             // bytes per wave
-    constexpr int NS = PIECE / 1024;          // 16-byte stores per lane
-    __shared__ __align__(16) uint8_t s_img[4][PIECE];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint8_t *img = s_img[wave];
-#pragma unroll
-    for (int u = 0; u < NS; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-
-    // chunk of this wave: class = blockIdx % 8 (pinned to the XCD the block lands on).  The wave index goes through
-    // readfirstlane so that the chunk arithmetic below is scalar-ALU work.
-    const int wave_s = MATH == 1 ? __builtin_amdgcn_readfirstlane(wave) : wave;
-    int64_t group = static_cast<int64_t>(blk >> 3);
-    int32_t cls = static_cast<int32_t>(blk & 7u);
-    const int64_t slot = group * 4 + wave_s;
-    const int64_t k = static_cast<int64_t>(cls) + 8 * slot;
-    if (k >= p.nchunks) return;
-    uint32_t gate = 0;
-    if constexpr (GATE) gate = __hip_atomic_load(reinterpret_cast<const uint32_t *>(p.tok) + (blk & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
-    const ST one = static_cast<ST>(p.one_bits);
-    const ChunkCoord cc = chunk_coord<MATH>(p, k, rowbytes);
-    if (!cc.live) return;
-    const int64_t lo = cc.lo, b_lo = cc.b_lo, t_lo = cc.t_lo;
-    const int32_t len = cc.len, skip = cc.skip, nr = cc.nr;
-    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
-    const uint8_t *tok = NIB ? p.tok + ((t_lo * p.Bp + b_lo) >> 1) : p.tok + t_lo * p.Bp + b_lo;
-    const int32_t par0 = NIB ? static_cast<int32_t>(b_lo & 1) : 0;
-    if constexpr (GATE) tok += (gate == 0xFEFEFEFDu && p.nchunks < 0) ? 1 : 0;  // never taken: the token loads wait for the gate load
-    constexpr uint32_t nmask = NIB ? 0xFu : kNone;  // "no one"
-    const int64_t wrap_at = p.B - b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
-    // scatter: row r_lo + i has its one at image byte i*rowbytes - skip + tok*sizeof(ST).
-    // NS (1..4) coalesced token loads in flight per step, straight-line per NS: the number of 64-row slots a
-    // step needs and the (rare) row-wrap case are wave-uniform, so they are scalar branches.
-    const int32_t nr_s = __builtin_amdgcn_readfirstlane(nr);
-    const bool wraps = wrap_at < nr_s;  // the piece runs over the end of position t_lo's rows
-    auto step = [&](auto ns_tag, int32_t i0) {
-        constexpr int NS = decltype(ns_tag)::value;
-        uint32_t tk[NS];
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const int32_t i = i0 + 64 * q + lane;
-            int64_t a = i;
-            if (wraps && i >= wrap_at) {
-                const int64_t w = (i - wrap_at) / p.B + 1;
-                a = i + w * (p.Bp - p.B);
-            }
-            if constexpr (NIB) {
-                const int64_t ia = a + par0;
-                tk[q] = i < nr_s ? (static_cast<uint32_t>(tok[ia >> 1]) >> ((static_cast<uint32_t>(ia) & 1u) << 2)) & 0xFu : nmask;
-            } else {
-                tk[q] = i < nr_s ? static_cast<uint32_t>(tok[a]) : kNone;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const int32_t i = i0 + 64 * q + lane;
-            const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk[q]) * static_cast<int32_t>(sizeof(ST));
-            if (tk[q] != nmask && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
-        }
-    };
-    for (int32_t i0 = 0; i0 < nr_s; i0 += 256) {
-        const int32_t left = p.force4 ? 256 : nr_s - i0;
-        if (left > 192) step(std::integral_constant<int, 4>{}, i0);
-        else if (left > 128) step(std::integral_constant<int, 3>{}, i0);
-        else if (left > 64) step(std::integral_constant<int, 2>{}, i0);
-        else step(std::integral_constant<int, 1>{}, i0);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    uint8_t *g = p.out + lo + t_lo * p.row_gap;
-    if (len == PIECE && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-        uint4 v[NS];
-#pragma unroll
-        for (int u = 0; u < NS; ++u) v[u] = *reinterpret_cast<const uint4 *>(img + u * 1024 + lane * 16);
-#pragma unroll
-        for (int u = 0; u < NS; ++u) store16<NT>(g + u * 1024 + lane * 16, v[u]);
-    } else {  // clipped first / last piece of the tensor
-        for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
-            *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
-    }
+#include "bsq_expand_chunks_text.h"
 }
-// (Twin: expand_chunks_body above, the same statements for k_expand_chunks_multi.  The one-batch kernel keeps its own text: as a call of that
-//  function it compiled to different code, and cfg3 ran 0.5 % slower.  A change here belongs in both.)
 template <typename ST, bool NT, int MATH, bool GATE = false, bool NIB = false>
 __global__ __launch_bounds__(kThreads) void k_expand_chunks(const EParams p) {
-    constexpr int PIECE = kChunk;             // bytes per wave
-    constexpr int NS = PIECE / 1024;          // 16-byte stores per lane
-    __shared__ __align__(16) uint8_t s_img[4][PIECE];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint8_t *img = s_img[wave];
-#pragma unroll
-    for (int u = 0; u < NS; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-
-    // chunk of this wave: class = blockIdx % 8 (pinned to the XCD the block lands on).  The wave index goes through
-    // readfirstlane so that the chunk arithmetic below is scalar-ALU work.
-    const int wave_s = MATH == 1 ? __builtin_amdgcn_readfirstlane(wave) : wave;
-    int64_t group = static_cast<int64_t>(blockIdx.x >> 3);
-    int32_t cls = static_cast<int32_t>(blockIdx.x & 7u);
-    const int64_t slot = group * 4 + wave_s;
-    const int64_t k = static_cast<int64_t>(cls) + 8 * slot;
-    if (k >= p.nchunks) return;
-    uint32_t gate = 0;
-    if constexpr (GATE) gate = __hip_atomic_load(reinterpret_cast<const uint32_t *>(p.tok) + (blockIdx.x & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
-    const ST one = static_cast<ST>(p.one_bits);
-    const ChunkCoord cc = chunk_coord<MATH>(p, k, rowbytes);
-    if (!cc.live) return;
-    const int64_t lo = cc.lo, b_lo = cc.b_lo, t_lo = cc.t_lo;
-    const int32_t len = cc.len, skip = cc.skip, nr = cc.nr;
-    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
-    const uint8_t *tok = NIB ? p.tok + ((t_lo * p.Bp + b_lo) >> 1) : p.tok + t_lo * p.Bp + b_lo;
-    const int32_t par0 = NIB ? static_cast<int32_t>(b_lo & 1) : 0;
-    if constexpr (GATE) tok += (gate == 0xFEFEFEFDu && p.nchunks < 0) ? 1 : 0;  // never taken: the token loads wait for the gate load
-    constexpr uint32_t nmask = NIB ? 0xFu : kNone;  // "no one"
-    const int64_t wrap_at = p.B - b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
-    // scatter: row r_lo + i has its one at image byte i*rowbytes - skip + tok*sizeof(ST).
-    // NS (1..4) coalesced token loads in flight per step, straight-line per NS: the number of 64-row slots a
-    // step needs and the (rare) row-wrap case are wave-uniform, so they are scalar branches.
-    const int32_t nr_s = __builtin_amdgcn_readfirstlane(nr);
-    const bool wraps = wrap_at < nr_s;  // the piece runs over the end of position t_lo's rows
-    auto step = [&](auto ns_tag, int32_t i0) {
-        constexpr int NS = decltype(ns_tag)::value;
-        uint32_t tk[NS];
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const int32_t i = i0 + 64 * q + lane;
-            int64_t a = i;
-            if (wraps && i >= wrap_at) {
-                const int64_t w = (i - wrap_at) / p.B + 1;
-                a = i + w * (p.Bp - p.B);
-            }
-            if constexpr (NIB) {
-                const int64_t ia = a + par0;
-                tk[q] = i < nr_s ? (static_cast<uint32_t>(tok[ia >> 1]) >> ((static_cast<uint32_t>(ia) & 1u) << 2)) & 0xFu : nmask;
-            } else {
-                tk[q] = i < nr_s ? static_cast<uint32_t>(tok[a]) : kNone;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const int32_t i = i0 + 64 * q + lane;
-            const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk[q]) * static_cast<int32_t>(sizeof(ST));
-            if (tk[q] != nmask && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
-        }
-    };
-    for (int32_t i0 = 0; i0 < nr_s; i0 += 256) {
-        const int32_t left = p.force4 ? 256 : nr_s - i0;
-        if (left > 192) step(std::integral_constant<int, 4>{}, i0);
-        else if (left > 128) step(std::integral_constant<int, 3>{}, i0);
-        else if (left > 64) step(std::integral_constant<int, 2>{}, i0);
-        else step(std::integral_constant<int, 1>{}, i0);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    uint8_t *g = p.out + lo + t_lo * p.row_gap;
-    if (len == PIECE && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-        uint4 v[NS];
-#pragma unroll
-        for (int u = 0; u < NS; ++u) v[u] = *reinterpret_cast<const uint4 *>(img + u * 1024 + lane * 16);
-#pragma unroll
-        for (int u = 0; u < NS; ++u) store16<NT>(g + u * 1024 + lane * 16, v[u]);
-    } else {  // clipped first / last piece of the tensor
-        for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
-            *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
-    }
+    const uint32_t blk = blockIdx.x;
+#include "bsq_expand_chunks_text.h"
 }
 
 // k_expand_rows1 (round 5): the same chunk stream for ONE-BYTE elements with rows of 3 ... 15 bytes (int8 one-hots of DNA-sized
@@ -426,261 +270,16 @@ __global__ __launch_bounds__(kThreads) void k_expand_chunks(const EParams p) {
 // over the end of a position row of a padded id matrix (Bp != B) take the byte loop at the end -- a few hundred chunks of a million.
 // NIB (end of round 5): the id matrix holds nibbles as in k_expand_chunks<..., NIB> -- a lane's <= 6 ids and the parity of its first one
 // are one unaligned 4-byte window.
+// The statements are bsq_expand_rows1_text.h, included by expand_rows1_body (k_expand_rows1_multi) and by the one-batch kernel, as with
+// k_expand_chunks.
 template <bool NT, int NR, bool NIB = false>
 __device__ __forceinline__ void expand_rows1_body(const uint32_t blk, const EParams &p) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int64_t slot = static_cast<int64_t>(blk >> 3) * 4 + wave_s;
-    const int64_t k = static_cast<int64_t>(blk & 7u) + 8 * slot;
-    if (k >= p.nchunks) return;
-    const int32_t rb = p.C;  // bytes per row (one-byte elements)
-    const ChunkCoord cc = chunk_coord<0>(p, k, rb);
-    if (!cc.live) return;
-    const int32_t len = cc.len, skip = cc.skip;
-    const int32_t nr_s = __builtin_amdgcn_readfirstlane(cc.nr);
-    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
-    const uint8_t *tok = NIB ? p.tok + ((cc.t_lo * p.Bp + cc.b_lo) >> 1) : p.tok + cc.t_lo * p.Bp + cc.b_lo;
-    const uint32_t par0 = NIB ? static_cast<uint32_t>(cc.b_lo & 1) : 0u;
-    constexpr uint32_t kNo = NIB ? 0xFu : kNone;  // "no one"
-    const int64_t wrap_at = p.B - cc.b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
-    const bool wraps = p.Bp != p.B && wrap_at < nr_s;  // (wave-uniform) the chunk runs over the end of a position row of a PADDED id matrix
-    uint8_t *g = p.out + cc.lo + cc.t_lo * p.row_gap;
-    const uint32_t one = static_cast<uint32_t>(p.one_bits) & 0xFFu;
-    // the id of row i of the chunk (rows behind wrap_at lie in later position rows of the matrix, Bp - B ids further each)
-    auto id_of = [&](uint32_t i) -> uint32_t {
-        int64_t at = i;
-        if (static_cast<int64_t>(i) >= wrap_at) at += ((static_cast<int64_t>(i) - wrap_at) / p.B + 1) * (p.Bp - p.B);
-        if constexpr (NIB) {
-            at += par0;
-            return (static_cast<uint32_t>(tok[at >> 1]) >> ((static_cast<uint32_t>(at) & 1u) << 2)) & 0xFu;
-        } else {
-            return static_cast<uint32_t>(tok[at]);
-        }
-    };
-    constexpr int IDB = NIB ? 4 : 8;  // bits per id in a lane's window
-    if (len == kChunk && (reinterpret_cast<uintptr_t>(g) & 15) == 0 && nr_s >= 8) {
-        uint64_t ids[4];
-        uint32_t ph[4];
-        if (!wraps && NIB) {
-            typedef uint32_t u32u __attribute__((aligned(1)));
-            uint32_t w[4], sh[4];
-            const uint32_t lb = (par0 + static_cast<uint32_t>(nr_s) - 1u) >> 1;  // the last byte of ids this chunk owns (>= 3: nr_s >= 8)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together: NR <= 6 nibbles + a parity fit four bytes
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-                const uint32_t n0 = q + par0, bo = n0 >> 1;
-                const uint32_t off = bo + 3u <= lb ? bo : lb - 3u;  // pulled back to END at the chunk's last id byte (rows < nr_s lie in bo ... lb)
-                sh[u] = (bo - off) * 8u + ((n0 & 1u) << 2);
-                w[u] = *reinterpret_cast<const u32u *>(tok + off);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ids[u] = w[u] >> sh[u];
-        } else if (!wraps) {
-            typedef uint32_t u32x2u __attribute__((ext_vector_type(2), aligned(1)));
-            u32x2u w[4];
-            uint32_t sh[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-                // the last lanes' windows are pulled back to END at the chunk's last row: never a byte beyond the ids this chunk owns
-                const uint32_t off = q + 8u <= static_cast<uint32_t>(nr_s) ? q : static_cast<uint32_t>(nr_s) - 8u;
-                sh[u] = (q - off) * 8u;
-                w[u] = *reinterpret_cast<const u32x2u *>(tok + off);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ids[u] = ((static_cast<uint64_t>(w[u].y) << 32) | w[u].x) >> sh[u];
-        } else {  // one chunk per position row: the NR ids of a window one by one, across the padding (all 4 NR byte loads in flight together)
-            uint32_t b[4][NR];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-#pragma unroll
-                for (int j = 0; j < NR; ++j) b[u][j] = q + j < static_cast<uint32_t>(nr_s) ? id_of(q + j) : kNo;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ids[u] = 0;
-#pragma unroll
-                for (int j = 0; j < NR; ++j) ids[u] |= static_cast<uint64_t>(b[u][j]) << (IDB * j);
-            }
-        }
-        const uint32_t cmask = (1u << rb) - 1u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            uint32_t bits = 0;
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                const uint32_t id = static_cast<uint32_t>(ids[u] >> (IDB * j)) & (NIB ? 0xFu : 0xFFu);
-                const uint32_t m = (1u << (id & 31u)) & cmask;  // id 255 (no one) -> bit 31 -> 0; nibble 15 -> bit 15 -> 0 (rows of <= 15 bytes)
-                const int32_t at = j * rb;                      // wave-uniform; strings that start at bit >= 32 lie beyond the lane's bits
-                if (at < 32) bits |= m << at;
-            }
-            bits >>= ph[u];
-            uint4 o;
-            o.x = (((bits >> 0) & 15u) * 0x204081u) & 0x01010101u;
-            o.y = (((bits >> 4) & 15u) * 0x204081u) & 0x01010101u;
-            o.z = (((bits >> 8) & 15u) * 0x204081u) & 0x01010101u;
-            o.w = (((bits >> 12) & 15u) * 0x204081u) & 0x01010101u;
-            if (one != 1u) {
-                o.x *= one;
-                o.y *= one;
-                o.z *= one;
-                o.w *= one;
-            }
-            store16<NT>(g + u * 1024 + lane * 16, o);
-        }
-        return;
-    }
-    // the clipped first / last chunk of the tensor, a result that is not 16-byte aligned: byte by byte, eight independent ids at a time
-    for (int32_t o0 = lane; o0 < len; o0 += 64 * 8) {
-        uint32_t idv[8], cv[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int32_t o = o0 + 64 * m;
-            const uint32_t a = static_cast<uint32_t>(o + skip);
-            const uint32_t i = fast_div(a, p.rb_magic, p.rb_shift, p.rb_pow2);
-            cv[m] = a - i * static_cast<uint32_t>(rb);
-            idv[m] = o < len ? id_of(i) : kNo;
-        }
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-            if (o0 + 64 * m < len) g[o0 + 64 * m] = idv[m] == cv[m] ? static_cast<uint8_t>(one) : uint8_t(0);
-    }
+#include "bsq_expand_rows1_text.h"
 }
-// (Twin: expand_rows1_body above, for k_expand_rows1_multi; the one-batch kernel keeps its own text as k_expand_chunks does.  A change here
-//  belongs in both.)
 template <bool NT, int NR, bool NIB = false>
 __global__ __launch_bounds__(kThreads) void k_expand_rows1(const EParams p) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int64_t slot = static_cast<int64_t>(blockIdx.x >> 3) * 4 + wave_s;
-    const int64_t k = static_cast<int64_t>(blockIdx.x & 7u) + 8 * slot;
-    if (k >= p.nchunks) return;
-    const int32_t rb = p.C;  // bytes per row (one-byte elements)
-    const ChunkCoord cc = chunk_coord<0>(p, k, rb);
-    if (!cc.live) return;
-    const int32_t len = cc.len, skip = cc.skip;
-    const int32_t nr_s = __builtin_amdgcn_readfirstlane(cc.nr);
-    // NIB: the byte that holds the chunk's first id, and that id's half (Bp is even: the parity of t_lo * Bp + b_lo is b_lo's)
-    const uint8_t *tok = NIB ? p.tok + ((cc.t_lo * p.Bp + cc.b_lo) >> 1) : p.tok + cc.t_lo * p.Bp + cc.b_lo;
-    const uint32_t par0 = NIB ? static_cast<uint32_t>(cc.b_lo & 1) : 0u;
-    constexpr uint32_t kNo = NIB ? 0xFu : kNone;  // "no one"
-    const int64_t wrap_at = p.B - cc.b_lo;  // rows i >= wrap_at belong to position t_lo + 1 (or later)
-    const bool wraps = p.Bp != p.B && wrap_at < nr_s;  // (wave-uniform) the chunk runs over the end of a position row of a PADDED id matrix
-    uint8_t *g = p.out + cc.lo + cc.t_lo * p.row_gap;
-    const uint32_t one = static_cast<uint32_t>(p.one_bits) & 0xFFu;
-    // the id of row i of the chunk (rows behind wrap_at lie in later position rows of the matrix, Bp - B ids further each)
-    auto id_of = [&](uint32_t i) -> uint32_t {
-        int64_t at = i;
-        if (static_cast<int64_t>(i) >= wrap_at) at += ((static_cast<int64_t>(i) - wrap_at) / p.B + 1) * (p.Bp - p.B);
-        if constexpr (NIB) {
-            at += par0;
-            return (static_cast<uint32_t>(tok[at >> 1]) >> ((static_cast<uint32_t>(at) & 1u) << 2)) & 0xFu;
-        } else {
-            return static_cast<uint32_t>(tok[at]);
-        }
-    };
-    constexpr int IDB = NIB ? 4 : 8;  // bits per id in a lane's window
-    if (len == kChunk && (reinterpret_cast<uintptr_t>(g) & 15) == 0 && nr_s >= 8) {
-        uint64_t ids[4];
-        uint32_t ph[4];
-        if (!wraps && NIB) {
-            typedef uint32_t u32u __attribute__((aligned(1)));
-            uint32_t w[4], sh[4];
-            const uint32_t lb = (par0 + static_cast<uint32_t>(nr_s) - 1u) >> 1;  // the last byte of ids this chunk owns (>= 3: nr_s >= 8)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together: NR <= 6 nibbles + a parity fit four bytes
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-                const uint32_t n0 = q + par0, bo = n0 >> 1;
-                const uint32_t off = bo + 3u <= lb ? bo : lb - 3u;  // pulled back to END at the chunk's last id byte (rows < nr_s lie in bo ... lb)
-                sh[u] = (bo - off) * 8u + ((n0 & 1u) << 2);
-                w[u] = *reinterpret_cast<const u32u *>(tok + off);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ids[u] = w[u] >> sh[u];
-        } else if (!wraps) {
-            typedef uint32_t u32x2u __attribute__((ext_vector_type(2), aligned(1)));
-            u32x2u w[4];
-            uint32_t sh[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {  // the four id windows of the lane in flight together
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-                // the last lanes' windows are pulled back to END at the chunk's last row: never a byte beyond the ids this chunk owns
-                const uint32_t off = q + 8u <= static_cast<uint32_t>(nr_s) ? q : static_cast<uint32_t>(nr_s) - 8u;
-                sh[u] = (q - off) * 8u;
-                w[u] = *reinterpret_cast<const u32x2u *>(tok + off);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ids[u] = ((static_cast<uint64_t>(w[u].y) << 32) | w[u].x) >> sh[u];
-        } else {  // one chunk per position row: the NR ids of a window one by one, across the padding (all 4 NR byte loads in flight together)
-            uint32_t b[4][NR];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t o = static_cast<uint32_t>(skip) + static_cast<uint32_t>(u * 1024 + lane * 16);
-                const uint32_t q = fast_div(o, p.rb_magic, p.rb_shift, p.rb_pow2);
-                ph[u] = o - q * static_cast<uint32_t>(rb);
-#pragma unroll
-                for (int j = 0; j < NR; ++j) b[u][j] = q + j < static_cast<uint32_t>(nr_s) ? id_of(q + j) : kNo;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ids[u] = 0;
-#pragma unroll
-                for (int j = 0; j < NR; ++j) ids[u] |= static_cast<uint64_t>(b[u][j]) << (IDB * j);
-            }
-        }
-        const uint32_t cmask = (1u << rb) - 1u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            uint32_t bits = 0;
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                const uint32_t id = static_cast<uint32_t>(ids[u] >> (IDB * j)) & (NIB ? 0xFu : 0xFFu);
-                const uint32_t m = (1u << (id & 31u)) & cmask;  // id 255 (no one) -> bit 31 -> 0; nibble 15 -> bit 15 -> 0 (rows of <= 15 bytes)
-                const int32_t at = j * rb;                      // wave-uniform; strings that start at bit >= 32 lie beyond the lane's bits
-                if (at < 32) bits |= m << at;
-            }
-            bits >>= ph[u];
-            uint4 o;
-            o.x = (((bits >> 0) & 15u) * 0x204081u) & 0x01010101u;
-            o.y = (((bits >> 4) & 15u) * 0x204081u) & 0x01010101u;
-            o.z = (((bits >> 8) & 15u) * 0x204081u) & 0x01010101u;
-            o.w = (((bits >> 12) & 15u) * 0x204081u) & 0x01010101u;
-            if (one != 1u) {
-                o.x *= one;
-                o.y *= one;
-                o.z *= one;
-                o.w *= one;
-            }
-            store16<NT>(g + u * 1024 + lane * 16, o);
-        }
-        return;
-    }
-    // the clipped first / last chunk of the tensor, a result that is not 16-byte aligned: byte by byte, eight independent ids at a time
-    for (int32_t o0 = lane; o0 < len; o0 += 64 * 8) {
-        uint32_t idv[8], cv[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int32_t o = o0 + 64 * m;
-            const uint32_t a = static_cast<uint32_t>(o + skip);
-            const uint32_t i = fast_div(a, p.rb_magic, p.rb_shift, p.rb_pow2);
-            cv[m] = a - i * static_cast<uint32_t>(rb);
-            idv[m] = o < len ? id_of(i) : kNo;
-        }
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-            if (o0 + 64 * m < len) g[o0 + 64 * m] = idv[m] == cv[m] ? static_cast<uint8_t>(one) : uint8_t(0);
-    }
+    const uint32_t blk = blockIdx.x;
+#include "bsq_expand_rows1_text.h"
 }
 
 // The two expansions of several one-piece two-pass batches in one launch each (bsq_onehot_device_multi, family 2; see k_onehot_chunks_multi
@@ -846,209 +445,29 @@ struct CFields {  // (what is per batch in k_onehot_chunks_multi: everything but
     double inv_rowbytes, inv_B;  // reciprocals for div_by()
     uint32_t rb_magic, rb_shift, rb_pow2;  // fast_div() constants of rowbytes
 };
+// The one-batch block: the alphabet table, then the fields (p.lut, p.chars: chunk_owner_fields fills a CParams or a CFields).
+struct CLut {
+    int8_t lut[256];
+};
+struct CParams : CLut, CFields {};
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // two bases with members: not standard-layout, which is why the layout is asserted
+static_assert(sizeof(CParams) == 256 + sizeof(CFields) && offsetof(CParams, chars) == 256, "the fields follow the table without a gap");
+#pragma clang diagnostic pop
 
-// The kernel's body for block `blk` of one batch's grid (k_onehot_chunks: blockIdx.x; k_onehot_chunks_multi: the block inside the batch's range).
+// The kernel's text (bsq_onehot_chunks_text.h) for block `blk` of one batch's grid: here for k_onehot_chunks_multi (the block inside the batch's
+// range), below for the one-batch kernel (blockIdx.x).  Included at both places, not called from the kernel: as a call the one-batch kernel
+// compiled to different code, and 8192 x 1024 AMINO20 f32 ran 1 % slower.
 // Fewer resident workgroups stream faster (see launch_chunks): the launch caps the occupancy at 4 per CU.
 template <typename ST, bool NT>
 __device__ __forceinline__ void onehot_chunks_body(const uint32_t blk, const int8_t *plut, const CFields &p) {
-    __shared__ __align__(16) uint8_t s_img[4][kChunk];
-    __shared__ __align__(16) uint8_t s_lut4[4][256];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint8_t *img = s_img[wave];
-    uint8_t *lut = s_lut4[wave];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-    {   // wave-private copy of the alphabet table (unmapped / >= 0x80 -> kNone): no workgroup barrier needed
-        uint32_t w = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = lane * 4 + q;
-            const int8_t v = plut[idx];
-            const uint32_t e = (idx < 128 && v >= 0) ? static_cast<uint32_t>(v) : kNone;
-            w |= e << (8 * q);
-        }
-        reinterpret_cast<uint32_t *>(lut)[lane] = w;
-    }
-    const int32_t cls = static_cast<int32_t>(blk & 7u);
-    const int64_t group = static_cast<int64_t>(blk >> 3);
-    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
-    const ST one = static_cast<ST>(p.one_bits);
-    int64_t j = (group * 4 + wave) * p.cpw;
-    for (int32_t it = 0; it < p.cpw; ++it, ++j) {
-        const int64_t k = cls + 8 * j;
-        if (k >= p.nchunks) break;  // wave-uniform
-        int64_t lo = k * kChunk - p.head, hi = lo + kChunk;
-        if (lo < 0) lo = 0;
-        if (hi > p.total) hi = p.total;
-        const int32_t len = static_cast<int32_t>(hi - lo);
-        int64_t skip64, b_lo;
-        const int64_t r_lo = div_by(lo, rowbytes, p.inv_rowbytes, &skip64);
-        const int32_t skip = static_cast<int32_t>(skip64);
-        const int32_t nr = static_cast<int32_t>(fast_div(static_cast<uint32_t>(skip + len + rowbytes - 1), p.rb_magic,
-                                                         p.rb_shift, p.rb_pow2));
-        const int64_t t_lo = div_by(r_lo, p.B, p.inv_B, &b_lo);
-        for (int32_t i0 = 0; i0 < nr; i0 += 64) {
-            const int32_t i = i0 + lane;
-            if (i < nr) {
-                int64_t b = b_lo + i, t = t_lo;
-                if (b >= p.B) {  // the chunk runs over the end of position t's rows
-                    const int64_t q = b / p.B;
-                    t += q;
-                    b -= q * p.B;
-                }
-                uint32_t tk;
-                const int64_t start = p.offsets[b];
-                int64_t L = p.offsets[b + 1] - start;
-                L = L > p.room ? p.room : L;
-                const int64_t jj = t - p.bos;
-                if (jj < 0) {
-                    tk = p.bos_id;
-                } else if (jj < L) {
-                    tk = lut[p.chars[start + jj]];
-                    if (p.mask && p.mask[start + jj] == 0) tk = kNone;
-                } else {
-                    tk = (jj == L) ? p.at_len_id : p.fill_id;
-                }
-                const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk) * static_cast<int32_t>(sizeof(ST));
-                if (tk != kNone && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint8_t *g = p.out + lo;
-        if (len == kChunk) {
-            const uint4 v0 = *reinterpret_cast<const uint4 *>(img + lane * 16);
-            const uint4 v1 = *reinterpret_cast<const uint4 *>(img + 1024 + lane * 16);
-            const uint4 v2 = *reinterpret_cast<const uint4 *>(img + 2048 + lane * 16);
-            const uint4 v3 = *reinterpret_cast<const uint4 *>(img + 3072 + lane * 16);
-            store16<NT>(g + lane * 16, v0);
-            store16<NT>(g + 1024 + lane * 16, v1);
-            store16<NT>(g + 2048 + lane * 16, v2);
-            store16<NT>(g + 3072 + lane * 16, v3);
-        } else {
-            for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
-                *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
-        }
-        if (it + 1 < p.cpw) {  // image is reused: wipe it (wave-private, in-order LDS)
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-        }
-    }
+#include "bsq_onehot_chunks_text.h"
 }
-
-// (Twin: onehot_chunks_body above, for k_onehot_chunks_multi.  A change here belongs in both.)
-// The one-batch form keeps its own parameter block and text (as k_expand_chunks does: moved into onehot_chunks_body it compiled to
-// different code, 8192 x 1024 AMINO20 f32 ran 1 % slower).
-struct CParams {
-    int8_t lut[256];
-    const uint8_t *chars;
-    const int64_t *offsets;
-    const uint8_t *mask;
-    uint8_t *out;
-    int64_t total;    // output bytes
-    int64_t nchunks;
-    int64_t B, P;
-    int32_t head;     // out & 4095
-    int32_t C;
-    int32_t bos;
-    uint32_t bos_id, at_len_id, fill_id;
-    int32_t room;     // P - bos - eos (length clamp)
-    int32_t cpw;
-    uint64_t one_bits;
-    double inv_rowbytes, inv_B;  // reciprocals for div_by()
-    uint32_t rb_magic, rb_shift, rb_pow2;  // fast_div() constants of rowbytes
-};
-
-// Fewer resident workgroups stream faster (see launch_chunks): the launch caps the occupancy at 4 per CU.
 template <typename ST, bool NT>
 __global__ __launch_bounds__(kThreads) void k_onehot_chunks(const CParams p) {
-    __shared__ __align__(16) uint8_t s_img[4][kChunk];
-    __shared__ __align__(16) uint8_t s_lut4[4][256];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint8_t *img = s_img[wave];
-    uint8_t *lut = s_lut4[wave];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-    {   // wave-private copy of the alphabet table (unmapped / >= 0x80 -> kNone): no workgroup barrier needed
-        uint32_t w = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = lane * 4 + q;
-            const int8_t v = p.lut[idx];
-            const uint32_t e = (idx < 128 && v >= 0) ? static_cast<uint32_t>(v) : kNone;
-            w |= e << (8 * q);
-        }
-        reinterpret_cast<uint32_t *>(lut)[lane] = w;
-    }
-    const int32_t cls = static_cast<int32_t>(blockIdx.x & 7u);
-    const int64_t group = static_cast<int64_t>(blockIdx.x >> 3);
-    const int32_t rowbytes = p.C * static_cast<int32_t>(sizeof(ST));
-    const ST one = static_cast<ST>(p.one_bits);
-    int64_t j = (group * 4 + wave) * p.cpw;
-    for (int32_t it = 0; it < p.cpw; ++it, ++j) {
-        const int64_t k = cls + 8 * j;
-        if (k >= p.nchunks) break;  // wave-uniform
-        int64_t lo = k * kChunk - p.head, hi = lo + kChunk;
-        if (lo < 0) lo = 0;
-        if (hi > p.total) hi = p.total;
-        const int32_t len = static_cast<int32_t>(hi - lo);
-        int64_t skip64, b_lo;
-        const int64_t r_lo = div_by(lo, rowbytes, p.inv_rowbytes, &skip64);
-        const int32_t skip = static_cast<int32_t>(skip64);
-        const int32_t nr = static_cast<int32_t>(fast_div(static_cast<uint32_t>(skip + len + rowbytes - 1), p.rb_magic,
-                                                         p.rb_shift, p.rb_pow2));
-        const int64_t t_lo = div_by(r_lo, p.B, p.inv_B, &b_lo);
-        for (int32_t i0 = 0; i0 < nr; i0 += 64) {
-            const int32_t i = i0 + lane;
-            if (i < nr) {
-                int64_t b = b_lo + i, t = t_lo;
-                if (b >= p.B) {  // the chunk runs over the end of position t's rows
-                    const int64_t q = b / p.B;
-                    t += q;
-                    b -= q * p.B;
-                }
-                uint32_t tk;
-                const int64_t start = p.offsets[b];
-                int64_t L = p.offsets[b + 1] - start;
-                L = L > p.room ? p.room : L;
-                const int64_t jj = t - p.bos;
-                if (jj < 0) {
-                    tk = p.bos_id;
-                } else if (jj < L) {
-                    tk = lut[p.chars[start + jj]];
-                    if (p.mask && p.mask[start + jj] == 0) tk = kNone;
-                } else {
-                    tk = (jj == L) ? p.at_len_id : p.fill_id;
-                }
-                const int32_t pos = i * rowbytes - skip + static_cast<int32_t>(tk) * static_cast<int32_t>(sizeof(ST));
-                if (tk != kNone && pos >= 0 && pos < len) *reinterpret_cast<ST *>(img + pos) = one;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint8_t *g = p.out + lo;
-        if (len == kChunk) {
-            const uint4 v0 = *reinterpret_cast<const uint4 *>(img + lane * 16);
-            const uint4 v1 = *reinterpret_cast<const uint4 *>(img + 1024 + lane * 16);
-            const uint4 v2 = *reinterpret_cast<const uint4 *>(img + 2048 + lane * 16);
-            const uint4 v3 = *reinterpret_cast<const uint4 *>(img + 3072 + lane * 16);
-            store16<NT>(g + lane * 16, v0);
-            store16<NT>(g + 1024 + lane * 16, v1);
-            store16<NT>(g + 2048 + lane * 16, v2);
-            store16<NT>(g + 3072 + lane * 16, v3);
-        } else {
-            for (int32_t o = lane * static_cast<int32_t>(sizeof(ST)); o < len; o += 64 * static_cast<int32_t>(sizeof(ST)))
-                *reinterpret_cast<ST *>(g + o) = *reinterpret_cast<const ST *>(img + o);
-        }
-        if (it + 1 < p.cpw) {  // image is reused: wipe it (wave-private, in-order LDS)
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4 *>(img + u * 1024 + lane * 16) = uint4{0, 0, 0, 0};
-        }
-    }
+    const uint32_t blk = blockIdx.x;
+    const int8_t *plut = p.lut;
+#include "bsq_onehot_chunks_text.h"
 }
 
 struct CMulti {
