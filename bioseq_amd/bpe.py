@@ -14,7 +14,11 @@ pre-tokenisation, no dropout, no fuse_unk.  include/bsq.h ("BPE ids of a packed 
 * `bpe_mlm_tokenize_packed`  (inputs, labels, lengths): masked-LM batches over those ids, drawn on the device in the same launch;
 * `bpe_mlm_tokenize_host`  its CPU twin;
 * `bpe_kernel_name`, `bpe_mlm_kernel_name`  the kernel a call takes;
-* `bpe_train_host`        a plain deterministic trainer for samples of a few MB (not a corpus-scale trainer).
+* `bpe_train_packed`      learns the merges from a packed store resident on the device (`bsq_bpe_train_*_device`: two launches per
+                          merge, the corpus read once per merge), or from numpy arrays through the library's CPU twin;
+* `bpe_train_kernel_name` the pass kernel such a call takes;
+* `bpe_train_host`        the same rule as plain numpy, a sort of the whole sample per merge: the independent statement the trainer is
+                          held against, for samples of a few MB (`bpe_train_packed` is the corpus-scale trainer).
 
 Rows longer than `max_chars` (at most 8192) get length -1 and an empty token row: crop first with `views.crop_packed`.
 """
@@ -345,6 +349,131 @@ def bpe_mlm_tokenize_packed(vocab, chars, offsets, padlen, destchar="q", batch_f
     return inputs, labels, lengths
 
 
+def _train_cfg(max_chars, form, n_merges, table_slots):
+    """bsq_bpe_train with the library's argument rules applied as ValueError."""
+    form = 0 if form is None else int(form)
+    table_slots = 0 if table_slots is None else int(table_slots)
+    max_chars, n_merges = int(max_chars), int(n_merges)
+    if not 1 <= max_chars <= MAX_CHARS:
+        raise ValueError("max_chars must lie in 1 .. %d, got %r" % (MAX_CHARS, max_chars))
+    if form not in (0, 1, 2) or (form == 1 and max_chars > WAVE_MAX_CHARS):
+        raise ValueError("form must be None, 1 (a wave per row: max_chars <= %d) or 2 (a workgroup per row), got %r at max_chars %d"
+                         % (WAVE_MAX_CHARS, form, max_chars))
+    if not 0 <= n_merges < 2 ** 31:
+        raise ValueError("n_merges must lie in 0 .. 2 ** 31 - 1, got %r" % n_merges)
+    if table_slots != 0 and (table_slots < 16 or table_slots > 2 ** 28 or table_slots & (table_slots - 1)):
+        raise ValueError("table_slots must be None or a power of two in 16 .. 2 ** 28, got %r" % table_slots)
+    return capi.BpeTrain(max_chars, form, n_merges, 0, table_slots)
+
+
+def _train_bound(longest, max_chars, form):
+    """The bound of a call whose longest row was read: the wave form's where it holds every row, else 8192; a longer row is refused."""
+    if max_chars is not None:
+        return max_chars
+    if longest > MAX_CHARS:
+        raise ValueError("a row of %d characters: bpe_train_packed takes rows of at most %d; crop first with views.crop_packed or "
+                         "FlatFile.windows_device, or pass max_chars to leave longer rows out" % (longest, MAX_CHARS))
+    return WAVE_MAX_CHARS if longest <= WAVE_MAX_CHARS and form != 2 else MAX_CHARS
+
+
+def bpe_train_kernel_name(max_chars=None, form=None):
+    """The pass kernel `bpe_train_packed` takes for this bound (host only: profiling labels, tests); None is 8192."""
+    max_chars = MAX_CHARS if max_chars is None else int(max_chars)
+    name = _lib.bsq_bpe_train_kernel_name(ctypes.byref(capi.BpeTrain(max_chars, 0 if form is None else int(form), 0, 0, 0))).decode()
+    if not name:
+        raise ValueError("max_chars must lie in 1 .. %d and form be None, 1 (max_chars <= %d) or 2" % (MAX_CHARS, WAVE_MAX_CHARS))
+    return name
+
+
+def _decode_records(best):
+    """(merges (M, 2) int64, counts (M,) int64) of a run's records (uint64): those in front of the first count below 2."""
+    best = np.asarray(best, dtype=np.uint64)
+    counts = (best >> np.uint64(32)).astype(np.int64)
+    stop = np.flatnonzero(counts < 2)
+    M = int(stop[0]) if stop.size else int(best.size)
+    key = (np.uint64(0xFFFFFFFF) - (best[:M] & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    return np.stack([key >> 16, key & 0xFFFF], axis=1).reshape(-1, 2), counts[:M]
+
+
+def bpe_train_packed(tok, chars, offsets, n_merges, *, max_chars=None, form=None, table_slots=None, steps_per_call=256, return_info=False):
+    """Learns a `BPEVocab` of at most `n_merges` merges from a packed store (chars uint8[total], offsets int64[B + 1]) by the rule of
+    `bpe_train_host` (include/bsq.h, "BPE training"): a row is a word, an unmapped byte a barrier; every step takes the most frequent
+    adjacent pair, counted without overlap, ties to the smallest (l, r), and stops when the best count is below 2.
+
+    Device tensors train on the device, on torch's current stream: `steps_per_call` steps (two launches each) are enqueued, then the
+    last record is read back (8 bytes) to see whether the stop was reached, until n_merges merges are made; the merges do not depend on
+    steps_per_call.  numpy arrays go through the library's CPU twin (`bsq_bpe_train_host`).  chars and offsets are never modified.
+
+    max_chars: None reads the longest row back (8 bytes, one synchronisation); a row above 8192 is a ValueError.  A number (1 .. 8192)
+    reads nothing back: longer rows take no part and are counted in `skipped_rows`.  At most 1024 takes the wave form; form: None = the
+    library chooses, 1 = a wave per row, 2 = a workgroup per row; the merges never depend on it.  table_slots: None sizes the pair table
+    for the last step (a power of two, at most 2 ** 28 slots of 8 bytes); a number overrides it, and a table that overflowed is a
+    RuntimeError after the read-back, never a wrong vocabulary.  More than 2 ** 31 - 1 characters is a ValueError.
+
+    return_info=True: (vocab, info) with info = {"counts": int64 winning count of each merge, "skipped_rows", "steps_launched",
+    "table_slots", "kernel"}."""
+    desc = capi.desc_of(tok)
+    steps_per_call = int(steps_per_call)
+    if steps_per_call < 1:
+        raise ValueError("steps_per_call must be at least 1")
+    if isinstance(chars, np.ndarray) and isinstance(offsets, np.ndarray):
+        hchars, hoffs = capi.host_batch(chars, offsets)
+        B = hoffs.size - 1
+        total = int(chars.size)
+        if total > 2 ** 31 - 1:
+            raise ValueError("bpe_train_packed takes at most 2 ** 31 - 1 characters, got %d" % total)
+        longest = int((hoffs[1:] - hoffs[:-1]).max()) if B > 0 and max_chars is None else 0
+        cfg = _train_cfg(_train_bound(longest, max_chars, form), form, n_merges, table_slots)
+        room = min(cfg.n_merges, 65536 - 4 - desc.nchars)
+        merges, counts = np.zeros((room, 2), np.int32), np.zeros(room, np.int64)
+        made, skipped = ctypes.c_int64(0), ctypes.c_int64(0)
+        if B > 0:
+            capi.check(_lib.bsq_bpe_train_host(ctypes.byref(desc), hchars.ctypes.data, hoffs.ctypes.data, B, total, ctypes.byref(cfg),
+                                               merges.ctypes.data, counts.ctypes.data, ctypes.byref(made), ctypes.byref(skipped)))
+        vocab = BPEVocab(tok, merges[:made.value].astype(np.int64))
+        info = {"counts": counts[:made.value].copy(), "skipped_rows": int(skipped.value), "steps_launched": 0,
+                "table_slots": int(_lib.bsq_bpe_train_table_slots(ctypes.byref(desc), B, total, ctypes.byref(cfg))),
+                "kernel": "bsq_bpe_train_host"}
+        return (vocab, info) if return_info else vocab
+    import torch
+    B = capi.packed_on_device(chars, offsets, "bpe_train_packed works on a packed store resident on the device (chars, offsets tensors), or on numpy arrays")
+    total = int(chars.numel())
+    if total > 2 ** 31 - 1:
+        raise ValueError("bpe_train_packed takes at most 2 ** 31 - 1 characters, got %d" % total)
+    longest = int((offsets[1:] - offsets[:-1]).max().item()) if B > 0 and max_chars is None else 0
+    cfg = _train_cfg(_train_bound(longest, max_chars, form), form, n_merges, table_slots)
+    room = min(cfg.n_merges, 65536 - 4 - desc.nchars)
+    slots = int(_lib.bsq_bpe_train_table_slots(ctypes.byref(desc), B, total, ctypes.byref(cfg)))
+    info = {"counts": np.zeros(0, np.int64), "skipped_rows": 0, "steps_launched": 0, "table_slots": slots,
+            "kernel": _lib.bsq_bpe_train_kernel_name(ctypes.byref(cfg)).decode()}
+    merges = np.zeros((0, 2), np.int64)
+    if B > 0:
+        nbytes = int(_lib.bsq_bpe_train_workspace_bytes(ctypes.byref(desc), B, total, ctypes.byref(cfg)))
+        if nbytes < 0:
+            raise ValueError("bpe_train_packed: " + _lib.bsq_last_error().decode())
+        src = capi.readable_chars(chars, offsets.device)  # (every row may be empty)
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=src.device)
+        done = 0
+        with capi.launching(src.device) as stream:
+            capi.check(_lib.bsq_bpe_train_begin_device(ctypes.byref(desc), src.data_ptr(), offsets.data_ptr(), B, total, ctypes.byref(cfg),
+                                                       work.data_ptr(), stream))
+            while done < room:
+                step = min(steps_per_call, room - done)
+                capi.check(_lib.bsq_bpe_train_steps_device(ctypes.byref(desc), offsets.data_ptr(), B, total, ctypes.byref(cfg), work.data_ptr(),
+                                                           done, step, stream))
+                done += step
+                if done < room and (int(work[2 + done - 1].item()) >> 32) & 0xFFFFFFFF < 2:  # (the last record: 8 bytes)
+                    break
+        head = work[:2 + room].cpu().numpy()
+        info["steps_launched"], info["skipped_rows"] = done, int(head[0])
+        if head[1] != 0:
+            raise RuntimeError("bpe_train_packed: the pair table of %d slots overflowed and pairs were dropped; pass a larger table_slots "
+                               "(None sizes it for the last step)" % slots)
+        merges, info["counts"] = _decode_records(head[2:2 + done].view(np.uint64))
+    vocab = BPEVocab(tok, merges)
+    return (vocab, info) if return_info else vocab
+
+
 def _taken(a, key, best):
     """The positions of `a` where the pair `best` is replaced, left to right without overlap: in a run of consecutive occurrences (they
     exist only when l == r) those at even distance from the run's start."""
@@ -404,4 +533,4 @@ def bpe_train_host(tok, chars, offsets, n_merges):
 
 
 __all__ = ["BPEVocab", "bpe_tokenize_packed", "bpe_tokenize_host", "bpe_vocab_size", "bpe_special_ids", "bpe_strings", "bpe_decode",
-           "bpe_external_ids", "bpe_kernel_name", "bpe_train_host", "bpe_mlm_tokenize_packed", "bpe_mlm_tokenize_host", "bpe_mlm_kernel_name", "TOO_LONG", "MAX_CHARS", "WAVE_MAX_CHARS"]
+           "bpe_external_ids", "bpe_kernel_name", "bpe_train_host", "bpe_train_packed", "bpe_train_kernel_name", "bpe_mlm_tokenize_packed", "bpe_mlm_tokenize_host", "bpe_mlm_kernel_name", "TOO_LONG", "MAX_CHARS", "WAVE_MAX_CHARS"]

@@ -95,6 +95,12 @@ class Bpe(ctypes.Structure):
     _fields_ = [("max_chars", ctypes.c_int32), ("form", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class BpeTrain(ctypes.Structure):
+    """struct bsq_bpe_train"""
+    _fields_ = [("max_chars", ctypes.c_int32), ("form", ctypes.c_int32), ("n_merges", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("table_slots", ctypes.c_int64)]
+
+
 class BpeMlm(ctypes.Structure):
     """struct bsq_bpe_mlm"""
     _fields_ = [("frac", ctypes.c_double), ("mask_prob", ctypes.c_double), ("random_prob", ctypes.c_double), ("mask_token", ctypes.c_int64),
@@ -275,6 +281,13 @@ def load():
         "bsq_bpe_mlm_tokenize_device": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), ctypes.POINTER(BpeMlm), c_int, vp, c_int, vp, vp, vp]),
         "bsq_bpe_mlm_tokenize_host": (i32, [dp, vp, vp, i64, i64, i32, vp, i64, ctypes.POINTER(Bpe), ctypes.POINTER(BpeMlm), c_int, vp, c_int, vp, vp]),
         "bsq_bpe_mlm_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(Bpe)]),
+        "bsq_bpe_train_workspace_bytes": (i64, [dp, i64, i64, ctypes.POINTER(BpeTrain)]),
+        "bsq_bpe_train_table_slots": (i64, [dp, i64, i64, ctypes.POINTER(BpeTrain)]),
+        "bsq_bpe_train_lds_slots": (i32, []),
+        "bsq_bpe_train_begin_device": (i32, [dp, vp, vp, i64, i64, ctypes.POINTER(BpeTrain), vp, vp]),
+        "bsq_bpe_train_steps_device": (i32, [dp, vp, i64, i64, ctypes.POINTER(BpeTrain), vp, i32, i32, vp]),
+        "bsq_bpe_train_host": (i32, [dp, vp, vp, i64, i64, ctypes.POINTER(BpeTrain), vp, vp, i64p, i64p]),
+        "bsq_bpe_train_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(BpeTrain)]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

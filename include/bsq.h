@@ -53,7 +53,9 @@ extern "C" {
                            * bsq_bpe_tokenize_host, bsq_bpe_kernel_name, bsq_bpe_mlm, bsq_bpe_mlm_tokenize_device, bsq_bpe_mlm_tokenize_host,
                            * bsq_bpe_mlm_kernel_name, bsq_greedy_scratch_bytes, bsq_greedy_pairs_device, bsq_greedy_pairs_host,
                            * bsq_greedy_kernel_name, bsq_lsh, bsq_lsh_keys_device, bsq_lsh_keys_host, bsq_lsh_count_device, bsq_lsh_emit_device,
-                           * bsq_sketch_compare_list_device, bsq_sketch_compare_list_host, bsq_lsh_pairs_host, bsq_lsh_kernel_name;
+                           * bsq_sketch_compare_list_device, bsq_sketch_compare_list_host, bsq_lsh_pairs_host, bsq_lsh_kernel_name,
+                           * bsq_bpe_train, bsq_bpe_train_workspace_bytes, bsq_bpe_train_table_slots, bsq_bpe_train_lds_slots,
+                           * bsq_bpe_train_begin_device, bsq_bpe_train_steps_device, bsq_bpe_train_host, bsq_bpe_train_kernel_name;
                            * nothing removed */
 
 typedef int32_t bsq_status;
@@ -1455,6 +1457,91 @@ bsq_status bsq_bpe_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, co
                                      void *inputs_or_null, bsq_dtype label_dtype, void *labels_or_null, int32_t *lengths);
 /* Host only: the kernel the device call takes ("k_bpe_mlm_wave", "k_bpe_mlm_block"); "" for a bsq_bpe the calls refuse. */
 const char *bsq_bpe_mlm_kernel_name(const bsq_bpe *bpe);
+
+/* ---- BPE training: the merges of bsq_bpe learned from a packed store that is resident on the device, so that a corpus gets the
+ * vocabulary of its own species mix without leaving the GPU.  The result is an ordered merge list for bsq_bpe_table_build.
+ *
+ * THE RULE (that of bioseq_amd.bpe.bpe_train_host, the numpy statement the kernels and the CPU twin are held against).
+ *     rows, classes  A row is a word.  Its symbols are the tokenizer's classes 0 .. C - 1; every unmapped byte (lut < 0) is a barrier,
+ *                    like a row's end: no pair spans a barrier and a barrier is never merged.  bos / eos / padchar play no part.
+ *     a step         Count every adjacent pair (l, r) over all rows WITHOUT OVERLAP: in a maximal run of consecutive positions with
+ *                    l == r only the positions at even distance from the run's start count (AAA holds (A, A) once, a run of n equal
+ *                    symbols holds n / 2 of them, rounded down).  Take the pair with the largest count, ties to the smallest (l, r).
+ *                    If that count is below 2, stop.  Otherwise record merge m and replace all its occurrences left to right without
+ *                    overlap by the id C + m -- the run-parity selection of bsq_bpe's step.
+ *     limit          at most min(n_merges, 65536 - 4 - C) merges.
+ *     rows above max_chars characters take no part and are counted in skipped_rows: the result is the training on the other rows.
+ * Known answers (DNA4, A C G T = 0 .. 3; "rows -> merges, winning counts"):
+ *     AAAAAAA                  -> (0,0); 3 -- then stop: the row is 4 4 4 0 and every pair counts once
+ *     ACGACGACG, CGCG          -> (1,2) (0,4); 5, 3
+ *     ACAC, GTGT               -> (0,1) (2,3); 2, 2 -- the tie goes to the smaller pair
+ *     ACACAC, ACACAC           -> (0,1) (4,4) (5,4); 6, 2, 2 -- a run of new symbols: 4 4 4 holds (4,4) once per row
+ *     AAAAANAAAA               -> (0,0) (4,4); 4, 2 -- N is a barrier
+ *     ACGTNACGT                -> (0,1) (2,3) (4,5); 2, 2, 2
+ *     AC, AC                   -> (0,1); 2
+ *     one row of 8192 A        -> (0,0) (4,4) (5,5) ... (14,14), 12 merges; 4096, 2048, ..., 2
+ *
+ * The workspace.  The library allocates nothing on the device: the caller owns bsq_bpe_train_workspace_bytes(d, B, total_chars, t)
+ * bytes, 8-byte aligned, and hands the same d, offsets, B, total_chars and t to every call of a run.  total_chars is the size of the
+ * character buffer (>= offsets[B], at most 2^31 - 1); a row that does not lie inside it counts as empty.  chars and offsets are only
+ * read.  Its head, the only part a caller reads back (16 + 8 n bytes, n = min(n_merges, 65536 - 4 - C)):
+ *     bytes 0 .. 7    int64   skipped_rows
+ *     bytes 8 .. 15   uint64  overflow: non-zero when a pair found no slot in the pair table and was dropped -- the merges are then
+ *                             NOT the rule's and must be thrown away (a larger table_slots, or 0 for the default, avoids it)
+ *     bytes 16 ..     uint64  best[n], the record of step m: (count << 32) | (0xFFFFFFFF - ((l << 16) | r)), 0 when nothing counted.
+ *                             The merges are the decoded records up to the first whose count is below 2 (all later records are 0).
+ * Behind it: an int32 live length per row, the store's symbols as 16-bit ids in the rows' own layout (row i at offsets[i], compacted
+ * to the row's front; 0xFFFF is the barrier) and the pair table of table_slots 8-byte slots.
+ *     bsq_bpe_train_begin_device  fills the workspace: symbols from characters, row lengths, the zeroed head and table.
+ *     bsq_bpe_train_steps_device  enqueues the steps first_step .. first_step + n_steps - 1 (those below n) behind it.  The device cannot
+ *                                 stop by itself: a caller enqueues a batch of steps, reads best[] back and goes on while the last
+ *                                 record's count is at least 2.  Steps past the stop are cheap (both launches return at once) and
+ *                                 change nothing, so the merges do not depend on how the steps are cut into calls.
+ * Both are stream-ordered and never synchronise.  Refused with BSQ_ERR_INVALID_ARG, the workspace untouched and bsq_last_error() set: a
+ * null descriptor, bsq_bpe_train, offsets, chars or workspace (B > 0), a workspace that is not 8-byte aligned, max_chars outside
+ * 1 .. 8192, form outside 0 .. 2 or 1 with max_chars > 1024, reserved != 0, n_merges < 0, table_slots neither 0 nor a power of two in
+ * 16 .. 2^28, B or total_chars outside 0 .. 2^31 - 1, a negative first_step or n_steps.  B == 0 is BSQ_OK with nothing launched and
+ * yields zero merges.
+ *
+ * Kernels (csrc/bsq_bpe_train.hip; csrc/bsq_bpe_train_dev.h has what the CPU twin shares).  A step is two launches and reads the corpus
+ * once.  k_bpe_train_pass<wave> (a wave per row, max_chars <= 1024) / <block> (a 256-thread workgroup per row): a workgroup walks a
+ * contiguous range of rows (at least 32 / 4; a row is never split); per row it loads the live symbols into LDS, applies the previous
+ * step's pair (candidate mask sym[q] == l && sym[q + 1] == r, then steps 2a-2d of the tokenizer's merge loop: a second text of them,
+ * without the rank array), writes the row and its length back only if it changed, and counts the row's pairs -- every position whose
+ * two symbols are no barrier, except a position of the mask sym[q] == sym[q + 1] that select_taken does not take (the same run parity,
+ * the same carry across 64-position boundaries).  Counts go into a per-workgroup LDS hash (bsq_bpe_train_lds_slots() = 2048 slots, 8
+ * probes) that is flushed with one global atomic add per distinct pair; a pair that finds no LDS slot goes to the global table at once.
+ * The global pair table: open addressing, 8-byte slots, key + 1 in the low half claimed by compare-and-swap, the count in the high half
+ * by atomic add; the probe loop is bounded by the capacity and a probe that fails sets the overflow flag.  Step m uses a prefix of the
+ * allocation: the power of two >= 2 min((C + m)^2, total_chars), at least 1024, at most table_slots.  table_slots = 0 sizes the
+ * allocation for m = n_merges, at most 2^28 slots.  k_bpe_train_pick scans the step's prefix, CLEARS IT AS IT READS, and folds the
+ * records by maximum into best[m]: a workgroup reduction and one atomic max per workgroup.  Step m + 1's pass reads best[m]; if its
+ * count is below 2 the pass applies nothing and counts nothing, so best[m + 1] stays 0 and so do all later records: the stop needs no
+ * flag and no commit launch.  The only cross-workgroup traffic is agent-scope atomics, nobody waits for another workgroup, vector
+ * stores and plain C++ only. */
+typedef struct bsq_bpe_train {
+    int32_t max_chars;   /* 1 .. 8192: rows of more characters take no part and are counted in skipped_rows */
+    int32_t form;        /* 0: the library chooses (wave up to 1024, else block); 1: wave per row; 2: workgroup per row */
+    int32_t n_merges;    /* >= 0; the run makes at most min(n_merges, 65536 - 4 - C) */
+    int32_t reserved;    /* 0 */
+    int64_t table_slots; /* 0: sized for the last step (at most 2^28); else a power of two in 16 .. 2^28 */
+} bsq_bpe_train;         /* 24 bytes */
+/* Host only: the bytes of a run's workspace / the slots of its pair table, or a negative bsq_status for arguments the calls refuse. */
+int64_t bsq_bpe_train_workspace_bytes(const bsq_desc *d, int64_t B, int64_t total_chars, const bsq_bpe_train *t);
+int64_t bsq_bpe_train_table_slots(const bsq_desc *d, int64_t B, int64_t total_chars, const bsq_bpe_train *t);
+/* Host only: the slots of the pass kernels' per-workgroup LDS hash. */
+int32_t bsq_bpe_train_lds_slots(void);
+bsq_status bsq_bpe_train_begin_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t total_chars,
+                                      const bsq_bpe_train *t, void *workspace, void *hip_stream);
+bsq_status bsq_bpe_train_steps_device(const bsq_desc *d, const int64_t *offsets, int64_t B, int64_t total_chars, const bsq_bpe_train *t,
+                                      void *workspace, int32_t first_step, int32_t n_steps, void *hip_stream);
+/* CPU twin on host buffers (one thread, a sequential walk per merge; no device is needed; form and table_slots are checked and change
+ * nothing): merges (n x 2 int32) and counts (n int64) receive the *n_made merges and their winning counts. */
+bsq_status bsq_bpe_train_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t total_chars,
+                              const bsq_bpe_train *t, int32_t *merges, int64_t *counts, int64_t *n_made, int64_t *skipped_rows);
+/* Host only: the pass kernel a run takes ("k_bpe_train_pass<wave>", "k_bpe_train_pass<block>"); "" for a bsq_bpe_train the calls
+ * refuse. */
+const char *bsq_bpe_train_kernel_name(const bsq_bpe_train *t);
 
 /* ---- k-mer masked-LM: span-masked k-mer batches, the objective DNA language models over k-mer ids are pretrained with (DNABERT).
  * With overlapping windows a nucleotide sits in k consecutive tokens, so one masked token is spelled out by its neighbours: the
