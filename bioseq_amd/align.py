@@ -53,26 +53,21 @@ MAX_LEN = 4096
 _FORM_HOLDS = {1: 256, 2: 1024, 3: 4096}
 
 
-def _edit(tok, max_len, form):
-    """(desc, bsq_edit) with the library's argument rules applied as ValueError (no device is touched)."""
+def _edit(tok, max_len, form, holds=_FORM_HOLDS):
+    """(desc, bsq_edit) with the library's argument rules applied as ValueError (no device is touched).  holds: the longest shorter side
+    that each of the forms 1, 2, 3 holds in the family that asks (the statistics kernels hold half of what the others do)."""
     desc = capi.desc_of(tok)
     if not 1 <= desc.nchars <= 30:
         raise ValueError("the edit distance takes alphabets of 1 .. 30 classes, %r has %d" % (tok.key, desc.nchars))
-    if isinstance(max_len, bool) or int(max_len) != max_len or not 1 <= int(max_len) <= MAX_LEN:
-        raise ValueError("max_len must be an integer in 1 .. %d, got %r" % (MAX_LEN, max_len))
+    max_len = capi.int_arg("max_len", max_len, 1, holds[3])
     form = 0 if form is None else form
-    if isinstance(form, bool) or form not in (0, 1, 2, 3) or (form and _FORM_HOLDS[form] < int(max_len)):
-        raise ValueError("form must be None or 1, 2, 3 (shorter sides up to 256, 1024, 4096), got %r at max_len %d" % (form, int(max_len)))
-    e = capi.Edit(int(max_len), int(form))
+    if isinstance(form, bool) or form not in (0, 1, 2, 3) or (form and holds[form] < max_len):
+        raise ValueError("form must be None or 1, 2, 3 (shorter sides up to %d, %d, %d), got %r at max_len %d"
+                         % (holds[1], holds[2], holds[3], form, max_len))
+    e = capi.Edit(max_len, int(form))
     if not _lib.bsq_edit_pairs_kernel_name(ctypes.byref(e)):  # (whatever the rules above do not restate)
         raise ValueError("the library refuses these arguments (include/bsq.h, \"edit distance of row pairs\")")
     return desc, e
-
-
-def _identity_q16(min_identity):
-    if not 0.0 <= float(min_identity) <= 1.0:  # (a NaN fails both comparisons)
-        raise ValueError("min_identity must lie in 0 .. 1, got %r" % (min_identity,))
-    return int(float(min_identity) * 65536 + 0.5)
 
 
 def edit_kernel_name(max_len=MAX_LEN, form=None):
@@ -81,35 +76,45 @@ def edit_kernel_name(max_len=MAX_LEN, form=None):
     return _lib.bsq_edit_pairs_kernel_name(ctypes.byref(e)).decode()
 
 
-def _host_lists(row, col):
-    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
-    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
-        raise ValueError("row and col are int64 arrays of one length")
-    return row, col
+def _pairs_host(entry, desc, rule, chars, offsets, row, col, chars_b, offsets_b, *outs):
+    """One call of a CPU twin over listed pairs of rows of two stores -- of one store where chars_b and offsets_b are None.  Every
+    output is described by (numpy dtype, shape behind the list's length), or by None where it was not asked for: that one is returned
+    as None and goes to the library as a null pointer.  Returns the outputs in order.  An empty list makes no call."""
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    row, col = capi.host_index_lists(row, col)
+    ca, oa = capi.host_batch(chars, offsets)
+    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
+    n = row.size
+    out = [None if o is None else np.empty((n,) + o[1], o[0]) for o in outs]
+    if n:
+        capi.check(entry(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
+                         row.ctypes.data, col.ctypes.data, n, ctypes.byref(rule), *[None if x is None else x.ctypes.data for x in out]))
+    return out
+
+
+_ON_DEVICE = "the pair calls work on packed batches resident on the device (chars, offsets tensors)"
+
+
+def _stores_on_device(chars, offsets, row, col, chars_b, offsets_b):
+    """What the three device calls check before they allocate: (Ba, Bb, device, n) of stores and lists resident on one device.  The
+    allocations and the launch stay written out in each of them: one shared call path over described outputs cost score_pairs
+    0.5 us a call (profiles/r31/pair_surface_refactor.txt)."""
+    if (chars_b is None) != (offsets_b is None):
+        raise ValueError("chars_b and offsets_b come together")
+    Ba = capi.packed_on_device(chars, offsets, _ON_DEVICE)
+    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, _ON_DEVICE)
+    if chars_b is not None and chars_b.device != chars.device:
+        raise ValueError("both stores must live on one device")
+    return Ba, Bb, capi.device_index_lists(row, col, chars.device), row.numel()
 
 
 def edit_distance_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, max_len=MAX_LEN, form=None):
     """The library's CPU twin (`bsq_edit_pairs_host`: the class and block-step text of the kernels in plain loops) on numpy arrays:
     dist as an int32 array, with `edit_distance_pairs`' meaning of every argument (form is checked and changes nothing)."""
     desc, e = _edit(tok, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    row, col = _host_lists(row, col)
-    ca, oa = capi.host_batch(chars, offsets)
-    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
-    dist = np.empty(row.size, np.int32)
-    if row.size:
-        capi.check(_lib.bsq_edit_pairs_host(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
-                                            row.ctypes.data, col.ctypes.data, row.size, ctypes.byref(e), dist.ctypes.data))
+    dist, = _pairs_host(_lib.bsq_edit_pairs_host, desc, e, chars, offsets, row, col, chars_b, offsets_b, (np.int32, ()))
     return dist
-
-
-def _device_lists(row, col, device):
-    import torch
-    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda and row.device == col.device == device):
-        raise ValueError("row and col are index tensors resident on the device of the stores")
-    if row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or row.shape != col.shape or not row.is_contiguous() or not col.is_contiguous():
-        raise ValueError("row and col are contiguous int64 tensors of one length")
 
 
 def edit_distance_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, max_len=MAX_LEN, form=None):
@@ -124,22 +129,15 @@ def edit_distance_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=N
     cheaper kernel: 16 (or 4) pairs share a wave instead of one."""
     import torch
     desc, e = _edit(tok, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    what = "edit_distance_pairs works on packed batches resident on the device (chars, offsets tensors)"
-    Ba = capi.packed_on_device(chars, offsets, what)
-    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, what)
-    if chars_b is not None and chars_b.device != chars.device:
-        raise ValueError("both stores must live on one device")
-    _device_lists(row, col, chars.device)
-    dist = torch.empty(row.numel(), dtype=torch.int32, device=chars.device)
-    if row.numel():
-        ca = capi.readable_chars(chars, chars.device)  # (every row may be empty)
-        cb = ca if chars_b is None else capi.readable_chars(chars_b, chars.device)
+    Ba, Bb, dev, n = _stores_on_device(chars, offsets, row, col, chars_b, offsets_b)
+    dist = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        ca = capi.readable_chars(chars, dev)  # (every row may be empty)
+        cb = ca if chars_b is None else capi.readable_chars(chars_b, dev)
         ob = offsets if offsets_b is None else offsets_b
-        with capi.launching(chars.device) as stream:
+        with capi.launching(dev) as stream:
             capi.check(_lib.bsq_edit_pairs_device(ctypes.byref(desc), ca.data_ptr(), offsets.data_ptr(), Ba, cb.data_ptr(), ob.data_ptr(), Bb,
-                                                  row.data_ptr(), col.data_ptr(), row.numel(), ctypes.byref(e), dist.data_ptr(), stream))
+                                                  row.data_ptr(), col.data_ptr(), n, ctypes.byref(e), dist.data_ptr(), stream))
     return dist
 
 
@@ -171,9 +169,9 @@ def _valid_lengths(xp, offsets, idx):
 
 def verify_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, min_identity=0.9, max_len=MAX_LEN):
     """`verify_pairs` on numpy arrays through the CPU twin: (keep, dist) as numpy arrays, the same bits."""
-    T = _identity_q16(min_identity)
+    T = capi.q16_arg("min_identity", min_identity)
     dist = edit_distance_host(tok, chars, offsets, row, col, chars_b, offsets_b, max_len=max_len)
-    row, col = _host_lists(row, col)
+    row, col = capi.host_index_lists(row, col)
     oa = np.asarray(offsets, np.int64).ravel()
     ob = oa if offsets_b is None else np.asarray(offsets_b, np.int64).ravel()
     L = np.maximum(_valid_lengths(np, oa, row), _valid_lengths(np, ob, col))
@@ -187,7 +185,7 @@ def verify_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *,
     pairs bit for bit.  A pair that got a code (-1, -2) is never kept; two empty rows pass any threshold.  `row[keep]`, `col[keep]` is
     the verified list, which `sketch.cluster_pairs` takes."""
     import torch
-    T = _identity_q16(min_identity)
+    T = capi.q16_arg("min_identity", min_identity)
     dist = edit_distance_pairs(tok, chars, offsets, row, col, chars_b, offsets_b, max_len=max_len)
     L = torch.maximum(_valid_lengths(torch, offsets, row), _valid_lengths(torch, offsets if offsets_b is None else offsets_b, col))
     return (dist >= 0) & (dist.to(torch.int64) * 65536 <= (65536 - T) * L), dist
@@ -205,11 +203,9 @@ def score_matrix(tok, match, mismatch):
     """The (C + 1, C + 1) int8 matrix with `match` where two classes are equal (the unmapped class against itself included) and
     `mismatch` elsewhere; C is the number of classes of the tokenizer's alphabet."""
     C = capi.desc_of(tok).nchars
-    for v in (match, mismatch):
-        if isinstance(v, bool) or int(v) != v or not -128 <= int(v) <= 127:
-            raise ValueError("match and mismatch are integers in -128 .. 127")
-    m = np.full((C + 1, C + 1), int(mismatch), np.int8)
-    np.fill_diagonal(m, int(match))
+    match, mismatch = capi.int_arg("match", match, -128, 127), capi.int_arg("mismatch", mismatch, -128, 127)
+    m = np.full((C + 1, C + 1), mismatch, np.int8)
+    np.fill_diagonal(m, match)
     return m
 
 
@@ -229,9 +225,9 @@ def blosum62_matrix(tok):
     return out
 
 
-def _score(tok, matrix, gap_open, gap_extend, mode, max_len, form):
-    """(desc, bsq_score) with the library's argument rules applied as ValueError (no device is touched)."""
-    desc, e = _edit(tok, max_len, form)
+def _score(tok, matrix, gap_open, gap_extend, mode, max_len, form, holds=_FORM_HOLDS):
+    """(desc, bsq_score) with the library's argument rules applied as ValueError (no device is touched); holds: as for `_edit`."""
+    desc, e = _edit(tok, max_len, form, holds)
     if mode not in _MODES:
         raise ValueError("mode is 'local' or 'global', got %r" % (mode,))
     for name, v in (("gap_open", gap_open), ("gap_extend", gap_extend)):
@@ -259,17 +255,8 @@ def score_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None
     """The library's CPU twin (`bsq_score_pairs_host`: the cell of the kernels in plain loops) on numpy arrays: score as an int32
     array, or (score, ends) with ends int32 of shape (n, 2); every argument means what it means to `score_pairs`."""
     desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    row, col = _host_lists(row, col)
-    ca, oa = capi.host_batch(chars, offsets)
-    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
-    score = np.empty(row.size, np.int32)
-    en = np.empty((row.size, 2), np.int32) if ends else None
-    if row.size:
-        capi.check(_lib.bsq_score_pairs_host(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
-                                             row.ctypes.data, col.ctypes.data, row.size, ctypes.byref(s), score.ctypes.data,
-                                             en.ctypes.data if ends else None))
+    score, en = _pairs_host(_lib.bsq_score_pairs_host, desc, s, chars, offsets, row, col, chars_b, offsets_b,
+                            (np.int32, ()), (np.int32, (2,)) if ends else None)
     return (score, en) if ends else score
 
 
@@ -286,23 +273,16 @@ def score_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, 
     have up to 2^20 characters.  Codes: `SCORE_TOO_LONG`, `SCORE_BAD_INDEX` (every score <= `CODE_BELOW` is one), ends (-1, -1)."""
     import torch
     desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    what = "score_pairs works on packed batches resident on the device (chars, offsets tensors)"
-    Ba = capi.packed_on_device(chars, offsets, what)
-    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, what)
-    if chars_b is not None and chars_b.device != chars.device:
-        raise ValueError("both stores must live on one device")
-    _device_lists(row, col, chars.device)
-    score = torch.empty(row.numel(), dtype=torch.int32, device=chars.device)
-    en = torch.empty((row.numel(), 2), dtype=torch.int32, device=chars.device) if ends else None
-    if row.numel():
-        ca = capi.readable_chars(chars, chars.device)  # (every row may be empty)
-        cb = ca if chars_b is None else capi.readable_chars(chars_b, chars.device)
+    Ba, Bb, dev, n = _stores_on_device(chars, offsets, row, col, chars_b, offsets_b)
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    en = torch.empty((n, 2), dtype=torch.int32, device=dev) if ends else None
+    if n:
+        ca = capi.readable_chars(chars, dev)  # (every row may be empty)
+        cb = ca if chars_b is None else capi.readable_chars(chars_b, dev)
         ob = offsets if offsets_b is None else offsets_b
-        with capi.launching(chars.device) as stream:
+        with capi.launching(dev) as stream:
             capi.check(_lib.bsq_score_pairs_device(ctypes.byref(desc), ca.data_ptr(), offsets.data_ptr(), Ba, cb.data_ptr(), ob.data_ptr(), Bb,
-                                                   row.data_ptr(), col.data_ptr(), row.numel(), ctypes.byref(s), score.data_ptr(),
+                                                   row.data_ptr(), col.data_ptr(), n, ctypes.byref(s), score.data_ptr(),
                                                    en.data_ptr() if ends else None, stream))
     return (score, en) if ends else score
 
@@ -334,14 +314,6 @@ def _valid_take(xp, values, idx):
     return xp.where(ok, values[xp.where(ok, idx, xp.zeros_like(idx))], xp.zeros_like(idx))
 
 
-def _ratio_q16(min_ratio, min_score):
-    if not 0.0 <= float(min_ratio) <= 1.0:  # (a NaN fails both comparisons)
-        raise ValueError("min_ratio must lie in 0 .. 1, got %r" % (min_ratio,))
-    if isinstance(min_score, bool) or int(min_score) != min_score:
-        raise ValueError("min_score is an integer, got %r" % (min_score,))
-    return int(float(min_ratio) * 65536 + 0.5), int(min_score)
-
-
 def _score_keep(xp, score64, self_a, self_b, T, min_score):
     least = xp.minimum(self_a, self_b)
     return (score64 > CODE_BELOW) & (score64 >= min_score) & (least > 0) & (score64 * 65536 >= T * least)
@@ -350,10 +322,10 @@ def _score_keep(xp, score64, self_a, self_b, T, min_score):
 def verify_score_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, matrix, gap_open, gap_extend, mode="local",
                             min_ratio=0.5, min_score=1, max_len=MAX_LEN):
     """`verify_score_pairs` on numpy arrays through the CPU twin: (keep, score) as numpy arrays, the same bits."""
-    T, min_score = _ratio_q16(min_ratio, min_score)
+    T, min_score = capi.q16_arg("min_ratio", min_ratio), capi.int_arg("min_score", min_score)
     score = score_pairs_host(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend, mode=mode,
                              max_len=max_len)
-    row, col = _host_lists(row, col)
+    row, col = capi.host_index_lists(row, col)
     sa = self_scores(tok, np.asarray(chars, np.uint8), offsets, matrix)
     sb = sa if chars_b is None else self_scores(tok, np.asarray(chars_b, np.uint8), offsets_b, matrix)
     return _score_keep(np, score.astype(np.int64), _valid_take(np, sa, row), _valid_take(np, sb, col), T, min_score), score
@@ -367,7 +339,7 @@ def verify_score_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=No
     device, nothing read back -- `verify_score_pairs_host` keeps the same pairs bit for bit.  `row[keep]`, `col[keep]` is the verified
     list, which `sketch.cluster_pairs` takes."""
     import torch
-    T, min_score = _ratio_q16(min_ratio, min_score)
+    T, min_score = capi.q16_arg("min_ratio", min_ratio), capi.int_arg("min_score", min_score)
     score = score_pairs(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend, mode=mode,
                         max_len=max_len)
     sa = self_scores(tok, chars, offsets, matrix)
@@ -384,14 +356,9 @@ _COVERAGE = ("both", "shorter", "longer", "a", "b")
 
 
 def _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form):
-    """(desc, bsq_score) for the statistics calls: `_score`'s rules with the narrower max_len and forms."""
-    if isinstance(max_len, bool) or int(max_len) != max_len or not 1 <= int(max_len) <= STATS_MAX_LEN:
-        raise ValueError("max_len must be an integer in 1 .. %d, got %r" % (STATS_MAX_LEN, max_len))
-    form = 0 if form is None else form
-    if isinstance(form, bool) or form not in (0, 1, 2, 3) or (form and _STATS_FORM_HOLDS[form] < int(max_len)):
-        raise ValueError("form must be None or 1, 2, 3 (shorter sides up to 128, 512, 2048), got %r at max_len %d" % (form, int(max_len)))
-    desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, None)
-    s.form = int(form)
+    """(desc, bsq_score) for the statistics calls: `_score`'s rules with the narrower max_len and forms (a form that holds a max_len
+    here holds it in the score kernels too, so `_score`'s own question to the library stands)."""
+    desc, s = _score(tok, matrix, gap_open, gap_extend, mode, max_len, form, _STATS_FORM_HOLDS)
     if not _lib.bsq_align_stats_kernel_name(ctypes.byref(s)):  # (whatever the rules above do not restate)
         raise ValueError("the library refuses these arguments (include/bsq.h, \"alignment statistics of row pairs\")")
     return desc, s
@@ -408,16 +375,7 @@ def stats_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets_b=None
     """The library's CPU twin (`bsq_align_stats_host`: the cell of the kernels in plain loops) on numpy arrays: (score int32, stats int32
     of shape (n, 6)); every argument means what it means to `stats_pairs`."""
     desc, s = _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    row, col = _host_lists(row, col)
-    ca, oa = capi.host_batch(chars, offsets)
-    cb, ob = (ca, oa) if chars_b is None else capi.host_batch(chars_b, offsets_b)
-    score = np.empty(row.size, np.int32)
-    stats = np.empty((row.size, 6), np.int32)
-    if row.size:
-        capi.check(_lib.bsq_align_stats_host(ctypes.byref(desc), ca.ctypes.data, oa.ctypes.data, oa.size - 1, cb.ctypes.data, ob.ctypes.data, ob.size - 1,
-                                             row.ctypes.data, col.ctypes.data, row.size, ctypes.byref(s), score.ctypes.data, stats.ctypes.data))
+    score, stats = _pairs_host(_lib.bsq_align_stats_host, desc, s, chars, offsets, row, col, chars_b, offsets_b, (np.int32, ()), (np.int32, (6,)))
     return score, stats
 
 
@@ -434,32 +392,17 @@ def stats_pairs(tok, chars, offsets, row, col, chars_b=None, offsets_b=None, *, 
     `verify_align_pairs` turn the statistics into the thresholds of cd-hit and mmseqs."""
     import torch
     desc, s = _stats(tok, matrix, gap_open, gap_extend, mode, max_len, form)
-    if (chars_b is None) != (offsets_b is None):
-        raise ValueError("chars_b and offsets_b come together")
-    what = "stats_pairs works on packed batches resident on the device (chars, offsets tensors)"
-    Ba = capi.packed_on_device(chars, offsets, what)
-    Bb = Ba if chars_b is None else capi.packed_on_device(chars_b, offsets_b, what)
-    if chars_b is not None and chars_b.device != chars.device:
-        raise ValueError("both stores must live on one device")
-    _device_lists(row, col, chars.device)
-    score = torch.empty(row.numel(), dtype=torch.int32, device=chars.device)
-    stats = torch.empty((row.numel(), 6), dtype=torch.int32, device=chars.device)
-    if row.numel():
-        ca = capi.readable_chars(chars, chars.device)  # (every row may be empty)
-        cb = ca if chars_b is None else capi.readable_chars(chars_b, chars.device)
+    Ba, Bb, dev, n = _stores_on_device(chars, offsets, row, col, chars_b, offsets_b)
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty((n, 6), dtype=torch.int32, device=dev)
+    if n:
+        ca = capi.readable_chars(chars, dev)  # (every row may be empty)
+        cb = ca if chars_b is None else capi.readable_chars(chars_b, dev)
         ob = offsets if offsets_b is None else offsets_b
-        with capi.launching(chars.device) as stream:
+        with capi.launching(dev) as stream:
             capi.check(_lib.bsq_align_stats_device(ctypes.byref(desc), ca.data_ptr(), offsets.data_ptr(), Ba, cb.data_ptr(), ob.data_ptr(), Bb,
-                                                   row.data_ptr(), col.data_ptr(), row.numel(), ctypes.byref(s), score.data_ptr(),
-                                                   stats.data_ptr(), stream))
+                                                   row.data_ptr(), col.data_ptr(), n, ctypes.byref(s), score.data_ptr(), stats.data_ptr(), stream))
     return score, stats
-
-
-def _xp(a):
-    if isinstance(a, np.ndarray):
-        return np
-    import torch
-    return torch
 
 
 def _ratio32(xp, num, den, bad):
@@ -481,18 +424,15 @@ def stats_identity(stats, over="columns", la=None, lb=None):
         raise ValueError("over is one of %r, got %r" % (_IDENTITY_OVER, over))
     if over != "columns" and (la is None or lb is None):
         raise ValueError("over=%r needs la and lb (pair_lengths)" % (over,))
-    xp = _xp(stats)
-    if xp is np:
-        st = stats.astype(np.int64)
-    else:
-        st = stats.to(xp.int64)
+    xp = capi.xp_of(stats)
+    st = stats.astype(np.int64) if xp is np else stats.to(xp.int64)
     den = st[:, 5] if over == "columns" else (xp.minimum(la, lb) if over == "shorter" else xp.maximum(la, lb))
     return _ratio32(xp, st[:, 4], den, st[:, 5] < 0)
 
 
 def stats_coverage(stats, la, lb):
     """(cov_a, cov_b): the share of each row the alignment covers, (end - start) / length as float32; NaN for a code and a length of 0."""
-    xp = _xp(stats)
+    xp = capi.xp_of(stats)
     st = stats.astype(np.int64) if xp is np else stats.to(xp.int64)
     bad = st[:, 5] < 0
     return _ratio32(xp, st[:, 2] - st[:, 0], la, bad), _ratio32(xp, st[:, 3] - st[:, 1], lb, bad)
@@ -503,11 +443,8 @@ def _align_thresholds(min_identity, min_coverage, identity_over, coverage, min_s
         raise ValueError("identity_over is 'columns' or 'shorter', got %r" % (identity_over,))
     if coverage not in _COVERAGE:
         raise ValueError("coverage is one of %r, got %r" % (_COVERAGE, coverage))
-    if not 0.0 <= float(min_coverage) <= 1.0:  # (a NaN fails both comparisons)
-        raise ValueError("min_coverage must lie in 0 .. 1, got %r" % (min_coverage,))
-    if isinstance(min_score, bool) or int(min_score) != min_score:
-        raise ValueError("min_score is an integer, got %r" % (min_score,))
-    return _identity_q16(min_identity), int(float(min_coverage) * 65536 + 0.5), int(min_score)
+    Tc, min_score = capi.q16_arg("min_coverage", min_coverage), capi.int_arg("min_score", min_score)
+    return capi.q16_arg("min_identity", min_identity), Tc, min_score
 
 
 def _align_keep(xp, score64, st, la, lb, Ti, Tc, min_score, identity_over, coverage):
@@ -535,7 +472,7 @@ def verify_align_pairs_host(tok, chars, offsets, row, col, chars_b=None, offsets
     Ti, Tc, min_score = _align_thresholds(min_identity, min_coverage, identity_over, coverage, min_score)
     score, stats = stats_pairs_host(tok, chars, offsets, row, col, chars_b, offsets_b, matrix=matrix, gap_open=gap_open, gap_extend=gap_extend,
                                     mode=mode, max_len=max_len)
-    row, col = _host_lists(row, col)
+    row, col = capi.host_index_lists(row, col)
     oa = np.asarray(offsets, np.int64).ravel()
     ob = oa if offsets_b is None else np.asarray(offsets_b, np.int64).ravel()
     la, lb = _valid_lengths(np, oa, row), _valid_lengths(np, ob, col)

@@ -450,6 +450,60 @@ def parse_layout(layout) -> bool:
     raise ValueError("layout must be 'tbc' (padlen, batch, channels) or 'bcl' (batch, channels, padlen)")
 
 
+_INF = float("inf")
+
+
+def int_arg(name, v, lo=-_INF, hi=_INF, none=False):
+    """int(v) of an integer argument in lo .. hi -- ValueError naming it and the bounds for a bool, a value with a fraction and one
+    outside them; what `int()` itself refuses (a string, None) raises what `int()` raises.  none=True lets None through as None."""
+    if none and v is None:
+        return None
+    if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+        span = " in %s .. %s" % (lo, hi) if hi < _INF else " >= %s" % lo if lo > -_INF else ""
+        raise ValueError("%s must be %san integer%s, got %r" % (name, "None or " if none else "", span, v))
+    return int(v)
+
+
+def q16_arg(name, x):
+    """floor(x * 65536 + 0.5) of a threshold in 0 .. 1: the 16-bit fixed-point form in which the library and the verify rules compare
+    ratios in integers.  ValueError naming the argument outside 0 .. 1."""
+    if not 0.0 <= float(x) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError("%s must lie in 0 .. 1, got %r" % (name, x))
+    return int(float(x) * 65536 + 0.5)
+
+
+def xp_of(a):
+    """numpy for a numpy array, torch for anything else: the module whose functions continue a computation on `a`."""
+    if isinstance(a, np.ndarray):
+        return np
+    import torch
+    return torch
+
+
+def host_index_lists(row, col):
+    """(row, col) of a pair list as a CPU twin reads it: contiguous int64 arrays, 1-D and of one length (ValueError otherwise)."""
+    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
+    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
+        raise ValueError("row and col are int64 arrays of one length")
+    return row, col
+
+
+def device_index_lists(row, col, device=None):
+    """The device of a pair list that a kernel can read as it is: row and col contiguous int64 tensors, 1-D and of one length, resident
+    on one device -- on `device` where the list indexes stores or sketches that live there (ValueError otherwise)."""
+    import torch
+    apart = "row and col are index tensors resident on one device, that of the stores or sketches they index"
+    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda):
+        raise ValueError(apart)
+    dev = row.device
+    if dev != col.device or (device is not None and dev != device):
+        raise ValueError(apart)
+    if (row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or col.ndim != 1 or row.numel() != col.numel()
+            or not row.is_contiguous() or not col.is_contiguous()):  # (ndim and numel: ints, where .shape builds a torch.Size each)
+        raise ValueError("row and col are contiguous int64 tensors of one length")
+    return dev
+
+
 def packed_on_device(chars, offsets, what, exact=True, apart="chars and offsets must live on one device") -> int:
     """B of a packed batch (chars, offsets) that is resident on ONE device -- ValueError `what` / `apart` otherwise -- and, with `exact`,
     already what the C ABI reads: contiguous uint8 characters and contiguous int64 offsets (a caller that converts passes exact=False)."""

@@ -119,19 +119,41 @@ def _pair_shape(a, b):
     return int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
 
 
+_HOST_CODES = {np.dtype(np.int32): capi.I32, np.dtype(np.int64): capi.U64, np.dtype(np.uint64): capi.U64}
+
+
+def _host_sketches(a, b=None):
+    """contiguous numpy matrices of one accepted element type and width: (a, b or None, Ba, Bb, S, dtype code); Bb = 0 without b"""
+    a = np.ascontiguousarray(a)
+    b = None if b is None else np.ascontiguousarray(b)
+    if a.dtype not in _HOST_CODES:
+        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
+    Ba, Bb, S = _pair_shape(a, a if b is None else b)
+    return a, b, Ba, Bb if b is not None else 0, S, _HOST_CODES[a.dtype]
+
+
+def _device_sketches(a, b, what):
+    """device matrices of one accepted element type, width and device: (Ba, Bb, S, dtype code); Bb = 0 without b"""
+    import torch
+    other = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(other, torch.Tensor) and a.is_cuda and other.is_cuda and a.device == other.device):
+        raise ValueError("%s works on sketch matrices resident on one device (numpy matrices go through the CPU twin)" % what)
+    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not other.is_contiguous():
+        raise ValueError("sketches are contiguous int32 or int64 tensors")
+    Ba, Bb, S = _pair_shape(a, other)
+    return Ba, Bb if b is not None else 0, S, capi.I32 if a.dtype == torch.int32 else capi.U64
+
+
 def sketch_compare_host(a, b=None, *, either=True):
     """The library's CPU twin of `sketch_compare` (`bsq_sketch_compare_host`) on numpy matrices of int32, int64 or uint64: (match,
     either or None), int32 (Ba, Bb)."""
-    a = np.ascontiguousarray(a)
-    b = a if b is None else np.ascontiguousarray(b)
-    codes = {np.dtype(np.int32): capi.I32, np.dtype(np.int64): capi.U64, np.dtype(np.uint64): capi.U64}
-    if a.dtype not in codes:
-        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
-    Ba, Bb, S = _pair_shape(a, b)
+    a, b, Ba, Bb, S, dt = _host_sketches(a, b)
+    if b is None:
+        b, Bb = a, Ba
     match = np.empty((Ba, Bb), np.int32)
     eith = np.empty((Ba, Bb), np.int32) if either else None
     if Ba and Bb:
-        capi.check(_lib.bsq_sketch_compare_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, codes[a.dtype], match.ctypes.data,
+        capi.check(_lib.bsq_sketch_compare_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, dt, match.ctypes.data,
                                                 eith.ctypes.data if either else None))
     return match, eith
 
@@ -144,64 +166,49 @@ def sketch_compare(a, b=None, *, either=True):
     match[i, j] = the buckets in which a[i] and b[j] hold the same non-EMPTY value; either[i, j] = the buckets that are non-EMPTY in a[i]
     or in b[j].  match / either estimates the Jaccard similarity of the two rows' k-mer sets (`sketch_jaccard`)."""
     import torch
-    b = a if b is None else b
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda and a.device == b.device):
-        raise ValueError("sketch_compare works on sketch matrices resident on one device")
-    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not b.is_contiguous():
-        raise ValueError("sketches are contiguous int32 or int64 tensors")
-    Ba, Bb, S = _pair_shape(a, b)
+    Ba, Bb, S, dt = _device_sketches(a, b, "sketch_compare")
+    if b is None:
+        b, Bb = a, Ba
     match = torch.empty((Ba, Bb), dtype=torch.int32, device=a.device)
     eith = torch.empty((Ba, Bb), dtype=torch.int32, device=a.device) if either else None
     if Ba and Bb:
         with capi.launching(a.device) as stream:
-            capi.check(_lib.bsq_sketch_compare_device(a.data_ptr(), Ba, b.data_ptr(), Bb, S, capi.I32 if a.dtype == torch.int32 else capi.U64,
-                                                      match.data_ptr(), eith.data_ptr() if either else None, stream))
+            capi.check(_lib.bsq_sketch_compare_device(a.data_ptr(), Ba, b.data_ptr(), Bb, S, dt, match.data_ptr(),
+                                                      eith.data_ptr() if either else None, stream))
     return match, eith
 
 
 def sketch_jaccard(a, b=None):
     """The Jaccard estimate of every pair of rows: float32 (Ba, Bb), match / either of `sketch_compare` and 0 where either == 0 -- the
     division of the exact integers.  Device tensors give a device tensor; numpy matrices go through the CPU twin and give numpy."""
-    if isinstance(a, np.ndarray):
+    xp = capi.xp_of(a)
+    if xp is np:
         m, e = sketch_compare_host(a, b)
         return np.where(e > 0, m.astype(np.float32) / np.maximum(e, 1).astype(np.float32), np.float32(0)).astype(np.float32)
-    import torch
     m, e = sketch_compare(a, b)
-    return torch.where(e > 0, m.to(torch.float32) / e.clamp(min=1).to(torch.float32), torch.zeros((), dtype=torch.float32, device=m.device))
-
-
-_HOST_CODES = {np.dtype(np.int32): capi.I32, np.dtype(np.int64): capi.U64, np.dtype(np.uint64): capi.U64}
+    return xp.where(e > 0, m.to(xp.float32) / e.clamp(min=1).to(xp.float32), xp.zeros((), dtype=xp.float32, device=m.device))
 
 
 def _pairs_rule(S, min_jaccard, min_match, max_pairs, segments, upper):
     """(bsq_sketch_pairs, max_pairs or None) with the library's argument rules applied as ValueError (no device is touched)."""
-    if not 0.0 <= float(min_jaccard) <= 1.0:  # (a NaN fails both comparisons)
-        raise ValueError("min_jaccard must lie in 0 .. 1, got %r" % (min_jaccard,))
-    if isinstance(min_match, bool) or int(min_match) != min_match or not 0 <= int(min_match) <= S:
-        raise ValueError("min_match must be an integer in 0 .. %d (the sketch width), got %r" % (S, min_match))
-    if max_pairs is not None and (int(max_pairs) != max_pairs or int(max_pairs) < 0):
-        raise ValueError("max_pairs must be None or an integer >= 0, got %r" % (max_pairs,))
-    segments = 0 if segments is None else segments
-    if isinstance(segments, bool) or int(segments) != segments or not 0 <= int(segments) <= 64:
-        raise ValueError("segments must be None or an integer in 1 .. 64, got %r" % (segments,))
-    rule = capi.SketchPairs(int(min_match), int(float(min_jaccard) * 65536 + 0.5), int(upper), int(segments))
-    return rule, None if max_pairs is None else int(max_pairs)
+    T, min_match = capi.q16_arg("min_jaccard", min_jaccard), capi.int_arg("min_match", min_match, 0, S)  # (S: the sketch width)
+    cap = capi.int_arg("max_pairs", max_pairs, 0, none=True)
+    segments = capi.int_arg("segments", segments, 0, 64, none=True) or 0  # (0 has always been taken and means what None means: the library chooses)
+    return capi.SketchPairs(min_match, T, int(upper), segments), cap
 
 
 def sketch_pairs_host(a, b=None, *, min_jaccard=0.5, min_match=1, max_pairs=None, either=True):
     """The library's CPU twin of `sketch_pairs` (`bsq_sketch_pairs_host`) on numpy matrices of int32, int64 or uint64: (row, col, match,
     either or None, pair_offsets) as numpy arrays, with `sketch_pairs`' meaning of every argument."""
-    a = np.ascontiguousarray(a)
     upper = b is None
-    b = a if upper else np.ascontiguousarray(b)
-    if a.dtype not in _HOST_CODES:
-        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
-    Ba, Bb, S = _pair_shape(a, b)
+    a, b, Ba, Bb, S, dt = _host_sketches(a, b)
+    if upper:
+        b, Bb = a, Ba
     rule, cap = _pairs_rule(S, min_jaccard, min_match, max_pairs, None, upper)
     offs = np.zeros(Ba + 1, np.int64)
 
     def call(n, *arrays):  # the twin counts and lists in one call; with max_pairs = 0 it only counts and takes no arrays
-        capi.check(_lib.bsq_sketch_pairs_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, _HOST_CODES[a.dtype], ctypes.byref(rule), offs.ctypes.data, n,
+        capi.check(_lib.bsq_sketch_pairs_host(a.ctypes.data, Ba, b.ctypes.data, Bb, S, dt, ctypes.byref(rule), offs.ctypes.data, n,
                                               *(None if x is None else x.ctypes.data for x in arrays)))
 
     if cap is None:
@@ -231,14 +238,11 @@ def sketch_pairs(a, b=None, *, min_jaccard=0.5, min_match=1, max_pairs=None, eit
     Train / test leakage: `sketch_pairs(train, test, min_jaccard=...)[1].unique()` are the test rows to drop."""
     import torch
     upper = b is None
-    b = a if upper else b
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda and a.device == b.device):
-        raise ValueError("sketch_pairs works on sketch matrices resident on one device")
-    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not b.is_contiguous():
-        raise ValueError("sketches are contiguous int32 or int64 tensors")
-    Ba, Bb, S = _pair_shape(a, b)
+    Ba, Bb, S, dt = _device_sketches(a, b, "sketch_pairs")
+    if upper:
+        b, Bb = a, Ba
     rule, cap = _pairs_rule(S, min_jaccard, min_match, max_pairs, segments, upper)
-    dev, dt = a.device, capi.I32 if a.dtype == torch.int32 else capi.U64
+    dev = a.device
     nseg = _lib.bsq_sketch_pairs_segments(Ba, Bb, rule.segments)
     if nseg < 1:
         raise ValueError("the library refuses these sizes (include/bsq.h, \"sketch pairs\")")
@@ -295,14 +299,11 @@ def sketch_pairs_kernel_name(Ba, Bb, segments=None):
 def sketch_clusters_host(a, *, min_jaccard=0.9, min_match=1):
     """The library's CPU twin of `sketch_clusters` (`bsq_sketch_clusters_host`) on a numpy matrix of int32, int64 or uint64: the int64
     labels as a numpy array."""
-    a = np.ascontiguousarray(a)
-    if a.dtype not in _HOST_CODES:
-        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
-    B, _, S = _pair_shape(a, a)
+    a, _, B, _, S, dt = _host_sketches(a)
     rule, _ = _pairs_rule(S, min_jaccard, min_match, None, None, True)
     labels = np.empty(B, np.int64)
     if B:
-        capi.check(_lib.bsq_sketch_clusters_host(a.ctypes.data, B, S, _HOST_CODES[a.dtype], ctypes.byref(rule), labels.ctypes.data))
+        capi.check(_lib.bsq_sketch_clusters_host(a.ctypes.data, B, S, dt, ctypes.byref(rule), labels.ctypes.data))
     return labels
 
 
@@ -324,14 +325,10 @@ def sketch_clusters(a, *, min_jaccard=0.9, min_match=1, segments=None):
     A train set together with a test set: `labels = sketch_clusters(torch.cat([train, test]))`, then `cluster_split(labels, ...)` for a
     new split of both, or compare `labels[:len(train)]` with `labels[len(train):]` for the clusters that straddle the old one."""
     if isinstance(a, np.ndarray):
-        _pairs_rule(1 << 14, 0.0, 0, None, segments, True)  # (the twin has no segments: the argument is checked all the same)
+        capi.int_arg("segments", segments, 0, 64, none=True)  # (the twin has no segments: the argument is checked all the same)
         return sketch_clusters_host(a, min_jaccard=min_jaccard, min_match=min_match)
     import torch
-    if not (isinstance(a, torch.Tensor) and a.is_cuda):
-        raise ValueError("sketch_clusters works on a sketch matrix resident on the device, or on a numpy matrix")
-    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous():
-        raise ValueError("sketches are contiguous int32 or int64 tensors")
-    B, _, S = _pair_shape(a, a)
+    B, _, S, dt = _device_sketches(a, None, "sketch_clusters")
     rule, _ = _pairs_rule(S, min_jaccard, min_match, None, segments, True)
     if _lib.bsq_sketch_pairs_segments(B, B, rule.segments) < 1:
         raise ValueError("the library refuses these sizes (include/bsq.h, \"sketch clusters\")")
@@ -339,23 +336,17 @@ def sketch_clusters(a, *, min_jaccard=0.9, min_match=1, segments=None):
     labels = torch.empty(B, dtype=torch.int64, device=a.device)
     if B:
         with capi.launching(a.device) as stream:
-            capi.check(_lib.bsq_sketch_clusters_device(a.data_ptr(), B, S, capi.I32 if a.dtype == torch.int32 else capi.U64, ctypes.byref(rule),
-                                                       parent.data_ptr(), labels.data_ptr(), stream))
+            capi.check(_lib.bsq_sketch_clusters_device(a.data_ptr(), B, S, dt, ctypes.byref(rule), parent.data_ptr(), labels.data_ptr(), stream))
     return labels
 
 
-def _edge_count(n):
-    if isinstance(n, bool) or int(n) != n or not 0 <= int(n) < 2 ** 31:
-        raise ValueError("n must be an integer in 0 .. 2 ** 31 - 1, got %r" % (n,))
-    return int(n)
+_MAX_NODES, _MAX_ROUNDS = 2 ** 31 - 1, 2 ** 30 - 1  # the most nodes an edge list may join, the most rounds a greedy run may take
 
 
 def cluster_pairs_host(row, col, n):
     """The library's CPU twin of `cluster_pairs` (`bsq_cluster_pairs_host`) on numpy index arrays: the int64 labels of n nodes."""
-    n = _edge_count(n)
-    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
-    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
-        raise ValueError("row and col are int64 arrays of one length")
+    n = capi.int_arg("n", n, 0, _MAX_NODES)
+    row, col = capi.host_index_lists(row, col)
     labels = np.empty(n, np.int64)
     if n:
         capi.check(_lib.bsq_cluster_pairs_host(row.ctypes.data if row.size else None, col.ctypes.data if row.size else None, row.size, n,
@@ -373,11 +364,8 @@ def cluster_pairs(row, col, n):
     if isinstance(row, np.ndarray) and isinstance(col, np.ndarray):
         return cluster_pairs_host(row, col, n)
     import torch
-    n = _edge_count(n)
-    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda and row.device == col.device):
-        raise ValueError("cluster_pairs works on index tensors resident on one device, or on numpy arrays")
-    if row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or row.shape != col.shape or not row.is_contiguous() or not col.is_contiguous():
-        raise ValueError("row and col are contiguous int64 tensors of one length")
+    n = capi.int_arg("n", n, 0, _MAX_NODES)
+    capi.device_index_lists(row, col)
     parent = torch.empty(n, dtype=torch.int64, device=row.device)
     labels = torch.empty(n, dtype=torch.int64, device=row.device)
     if n:
@@ -393,10 +381,8 @@ def sketch_clusters_kernel_name(B, segments=None):
 
 
 def _greedy_host_args(row, col, n, key, weight):
-    n = _edge_count(n)
-    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
-    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
-        raise ValueError("row and col are int64 arrays of one length")
+    n = capi.int_arg("n", n, 0, _MAX_NODES)
+    row, col = capi.host_index_lists(row, col)
     if key is not None:
         key = np.ascontiguousarray(key)
         if key.dtype != np.int64 or key.shape != (n,):
@@ -419,12 +405,6 @@ def greedy_pairs_host(row, col, n, *, key=None, weight=None):
     return rep
 
 
-def _round_count(value, name):
-    if isinstance(value, bool) or int(value) != value or not 0 <= int(value) < 1 << 30:
-        raise ValueError("%s must be an integer in 0 .. 2 ** 30 - 1, got %r" % (name, value))
-    return int(value)
-
-
 def greedy_pairs(row, col, n, *, key=None, weight=None, max_rounds=None, rounds_per_call=16):
     """Greedy representatives of an edge list (cd-hit's rule; include/bsq.h, "greedy representatives"): rep (int64, n).  Entry k links
     nodes row[k] and col[k] (either orientation, duplicates allowed; an entry with row == col or an index outside 0 .. n - 1 is ignored,
@@ -442,20 +422,16 @@ def greedy_pairs(row, col, n, *, key=None, weight=None, max_rounds=None, rounds_
     (rep, undecided) with rep[i] = -1 where node i is not decided yet, final everywhere else, and `undecided` (a 0-d tensor) the
     number of those.  numpy arrays go through the CPU twin (`greedy_pairs_host`) and give numpy -- rep, or (rep, 0) with max_rounds;
     the two agree bit for bit."""
-    if max_rounds is not None:
-        max_rounds = _round_count(max_rounds, "max_rounds")
-    rounds_per_call = _round_count(rounds_per_call, "rounds_per_call")
+    max_rounds = capi.int_arg("max_rounds", max_rounds, 0, _MAX_ROUNDS, none=True)
+    rounds_per_call = capi.int_arg("rounds_per_call", rounds_per_call, 0, _MAX_ROUNDS)
     if rounds_per_call < 1:
         raise ValueError("rounds_per_call must be at least 1")
     if isinstance(row, np.ndarray) and isinstance(col, np.ndarray):
         rep = greedy_pairs_host(row, col, n, key=key, weight=weight)
         return rep if max_rounds is None else (rep, np.int64(0))
     import torch
-    n = _edge_count(n)
-    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.is_cuda and row.device == col.device):
-        raise ValueError("greedy_pairs works on index tensors resident on one device, or on numpy arrays")
-    if row.dtype != torch.int64 or col.dtype != torch.int64 or row.ndim != 1 or row.shape != col.shape or not row.is_contiguous() or not col.is_contiguous():
-        raise ValueError("row and col are contiguous int64 tensors of one length")
+    n = capi.int_arg("n", n, 0, _MAX_NODES)
+    capi.device_index_lists(row, col)
     if key is not None and not (isinstance(key, torch.Tensor) and key.device == row.device and key.dtype == torch.int64 and key.shape == (n,)
                                 and key.is_contiguous()):
         raise ValueError("key is a contiguous int64 tensor of n entries on the list's device")
@@ -515,49 +491,19 @@ def lsh_rows_per_band(S, min_jaccard, recall=0.95):
 
 def _lsh_rule(S, rows_per_band, max_bucket, seed, max_candidates=None):
     """(bsq_lsh, bands) with the library's argument rules applied as ValueError (no device is touched)."""
-    if isinstance(rows_per_band, bool) or int(rows_per_band) != rows_per_band or not 1 <= int(rows_per_band) <= S:
-        raise ValueError("rows_per_band must be an integer in 1 .. %d (the sketch width), got %r" % (S, rows_per_band))
-    if isinstance(max_bucket, bool) or int(max_bucket) != max_bucket or not 2 <= int(max_bucket) < 2 ** 31:
-        raise ValueError("max_bucket must be an integer in 2 .. 2 ** 31 - 1, got %r" % (max_bucket,))
-    if max_candidates is not None and (isinstance(max_candidates, bool) or int(max_candidates) != max_candidates or int(max_candidates) < 0):
-        raise ValueError("max_candidates must be None or an integer >= 0, got %r" % (max_candidates,))
-    return capi.Lsh(int(rows_per_band), int(max_bucket), int(seed) & (2 ** 64 - 1), 0), S // int(rows_per_band)
-
-
-def _host_sketches(a, b=None):
-    """contiguous numpy matrices of one accepted element type and width: (a, b or None, Ba, Bb, S, dtype code)"""
-    a = np.ascontiguousarray(a)
-    b = None if b is None else np.ascontiguousarray(b)
-    if a.dtype not in _HOST_CODES:
-        raise ValueError("sketches are int32, int64 or uint64, got %s" % a.dtype)
-    Ba, Bb, S = _pair_shape(a, a if b is None else b)
-    return a, b, Ba, Bb if b is not None else 0, S, _HOST_CODES[a.dtype]
-
-
-def _device_sketches(a, b, what):
-    """device matrices of one accepted element type, width and device: (Ba, Bb, S, dtype code)"""
-    import torch
-    other = a if b is None else b
-    if not (isinstance(a, torch.Tensor) and isinstance(other, torch.Tensor) and a.is_cuda and other.is_cuda and a.device == other.device):
-        raise ValueError("%s works on sketch matrices resident on one device, or on numpy matrices" % what)
-    if a.dtype not in (torch.int32, torch.int64) or not a.is_contiguous() or not other.is_contiguous():
-        raise ValueError("sketches are contiguous int32 or int64 tensors")
-    Ba, Bb, S = _pair_shape(a, other)
-    return Ba, Bb if b is not None else 0, S, capi.I32 if a.dtype == torch.int32 else capi.U64
+    rows_per_band = capi.int_arg("rows_per_band", rows_per_band, 1, S)  # (S: the sketch width)
+    max_bucket = capi.int_arg("max_bucket", max_bucket, 2, 2 ** 31 - 1)
+    capi.int_arg("max_candidates", max_candidates, 0, none=True)
+    return capi.Lsh(rows_per_band, max_bucket, int(seed) & (2 ** 64 - 1), 0), S // rows_per_band
 
 
 def _lsh_width(a, b, what):
+    """The width of sketch matrices of either kind, which `lsh_candidates` and `lsh_pairs` need for their rules before numpy and torch
+    part ways (`_host_sketches` / `_device_sketches` then check everything else)."""
     other = a if b is None else b
     if not (hasattr(a, "ndim") and hasattr(other, "ndim")):
         raise ValueError("%s works on sketch matrices resident on one device, or on numpy matrices" % what)
     return _pair_shape(a, other)[2]
-
-
-def _host_indices(row, col):
-    row, col = np.ascontiguousarray(row), np.ascontiguousarray(col)
-    if row.dtype != np.int64 or col.dtype != np.int64 or row.ndim != 1 or row.shape != col.shape:
-        raise ValueError("row and col are int64 arrays of one length")
-    return row, col
 
 
 def lsh_kernel_name(S, destchar="i"):
@@ -597,7 +543,7 @@ def lsh_keys(a, rows_per_band, seed=0):
 def sketch_compare_list_host(a, row, col, b=None, *, either=True):
     """The library's CPU twin of `sketch_compare_list` (`bsq_sketch_compare_list_host`) on numpy arrays: (match, either or None)."""
     a, b, Ba, Bb, S, dt = _host_sketches(a, b)
-    row, col = _host_indices(row, col)
+    row, col = capi.host_index_lists(row, col)
     n = row.size
     match = np.empty(n, np.int32)
     eith = np.empty(n, np.int32) if either else None
@@ -619,10 +565,7 @@ def sketch_compare_list(a, row, col, b=None, *, either=True):
     import torch
     Ba, Bb, S, dt = _device_sketches(a, b, "sketch_compare_list")
     other = a if b is None else b
-    if not (isinstance(row, torch.Tensor) and isinstance(col, torch.Tensor) and row.device == a.device and col.device == a.device
-            and row.dtype == torch.int64 and col.dtype == torch.int64 and row.ndim == 1 and row.shape == col.shape
-            and row.is_contiguous() and col.is_contiguous()):
-        raise ValueError("row and col are contiguous int64 tensors of one length on the sketches' device")
+    capi.device_index_lists(row, col, a.device)
     n = row.numel()
     match = torch.empty(n, dtype=torch.int32, device=a.device)
     eith = torch.empty(n, dtype=torch.int32, device=a.device) if either else None

@@ -315,6 +315,9 @@ def test_surface_on_a_side_stream(gpu, bsq):
         align.stats_pairs(tok, chars, offs, row, col, **kw)  # numpy arrays are the host twin's
     with pytest.raises(ValueError):
         align.stats_pairs(tok, dc, do, dr.to(torch.int32), dl, **kw)
+    for bad_row, bad_col in ((torch.stack([dr, dr], 1)[:, 0], dl), (dr, dl[:-1])):  # a row that is not contiguous; two lengths
+        with pytest.raises(ValueError):
+            align.stats_pairs(tok, dc, do, bad_row, bad_col, **kw)
     with pytest.raises(ValueError):
         align.stats_pairs(tok, dc, do, dr, dl, matrix=S, gap_open=128, gap_extend=1)
     with pytest.raises(ValueError):

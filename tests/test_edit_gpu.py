@@ -255,6 +255,9 @@ def test_surface_on_a_side_stream(gpu, bsq):
         align.edit_distance_pairs(tok, chars, offs, row, col)  # numpy arrays are the host twin's
     with pytest.raises(ValueError):
         align.edit_distance_pairs(tok, dc, do, dr.to(torch.int32), dl)
+    for bad_row, bad_col in ((torch.stack([dr, dr], 1)[:, 0], dl), (dr, dl[:-1])):  # a row that is not contiguous; two lengths
+        with pytest.raises(ValueError):
+            align.edit_distance_pairs(tok, dc, do, bad_row, bad_col)
     with pytest.raises(ValueError):
         align.verify_pairs(tok, dc, do, dr, dl, min_identity=1.1)
 

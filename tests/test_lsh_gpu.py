@@ -307,6 +307,15 @@ def test_whole_call_with_two_matrices_and_the_centre_rule(gpu):
     for x, y in ((a[:0], None), (a[:0], a), (a, a[:0])):
         got = sketch.lsh_pairs(_dev(gpu, x), None if y is None else _dev(gpu, y), rows_per_band=3)
         assert got[0].numel() == 0 and got[4].cpu().tolist() == [0] * (x.shape[0] + 1)
+    # what the device calls refuse: a `b` of another width or element type; a row that is not contiguous, an int32 row, two lengths
+    import torch
+    da, idx = _dev(gpu, a), torch.zeros(4, dtype=torch.int64, device=gpu)
+    for call in (lambda: sketch.lsh_pairs(da, da[:, :64].contiguous(), rows_per_band=3), lambda: sketch.lsh_pairs(da, _dev(gpu, wide), rows_per_band=3),
+                 lambda: sketch.sketch_compare_list(da, idx[::2], idx[:2]), lambda: sketch.sketch_compare_list(da, idx.to(torch.int32), idx),
+                 lambda: sketch.sketch_compare_list(da, idx, idx[:3]), lambda: sketch.sketch_compare_list(da, idx, idx, da[:, :64].contiguous()),
+                 lambda: sketch.sketch_compare_list(da, idx, idx, _dev(gpu, wide))):
+        with pytest.raises(ValueError):
+            call()
 
 
 def test_whole_call_on_a_side_stream_feeds_the_clustering_calls(gpu):

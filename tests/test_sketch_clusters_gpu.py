@@ -192,6 +192,7 @@ def test_python_surface_and_refusals(gpu, bsq):
                  lambda: sketch.sketch_clusters(a.t()), lambda: sketch.sketch_clusters(a, min_jaccard=1.01),
                  lambda: sketch.sketch_clusters(a, min_jaccard=float("nan")), lambda: sketch.sketch_clusters(a, min_match=17),
                  lambda: sketch.sketch_clusters(a, segments=65), lambda: sketch.cluster_pairs(edges, edges[:3], 6),
+                 lambda: sketch.cluster_pairs(edges[::2], edges[:2], 6),  # a row that is not contiguous
                  lambda: sketch.cluster_pairs(edges.to(torch.int32), edges.to(torch.int32), 6), lambda: sketch.cluster_pairs(edges, edges.cpu(), 6),
                  lambda: sketch.cluster_pairs(edges, edges, -1), lambda: sketch.cluster_pairs(edges, edges, 2 ** 31)):
         with pytest.raises(ValueError):
