@@ -2,7 +2,10 @@
 and on small cases against the cell-by-cell programme of tests/align_stats_twin.py: pattern lengths at every lane and form edge, text
 lengths at the tile edges, forced forms, waves that mix orientations, empty rows and codes with guards around both outputs, alignments
 that cross a lane's 32-row boundary, lists full of ties in every form, both packed fields at the top of their range, a start beyond
-text column 65 536, two stores, a side stream, the verification rule and the pipeline from sketches to identity / coverage clusters."""
+text column 65 536, two stores, a side stream, the verification rule and the pipeline from sketches to identity / coverage clusters.
+Then against the anti-diagonal sweep of the same module, which shares nothing with the library, at full length: related pairs of up to
+2048 x 2110 with gaps all along them, gaps planted where lanes 17, 40 and 63 begin, 2048 x 4500, two-letter rows of 2048 under gaps
+that cost little or nothing, the ends of the scoring ranges, and the three pair-walk families against each other."""
 import ctypes
 import functools
 
@@ -233,7 +236,7 @@ def _tie_case(mode, gaps):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("gaps", [(0, 1), (1, 1)])
+@pytest.mark.parametrize("gaps", [(0, 1), (1, 1), (3, 0), (0, 0)])
 def test_ties_in_every_form(gpu, bsq, mode, gaps):
     """Most cells tie between the diagonal and a gap or between the two gaps, and the tie between the gaps is in A / B terms: a wave holds
     pairs of both orientations."""
@@ -362,3 +365,209 @@ def test_sketches_to_identity_and_coverage_clusters(gpu, bsq):
     assert keep_h.any() and (by_identity & ~keep_h).any() and (~by_identity).any(), "kept, rejected by coverage, rejected by identity"
     want = sketch.cluster_pairs_host(r[keep_h], c[keep_h], 300)
     assert labels.cpu().numpy().tobytes() == want.tobytes() and 10 <= (want != np.arange(300)).sum() <= 40
+
+
+# ---- against the anti-diagonal sweep of tests/align_stats_twin.py (align_stats_diag), which shares nothing with the library: patterns of
+# ---- full length, where lanes 17 .. 63 of k_align_stats<64, *> carry real alignments -- gaps, ties and tuples taken from E and F
+
+FULL_SIZES = ((545, 600), (1300, 1301), (2047, 2110), (2048, 2048))
+
+
+def _sweep(key_or_tok, stores, S, o, e, mode, counts=None, **kw):
+    tok = _tok(key_or_tok) if isinstance(key_or_tok, str) else key_or_tok
+    lut, nchars = _lut(tok)
+    ca, oa, cb, ob, row, col = stores
+    return twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode, one=twin.align_stats_diag, counts=counts, **kw)
+
+
+def _without_runs(x, lanes, length=3):
+    """x without `length` characters from row 32 k - 1 on (1-based) for every k of `lanes`: aligned with x, the gap that bridges such a
+    run opens in the last rows of lane k - 1 and is extended into the first row of lane k, so lane k continues an F state, and the
+    tuple beside it, that it did not open."""
+    keep = np.ones(x.size, bool)
+    for k in lanes:
+        keep[32 * k - 2:32 * k - 2 + length] = False
+    return x[keep]
+
+
+@functools.lru_cache(maxsize=None)
+def _full_pairs(key):
+    """Ten pairs, three workgroups of the widest form: related pairs (6 %) of every size of FULL_SIZES, one unrelated 2048 x 2048 pair, the
+    three sizes with unequal sides once more, and two 2048 x 2110 pairs whose longer row is a mutated copy (6 %) of the shorter one
+    without three characters at every fourth lane boundary; every second pair has the shorter side in store B.  meta: (m, n, related)."""
+    rng = np.random.default_rng(len(key) + 70)
+    letters = LETTERS[key]
+    sizes = [s + (True,) for s in FULL_SIZES] + [(2048, 2048, False), (2047, 2110, True), (1300, 1301, True), (545, 600, True)]
+    sizes += [(2048, 2110, "runs"), (2048, 2110, "runs")]
+    pairs = []
+    for k, (m, n, related) in enumerate(sizes):
+        if related == "runs":
+            x = twin.random_row(rng, m, letters)
+            p = (x, twin.fit(rng, twin.mutate(rng, _without_runs(x, range(2 + k % 2, 64, 4)), letters, 0.06), n, letters))
+        elif related:
+            p = twin.related_pair(rng, m, n, letters, rate=0.06)
+        else:
+            p = (twin.random_row(rng, m, letters), twin.random_row(rng, n, letters))
+        pairs.append(p[::-1] if k % 2 else p)
+    return twin.store_of(pairs), sizes
+
+
+@functools.lru_cache(maxsize=None)
+def _full_case(key, mode):
+    """The stores and list of _full_pairs, and the sweep's answers under the key's scoring (once per alphabet and mode)."""
+    stores, meta = _full_pairs(key)
+    return stores, meta, _sweep(key, stores, *_scoring(key), mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("key", ["DNA4", "AMINO20"])
+def test_full_length_patterns_against_the_sweep(gpu, bsq, key, mode):
+    """Patterns of 545 .. 2048 rows with insertions, deletions and substitutions all along them: every lane of the widest form carries H, F
+    and tuples that came through gaps, and the best cell sits in the top lanes.  The 545-row pairs also with max_len = 545."""
+    from bioseq_amd import align
+    stores, meta, exp = _full_case(key, mode)
+    ca, oa, cb, ob, row, col = stores
+    tok = _tok(key)
+    S, o, e = _scoring(key)
+    kw = dict(matrix=S, gap_open=o, gap_extend=e, mode=mode)
+    if mode == "local":  # not vacuous, from the reference alone: the alignment runs from the first lane to the last one and has gaps
+        for k, (m, n, related) in enumerate(meta):
+            if related:
+                sa, sb, ea, eb, matches, columns = exp[1][k].tolist()
+                start, end = (sb, eb) if k % 2 and m < n else (sa, ea)  # (on the pattern's side)
+                assert start < 32 and end > m - 32 and columns - ((ea - sa) + (eb - sb) - columns) >= 20, (k, m, n, exp[1][k].tolist())
+    assert align.stats_kernel_name(mode=mode, max_len=2048) == align.stats_kernel_name(mode=mode, max_len=545) == "k_align_stats<64, %s>" % mode
+    _same(_device(gpu, tok, ca, oa, row, col, cb, ob, max_len=2048, **kw), exp, meta)
+    small = np.array([k for k, s in enumerate(meta) if s[0] == 545], np.int64)
+    _same(_device(gpu, tok, ca, oa, row[small], col[small], cb, ob, max_len=545, **kw), (exp[0][small], exp[1][small]), [meta[k] for k in small])
+
+
+@pytest.mark.parametrize("key", ["DNA4", "AMINO20"])
+def test_the_three_families_agree_at_full_length(gpu, bsq, key):
+    """No reference, three kernels: over the full-length list the statistics' score and ends are those of k_score_pairs, and under unit
+    costs in global mode columns - matches is the distance of k_edit_pairs and the score its negative."""
+    import torch
+    from bioseq_amd import align
+    (ca, oa, cb, ob, row, col), meta = _full_pairs(key)
+    tok = _tok(key)
+    S, o, e = _scoring(key)
+    d = [_dev(x, gpu) for x in (ca, oa, row, col, cb, ob)]
+    for mode in MODES:
+        kw = dict(matrix=S, gap_open=o, gap_extend=e, mode=mode, max_len=2048)
+        s, st = align.stats_pairs(tok, *d, **kw)
+        s2, ends = align.score_pairs(tok, *d, ends=True, **kw)
+        assert torch.equal(s, s2) and torch.equal(st[:, 2:4], ends), mode
+    s, st = align.stats_pairs(tok, *d, matrix=align.score_matrix(tok, 0, -1), gap_open=0, gap_extend=1, mode="global", max_len=2048)
+    dist = align.edit_distance_pairs(tok, *d, max_len=2048)
+    assert torch.equal(st[:, 5] - st[:, 4], dist) and torch.equal(-s, dist) and int(dist.min()) > 50 and int(dist.max()) > 500
+
+
+def test_gaps_across_high_lane_boundaries(gpu, bsq):
+    """The last case of test_alignments_across_a_lane_boundary in a pattern of 2048 rows: the core sits at rows 32 k - 18 .. 32 k + 21
+    between poly-P, and the text's copy lacks the characters of rows 32 k - 1 .. 32 k + 1, so the alignment's gap opens where lane k - 1
+    hands its bottom row to lane k -- for k = 17, 40 and 63, in both store orders."""
+    rng = np.random.default_rng(18)
+    tok = _tok("AMINO20")
+    S, o, e = _scoring("AMINO20")
+    core_letters = LETTERS["AMINO20"].replace("P", "").replace("W", "")
+    pairs, want = [], []
+    for k in (17, 40, 63):
+        core = twin.random_row(rng, 40, core_letters)
+        before = 32 * k - 19
+        pat = np.concatenate([np.full(before, ord("P"), np.uint8), core, np.full(2048 - before - 40, ord("P"), np.uint8)])
+        text = np.concatenate([np.full(30, ord("W"), np.uint8), core[:18], core[21:], np.full(2049 - 67, ord("W"), np.uint8)])
+        pairs += [(pat, text), (text, pat)]
+        want += [[before, 30, before + 40, 67, 37, 40], [30, before, 67, before + 40, 37, 40]]
+    stores = twin.store_of(pairs)
+    exp = _sweep(tok, stores, S, o, e, "local")
+    assert exp[1].tolist() == want
+    ca, oa, cb, ob, row, col = stores
+    _same(_device(gpu, tok, ca, oa, row, col, cb, ob, matrix=S, gap_open=o, gap_extend=e, max_len=2048), exp)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_long_text_in_the_widest_form(gpu, bsq, mode):
+    """2048 x 4500, the related part of the text from column 2100 on, in both store orders: 71 text tiles of 64 columns with every lane of
+    the group at work; one of the two texts also bridges gaps of three rows across lane boundaries."""
+    rng = np.random.default_rng(33)
+    tok = _tok("AMINO20")
+    S, o, e = _scoring("AMINO20")
+    pairs = []
+    for k in range(2):
+        short, long_ = twin.related_pair(rng, 2048, 4500, LETTERS["AMINO20"], rate=0.06)
+        if k:  # the second copy also lacks three characters at every fourth lane boundary
+            long_ = twin.fit(rng, twin.mutate(rng, _without_runs(short, range(3, 64, 4)), LETTERS["AMINO20"], 0.06), 4500, LETTERS["AMINO20"])
+        pairs.append((short, np.concatenate([long_[2400:], long_[:2400]])))
+    pairs[1] = pairs[1][::-1]
+    stores = twin.store_of(pairs)
+    exp = _sweep(tok, stores, S, o, e, mode)
+    if mode == "local":
+        st = exp[1].tolist()
+        assert 2050 < st[0][1] < 2150 and 2050 < st[1][0] < 2150 and min(st[0][4], st[1][4]) > 1500 and st[0][5] - st[0][4] > 100, st
+    ca, oa, cb, ob, row, col = stores
+    _same(_device(gpu, tok, ca, oa, row, col, cb, ob, matrix=S, gap_open=o, gap_extend=e, mode=mode, max_len=2048), exp)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_tie_stores():
+    """Two-letter rows of 513, 1025 and 2048 characters against rows of m and m + 9, in both store orders."""
+    rng = np.random.default_rng(19)
+    pairs = []
+    for m in (513, 1025, 2048):
+        for n in (m, m + 9):
+            x, y = twin.random_row(rng, m, "AC"), twin.random_row(rng, n, "AC")
+            pairs += [(x, y), (y, x)]
+    return twin.store_of(pairs)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("gaps", [(0, 1), (1, 1), (3, 0), (0, 0)])
+def test_ties_at_scale(gpu, bsq, mode, gaps):
+    """Two letters, +1 / -1, gaps that cost little or nothing: most cells of a 2048-row table tie between the diagonal and a gap or between
+    the two gaps, in every lane, and (local mode, by the sweep's count) the best cell is one of several."""
+    from bioseq_amd import align
+    tok = _tok("DNA4")
+    S = align.score_matrix(tok, 1, -1)
+    stores = _big_tie_stores()
+    counts = []
+    exp = _sweep(tok, stores, S, gaps[0], gaps[1], mode, counts=counts)
+    if mode == "local":
+        assert max(counts) > 1, counts
+    ca, oa, cb, ob, row, col = stores
+    _same(_device(gpu, tok, ca, oa, row, col, cb, ob, matrix=S, gap_open=gaps[0], gap_extend=gaps[1], mode=mode, max_len=2048), exp)
+
+
+@functools.lru_cache(maxsize=None)
+def _range_end_stores():
+    """Patterns of 1 .. 300 rows, none a multiple of 32 (so rows of the pad class lie beside real rows that score -128), against texts of
+    m, m + 3 and m + 40 characters, related (3 %) and unrelated, every second pair with the shorter side in store B."""
+    rng = np.random.default_rng(27)
+    pairs, meta = [], []
+    for m in (1, 5, 31, 33, 65, 100, 127, 129, 200, 300):
+        for n in (m, m + 3, m + 40):
+            pairs.append(twin.related_pair(rng, m, n, "ACGT", rate=0.03))
+            meta.append((m, n))
+        pairs.append((twin.random_row(rng, m, "ACGT"), twin.random_row(rng, m + 7, "ACGT")))
+        meta.append((m, m + 7))
+    for k in range(1, len(pairs), 2):
+        pairs[k] = pairs[k][::-1]
+    return twin.store_of(pairs), meta
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("gaps", [(127, 127), (0, 127)])
+def test_ends_of_the_scoring_ranges(gpu, bsq, mode, gaps):
+    """A matrix of 127 on the diagonal and -128 off it with gap costs of 127: the largest and smallest entries a cell can add, in every
+    form."""
+    from bioseq_amd import align
+    tok = _tok("DNA4")
+    S = align.score_matrix(tok, 127, -128)
+    stores, meta = _range_end_stores()
+    ca, oa, cb, ob, row, col = stores
+    exp = _sweep(tok, stores, S, gaps[0], gaps[1], mode)
+    assert exp[0].max() > 127 * 200 and (mode == "local" or exp[0].min() < -128 * 30)
+    kw = dict(matrix=S, gap_open=gaps[0], gap_extend=gaps[1], mode=mode)
+    for form in (2, 3):
+        _same(_device(gpu, tok, ca, oa, row, col, cb, ob, max_len=300, form=form, **kw), exp, meta)
+    small = np.array([k for k, (m, n) in enumerate(meta) if min(m, n) <= 128], np.int64)
+    _same(_device(gpu, tok, ca, oa, row[small], col[small], cb, ob, max_len=128, form=1, **kw), (exp[0][small], exp[1][small]), [meta[k] for k in small])

@@ -1,7 +1,8 @@
 """CPU: the alignment statistics of row pairs (include/bsq.h, "alignment statistics of row pairs") -- the declared symbols, the header's
 known answers, the library's host twin bsq_align_stats_host against the cell-by-cell programme of tests/align_stats_twin.py on pairs
-full of ties, related protein pairs, asymmetric matrices and both store orders, the properties that tie the statistics to the score, the
-ends and the edit distance, codes, every refusal, and the verification rule at its exact boundary.  No device is needed."""
+full of ties, related protein pairs, asymmetric matrices and both store orders, that programme's anti-diagonal sweep against it and the
+host twin against the sweep on patterns of up to 2048 rows, the properties that tie the statistics to the score, the ends and the edit
+distance, codes, every refusal, and the verification rule at its exact boundary.  No device is needed."""
 import ctypes
 import functools
 
@@ -158,24 +159,31 @@ def test_pairs_full_of_ties(mode, gaps):
     assert len({tuple(r) for r in got[1].tolist()}) > 100  # (a check of something)
 
 
-@pytest.mark.parametrize("mode", MODES)
-def test_related_proteins_and_asymmetric_matrices(mode):
-    """Related AMINO20 pairs around the 32-row edges under BLOSUM62 {11, 1}, both store orders; then an asymmetric matrix, where swapping
-    the stores needs the transposed matrix and swaps the statistics wherever one cell alone is best."""
-    from bioseq_amd import align
+@functools.lru_cache(maxsize=None)
+def _protein_pairs():
+    """Related AMINO20 pairs around the 32-row edges, every second one with the shorter row in B, and a matrix that is not symmetric."""
     rng = np.random.default_rng(7)
-    tok = _tok("AMINO20")
-    lut, nchars = _lut(tok)
     letters = LETTERS["AMINO20"]
     pairs = []
     for m, n in ((5, 9), (31, 31), (32, 40), (33, 33), (64, 70), (65, 65), (90, 140), (100, 100), (129, 160)):
         pairs.append(twin.related_pair(rng, m, n, letters, rate=0.1))
         pairs.append(twin.related_pair(rng, m, n, letters, rate=0.25)[::-1])
-    ca, oa, cb, ob, row, col = twin.store_of(pairs)
-    B62 = align.blosum62_matrix(tok)
     asym = rng.integers(-5, 3, size=(21, 21)).astype(np.int8)
     asym[np.arange(21), np.arange(21)] = rng.integers(3, 9, size=21)
     assert (asym != asym.T).any()
+    return pairs, asym
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_related_proteins_and_asymmetric_matrices(mode):
+    """Related AMINO20 pairs around the 32-row edges under BLOSUM62 {11, 1}, both store orders; then an asymmetric matrix, where swapping
+    the stores needs the transposed matrix and swaps the statistics wherever one cell alone is best."""
+    from bioseq_amd import align
+    tok = _tok("AMINO20")
+    lut, nchars = _lut(tok)
+    pairs, asym = _protein_pairs()
+    ca, oa, cb, ob, row, col = twin.store_of(pairs)
+    B62 = align.blosum62_matrix(tok)
     for S, o, e in ((B62, 11, 1), (asym, 4, 1), (asym, 0, 2)):
         exp = twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode)
         got = align.stats_pairs_host(tok, ca, oa, row, col, cb, ob, matrix=S, gap_open=o, gap_extend=e, mode=mode)
@@ -188,6 +196,76 @@ def test_related_proteins_and_asymmetric_matrices(mode):
         back = twin.stats_pairs(lut, nchars, cb, ob, ca, oa, col, row, St, o, e, mode)
         _same(align.stats_pairs_host(tok, cb, ob, col, row, ca, oa, matrix=St, gap_open=o, gap_extend=e, mode=mode), back)
         assert back[0].tobytes() == exp[0].tobytes()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_the_sweep_equals_the_cell_programme(mode):
+    """align_stats_diag == align_stats, statistics and all: on the pairs full of ties under gaps that cost an opening, an extension, only
+    one of them and nothing, and on the related proteins under BLOSUM62 {11, 1} and the matrix that is not symmetric.  The count of best
+    cells is that of score_twin.gotoh_cells."""
+    import score_twin
+    from bioseq_amd import align
+    tok = _tok("DNA4")
+    lut, nchars = _lut(tok)
+    S = align.score_matrix(tok, 1, -1)
+    ca, oa, cb, ob, row, col = twin.store_of(_tie_pairs())
+    many = 0
+    for o, e in ((0, 1), (1, 1), (3, 0), (0, 0)):
+        counts = []
+        swept = twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode, one=twin.align_stats_diag, counts=counts)
+        _same(swept, twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode))
+        for k in range(0, len(row), 7):
+            x, y = (twin.classes(lut, nchars, c[f[k]:f[k + 1]]) for c, f in ((ca, oa), (cb, ob)))
+            assert counts[k] == score_twin.gotoh_cells(x, y, S, o, e, mode)[3], (k, o, e)
+        many += sum(c > 1 for c in counts)
+    assert mode == "global" or many > 400  # (most best cells are one of many)
+    tok = _tok("AMINO20")
+    lut, nchars = _lut(tok)
+    pairs, asym = _protein_pairs()
+    ca, oa, cb, ob, row, col = twin.store_of(pairs)
+    for S, o, e in ((align.blosum62_matrix(tok), 11, 1), (asym, 4, 1), (asym, 0, 2)):
+        swept = twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode, one=twin.align_stats_diag)
+        _same(swept, twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode))
+
+
+FULL_SIZES = ((129, 160), (511, 600), (513, 513), (1000, 1500), (2047, 2048), (2048, 2048), (2048, 3000), (700, 5000))
+
+
+@functools.lru_cache(maxsize=None)
+def _full_length_pairs():
+    """Every size of FULL_SIZES three times: a DNA4 pair related at 8 %, a two-letter related pair with the shorter row in B, and two
+    unrelated two-letter rows.  The stores and the list, shared by every scoring and mode."""
+    rng = np.random.default_rng(29)
+    pairs, meta = [], []
+    for m, n in FULL_SIZES:
+        pairs.append(twin.related_pair(rng, m, n, "ACGT", rate=0.08))
+        pairs.append(twin.related_pair(rng, m, n, "AC", rate=0.08)[::-1])
+        pairs.append((twin.random_row(rng, m, "AC"), twin.random_row(rng, n, "AC")))
+        meta += [(m, n, "related"), (n, m, "two letters, related"), (m, n, "two letters")]
+    return twin.store_of(pairs), meta
+
+
+@pytest.mark.parametrize("scoring", [(2, -3, 5, 2, "local"), (2, -3, 5, 2, "global"), (1, -1, 0, 1, "local"), (1, -1, 3, 0, "local"), (1, -1, 0, 0, "local")])
+def test_host_twin_against_the_sweep_at_full_length(scoring):
+    """bsq_align_stats_host == align_stats_diag on patterns of up to 2048 rows -- every lane of the widest form's pattern, texts of up to
+    5000 columns: the two share no cell, no packing and no orientation, so a mistake in what the host twin and the kernels compile
+    together shows here."""
+    from bioseq_amd import align
+    match, mismatch, o, e, mode = scoring
+    tok = _tok("DNA4")
+    lut, nchars = _lut(tok)
+    S = align.score_matrix(tok, match, mismatch)
+    (ca, oa, cb, ob, row, col), meta = _full_length_pairs()
+    counts = []
+    exp = twin.stats_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, o, e, mode, one=twin.align_stats_diag, counts=counts)
+    got = align.stats_pairs_host(tok, ca, oa, row, col, cb, ob, matrix=S, gap_open=o, gap_extend=e, mode=mode)
+    _same(got, exp, meta)
+    _properties(got[0], got[1], np.diff(oa)[row], np.diff(ob)[col], mode == "local")
+    if mode == "local":
+        if (o, e) == (5, 2):  # (not vacuous: the related pairs align over most of the shorter row)
+            assert all(st[4] > min(m, n) // 2 for st, (m, n, kind) in zip(exp[1].tolist(), meta) if kind == "related")
+        else:
+            assert sum(c > 1 for c in counts) >= 8  # (best cells that are one of many)
 
 
 def test_unit_costs_give_the_edit_distance():

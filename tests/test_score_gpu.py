@@ -1,7 +1,7 @@
 """GPU: the scored alignment of row pairs (bioseq_amd.align, bsq_score_pairs_device) against the plain Gotoh programme of
 tests/score_twin.py and the library's host twin, byte for byte, scores and ends: shorter sides at every lane and group edge with four
 longer sides each in both modes, a long deletion that tells affine gaps from linear ones, every form on the pairs it holds, rows full
-of ties, an asymmetric matrix, waves whose groups finish at different steps with guards around both outputs, the codes, long texts,
+of ties, an asymmetric matrix, the ends of the scoring ranges, waves whose groups finish at different steps with guards around both outputs, the codes, long texts,
 unmapped bytes, the Python surface on a side stream, and the pipeline from sketches to score-verified clusters."""
 import ctypes
 import functools
@@ -197,6 +197,43 @@ def test_asymmetric_matrix(gpu, bsq):
         _same(_device(gpu, tok, cb, ob, col, row, ca, oa, matrix=np.ascontiguousarray(S.T), gap_open=4, gap_extend=1, mode=mode), back)
         wrong = _device(gpu, tok, cb, ob, col, row, ca, oa, matrix=S, gap_open=4, gap_extend=1, mode=mode, ends=False)
         assert (wrong != exp[0]).any(), "the matrix matters"
+
+
+@functools.lru_cache(maxsize=None)
+def _range_end_stores():
+    """Shorter sides of 1 .. 300 characters, none a multiple of 32 or 64 (so rows of the pad class lie beside real rows that score -128),
+    against longer sides of m, m + 3 and m + 40, related (3 %) and unrelated, every second pair with the shorter side in store B."""
+    rng = np.random.default_rng(27)
+    pairs, meta = [], []
+    for m in (1, 5, 31, 33, 65, 100, 127, 129, 200, 300):
+        for n in (m, m + 3, m + 40):
+            pairs.append(twin.related_pair(rng, m, n, "ACGT", rate=0.03))
+            meta.append((m, n))
+        pairs.append((twin.random_row(rng, m, "ACGT"), twin.random_row(rng, m + 7, "ACGT")))
+        meta.append((m, m + 7))
+    for k in range(1, len(pairs), 2):
+        pairs[k] = pairs[k][::-1]
+    return twin.store_of(pairs), meta
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("gaps", [(127, 127), (0, 127)])
+def test_ends_of_the_scoring_ranges(gpu, bsq, mode, gaps):
+    """A matrix of 127 on the diagonal and -128 off it with gap costs of 127: the largest and smallest entries a cell can add, in every
+    form."""
+    from bioseq_amd import align
+    tok = _tok("DNA4")
+    lut, nchars = _lut(tok)
+    S = align.score_matrix(tok, 127, -128)
+    (ca, oa, cb, ob, row, col), meta = _range_end_stores()
+    exp = twin.score_pairs(lut, nchars, ca, oa, cb, ob, row, col, S, gaps[0], gaps[1], mode)
+    assert exp[0].max() > 127 * 200 and (mode == "local" or exp[0].min() < -128 * 30)
+    kw = dict(matrix=S, gap_open=gaps[0], gap_extend=gaps[1], mode=mode)
+    _same(align.score_pairs_host(tok, ca, oa, row, col, cb, ob, ends=True, **kw), exp, meta)
+    for form in (2, 3):
+        _same(_device(gpu, tok, ca, oa, row, col, cb, ob, max_len=300, form=form, **kw), exp, meta)
+    small = np.array([k for k, (m, n) in enumerate(meta) if min(m, n) <= 256], np.int64)
+    _same(_device(gpu, tok, ca, oa, row[small], col[small], cb, ob, max_len=256, form=1, **kw), (exp[0][small], exp[1][small]), [meta[k] for k in small])
 
 
 def test_ragged_waves_and_guards(gpu, bsq):
