@@ -21,7 +21,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libbsq_hip.so")
 EXT = os.path.join(HERE, "cbioseq" + sysconfig.get_config_var("EXT_SUFFIX"))
 
-LIB_SRCS = ["bsq_onehot.hip", "bsq_tokens.hip", "bsq_generic.hip", "bsq_tokens8.hip", "bsq_decode.hip", "bsq_augment.hip", "bsq_mlm.hip", "bsq_kmer.hip", "bsq_kmer_mlm.hip", "bsq_kmer_spectrum.hip", "bsq_pack.hip", "bsq_pack_mlm.hip", "bsq_gather.hip", "bsq_views.hip", "bsq_translate.hip", "bsq_orf.hip", "bsq_sketch.hip", "bsq_edit.hip", "bsq_score.hip", "bsq_align_stats.hip", "bsq_bpe.hip", "bsq_bpe_mlm.hip", "bsq_bpe_train.hip", "bsq_greedy.hip", "bsq_lsh.hip", "bsq_diag.hip", "bsq_host.cpp", "bsq_pack_host.cpp", "bsq_kmer_mlm_host.cpp", "bsq_translate_host.cpp", "bsq_orf_host.cpp", "bsq_sketch_host.cpp", "bsq_edit_host.cpp", "bsq_score_host.cpp", "bsq_align_stats_host.cpp", "bsq_bpe_host.cpp", "bsq_bpe_mlm_host.cpp", "bsq_bpe_train_host.cpp", "bsq_greedy_host.cpp", "bsq_lsh_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
+LIB_SRCS = ["bsq_onehot.hip", "bsq_tokens.hip", "bsq_generic.hip", "bsq_tokens8.hip", "bsq_decode.hip", "bsq_augment.hip", "bsq_mlm.hip", "bsq_kmer.hip", "bsq_kmer_mlm.hip", "bsq_kmer_spectrum.hip", "bsq_pack.hip", "bsq_pack_mlm.hip", "bsq_gather.hip", "bsq_views.hip", "bsq_translate.hip", "bsq_orf.hip", "bsq_sketch.hip", "bsq_edit.hip", "bsq_score.hip", "bsq_align_stats.hip", "bsq_bpe.hip", "bsq_bpe_mlm.hip", "bsq_bpe_train.hip", "bsq_greedy.hip", "bsq_lsh.hip", "bsq_span.hip", "bsq_diag.hip", "bsq_host.cpp", "bsq_pack_host.cpp", "bsq_kmer_mlm_host.cpp", "bsq_translate_host.cpp", "bsq_orf_host.cpp", "bsq_sketch_host.cpp", "bsq_edit_host.cpp", "bsq_score_host.cpp", "bsq_align_stats_host.cpp", "bsq_bpe_host.cpp", "bsq_bpe_mlm_host.cpp", "bsq_bpe_train_host.cpp", "bsq_greedy_host.cpp", "bsq_lsh_host.cpp", "bsq_span_host.cpp", "bsq_alphabet.cpp", "bsq_fastx.cpp"]
 EXT_SRCS = ["cbioseq_module.cpp"]
 EXT_HDRS = ["bsq_worker_pool.h"]
 

@@ -107,6 +107,12 @@ class BpeMlm(ctypes.Structure):
                 ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
 
 
+class SpanCorrupt(ctypes.Structure):
+    """struct bsq_span_corrupt"""
+    _fields_ = [("anchor_prob", ctypes.c_double), ("span", ctypes.c_int32), ("max_sentinels", ctypes.c_int32), ("sentinel_first", ctypes.c_int64),
+                ("sentinel_step", ctypes.c_int32), ("ignore_index", ctypes.c_int64), ("seed", ctypes.c_uint64), ("first_row", ctypes.c_int64)]
+
+
 class Score(ctypes.Structure):
     """struct bsq_score"""
     _fields_ = [("max_len", ctypes.c_int32), ("form", ctypes.c_int32), ("mode", ctypes.c_int32), ("gap_open", ctypes.c_int32),
@@ -288,6 +294,9 @@ def load():
         "bsq_bpe_train_steps_device": (i32, [dp, vp, i64, i64, ctypes.POINTER(BpeTrain), vp, i32, i32, vp]),
         "bsq_bpe_train_host": (i32, [dp, vp, vp, i64, i64, ctypes.POINTER(BpeTrain), vp, vp, i64p, i64p]),
         "bsq_bpe_train_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(BpeTrain)]),
+        "bsq_span_corrupt_device": (i32, [dp, vp, vp, i64, i64, i64, ctypes.POINTER(SpanCorrupt), c_int, vp, c_int, vp, vp, vp, vp]),
+        "bsq_span_corrupt_host": (i32, [dp, vp, vp, i64, i64, i64, ctypes.POINTER(SpanCorrupt), c_int, vp, c_int, vp, vp, vp]),
+        "bsq_span_corrupt_kernel_name": (ctypes.c_char_p, [dp, ctypes.POINTER(SpanCorrupt), i64, i64, i64, c_int, c_int]),
         "bsq_pack_plan_device": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp]),
         "bsq_pack_plan_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),
         "bsq_pack_plan_parallel_host": (i32, [vp, i64, i64, i32, i32, i32, i64, vp, vp, vp]),

@@ -104,6 +104,16 @@ class FlatFileDataset(torch.utils.data.Dataset):
     bpe.bpe_vocab_size, labels int64 with ignore_index -100.  Keyed like kmer_mlm=True: a fresh key per call and per `batches()` epoch,
     a row keyed by its index in the epoch's order, so `group` and `prefetch` hand out the same masks.
 
+    span_corrupt=True (keyword; off by default; token rows only): the batches are T5's span-corruption batches drawn on the device
+    (masking.span_corrupt_packed, one launch) -- `get_batch`, `__getitems__`, `__getitem__` and `batches()` hand out (inputs, labels):
+    anchors open spans of `span` characters so that a share `maskfrac` of a long row is covered, every run of covered characters
+    becomes one sentinel (tokenizer.alphabet_size() upwards, at most 100 per row) in the (B, max_seq_len) inputs, and the labels,
+    (B, `target_len`) int64 with ignore_index -100, hold each sentinel followed by the tokens it stands for.  target_len=None is the
+    input width: a target body is at most one element longer than its sequence, so only a longest sequence that is cut out whole, of
+    a tokenizer without BOS, loses its last label; a smaller one cuts label rows at it.  Keyed exactly like kmer_mlm=True: a fresh key
+    per call and per `batches()` epoch, a row keyed by its index in the epoch's order.  It composes with crop, revcomp_frac, translate,
+    shuffle, group and prefetch.  With cnn=True, augment > 0, masked=True, kmer=, bpe=, pack= or spectrum= it raises ValueError.
+
     pack="nextfit" | "stream" (keyword; off by default; token rows only): batches are sequence-packed -- several sequences per row
     of max_seq_len positions (packing.pack_tokenize_packed) -- and `get_batch`, `__getitems__` and `batches()` hand out
     (tokens, segment_ids, position_ids), each (rows, max_seq_len), rows being what the batch needs (one 8-byte read-back per batch:
@@ -126,7 +136,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
     def __init__(self, ff, tokenizer, *, augment=0, augment_frac=0.5, cnn=False, device=None, maskfrac=0.15, seed=13, token_dtype="q", prefetch=0, masked=False,
                  crop=None, crop_mode="random", revcomp_frac=0.0, kmer=None, kmer_stride=1, pack=None, pack_mlm=False,
                  kmer_mlm=False, kmer_span=None, spectrum=None, spectrum_stride=1, spectrum_both_strands=False, spectrum_normalize=True,
-                 translate=None, codon_table=1, bpe=None, bpe_padlen=None, bpe_mlm=False):
+                 translate=None, codon_table=1, bpe=None, bpe_padlen=None, bpe_mlm=False, span_corrupt=False, span=3, target_len=None):
         super().__init__()
         if not isinstance(ff, FlatFile):
             raise TypeError("FlatFileDataset expects a FlatFile")
@@ -234,6 +244,17 @@ class FlatFileDataset(torch.utils.data.Dataset):
             else:
                 bpe_ids._bpe(bpe, token_dtype, self._bpe_max_chars, None)
 
+        self.span_corrupt, self.span = bool(span_corrupt), span
+        self.target_len = None
+        if self.span_corrupt:
+            if cnn or augment or masked or kmer is not None or bpe is not None or pack is not None or spectrum is not None:
+                raise ValueError("span_corrupt=True gives span-corruption batches of the plain token rows: it cannot be combined with cnn=True, "
+                                 "augment > 0, masked=True, kmer=, bpe=, pack= or spectrum=")
+            if target_len is not None and int(target_len) <= 0:
+                raise ValueError("target_len must be a positive number of positions, got %r" % (target_len,))
+            self.target_len = self.max_seq_len if target_len is None else int(target_len)
+            masking._span_params(tokenizer, token_dtype, "q", maskfrac, span, None, None, 1, 100, -100, 0, 0)  # (checked here)
+
     def __len__(self):
         return self.ff.nseqs()
 
@@ -320,6 +341,10 @@ class FlatFileDataset(torch.utils.data.Dataset):
                                               stride=self.kmer_stride, frac=self.maskfrac, span=self.kmer_span, seed=mask_seed,
                                               first_row=first_row, validate=not self._trusted_lengths)
 
+    def _encode_span_corrupt(self, chars, offs, mask_seed, first_row):
+        return masking.span_corrupt_packed(self.tokenizer, chars, offs, self.max_seq_len, self.target_len, self.token_dtype, frac=self.maskfrac,
+                                           span=self.span, seed=mask_seed, first_row=first_row, validate=not self._trusted_lengths)[:2]
+
     def _bpe_lengths_checked(self, lengths):
         """A store whose lengths are not trusted may hold a row of more than max_chars characters: its batch raises (one read-back)."""
         if not self._trusted_lengths and bool((lengths < 0).any()):
@@ -375,6 +400,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_kmer_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
         if self.bpe_mlm:
             return self._encode_bpe_mlm(*self._packed_device(start, stop), self._mask_key(), 0)
+        if self.span_corrupt:
+            return self._encode_span_corrupt(*self._packed_device(start, stop), self._mask_key(), 0)
         return self._encode(*self._packed_device(start, stop))
 
     def _index(self, i):
@@ -406,6 +433,8 @@ class FlatFileDataset(torch.utils.data.Dataset):
             return self._encode_kmer_mlm(*packed, self._mask_key(), 0)
         if self.bpe_mlm:
             return self._encode_bpe_mlm(*packed, self._mask_key(), 0)
+        if self.span_corrupt:
+            return self._encode_span_corrupt(*packed, self._mask_key(), 0)
         return self._encode(*packed)
 
     def batches(self, batch_size, shuffle=True, drop_last=False, generator=None, prefetch=None, group=1):
@@ -442,11 +471,11 @@ class FlatFileDataset(torch.utils.data.Dataset):
             raise ValueError("group > 1 cannot be combined with pack=: a super-batch's row blocks are not the batches' own packings")
         if self.spectrum is not None and int(group) > 1:
             raise ValueError("group > 1 cannot be combined with spectrum=")
-        pairs = self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm  # a batch is a tuple of tensors
+        pairs = self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm or self.span_corrupt  # a batch is a tuple of tensors
         span = batch_size * max(1, int(group))
         n_eff = n - n % batch_size if drop_last else n
         firsts = list(range(0, n_eff, span))
-        mask_seed = self._mask_key() if self.masked or self.pack_mlm or self.kmer_mlm or self.bpe_mlm else None
+        mask_seed = self._mask_key() if self.masked or self.pack_mlm or self.kmer_mlm or self.bpe_mlm or self.span_corrupt else None
         crop_seed = self._crop_key() if self._views else None
 
         def encode(first):
@@ -462,13 +491,15 @@ class FlatFileDataset(torch.utils.data.Dataset):
                 return self._encode_kmer_mlm(*packed, mask_seed, first)
             if self.bpe_mlm:
                 return self._encode_bpe_mlm(*packed, mask_seed, first)
+            if self.span_corrupt:
+                return self._encode_span_corrupt(*packed, mask_seed, first)
             return self._encode(*packed)
 
         def hand_out(big):
             rows = big[0].shape[0] if pairs else big.shape[0]
             if rows <= batch_size or self.pack is not None:
                 yield big
-            elif self.masked or self.kmer_mlm or self.bpe_mlm:
+            elif self.masked or self.kmer_mlm or self.bpe_mlm or self.span_corrupt:
                 for r in range(0, rows, batch_size):
                     yield big[0][r:r + batch_size], big[1][r:r + batch_size]
             else:
@@ -533,7 +564,7 @@ class FlatFileDataset(torch.utils.data.Dataset):
             s, e, st = index.indices(len(self))
             return self.__getitems__(list(range(s, e, st)))
         index = self._index(index)
-        if self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm:
+        if self.masked or self.pack is not None or self.kmer_mlm or self.bpe_mlm or self.span_corrupt:
             return tuple(t[0] for t in self.get_batch(index, index + 1))
         return self.get_batch(index, index + 1)[0]
 

@@ -55,7 +55,8 @@ extern "C" {
                            * bsq_greedy_kernel_name, bsq_lsh, bsq_lsh_keys_device, bsq_lsh_keys_host, bsq_lsh_count_device, bsq_lsh_emit_device,
                            * bsq_sketch_compare_list_device, bsq_sketch_compare_list_host, bsq_lsh_pairs_host, bsq_lsh_kernel_name,
                            * bsq_bpe_train, bsq_bpe_train_workspace_bytes, bsq_bpe_train_table_slots, bsq_bpe_train_lds_slots,
-                           * bsq_bpe_train_begin_device, bsq_bpe_train_steps_device, bsq_bpe_train_host, bsq_bpe_train_kernel_name;
+                           * bsq_bpe_train_begin_device, bsq_bpe_train_steps_device, bsq_bpe_train_host, bsq_bpe_train_kernel_name,
+                           * bsq_span_corrupt, bsq_span_corrupt_device, bsq_span_corrupt_host, bsq_span_corrupt_kernel_name;
                            * nothing removed */
 
 typedef int32_t bsq_status;
@@ -1610,6 +1611,79 @@ bsq_status bsq_kmer_mlm_tokenize_host(const bsq_desc *d, const uint8_t *chars, c
  * "k_kmer_mlm_generic"), from the predicate the launch uses; "" for arguments the device call refuses. */
 const char *bsq_kmer_mlm_kernel_name(const bsq_desc *d, const bsq_kmer *km, const bsq_kmer_mlm *m, int64_t B, int64_t P,
                                      int32_t batch_first, bsq_dtype in_dtype, bsq_dtype label_dtype);
+
+/* ---- span corruption: the pretraining objective of the encoder-decoder models (T5; ProtT5, Ankh, the T5-style DNA models).  Runs of
+ * selected tokens are cut out of the encoder input and replaced by one sentinel id each; the decoder target is the sentinels, each
+ * followed by the tokens it stands for.  Both outputs are SHORTER than the row, by amounts that depend on the draw: encoder inputs,
+ * decoder targets and both body lengths of a packed batch in ONE launch, over bsq_tokenize_device's character ids.
+ *
+ * THE DRAW.  L is the row's length (a negative one counts as 0), c_j its characters, tok_j what bsq_tokenize_device stores for c_j
+ * (lut[c_j], 0 for an unmapped byte); row = first_row + i for sequence i of the batch.  With mix64 the splitmix64 finalizer and
+ * T_anchor = floor(anchor_prob * 65536 + 0.5):
+ *     h_row       = mix64((seed ^ 0x5350414E43525054) + 0x9E3779B97F4A7C15 * (row + 1))    "SPANCRPT": a domain of its own
+ *     w(q)        = mix64(h_row + 0xD1342543DE82EF95 * (q + 1))                             one word per 4 character indices
+ *     anchor(a)   <=>  a >= 0  and  ((w(a >> 2) >> (16 * (a & 3))) & 0xFFFF) < T_anchor       independent of the characters
+ *     covered(j)  <=>  some a in [max(0, j - span + 1), j] has anchor(a)
+ *     cand(j)     <=>  covered(j) and 0 <= j < L and lut[c_j] >= 0                           an unmapped byte is never cut out and ends a run
+ *     run g        =   the g-th maximal run of consecutive cand positions of the row, g = 0, 1, ...
+ *     selected(j) <=>  cand(j) and g(j) < max_sentinels                                      later runs stay in the input untouched
+ *     sentinel(g)  =   sentinel_first + g * sentinel_step                                    step +1 or -1 (HF T5 counts down from vocab - 1)
+ * THE BODIES.  The input body is the row walked left to right: an unselected j gives tok_j, the first position of a selected run gives
+ * sentinel(g), the other selected positions give nothing.  The target body is, for every selected run in order, sentinel(g) followed by
+ * the run's tok_j.
+ * THE ROWS.
+ *     inputs (B, P_in):   [BOS] first min(in_len,  max(P_in  - bos - eos, 0)) body elements [EOS] PAD ...
+ *     labels (B, P_tgt):        first min(tgt_len, max(P_tgt - eos, 0))       body elements [EOS] ignore_index ...
+ * each cut at its width (P_in = 1 with BOS and EOS holds the BOS alone).  BOS, EOS and PAD are the tokenizer's, as bsq_tokenize_device
+ * stores them: pad positions hold bsq_pad_id with padchar and 0 without.  in_len and tgt_len (int32, (B), either may be NULL) hold the
+ * body lengths BEFORE the cut, so a caller sees a cut row: in_len > P_in - bos - eos or tgt_len > P_tgt - eos.  Every output element is
+ * written exactly once: no memset, no atomic.
+ * A character's fate depends on (seed, row, j, span, T_anchor, max_sentinels) and the row's characters only -- never on the widths, the
+ * element types, batch size, shard, piece or stream.  anchor_prob = 0: the inputs are bsq_tokenize_device's (B, P_in) rows, bit for
+ * bit, and the labels hold only [EOS]; anchor_prob = 1: every maximal run of mapped characters is one gap.  The struct carries the anchor
+ * rate: bsq_kmer_mlm_anchor_prob(frac, span) is the rate at which a share `frac` of a long row is covered.  With frac 0.15 and span 1 a
+ * 512-character row holds about 66 runs and a 1024-character row about 130 -- above T5's 100 sentinels, so the cutoff is no corner case.
+ *
+ * Known answers (DNA4, span 3, anchor_prob 0.2, seed 7, first_row 0, P_in 16, P_tgt 10, ignore_index written as "-", no flags,
+ * sentinel_first 4, step 1, max_sentinels 100; the batch ACGTACGTACGTACGTACGT, ACGNNCGTACGTAC, AC, "", TTTTTTTTTTTTTTTTTTTTTTTT, rows
+ * 0, 1 and 4):
+ *     row 0 -> inputs 0 1 2 3 4 3 0 5 1 2 3 0 6 0 0 0      labels 4 0 1 2 5 1 2 3 0 6    in_len 13  tgt_len 13
+ *     row 1 -> inputs 4 0 0 5 3 0 6 0 0 0 0 0 0 0 0 0      labels 4 0 1 2 5 1 2 6 1 2    in_len 7   tgt_len 13
+ *     row 4 -> inputs 3 3 4 3 5 3 3 3 3 6 3 0 0 0 0 0      labels 4 3 3 3 3 5 3 3 3 6    in_len 11  tgt_len 19
+ * the same with max_sentinels 1, row 0 -> inputs 0 1 2 3 4 3 0 1 2 3 0 1 2 3 0 1, labels 4 0 1 2 - - - - - -, in_len 18, tgt_len 4;
+ * with BOS, EOS and PAD (sentinel_first 7), row 0 -> inputs 4 0 1 2 3 7 3 0 8 1 2 3 0 9 5 6, labels 7 0 1 2 8 1 2 3 0 5.
+ *
+ * Refused before anything is launched, BSQ_ERR_INVALID_ARG: a probability outside [0, 1] or NaN, span outside 1 .. 16, max_sentinels
+ * outside 1 .. 65535, sentinel_step not +1 or -1, a sentinel range [sentinel(0), sentinel(max_sentinels - 1)] that leaves [0, 2^31) or
+ * meets [0, bsq_alphabet_size), first_row < 0, P_in <= 0 or P_tgt <= 0, both matrices NULL; BSQ_ERR_DTYPE, by bsq_dtype_holds: an input
+ * type that does not hold [0, largest sentinel], a label type that does not hold [min(ignore_index, 0), max(ignore_index, largest
+ * sentinel)] -- a matrix that is NULL holds nothing and its type is not asked beyond being a bsq_dtype (the kernel-name call, which
+ * has no matrices, asks both).  All six bsq_dtypes for each matrix; stream-ordered, never synchronises; B == 0 is BSQ_OK with nothing
+ * launched.
+ * Kernel: k_span_corrupt -- a wave per row, four rows per workgroup, a row of any length in tiles of 1024 characters (16 per lane) with
+ * the running (run index, input position, target position) carried between tiles; per tile four selection hashes per lane, one
+ * neighbour exchange for the look-back, two wave scans, both bodies compacted through the wave's own LDS region and stored from there
+ * as 16-byte vectors aligned in memory, what a tile leaves over carried to the next; element types chosen at run time. */
+typedef struct bsq_span_corrupt {
+    double anchor_prob;     /* share of the character indices that open a span, in [0, 1] */
+    int32_t span;           /* consecutive characters an anchor covers, 1 .. 16 */
+    int32_t max_sentinels;  /* runs of a row that are cut out, 1 .. 65535 (T5: 100); later runs stay in the input */
+    int64_t sentinel_first; /* id of the first run's sentinel (usually bsq_alphabet_size(d)) */
+    int32_t sentinel_step;  /* +1 or -1 */
+    int64_t ignore_index;   /* label of every position behind the target's [EOS] (torch: -100) */
+    uint64_t seed;
+    int64_t first_row;      /* row key of the batch's first sequence (a shard or a piece of a larger batch: its first row there) */
+} bsq_span_corrupt;
+bsq_status bsq_span_corrupt_device(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P_in, int64_t P_tgt,
+                                   const bsq_span_corrupt *m, bsq_dtype in_dtype, void *inputs_or_null, bsq_dtype label_dtype,
+                                   void *labels_or_null, int32_t *in_len_or_null, int32_t *tgt_len_or_null, void *hip_stream);
+/* CPU twin on host buffers (the same lane code; no device is needed). */
+bsq_status bsq_span_corrupt_host(const bsq_desc *d, const uint8_t *chars, const int64_t *offsets, int64_t B, int64_t P_in, int64_t P_tgt,
+                                 const bsq_span_corrupt *m, bsq_dtype in_dtype, void *inputs_or_null, bsq_dtype label_dtype,
+                                 void *labels_or_null, int32_t *in_len_or_null, int32_t *tgt_len_or_null);
+/* Host only: the kernel bsq_span_corrupt_device takes ("k_span_corrupt"); "" for arguments the device call refuses. */
+const char *bsq_span_corrupt_kernel_name(const bsq_desc *d, const bsq_span_corrupt *m, int64_t B, int64_t P_in, int64_t P_tgt,
+                                         bsq_dtype in_dtype, bsq_dtype label_dtype);
 
 /* ---- sequence packing: several sequences per token row.  Every other encode path writes one sequence per row and fills the rest with
  * PAD; a transformer pays for every position of the matrix, and at protein-like or read-like length distributions most of them are
